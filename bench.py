@@ -4,16 +4,21 @@
 
 A "step" is one camera frame through the hot path, timed the way the reference times it (app/larvioMain.cpp:106-116: processImage,
 then processFeatures when a message was produced).  The image is handed over as a HOST buffer (the reference's cv::Mat): the copy
-into the front-end's pinned staging and the H2D transfer are inside the timed region.  A second pass over the same frames with the
-images already resident in HBM is reported beside it (`device_resident`).
+into the front-end's pinned staging and the H2D transfer are inside the timed region.  With --full, a second pass over the same frames
+with the images already resident in HBM is reported beside it (`device_resident`).
 
 The timed region always starts from the STATED steady state, whatever --steps/--warmup say: an untimed pre-roll runs until the
 sliding window has filled and cycled (clones >= sw_size - 2 and >= 2 pruning MSCKF updates, larvio.cpp:2316-2320), then >= 20 more
 updates with the H P GEMM bracketed by HIP events (MFMA utilisation); only then come the W warm-up and the K timed steps.  If the
 steady state is not reached no value is printed.
 
-  python bench.py --gpus N --steps K --warmup W [--config A|3|4|5] [--sequential] [--sharded]
+  python bench.py --gpus N --steps K --warmup W [--config A|3|4|5] [--sequential] [--sharded] [--full] [--dump-outputs DIR]
   (N>1: launched by torch.distributed.run; --sharded needs --config 5)
+
+A plain run measures the headline only: set-up, pre-roll, warm-up, the K timed steps, the result line.  --full adds everything measured
+beside it - the CPU baseline, the device-resident pass, the adapter's schedules and its C++ binary, the off-grid-stamp pass and the
+configs[4]-depth filter probe (each still switched off by its own --no-* option).  --dump-outputs DIR writes what the timed path computed
+in its last step (filter state, covariance, window, in-state features, the tracker's tracks) as DIR/<name>.npy.
 
 N>1 without --sharded runs N independent estimators, one camera stream per GPU (replicas: at 150 tracks the R-factor all-gather
 costs more than the whole update); with --sharded every rank sees the same stream, builds the measurement rows of its
@@ -366,7 +371,7 @@ def backend_only(args, rank, world, local_rank, dist, torch, K=None, W=None, sha
     sharded = args.sharded if sharded is None else sharded
     max_features = (args.max_features if args.backend_only else None) or 2000
     sw_size = (args.sw_size if args.backend_only else None) or 60
-    want_cpu = rank == 0 and world == 1 and not getattr(args, "no_cpu_baseline", False)
+    want_cpu = rank == 0 and world == 1 and args.full and not args.no_cpu_baseline
     n_pre = 2 * 60 + 12
     sim = S.simulate_features(21 + (0 if sharded else rank), t0=2.0, t1=2.0 + 0.1 * (n_pre + W + K + 2), max_feat=max_features,
                               n_per_batch=500, sw_size=sw_size, max_features_in_one_grid=2, estimate_td=1, estimate_extrin=1,
@@ -417,7 +422,8 @@ def backend_only(args, rank, world, local_rank, dist, torch, K=None, W=None, sha
             elapsed = max_over_ranks(dist, torch, elapsed)
         c1 = be.counters(); s1 = be.shard_stats()
         r = dict(elapsed=elapsed, lat=lat, dim=be.dim, clones=len(be.clones()), n_feat=len(msgs[i - 1][1]), qr=qr, hp=hp,
-                 timed={k: c1[k] - c0[k] for k in ("hybrid", "msckf", "gated_in", "gated_out", "triangulations")}, shard={k: s1[k] - s0[k] for k in s1})
+                 timed={k: c1[k] - c0[k] for k in ("hybrid", "msckf", "gated_in", "gated_out", "triangulations")}, shard={k: s1[k] - s0[k] for k in s1},
+                 outputs=filter_outputs(be) if (profile and args.dump_outputs) else None)
         be.close()
         if shard is not None:
             shard.close()
@@ -442,6 +448,8 @@ def backend_only(args, rank, world, local_rank, dist, torch, K=None, W=None, sha
     streams = 1 if sharded else world
     if rank != 0:
         return None
+    if m["outputs"] is not None:
+        dump_outputs(args.dump_outputs, m["outputs"])
     qr, hp = m["qr"], m["hp"]
     roof_qr = None
     if qr and qr["launches"] > 0 and qr["ms"] > 0:
@@ -547,7 +555,7 @@ def shard_probe(rank, world, local_rank):
     for k in [k for k in env if k.startswith("TORCHELASTIC_") or k in ("GROUP_RANK", "ROLE_RANK", "ROLE_NAME", "GROUP_WORLD_SIZE", "ROLE_WORLD_SIZE")]:
         del env[k]                                       # the children rendezvous among themselves: with torchrun's TORCHELASTIC_USE_AGENT_STORE
                                                          # rank 0 would wait for an agent-hosted store on the new port instead of creating it
-    cmd = [sys.executable, os.path.abspath(__file__), "--backend-only", "--gpus", str(world), "--steps", "40", "--warmup", "4"] + (["--sharded"] if world > 1 else ["--loopback-probe"])
+    cmd = [sys.executable, os.path.abspath(__file__), "--backend-only", "--full", "--gpus", str(world), "--steps", "40", "--warmup", "4"] + (["--sharded"] if world > 1 else ["--loopback-probe"])
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
     except subprocess.TimeoutExpired:
@@ -595,6 +603,47 @@ def cpu_model():
     return "unknown"
 
 
+DUMP_MAX_BYTES = 60 * 10 ** 6                # under the 64 MB an output dump may take, .npy headers included
+
+
+def filter_outputs(be):
+    """What a caller of the filter reads after its last update (larvio.cpp:2644-2735's getters and the window): state, covariance,
+    clones, in-state features; all float64."""
+    from numpy.lib import recfunctions
+    out = {"state_" + k: np.asarray(v, np.float64) for k, v in be.state().items()}
+    out["cov"] = be.cov()
+    out["clones"] = recfunctions.structured_to_unstructured(be.clones(), np.float64)        # columns in larvio_amd.larvio.CLONE's field order
+    ids, idp, pos = be.features()
+    out["feature_ids"] = ids.astype(np.float64); out["feature_idp"] = idp; out["feature_pos"] = pos
+    return out
+
+
+def pipeline_outputs(run):
+    """filter_outputs + the tracker's tracks after the last frame (points in float32, as the front-end computes them)."""
+    out = filter_outputs(run.be)
+    tr = run.fe.tracks()
+    out.update(track_ids=tr["ids"].astype(np.float64), track_pts=tr["pts"], track_init=tr["init"], track_lifetime=tr["lifetime"].astype(np.float32),
+               track_desc=tr["desc"].astype(np.float32))
+    return out
+
+
+def dump_outputs(d, arrays):
+    """DIR/<name>.npy per array, float32 or float64.  An array that would take the total past DUMP_MAX_BYTES is replaced by a sample of
+    its entries at fixed, seeded flat indices (<name>.npy), with those indices beside it (<name>_index.npy)."""
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if total + a.nbytes > DUMP_MAX_BYTES:
+            n = min(a.size, max(0, (DUMP_MAX_BYTES - total) // (a.itemsize + 8)))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))
+            np.save(os.path.join(d, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]; total += idx.size * 8
+        np.save(os.path.join(d, name + ".npy"), a)
+        total += a.nbytes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -618,6 +667,9 @@ def main():
     ap.add_argument("--loopback-probe", action="store_true", help="with --backend-only at N=1: run the filter a second time through the sharded branch with a one-rank RCCL communicator")
     ap.add_argument("--backend-only", action="store_true", help="the filter alone at configs[4] depth on simulated feature messages (no images): "
                                                                   "the cheap way to time the (sharded) update at 2000 features")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: CPU baseline, device-resident pass, adapter "
+                                                          "schedules and binary, off-grid-stamp pass, configs[4]-depth filter probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step as DIR/<name>.npy")
     args = ap.parse_args()
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -641,18 +693,22 @@ def main():
     K, W = args.steps, args.warmup
     sw = wl["sw_size"]
     n_pre_max = 2 * sw + 40 + 48                         # fill (one clone per message, every other frame) + cycle + 20 bracketed updates
-    n_cpu = 0 if (args.no_cpu_baseline or world > 1) else (args.cpu_baseline_frames or (24 if args.config == "5" else 300))
+    n_cpu = 0 if (not args.full or args.no_cpu_baseline or world > 1) else (args.cpu_baseline_frames or (24 if args.config == "5" else 300))
     period = max(1, int(round(wl["img_rate"] / wl["fcfg"]["pub_frequency"])))      # frames per feature message
-    n_frames = n_pre_max + period + max(W + K, 3 * n_cpu + 8 * 16) + 2
+    # frames are rendered (and cached on disk, one file each) before anything else: the set-up of a run grows with --steps
+    n_frames = n_pre_max + period + (max(W + K, 3 * n_cpu + 8 * 16) if n_cpu else W + K) + 2
     first = int(2.0 * wl["img_rate"])                    # t = 2.0 s: the trajectory is moving
     all_cpus = set(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else set()
     seed_off = 0 if args.sharded else rank               # sharded: every rank sees the same camera
     procs = max(1, min(32, (len(all_cpus) or os.cpu_count() or 1) // max(world, 1)))
-    ts, frames = S.render_frames(first, n_frames, cam=wl["cam"], seed=S.MASTER_SEED + seed_off, img_rate=wl["img_rate"], procs=procs)
-    cpp_leg = rank == 0 and world == 1 and args.config == "A" and not args.sequential and not args.no_adapter_cpp and not args.unaligned
+    # the render workers are forked processes: a multi-threaded BLAS in each of them oversubscribes the cores (same frames, bit for bit)
+    from threadpoolctl import threadpool_limits
+    cpp_leg = args.full and rank == 0 and world == 1 and args.config == "A" and not args.sequential and not args.no_adapter_cpp and not args.unaligned
     n_cpp_timed = 200
-    if cpp_leg:                                           # the C++ adapter binary starts at rest: frames from t = 0 (static start 1.2 s, window fill, 200 timed frames)
-        ts0, frames0 = S.render_frames(0, 30 + n_pre_max + n_cpp_timed, cam=wl["cam"], seed=S.MASTER_SEED, img_rate=wl["img_rate"], procs=procs)
+    with threadpool_limits(1, "blas"):
+        ts, frames = S.render_frames(first, n_frames, cam=wl["cam"], seed=S.MASTER_SEED + seed_off, img_rate=wl["img_rate"], procs=procs)
+        if cpp_leg:                                       # the C++ adapter binary starts at rest: frames from t = 0 (static start 1.2 s, window fill, 200 timed frames)
+            ts0, frames0 = S.render_frames(0, 30 + n_pre_max + n_cpp_timed, cam=wl["cam"], seed=S.MASTER_SEED, img_rate=wl["img_rate"], procs=procs)
     seq = S.imu_only_sequence(S.MASTER_SEED + seed_off, cam=wl["cam"])
     k_lo = max(int(ts[0] * 200) - 4, 0)
     imu_all = seq.imu_array(k_lo, int(ts[-1] * 200) + 40)
@@ -690,6 +746,8 @@ def main():
     run = Run(wl, args, local_rank, imu_all, seq, ts, args.sequential, torch_stream=stream.cuda_stream, shard=shard)
     n_pre, hp = preroll(run, frames, None, n_pre_max, sw, 20, warmup=W, period=period)
     m = timed(run, frames, None, W, K, dist, torch)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pipeline_outputs(run))
     state_dim = run.be.dim; n_clones = len(run.be.clones()); counters = run.be.counters()
     if args.dump_latencies and rank == 0:
         sys.stderr.write("caller us per step: %s\nmessage steps: %s\nelapsed %.1f us, sum of steps %.1f us\n" % (
@@ -701,7 +759,7 @@ def main():
         raise SystemExit("bench.py: the tracker held only %d tracks per message in the timed region (the metric is quoted at ~150): no value printed" % live)
     # ---- pass 2: the same frames already resident in HBM (camera DMA case)
     md = None
-    if not args.no_device_pass:
+    if args.full and not args.no_device_pass:
         d_frames = torch.from_numpy(frames[:n_pre_max + period + W + K + 2]).cuda()
         run2 = Run(wl, args, local_rank, imu_all, seq, ts, args.sequential, torch_stream=stream.cuda_stream, shard=shard)
         while run2.i < n_pre:                            # same pre-roll length as pass 1: the timed frames are the same frames
@@ -715,7 +773,7 @@ def main():
     #      message, processFeatures is deferred (lvk_ekf_process_async), the pose is read (a) right after processFeatures, as
     #      app/larvioMain.cpp:139 does, (b) one frame late.  Same frames, same pre-roll, same K timed steps.
     adapter = None
-    if not args.sequential and not args.no_adapter_pass and shard is None:
+    if args.full and not args.sequential and not args.no_adapter_pass and shard is None:
         adapter = {}
         for getters in ("immediate", "late"):
             run3 = Run(wl, args, local_rank, imu_all, seq, ts, True, torch_stream=stream.cuda_stream, deferred=getters)
@@ -727,7 +785,7 @@ def main():
     # ---- the same pipelined schedule on a camera that is NOT on the IMU grid (every real one): the early erase count is only taken when
     #      no IMU sample lies within 0.5 ms of its bound, otherwise the frame waits for the running update (larvio.cpp:464-512)
     unal = None
-    if not args.unaligned and not args.no_unaligned_pass and not args.sequential and shard is None and world == 1:
+    if args.full and not args.unaligned and not args.no_unaligned_pass and not args.sequential and shard is None and world == 1:
         ts_u, imu_u = S.unaligned_stamps(ts_grid, imu_grid, seed=S.MASTER_SEED + seed_off)
         run4 = Run(wl, args, local_rank, imu_u, seq, ts_u, False, torch_stream=stream.cuda_stream)
         while run4.i < n_pre:
@@ -746,7 +804,7 @@ def main():
     # justifies it"; the headline value above stays the metric's own configuration.
     cpp = adapter_cpp(wl, frames0, ts0, seq, n_cpp_timed, period) if cpp_leg else None
     probe = None
-    if not args.no_shard_probe and args.config == "A" and not args.sequential:
+    if args.full and not args.no_shard_probe and args.config == "A" and not args.sequential:
         probe = shard_probe(rank, world, local_rank)
     if rank == 0:
         win = wl["fcfg"]["patch_size"]

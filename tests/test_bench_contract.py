@@ -1,5 +1,5 @@
-"""The JSON line bench.py prints, as committed under profiles/ from the last MI355X run: every field of the driver's contract is
-there with the right type (bench.py itself needs a GPU; this keeps the contract from drifting unnoticed)."""
+"""The JSON line `bench.py --full` prints, as committed under profiles/ from the last MI355X run: every field of the driver's contract
+is there with the right type (bench.py itself needs a GPU; this keeps the contract from drifting unnoticed)."""
 import glob
 import json
 import os
@@ -71,3 +71,32 @@ def test_every_committed_counter_table_parses():
     assert files
     got = {os.path.basename(f): bench.pmc_lk_traffic(f) for f in files}
     assert got["r6_n_c5_pmc_fetch_size.csv"] > 4e7 and got["r6_i_a_pmc_fetch_size.csv"] > 4e6
+
+
+def test_bench_options_for_a_plain_run_and_its_outputs():
+    """--full gates everything measured beside the headline; --dump-outputs writes float32 / float64 arrays, a seeded sample of any that
+    would take the dump past its cap (same indices on every run)"""
+    import subprocess
+    import sys
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    main = open(os.path.join(ROOT, "bench.py")).read()
+    main = main[main.index("def main()"):]
+    for gate in ("cpp_leg = args.full and", "if args.full and not args.no_device_pass", "if args.full and not args.sequential and not args.no_adapter_pass",
+                 "if args.full and not args.unaligned", "if args.full and not args.no_shard_probe", "n_cpu = 0 if (not args.full"):
+        assert gate in main, gate
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        big = np.arange(bench.DUMP_MAX_BYTES // 8 + 1000, dtype=np.float64)
+        bench.dump_outputs(d, dict(a=np.ones((3, 4), np.float32), b=np.arange(5.0), big=big))
+        assert np.load(os.path.join(d, "a.npy")).dtype == np.float32 and np.array_equal(np.load(os.path.join(d, "b.npy")), np.arange(5.0))
+        s, idx = np.load(os.path.join(d, "big.npy")), np.load(os.path.join(d, "big_index.npy"))
+        assert 0 < s.size < big.size and np.array_equal(s, big[idx.astype(np.int64)])
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64 * 10 ** 6
+        with tempfile.TemporaryDirectory() as d2:
+            bench.dump_outputs(d2, dict(a=np.ones((3, 4), np.float32), b=np.arange(5.0), big=big))
+            assert np.array_equal(np.load(os.path.join(d2, "big_index.npy")), idx)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REF_CONFIG = os.path.join(ROOT, "tests", "golden", "ref_config")        # the configuration files the reference ships, unchanged
 sys.path.insert(0, os.path.join(ROOT, "examples"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 TOOL = os.path.join(ROOT, "examples", "host_tools")
@@ -131,9 +132,7 @@ def test_config_file_refusals(host_tools, tmp_path):
 
 
 def test_reads_the_reference_configuration_unchanged(host_tools):
-    ref = "/root/reference/config/euroc.yaml"
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not present")
+    ref = os.path.join(REF_CONFIG, "euroc.yaml")
     rc, out, err = _run("config", ref)
     assert rc == 0, err
     got = _parse_fields(out)
@@ -376,9 +375,7 @@ def test_python_config_reader_agrees_with_the_cpp_reader(host_tools, tmp_path):
     write_config_yaml(str(p), S.frontend_config(max_features_num=150, pyramid_levels=3), S.backend_config(sw_size=30, calib_imu_instrinsic=1, td=-0.004),
                       output_dir="/tmp/o/")
     paths.append(str(p))
-    for ref in ("/root/reference/config/euroc.yaml", "/root/reference/config/mynteye.yaml"):
-        if os.path.exists(ref):
-            paths.append(ref)
+    paths += [os.path.join(REF_CONFIG, "euroc.yaml"), os.path.join(REF_CONFIG, "mynteye.yaml")]
     for path in paths:
         rc, out, err = _run("config", path); assert rc == 0, err
         got = _parse_fields(out)
