@@ -222,6 +222,31 @@ lvk_status lvk_ekf_update(lvk_context* ctx, double* d_P, int ldp, int n, const d
 lvk_status lvk_dgemm(lvk_context* ctx, int transa, int transb, int M, int N, int K, double alpha, const double* d_A, int lda,
                      const double* d_B, int ldb, double beta, double* d_C, int ldc);
 
+/* The structural covariance operations the filter runs on its device-resident P between updates, one call each (parity tests;
+ * callers that want a single stage).  P is row-major with an explicit leading dimension; Pin and Pout are different buffers.  Each
+ * call waits for its launch.  LVK_ERR_CAPACITY (with a message, nothing launched, the context stays usable) for sizes the kernels'
+ * LDS cannot hold: the propagation's strip above 160 KB, n + 256 doubles above 64 KB for the re-anchoring and the append.
+ *
+ * lvk_ekf_cov_propagate_augment: processModel's covariance part (larvio.cpp:553-571: P_II <- Phi P_II Phi^T + Q, P_IC <- Phi P_IC,
+ *   symmetrised) followed by stateAugmentation (:752-798: the new clone's six rows and columns are copies of rows {0,1,2,6,7,8}),
+ *   in one launch.  Pin is (n_out - 6) x (n_out - 6): the IMU block (L = 22, or 46 with IMU intrinsics), clones up to pose_rows,
+ *   in-state features after them; the new clone is inserted at pose_rows of Pout (n_out x n_out).  h_phi, h_q: L x L, row-major, on
+ *   the host.  For L = 22 Phi's rows 9..21 must be identity rows and Q zero outside its leading 15 x 15 (the composed transition
+ *   always is; the kernel receives only what that leaves): anything else is LVK_ERR_ARG.
+ * lvk_ekf_cov_gather: Pout[a][b] = Pin[idx[a]][idx[b]], a, b < n, 0 <= idx < ldin (clone augmentation without propagation,
+ *   :752-798; clone deletion :2563-2638; deletion of lost in-state features :3311-3327).
+ * lvk_ekf_cov_reanchor: an in-state feature moves to a new anchor (updateFeatureCov_1didp, :3125-3293): row and column fc of the
+ *   n x n P become J P, entry (fc, fc) J P J^T; J (n doubles, host) has at most 64 non-zeros (LVK_ERR_ARG otherwise).
+ * lvk_ekf_cov_append_features: delayed initialisation of nn new 1-D in-state features (:1821-1854).  HH = diag(H2)^-1 H1 (H1: nn x n,
+ *   ldh; H2: nn doubles on the host); rows and columns n..n+nn-1 of P (ld >= n + nn) become -HH P and HH P HH^T + sigma2 / H2^2
+ *   (diagonal); d_dx_new (nn) = -HH dx + r1 / H2.  The old n x n block is not touched. */
+lvk_status lvk_ekf_cov_propagate_augment(lvk_context* ctx, const double* d_Pin, int ldin, double* d_Pout, int ldout, int n_out, int pose_rows,
+                                         int L, const double* h_phi, const double* h_q);
+lvk_status lvk_ekf_cov_gather(lvk_context* ctx, const double* d_Pin, int ldin, double* d_Pout, int ldout, const int* h_idx, int n);
+lvk_status lvk_ekf_cov_reanchor(lvk_context* ctx, double* d_P, int ld, int n, const double* h_J, int fc);
+lvk_status lvk_ekf_cov_append_features(lvk_context* ctx, double* d_P, int ld, int n, int nn, const double* d_H1, int ldh, const double* h_H2,
+                                       const double* d_r1, const double* d_dx, double sigma2, double* d_dx_new);
+
 typedef struct {
     /* names and meaning as LarVio::loadParameters reads them (larvio.cpp:58-311, config/euroc.yaml) */
     int if_fej, estimate_extrin, estimate_td, if_zupt_valid;

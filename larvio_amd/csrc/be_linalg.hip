@@ -858,8 +858,12 @@ lvk_status lvk_cov_propagate_augment(lvk_context* ctx, const double* Pin, int ld
     LVK_LAUNCH_CHECK(ctx);
     return LVK_OK;
 }
+// k_cov_reanchor and k_cov_append_rows hold a row of n doubles in LDS plus at most 2 KB of their own; they never opt in above the
+// 64 KB every kernel may use
+static bool cov_row_fits_lds(int n) { return sizeof(double) * ((size_t)n + 256) <= 64 * 1024; }
 lvk_status lvk_cov_reanchor(lvk_context* ctx, double* P, int ld, int n, const double* d_J, int fc)
 {
+    if (!cov_row_fits_lds(n)) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "covariance dimension %d too large for the re-anchoring kernel's LDS", n);
     hipLaunchKernelGGL(k_cov_reanchor, dim3(1), dim3(256), sizeof(double) * (size_t)n, ctx->stream, P, ld, n, d_J, fc);
     LVK_LAUNCH_CHECK(ctx);
     return LVK_OK;
@@ -868,6 +872,7 @@ lvk_status lvk_cov_append_features(lvk_context* ctx, double* P, int ld, int n, i
                                    const double* dx, double sigma2, double* tmp, double* dx_new)
 {
     if (nn <= 0) return LVK_OK;
+    if (!cov_row_fits_lds(n)) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "covariance dimension %d too large for the feature-append kernel's LDS", n);
     hipLaunchKernelGGL(k_cov_append_rows, dim3((n + 63) / 64 + 1, nn), dim3(256), sizeof(double) * ((size_t)n + 256), ctx->stream, P, ld, n, nn, H1, ldh, H2, tmp, r1, dx, dx_new);
     hipLaunchKernelGGL(k_cov_append_corner, dim3(1), dim3(256), 0, ctx->stream, P, ld, n, nn, H1, ldh, H2, sigma2, (const double*)tmp);
     LVK_LAUNCH_CHECK(ctx);
@@ -909,4 +914,78 @@ extern "C" lvk_status lvk_dgemm(lvk_context* ctx, int transa, int transb, int M,
     else launch_dgemm<true, true>(s, M, N, K, d_A, lda, d_B, ldb, d_C, ldc, alpha, beta, 0.0);
     LVK_LAUNCH_CHECK(ctx);
     return LVK_OK;
+}
+
+// ------------------------------------------------------------------------- stage-level entries of the structural covariance operations
+// (C ABI, include/lvk_c.h): the launchers above on caller-owned device matrices, host-side checks of what each kernel assumes, one
+// wait per call.  Small host tables go to scratch slot 13, the append's nn x n intermediate to slot 14.
+static lvk_status cov_stage_wait(lvk_context* ctx, lvk_status st)
+{
+    if (st != LVK_OK) return st;
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LVK_OK;
+}
+static const void* cov_stage_upload(lvk_context* ctx, const void* h, size_t bytes)
+{
+    void* d = lvk_ctx_scratch(ctx, 13, bytes);
+    if (!d || hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return nullptr;
+    return d;
+}
+
+extern "C" lvk_status lvk_ekf_cov_propagate_augment(lvk_context* ctx, const double* d_Pin, int ldin, double* d_Pout, int ldout, int n_out, int pose_rows,
+                                                    int L, const double* h_phi, const double* h_q)
+{
+    if (!ctx || !d_Pin || !d_Pout || d_Pin == d_Pout || !h_phi || !h_q || (L != 22 && L != 46) || pose_rows < L || n_out < pose_rows + 6 || ldin < n_out - 6 || ldout < n_out)
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_cov_propagate_augment: bad argument");
+    if (L == 22) {          // what the by-value path encodes (k_cov_propagate_augment<22, true>): rows 9.. of Phi identity, Q zero outside 15 x 15
+        for (int i = 9; i < 22; ++i)
+            for (int k = 0; k < 22; ++k)
+                if (h_phi[i * 22 + k] != (i == k ? 1.0 : 0.0))
+                    return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_cov_propagate_augment: Phi(%d, %d) = %g, rows 9..21 must be identity rows for L = 22", i, k, h_phi[i * 22 + k]);
+        for (int i = 0; i < 22; ++i)
+            for (int j = 0; j < 22; ++j)
+                if ((i >= 15 || j >= 15) && h_q[i * 22 + j] != 0.0)
+                    return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_cov_propagate_augment: Q(%d, %d) = %g, Q must be zero outside its leading 15 x 15 for L = 22", i, j, h_q[i * 22 + j]);
+        return cov_stage_wait(ctx, lvk_cov_propagate_augment(ctx, d_Pin, ldin, d_Pout, ldout, n_out, pose_rows, L, h_phi, h_q, nullptr));
+    }
+    double* d_phiq = (double*)lvk_ctx_scratch(ctx, 13, sizeof(double) * 2 * L * L);
+    if (!d_phiq) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
+    LVK_HIP(ctx, hipMemcpyAsync(d_phiq, h_phi, sizeof(double) * L * L, hipMemcpyHostToDevice, ctx->stream));
+    LVK_HIP(ctx, hipMemcpyAsync(d_phiq + L * L, h_q, sizeof(double) * L * L, hipMemcpyHostToDevice, ctx->stream));
+    return cov_stage_wait(ctx, lvk_cov_propagate_augment(ctx, d_Pin, ldin, d_Pout, ldout, n_out, pose_rows, L, h_phi, h_q, d_phiq));
+}
+
+extern "C" lvk_status lvk_ekf_cov_gather(lvk_context* ctx, const double* d_Pin, int ldin, double* d_Pout, int ldout, const int* h_idx, int n)
+{
+    if (!ctx || !d_Pin || !d_Pout || d_Pin == d_Pout || !h_idx || n <= 0 || ldout < n || ldin <= 0)
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_cov_gather: bad argument");
+    for (int a = 0; a < n; ++a)
+        if (h_idx[a] < 0 || h_idx[a] >= ldin) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_cov_gather: idx[%d] = %d outside [0, ldin)", a, h_idx[a]);
+    const int* d_idx = (const int*)cov_stage_upload(ctx, h_idx, sizeof(int) * (size_t)n);
+    if (!d_idx) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_ekf_cov_gather: index upload failed");
+    return cov_stage_wait(ctx, lvk_cov_gather(ctx, d_Pin, ldin, d_Pout, ldout, d_idx, n));
+}
+
+extern "C" lvk_status lvk_ekf_cov_reanchor(lvk_context* ctx, double* d_P, int ld, int n, const double* h_J, int fc)
+{
+    if (!ctx || !d_P || !h_J || n <= 0 || ld < n || fc < 0 || fc >= n)
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_cov_reanchor: bad argument");
+    int nnz = 0;
+    for (int k = 0; k < n; ++k) nnz += h_J[k] != 0.0;
+    if (nnz > 64) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_cov_reanchor: J has %d non-zeros, the kernel holds at most 64", nnz);
+    const double* d_J = (const double*)cov_stage_upload(ctx, h_J, sizeof(double) * (size_t)n);
+    if (!d_J) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_ekf_cov_reanchor: upload of J failed");
+    return cov_stage_wait(ctx, lvk_cov_reanchor(ctx, d_P, ld, n, d_J, fc));
+}
+
+extern "C" lvk_status lvk_ekf_cov_append_features(lvk_context* ctx, double* d_P, int ld, int n, int nn, const double* d_H1, int ldh, const double* h_H2,
+                                                  const double* d_r1, const double* d_dx, double sigma2, double* d_dx_new)
+{
+    if (!ctx || !d_P || n <= 0 || nn < 0 || ld < n + nn || (nn > 0 && (!d_H1 || !h_H2 || !d_r1 || !d_dx || !d_dx_new || ldh < n)))
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_cov_append_features: bad argument");
+    if (nn == 0) return LVK_OK;
+    const double* d_H2 = (const double*)cov_stage_upload(ctx, h_H2, sizeof(double) * (size_t)nn);
+    double* tmp = (double*)lvk_ctx_scratch(ctx, 14, sizeof(double) * (size_t)nn * n);
+    if (!d_H2 || !tmp) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_ekf_cov_append_features: scratch allocation failed");
+    return cov_stage_wait(ctx, lvk_cov_append_features(ctx, d_P, ld, n, nn, d_H1, ldh, d_H2, d_r1, d_dx, sigma2, tmp, d_dx_new));
 }

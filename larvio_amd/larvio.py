@@ -51,6 +51,10 @@ def _L():
         L.lvk_ekf_compress_qr_groups.argtypes = [vp, vp, i, i, i, vp, i, vp, vp, vp, pi]; L.lvk_ekf_compress_qr_groups.restype = i
         L.lvk_ekf_qr_plan.argtypes = [i, i, vp, vp, vp, vp, i, vp, i, vp, vp, i, pi]; L.lvk_ekf_qr_plan.restype = i
         L.lvk_dgemm.argtypes = [vp, i, i, i, i, i, d, vp, i, vp, i, d, vp, i]; L.lvk_dgemm.restype = i
+        L.lvk_ekf_cov_propagate_augment.argtypes = [vp, vp, i, vp, i, i, i, i, vp, vp]; L.lvk_ekf_cov_propagate_augment.restype = i
+        L.lvk_ekf_cov_gather.argtypes = [vp, vp, i, vp, i, vp, i]; L.lvk_ekf_cov_gather.restype = i
+        L.lvk_ekf_cov_reanchor.argtypes = [vp, vp, i, i, vp, i]; L.lvk_ekf_cov_reanchor.restype = i
+        L.lvk_ekf_cov_append_features.argtypes = [vp, vp, i, i, i, vp, i, vp, vp, vp, d, vp]; L.lvk_ekf_cov_append_features.restype = i
         L.lvk_ekf_create.argtypes = [vp, C.POINTER(EkfConfig), C.POINTER(vp)]; L.lvk_ekf_create.restype = i
         L.lvk_ekf_destroy.argtypes = [vp]; L.lvk_ekf_destroy.restype = None
         L.lvk_ekf_process.argtypes = [vp, d, vp, i, vp, i, pi, pi]; L.lvk_ekf_process.restype = i
@@ -107,21 +111,73 @@ def gate_and_stack(ctx, clones, feats, clone_rank, obs, obs_vel, P, sigma2, if_f
     return H[:rows.value].copy(), r[:rows.value].copy(), gamma, acc.astype(bool)
 
 
-def dgemm(ctx, A, B, transa=False, transb=False, alpha=1.0, beta=0.0, Cin=None):
+def _padded(X, ld, rows=None):
+    """X (r x c) in a buffer of `rows` (>= r) rows of ld (>= c) doubles; everything outside X is NaN, as a padded buffer of the
+    filter may hold anything there"""
+    X = np.asarray(X, np.float64)
+    buf = np.full((X.shape[0] if rows is None else rows, ld), np.nan)
+    buf[:X.shape[0], :X.shape[1]] = X
+    return buf
+
+
+def dgemm(ctx, A, B, transa=False, transb=False, alpha=1.0, beta=0.0, Cin=None, ld=None):
+    """C = alpha op(A) op(B) + beta Cin.  ld: A, B and C all stored with that leading dimension (NaN padding, as the filter's
+    buffers); the whole C buffer (M x ld) is then returned, padding included."""
     A = np.ascontiguousarray(A, np.float64); B = np.ascontiguousarray(B, np.float64)
     M = A.shape[1] if transa else A.shape[0]; K = A.shape[0] if transa else A.shape[1]; N = B.shape[0] if transb else B.shape[1]
     Cm = np.zeros((M, N)) if Cin is None else np.array(Cin, np.float64, order="C")
+    if ld is not None:
+        A, B, Cm = _padded(A, ld), _padded(B, ld), _padded(Cm, ld)
     dA, dB, dC = ctx.to_device(A), ctx.to_device(B), ctx.to_device(Cm)
-    ctx.check(_L().lvk_dgemm(ctx.h, int(transa), int(transb), M, N, K, alpha, _p(dA), A.shape[1], _p(dB), B.shape[1], beta, _p(dC), N))
-    return ctx.to_host(dC, np.float64, (M, N))
+    ctx.check(_L().lvk_dgemm(ctx.h, int(transa), int(transb), M, N, K, alpha, _p(dA), A.shape[1], _p(dB), B.shape[1], beta, _p(dC), Cm.shape[1]))
+    return ctx.to_host(dC, np.float64, Cm.shape)
 
 
-def ekf_update(ctx, P, H, r, sigma2):
+def ekf_update(ctx, P, H, r, sigma2, ld=None):
+    """ld: P and H stored with that leading dimension (NaN padding, as the filter's buffers); the whole P buffer (n x ld) is then
+    returned, padding included."""
     P = np.array(P, np.float64, order="C"); H = np.ascontiguousarray(H, np.float64); r = np.ascontiguousarray(r, np.float64)
     n, m = P.shape[0], H.shape[0]
+    if ld is not None:
+        P, H = _padded(P, ld), _padded(H, ld)
     dP, dH, dr, ddx = ctx.to_device(P), ctx.to_device(H), ctx.to_device(r), ctx.alloc(8 * n)
-    ctx.check(_L().lvk_ekf_update(ctx.h, _p(dP), n, n, _p(dH), H.shape[1], m, _p(dr), sigma2, _p(ddx)))
-    return ctx.to_host(ddx, np.float64, (n,)), ctx.to_host(dP, np.float64, (n, n))
+    ctx.check(_L().lvk_ekf_update(ctx.h, _p(dP), P.shape[1], n, _p(dH), H.shape[1], m, _p(dr), sigma2, _p(ddx)))
+    return ctx.to_host(ddx, np.float64, (n,)), ctx.to_host(dP, np.float64, P.shape)
+
+
+# The structural covariance operations (lvk_ekf_cov_*).  Matrices are passed as whole row-major buffers: the leading dimension is
+# the buffer's row length, and the output buffer's previous contents (padding, rows the operation must not touch) go to the device
+# as they are.  Each returns the whole output buffer after the call.
+def cov_propagate_augment(ctx, Pin, Pout, n_out, pose_rows, phi, q):
+    Pin = np.ascontiguousarray(Pin, np.float64); Pout = np.ascontiguousarray(Pout, np.float64)
+    phi = np.ascontiguousarray(phi, np.float64); q = np.ascontiguousarray(q, np.float64)
+    dI, dO = ctx.to_device(Pin), ctx.to_device(Pout)
+    ctx.check(_L().lvk_ekf_cov_propagate_augment(ctx.h, _p(dI), Pin.shape[1], _p(dO), Pout.shape[1], int(n_out), int(pose_rows), phi.shape[0], _p(phi), _p(q)))
+    return ctx.to_host(dO, np.float64, Pout.shape)
+
+
+def cov_gather(ctx, Pin, Pout, idx):
+    Pin = np.ascontiguousarray(Pin, np.float64); Pout = np.ascontiguousarray(Pout, np.float64); idx = np.ascontiguousarray(idx, np.int32)
+    dI, dO = ctx.to_device(Pin), ctx.to_device(Pout)
+    ctx.check(_L().lvk_ekf_cov_gather(ctx.h, _p(dI), Pin.shape[1], _p(dO), Pout.shape[1], _p(idx), len(idx)))
+    return ctx.to_host(dO, np.float64, Pout.shape)
+
+
+def cov_reanchor(ctx, P, n, J, fc):
+    P = np.ascontiguousarray(P, np.float64); J = np.ascontiguousarray(J, np.float64)
+    dP = ctx.to_device(P)
+    ctx.check(_L().lvk_ekf_cov_reanchor(ctx.h, _p(dP), P.shape[1], int(n), _p(J), int(fc)))
+    return ctx.to_host(dP, np.float64, P.shape)
+
+
+def cov_append_features(ctx, P, n, H1, H2, r1, dx, sigma2):
+    """-> (P buffer, dx_new).  H1: nn x ldh buffer; H2, r1: nn; dx: n."""
+    P = np.ascontiguousarray(P, np.float64); H1 = np.ascontiguousarray(H1, np.float64)
+    H2 = np.ascontiguousarray(H2, np.float64); r1 = np.ascontiguousarray(r1, np.float64); dx = np.ascontiguousarray(dx, np.float64)
+    nn = len(H2)
+    dP, dH1, dr1, ddx, dxn = ctx.to_device(P), ctx.to_device(H1), ctx.to_device(r1), ctx.to_device(dx), ctx.alloc(8 * max(nn, 1))
+    ctx.check(_L().lvk_ekf_cov_append_features(ctx.h, _p(dP), P.shape[1], int(n), nn, _p(dH1), H1.shape[1], _p(H2), _p(dr1), _p(ddx), float(sigma2), _p(dxn)))
+    return ctx.to_host(dP, np.float64, P.shape), ctx.to_host(dxn, np.float64, (nn,))
 
 
 def compress_qr(ctx, H, r):

@@ -3,6 +3,7 @@ and the device-resident LarVio against the oracle's, update by update (state and
 the tolerance BASELINE.json's north_star states)."""
 import numpy as np
 import pytest
+from tests.cov_compare import corr_error, CORR
 
 pytestmark = pytest.mark.gpu
 REL = 1e-5
@@ -47,6 +48,39 @@ def test_ekf_update_matches_oracle(gpu_ctx, N, m):
     assert _rel(P_g, P_o) < 1e-10
     assert np.array_equal(P_g, P_g.T)                              # P - W^T W is symmetric by construction
     assert np.linalg.eigvalsh(P_g).min() > -1e-12
+
+
+def _filter_ld(n):
+    return ((n + 15) & ~15) + 8                  # the filter's padded leading dimension (backend.hip, lvk_ekf_create)
+
+
+@pytest.mark.parametrize("shape", [(232, 262, 232), (17, 5, 33), (33, 47, 193), (216, 217, 110)])
+@pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, False)])
+def test_dgemm_mfma_f64_padded_ld(gpu_ctx, shape, ta, tb):
+    """the filter's strided operands (ld > every dimension, NaN in the padding): the same bits as the packed call, no padding read
+    (NaN would reach C) and none written.  The summation order depends on k only, never on ld or alignment."""
+    from larvio_amd import larvio as lv
+    M, N, K = shape
+    rng = np.random.default_rng(M * 1000 + N + 1)
+    A = rng.normal(0, 1, (K, M) if ta else (M, K)); B = rng.normal(0, 1, (N, K) if tb else (K, N)); C0 = rng.normal(0, 1, (M, N))
+    ld = _filter_ld(max(M, N, K))
+    packed = lv.dgemm(gpu_ctx, A, B, ta, tb, alpha=0.7, beta=-0.3, Cin=C0)
+    padded = lv.dgemm(gpu_ctx, A, B, ta, tb, alpha=0.7, beta=-0.3, Cin=C0, ld=ld)
+    assert np.array_equal(padded[:, :N].view(np.uint64), packed.view(np.uint64))
+    assert np.isnan(padded[:, N:]).all() and np.array_equal(padded[:, N:].view(np.uint64), np.full((M, ld - N), np.nan).view(np.uint64))
+
+
+@pytest.mark.parametrize("N,m", [(232, 262), (118, 40), (46, 9), (250, 1), (470, 485)])
+def test_ekf_update_padded_ld(gpu_ctx, N, m):
+    """lvk_ekf_update as the filter calls it (P and H with ld > n, NaN padding): bit-identical to the packed call, padding untouched"""
+    from larvio_amd import larvio as lv
+    P, H, r = _update_problem(N + m, N, m)
+    ld = _filter_ld(N)
+    dx_p, P_p = lv.ekf_update(gpu_ctx, P, H, r, 0.008 ** 2)
+    dx_s, buf = lv.ekf_update(gpu_ctx, P, H, r, 0.008 ** 2, ld=ld)
+    assert np.array_equal(dx_s.view(np.uint64), dx_p.view(np.uint64))
+    assert np.array_equal(buf[:, :N].view(np.uint64), P_p.view(np.uint64))
+    assert np.array_equal(buf[:, N:].view(np.uint64), np.full((N, ld - N), np.nan).view(np.uint64))
 
 
 @pytest.mark.parametrize("N,m,bad", [(120, 40, 7), (232, 150, 149), (232, 200, 170), (232, 330, 5)])
@@ -175,6 +209,8 @@ def _run_pair(gpu_ctx, msgs, imu_all, seq, cfg, init_from_gt=True, init_args=Non
     if init_args is not None:
         ora.set_state(*init_args); gpu.set_state(*init_args); inited = True
     n_upd, worst_x, worst_P = 0, 0.0, 0.0
+    worst_c, worst_c_at = 0.0, ""
+    leg = 46 if cfg.get("calib_imu_instrinsic") else 22
     for ts, msg in msgs:
         bo = buf_o[:int(np.searchsorted(buf_o["t"], ts + 0.05))]
         bg = buf_g[:int(np.searchsorted(buf_g["t"], ts + 0.05))]
@@ -202,6 +238,10 @@ def _run_pair(gpu_ctx, msgs, imu_all, seq, cfg, init_from_gt=True, init_args=Non
         assert np.array_equal(Pi, Pg[:9, :9])            # ... and bit for bit the covariance's own leading block
         worst_P = max(worst_P, _rel(Pg, Po))
         co, cg = ora.clones(), gpu.clones()
+        e_c, at = corr_error(Pg, Po, leg, len(co["id"]))
+        if e_c > worst_c:
+            worst_c, worst_c_at = e_c, f"update {n_upd}: {at}"
+        assert np.isfinite(e_c) and worst_c < CORR, (n_upd, e_c, at, worst_c, worst_c_at)
         assert np.array_equal(cg["id"], co["id"])
         assert _rel(cg["p"], co["p"]) < REL and _rel(cg["q"], co["q"]) < REL
         io, do_, po = ora.features(); ig, dg, pg = gpu.features()
@@ -214,6 +254,7 @@ def _run_pair(gpu_ctx, msgs, imu_all, seq, cfg, init_from_gt=True, init_args=Non
     cg, co = gpu.counters(), ora.counters()
     for k in ("hybrid", "msckf", "zupt", "gated_in", "gated_out", "map"):
         assert cg[k] == co[k], (k, cg, co)
+    print(f"correlation-scaled P error: worst {worst_c:.3e} ({worst_c_at or 'Pg == Po at every update'})")
     gpu.close()
     return n_upd, worst_x, worst_P, co, ora
 

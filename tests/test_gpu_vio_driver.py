@@ -4,6 +4,8 @@ Front-end message identity is implied: any differing track id / coordinate would
 import numpy as np
 import pytest
 
+from tests.cov_compare import block_name, corr_error, CORR
+
 pytestmark = pytest.mark.gpu
 REL = 1e-5
 
@@ -38,7 +40,7 @@ def test_driver_loop_matches_oracle(gpu_ctx, device_frames):
     d_frames = None
     if device_frames:
         d_frames = gpu_ctx.to_device(np.stack([f[1] for f in frames]))      # frames already in HBM (camera DMA case)
-    lo = 0; n_upd = 0; worst = 0.0
+    lo = 0; n_upd = 0; worst = 0.0; worst_c, worst_c_at = 0.0, ""
     for i, (t, img) in enumerate(frames):
         hi = drv.visible_end(t)
         if i == 1:
@@ -73,13 +75,16 @@ def test_driver_loop_matches_oracle(gpu_ctx, device_frames):
             ij = np.unravel_index(np.argmax(np.abs(Pg - Po)), Po.shape); leg = 46 if bcfg.get("calib_imu_instrinsic") else 22
             nc = len(obe.clones()["id"])
             def blk(x):
-                if x < leg: return ("th", "v", "p", "bg", "ba", "th_ext", "t_ext", "td/imx")[min(x // 3, 7)]
-                return f"clone{(x - leg) // 6}.{'th' if (x - leg) % 6 < 3 else 'p'}" if x < leg + 6 * nc else f"feat{x - leg - 6 * nc}"
+                return block_name(x, leg, nc)
             worst = e_p; _WORST_AT.update(update=n_upd, frame=i, what="P", detail=f"entry ({blk(ij[0])},{blk(ij[1])}) = {Po[ij]:.3e} differs by {abs(Pg[ij] - Po[ij]):.3e}; max|P| = {np.abs(Po).max():.3e} "
                                           f"at {blk(np.unravel_index(np.argmax(np.abs(Po)), Po.shape)[0])}; rows of the last update {be.counters().get('last_rows')}")
         assert np.array_equal(be.clones()["id"], obe.clones()["id"])
         assert np.array_equal(be.features()[0], obe.features()[0])
         assert worst < REL, (i, worst)
+        e_c, at = corr_error(Pg, Po, 46 if bcfg.get("calib_imu_instrinsic") else 22, len(obe.clones()["id"]))
+        if e_c > worst_c:
+            worst_c, worst_c_at = e_c, f"update {n_upd}, frame {i}: {at}"
+        assert np.isfinite(e_c) and worst_c < CORR, (i, e_c, at, worst_c, worst_c_at)
     assert n_upd >= 25
     tg, to = fe.tracks(), ofe.tracks()
     assert np.array_equal(tg["ids"], to["ids"]) and np.array_equal(tg["pts"], to["pts"])
@@ -87,6 +92,7 @@ def test_driver_loop_matches_oracle(gpu_ctx, device_frames):
     for k in ("hybrid", "msckf", "gated_in", "gated_out", "map"):
         assert cg[k] == co[k]
     print("driver loop parity: updates", n_upd, "worst rel", worst)
+    print(f"correlation-scaled P error: worst {worst_c:.3e} ({worst_c_at or 'Pg == Po at every update'})")
 
 
 def _disturb(frames):
@@ -255,7 +261,7 @@ def _driver_pair(gpu_ctx, cam, first, count, fcfg_over, bcfg_over, init_from_gt,
     ofe = lvo.Frontend(fcfg); obe = lvo_be.Ekf(bcfg)
     lvo.set_threads(oracle_threads)                # same bits for any count (tests/test_oracle_frontend.py); only the wall time changes
     drv = VioDriver(fe, be, imu_all)
-    lo = 0; n_upd = 0; worst = 0.0
+    lo = 0; n_upd = 0; worst = 0.0; worst_c, worst_c_at = 0.0, ""
     for i, (t, img) in enumerate(frames):
         hi = drv.visible_end(t)
         if init_from_gt and i == 1:
@@ -286,13 +292,17 @@ def _driver_pair(gpu_ctx, cam, first, count, fcfg_over, bcfg_over, init_from_gt,
             ij = np.unravel_index(np.argmax(np.abs(Pg - Po)), Po.shape); leg = 46 if bcfg.get("calib_imu_instrinsic") else 22
             nc = len(obe.clones()["id"])
             def blk(x):
-                if x < leg: return ("th", "v", "p", "bg", "ba", "th_ext", "t_ext", "td/imx")[min(x // 3, 7)]
-                return f"clone{(x - leg) // 6}.{'th' if (x - leg) % 6 < 3 else 'p'}" if x < leg + 6 * nc else f"feat{x - leg - 6 * nc}"
+                return block_name(x, leg, nc)
             worst = e_p; _WORST_AT.update(update=n_upd, frame=i, what="P", detail=f"entry ({blk(ij[0])},{blk(ij[1])}) = {Po[ij]:.3e} differs by {abs(Pg[ij] - Po[ij]):.3e}; max|P| = {np.abs(Po).max():.3e} "
                                           f"at {blk(np.unravel_index(np.argmax(np.abs(Po)), Po.shape)[0])}; rows of the last update {be.counters().get('last_rows')}")
         assert np.array_equal(be.clones()["id"], obe.clones()["id"]) and np.array_equal(be.features()[0], obe.features()[0])
         assert worst < REL, (i, worst)
+        e_c, at = corr_error(Pg, Po, 46 if bcfg.get("calib_imu_instrinsic") else 22, len(obe.clones()["id"]))
+        if e_c > worst_c:
+            worst_c, worst_c_at = e_c, f"update {n_upd}, frame {i}: {at}"
+        assert np.isfinite(e_c) and worst_c < CORR, (i, e_c, at, worst_c, worst_c_at)
     assert n_upd >= min_updates
+    print(f"correlation-scaled P error: worst {worst_c:.3e} ({worst_c_at or 'Pg == Po at every update'})")
     tg, to = fe.tracks(), ofe.tracks()
     assert np.array_equal(tg["ids"], to["ids"]) and np.array_equal(tg["pts"], to["pts"])
     co, cg = obe.counters(), be.counters()
