@@ -396,6 +396,42 @@ lvk_status lvk_ekf_gate_and_stack(lvk_context* ctx, const lvk_clone* h_clones, i
                                   int if_fej, int estimate_td, double sigma2, double* h_H, double* h_r, int rows_cap, int* rows_out,
                                   double* h_gamma, int* h_accept);
 
+/* lvk_ekf_feature_rows: the per-feature row stage of the filter's update, launched as the filter launches it (the triangulation of
+ * tri_pending jobs, the feature-row kernel, the stacking kernel), for a batch of jobs of the three kinds the filter builds:
+ *   LVK_FJ_MSCKF        featureJacobian_msckf (larvio.cpp:859-981): 2M rows, null-space projected, rows 3.. are the output;
+ *   LVK_FJ_EKF_NEW      a new 1-D inverse-depth feature (:1117-1244), M observing clones other than the anchor: projected on the
+ *                       left null space of its feature column, row 0 is the range row (h2 = its feature entry), rows 1.. the output;
+ *   LVK_FJ_EKF_TRACKED  a tracked in-state feature: its 2M raw rows.
+ * Clone ranks, z and zv (2 doubles each) are indexed by obs_off + k; P is N x N with leading dimension ldp.  gate > 0 gates the job
+ * with dof = gate against lvk_chi2_005(dof) (gatingTest, :1865-1880); gate 0 accepts it.  tri_pending (MSCKF only): the landmark is
+ * triangulated first from the camera poses h_cams[obs_off + k] (lvk_triangulate with use_position 0) and read by the row kernel
+ * from the triangulation's result slot; a failed triangulation rejects the job.
+ * Outputs: h_res[j]; the compact block [G | r] of every job (2M x (c + 1), row-major, jobs one after the other in h_blocks) and its
+ * column map (c ints per job in h_ccols); and the dense rows: every MSCKF and EKF_TRACKED job owns rows (2M - 3, respectively 2M)
+ * of h_H (ldh >= N, h_rows rows) and h_r in job order (EKF_NEW rows never reach it, as in the filter: their feature column is a new
+ * state).  h_rows must hold every candidate row (the sum over those jobs), whichever the mode.  h_H and h_r are read first and only
+ * the written rows change.  Without LVK_FR_DIRECT or LVK_FR_DEVICE_ZERO the host reads
+ * the gate back and stacks only accepted jobs' rows, one after the other; otherwise a rejected job's rows are zero rows with a zero
+ * residual.
+ * *rows_out = dense rows written.  LVK_ERR_ARG / LVK_ERR_CAPACITY for input the kernels do not handle; nothing is launched then. */
+enum { LVK_FJ_MSCKF = 0, LVK_FJ_EKF_NEW = 1, LVK_FJ_EKF_TRACKED = 2 };
+enum {
+    LVK_FR_GENERAL = 1,      /* force the general kernel (otherwise the filter's routing picks it) */
+    LVK_FR_STRIDE = 2,       /* observations in fixed-stride slots (stride = the batch's largest M), as the filter stages short tracks */
+    LVK_FR_DIRECT = 4,       /* the row kernel writes the dense rows itself (no stacking launch) */
+    LVK_FR_DEVICE_ZERO = 8   /* the stacking kernel zeroes rejected jobs' rows on the device */
+};
+typedef struct {
+    int type, n_obs, obs_off, anchor_rank, fcol, gate, tri_pending, pad;
+    double p_w[3], p_fej[3], inv_depth, obs_anchor[3];
+} lvk_feature_job;
+typedef struct { double gamma, h2; int rows, first_row, c, accept; } lvk_feature_result;
+lvk_status lvk_ekf_feature_rows(lvk_context* ctx, const lvk_clone* h_clones, int n_clones, const lvk_feature_job* h_jobs, int n_jobs,
+                                const int* h_clone_rank, const double* h_obs, const double* h_obs_vel, const lvk_cam_pose* h_cams, int n_obs,
+                                const double* h_P, int N, int ldp, int leg_dim, int if_fej, int estimate_td, double sigma2, int mode,
+                                lvk_feature_result* h_res, double* h_blocks, int* h_ccols, double* h_H, int ldh, int h_rows, double* h_r,
+                                int* rows_out);
+
 /* ==================================================================== the driver step
  * One camera frame through both halves, exactly the two calls the reference's drivers make per image
  * (app/larvioMain.cpp:104-116: processImage, then processFeatures when it returned true), with the driver's IMU buffer

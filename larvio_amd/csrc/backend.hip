@@ -49,6 +49,7 @@ lvk_status lvk_launch_feature_rows(lvk_context* ctx, const FeatJob* d_jobs, int 
                                    const double* d_z, const double* d_zv, const double* d_P, int ldp, FilterFlags fl, double* d_staging, int* d_ccols, FeatResult* d_out, FeatResult* d_out_host,
                                    double* d_Hout, int ldh, int ncols_out, double* d_rout, int obs_stride, int n_clones, const TriResult* d_tri);
 lvk_status lvk_launch_stack_rows(lvk_context* ctx, const FeatResult* d_fout, const StackRow* d_map, int n_rows, const double* d_staging, const int* d_ccols, double* d_H, int ldh, int ncols, double* d_r);
+int lvk_feature_rows_route(int max_rows, int gate_rows_max);
 lvk_status lvk_qr_compress_dev(lvk_context* ctx, double* d_H, int ldh, int rows, int cols, double* d_r, int* rows_out);
 
 double lvk_chi2_005(int dof);
@@ -1069,10 +1070,7 @@ static lvk_status launch_feature_rows(lvk_ekf* e, std::vector<RowJob>& jobs, con
         if (j.want_gate) gate_max = std::max(gate_max, 2 * M - (j.type == JOB_MSCKF ? 3 : j.type == JOB_EKF_NEW ? 1 : 0));
         hj[i] = d; j.hdev = &hj[i];
     }
-    // the SMALL row kernel's gate holds [S r; r^T 0] in ONE 16x16 MFMA tile (be_feature.hip): at most 15 gated rows.  MSCKF jobs of up
-    // to 8 observations (2M - 3 <= 13) and the one-observation jobs of tracked in-state features are; a batch with anything else
-    // takes the general kernel
-    if (gate_max > 15) max_rows = std::max(max_rows, 18);
+    max_rows = lvk_feature_rows_route(max_rows, gate_max);
     if (stage > e->staging_cap || ccols > e->ccols_cap) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "staging buffer too small (%zu doubles needed)", stage);
     FilterFlags fl; fl.leg_dim = LEG; fl.if_fej = e->if_fej ? 1 : 0; fl.estimate_td = e->cfg.estimate_td; fl.pad = 0; fl.sigma2 = e->sigma2;
     const FeatJob* d_j = dev(e, hj); const int* d_r = dev(e, hr); const double* d_z = dev(e, hz); const double* d_v = dev(e, hv);

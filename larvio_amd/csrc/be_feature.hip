@@ -452,8 +452,7 @@ __global__ void __launch_bounds__(FR_THREADS) k_feature_rows(const FeatJob* __re
     // on the update's dependent chain) is not needed.  Same values as k_stack_rows writes.
     if (job.dst_row1 > 0 && H_out) {
         const int d0 = job.dst_row1 - 1;
-        const int src0 = (job.type == JOB_EKF_TRACKED) ? 0 : first_row;
-        const int nout = (job.type == JOB_EKF_TRACKED) ? 2 : k_rows;
+        const int src0 = first_row, nout = k_rows;                  // a tracked job's 2M raw rows (first_row 0), a projected job's output rows
         for (int e = t; e < nout * ncols_out; e += FR_THREADS) { const int a = e / ncols_out, j = e - a * ncols_out; H_out[(size_t)(d0 + a) * ldh + j] = 0.; }
         if (t < nout) r_out[d0 + t] = accept ? rr[src0 + t] : 0.;
         __syncthreads();
@@ -485,6 +484,12 @@ __global__ void __launch_bounds__(128) k_stack_rows(const StackRow* __restrict__
 }
 
 // ========================================================================= host launchers (internal)
+// The max_rows a batch is launched with.  The SMALL row kernel's gate holds [S r; r^T 0] in ONE 16x16 MFMA tile: at most 15 gated
+// rows.  MSCKF jobs of up to 8 observations (2M - 3 <= 13), new in-state features of up to 8 (2M - 1 <= 15) and the one-observation
+// jobs of tracked in-state features are; a batch with anything else (gate_rows_max > 15) takes the general kernel.  Every caller of
+// lvk_launch_feature_rows passes its max_rows through this.
+int lvk_feature_rows_route(int max_rows, int gate_rows_max) { return gate_rows_max > 15 ? std::max(max_rows, 18) : max_rows; }
+
 lvk_status lvk_launch_triangulate(lvk_context* ctx, const TriJob* d_jobs, int n_jobs, const CamPose* d_cams, const int* d_rank, const double* d_z,
                                   TriResult* d_out, TriResult* d_out_dev)
 {
@@ -640,6 +645,189 @@ extern "C" lvk_status lvk_ekf_gate_and_stack(lvk_context* ctx, const lvk_clone* 
     if (st != LVK_OK) return st;
     LVK_HIP(ctx, hipMemcpy2DAsync(h_H, sizeof(double) * N, d_out + oH, sizeof(double) * ld, sizeof(double) * N, rows, hipMemcpyDeviceToHost, ctx->stream));
     LVK_HIP(ctx, hipMemcpyAsync(h_r, d_out + o_r, sizeof(double) * rows, hipMemcpyDeviceToHost, ctx->stream));
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LVK_OK;
+}
+
+extern "C" lvk_status lvk_ekf_feature_rows(lvk_context* ctx, const lvk_clone* h_clones, int n_clones, const lvk_feature_job* h_jobs, int n_jobs,
+                                           const int* h_clone_rank, const double* h_obs, const double* h_obs_vel, const lvk_cam_pose* h_cams, int n_obs,
+                                           const double* h_P, int N, int ldp, int leg_dim, int if_fej, int estimate_td, double sigma2, int mode,
+                                           lvk_feature_result* h_res, double* h_blocks, int* h_ccols, double* h_H, int ldh, int h_rows, double* h_r,
+                                           int* rows_out)
+{
+    static_assert(sizeof(lvk_feature_result) == sizeof(FeatResult), "lvk_feature_result is FeatResult");
+    if (!ctx || !h_clones || n_clones <= 0 || !h_jobs || n_jobs <= 0 || !h_clone_rank || !h_obs || !h_obs_vel || n_obs <= 0 || !h_P || !h_res ||
+        !h_blocks || !h_ccols || !h_H || !h_r || !rows_out || N < 22 || ldp < N || ldh < N || h_rows < 0)
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_feature_rows: bad argument");
+    if (leg_dim != 22 && leg_dim != 46) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_feature_rows: leg_dim %d (22 or 46)", leg_dim);
+    if (N < leg_dim + 6 * n_clones) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_feature_rows: N %d < leg_dim + 6 n_clones", N);
+    if ((mode & ~15) || ((mode & LVK_FR_DIRECT) && (mode & LVK_FR_DEVICE_ZERO)))
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_feature_rows: mode %d (LVK_FR_DIRECT and LVK_FR_DEVICE_ZERO exclude each other)", mode);
+    // the kernel's assumptions, checked before anything is launched
+    const int col0 = leg_dim + 6 * n_clones;                          // first column after the clones: in-state features
+    int m_max = 1, max_rows = 2, gate_max = 0, cand_rows = 0, n_tri = 0;
+    size_t stage = 0, ccols = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const lvk_feature_job& f = h_jobs[j];
+        const int M = f.n_obs;
+        if (f.type < LVK_FJ_MSCKF || f.type > LVK_FJ_EKF_TRACKED) return lvk_set_error(ctx, LVK_ERR_ARG, "job %d: unknown type %d", j, f.type);
+        if (M < (f.type == LVK_FJ_MSCKF ? 2 : 1) || M > 64) return lvk_set_error(ctx, LVK_ERR_ARG, "job %d: %d observations (MSCKF 2..64, EKF 1..64)", j, M);
+        if (f.obs_off < 0 || f.obs_off + M > n_obs) return lvk_set_error(ctx, LVK_ERR_ARG, "job %d: observations out of range", j);
+        if (f.gate < 0 || f.tri_pending < 0 || f.tri_pending > 1) return lvk_set_error(ctx, LVK_ERR_ARG, "job %d: bad gate / tri_pending", j);
+        if (f.tri_pending && (f.type != LVK_FJ_MSCKF || !h_cams)) return lvk_set_error(ctx, LVK_ERR_ARG, "job %d: tri_pending needs an MSCKF job and camera poses", j);
+        for (int k = 0; k < M; ++k) {                                 // the compact column map must name every clone block once: the scatter writes, it does not add
+            const int cr = h_clone_rank[f.obs_off + k];
+            if (cr < 0 || cr >= n_clones) return lvk_set_error(ctx, LVK_ERR_ARG, "job %d: clone rank %d out of range", j, cr);
+            for (int q = 0; q < k; ++q) if (h_clone_rank[f.obs_off + q] == cr) return lvk_set_error(ctx, LVK_ERR_ARG, "job %d: clone rank %d observed twice", j, cr);
+        }
+        if (f.type != LVK_FJ_MSCKF) {
+            if (f.anchor_rank < 0 || f.anchor_rank >= n_clones) return lvk_set_error(ctx, LVK_ERR_ARG, "job %d: anchor rank %d out of range", j, f.anchor_rank);
+            for (int k = 0; k < M; ++k)
+                if (h_clone_rank[f.obs_off + k] == f.anchor_rank) return lvk_set_error(ctx, LVK_ERR_ARG, "job %d: the anchor clone %d is also an observing clone", j, f.anchor_rank);
+            if (f.fcol < col0 || (f.gate && f.fcol >= N)) return lvk_set_error(ctx, LVK_ERR_ARG, "job %d: feature column %d outside the feature states", j, f.fcol);
+            if (!(f.inv_depth != 0.)) return lvk_set_error(ctx, LVK_ERR_ARG, "job %d: zero inverse depth", j);
+        }
+        const int c = (f.type == LVK_FJ_MSCKF) ? 7 + 6 * M : 7 + 6 + 6 * M + 1;
+        const int first = f.type == LVK_FJ_MSCKF ? 3 : f.type == LVK_FJ_EKF_NEW ? 1 : 0;
+        m_max = std::max(m_max, M); max_rows = std::max(max_rows, 2 * M);
+        if (f.gate) gate_max = std::max(gate_max, 2 * M - first);
+        if (f.type != LVK_FJ_EKF_NEW) cand_rows += 2 * M - first;
+        stage += (size_t)4 * M * c + 2 * M; ccols += c; n_tri += f.tri_pending;
+    }
+    max_rows = lvk_feature_rows_route(max_rows, gate_max);
+    if (mode & LVK_FR_GENERAL) max_rows = std::max(max_rows, FRS_ROWS + 2);
+    const bool slots = (mode & (LVK_FR_DIRECT | LVK_FR_DEVICE_ZERO)) != 0;
+    if (cand_rows > h_rows) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "%d candidate dense rows exceed h_rows %d", cand_rows, h_rows);
+    const int stride = (mode & LVK_FR_STRIDE) ? m_max : 0;
+    const int tot = stride ? stride * n_jobs : n_obs;
+    // one input blob (clones, jobs, observations, P, triangulation jobs + poses, the stacking map), staging, one output blob
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t at = o; o = (o + bytes + 63) & ~(size_t)63; return at; };
+    const size_t o_cl = take(sizeof(CloneDev) * n_clones), o_job = take(sizeof(FeatJob) * n_jobs), o_rk = take(sizeof(int) * tot), o_z = take(16 * (size_t)tot),
+                 o_zv = take(16 * (size_t)tot), o_P = take(sizeof(double) * (size_t)N * ldp), o_tj = take(sizeof(TriJob) * std::max(n_tri, 1)),
+                 o_cam = take(sizeof(CamPose) * tot), o_crk = take(sizeof(int) * tot), o_map = take(sizeof(StackRow) * (size_t)std::max(cand_rows, 1)), in_bytes = o;
+    o = 0;
+    const size_t o_H = take(sizeof(double) * (size_t)std::max(h_rows, 1) * ldh), o_r = take(sizeof(double) * std::max(h_rows, 1)), o_fo = take(sizeof(FeatResult) * n_jobs),
+                 o_tri = take(sizeof(TriResult) * n_jobs), o_tridev = take(sizeof(TriResult) * n_jobs), out_bytes = o;
+    const size_t o_cc = (sizeof(double) * stage + 63) & ~(size_t)63;
+    char* d_in = (char*)lvk_ctx_scratch(ctx, 9, in_bytes);
+    char* d_st = (char*)lvk_ctx_scratch(ctx, 10, o_cc + sizeof(int) * ccols);
+    char* d_out = (char*)lvk_ctx_scratch(ctx, 11, out_bytes);
+    if (!d_in || !d_st || !d_out) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
+    std::vector<char> h(in_bytes, 0);
+    CloneDev* hc = (CloneDev*)(h.data() + o_cl);
+    for (int i = 0; i < n_clones; ++i) {
+        memcpy(hc[i].q, h_clones[i].q, 32); memcpy(hc[i].p, h_clones[i].p, 24); memcpy(hc[i].p_fej, h_clones[i].p_fej, 24);
+        memcpy(hc[i].R_b2c, h_clones[i].R_b2c, 72); memcpy(hc[i].t_c_b, h_clones[i].t_c_b, 24);
+    }
+    FeatJob* hj = (FeatJob*)(h.data() + o_job);
+    int* hr = (int*)(h.data() + o_rk); double* hz = (double*)(h.data() + o_z); double* hv = (double*)(h.data() + o_zv);
+    TriJob* htj = (TriJob*)(h.data() + o_tj); CamPose* hcam = (CamPose*)(h.data() + o_cam);
+    std::vector<StackRow> map;
+    size_t s_off = 0, c_off = 0; int d0 = 0, it = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const lvk_feature_job& f = h_jobs[j];
+        const int M = f.n_obs, c = (f.type == LVK_FJ_MSCKF) ? 7 + 6 * M : 7 + 6 + 6 * M + 1;
+        const int first = f.type == LVK_FJ_MSCKF ? 3 : f.type == LVK_FJ_EKF_NEW ? 1 : 0;
+        FeatJob& d = hj[j];
+        d.type = f.type; d.n_obs = M; d.obs_off = stride ? j * stride : f.obs_off; d.anchor_rank = f.type == LVK_FJ_MSCKF ? 0 : f.anchor_rank;
+        d.fcol = f.type == LVK_FJ_MSCKF ? 0 : f.fcol;
+        d.want_gate = (f.gate ? FJ_GATE : 0) | (f.tri_pending ? FJ_TRI_PENDING : 0);
+        d.ccol_off = (int)c_off; d.dst_row1 = 0; d.stage_off = (long long)s_off;
+        memcpy(d.p_w, f.p_w, 24); memcpy(d.p_fej, f.p_fej, 24); d.inv_depth = f.inv_depth; memcpy(d.obs_anchor, f.obs_anchor, 24);
+        d.gate_thr = f.gate ? lvk_chi2_005(f.gate) : 0.0;
+        if (stride) {
+            for (int k = 0; k < M; ++k) {
+                const int si = f.obs_off + k, di = j * stride + k;
+                hr[di] = h_clone_rank[si]; hz[2 * di] = h_obs[2 * si]; hz[2 * di + 1] = h_obs[2 * si + 1]; hv[2 * di] = h_obs_vel[2 * si]; hv[2 * di + 1] = h_obs_vel[2 * si + 1];
+                if (f.tri_pending) memcpy(&hcam[di], &h_cams[si], sizeof(CamPose));
+            }
+        }
+        if (f.tri_pending) {
+            TriJob& t = htj[it++];
+            t.n = M; t.use_position = 0; t.obs_off = d.obs_off; t.out_slot1 = j + 1;      // the view poses lie in the observations' layout
+            memcpy(t.position_in, f.p_w, 24);
+        }
+        if (f.type != LVK_FJ_EKF_NEW && slots) {
+            const int nout = 2 * M - first;
+            if (mode & LVK_FR_DIRECT) d.dst_row1 = d0 + 1;
+            else
+                for (int k = 0; k < nout; ++k) {
+                    StackRow s; s.g_off = d.stage_off; s.r_off = d.stage_off + (long long)4 * M * c; s.src_row = first + k; s.c = c; s.ccol_off = d.ccol_off;
+                    s.dst_row = d0 + k; s.job = j; s.pad = 0;
+                    map.push_back(s);
+                }
+            d0 += nout;
+        }
+        s_off += (size_t)4 * M * c + 2 * M; c_off += c;
+    }
+    if (!stride) {
+        memcpy(hr, h_clone_rank, sizeof(int) * n_obs);
+        memcpy(hz, h_obs, 16 * (size_t)n_obs); memcpy(hv, h_obs_vel, 16 * (size_t)n_obs);
+    }
+    memcpy(h.data() + o_P, h_P, sizeof(double) * (size_t)N * ldp);
+    if (n_tri) {
+        if (!stride) memcpy(hcam, h_cams, sizeof(CamPose) * n_obs);
+        for (int i = 0; i < tot; ++i) ((int*)(h.data() + o_crk))[i] = i;
+    }
+    if (!map.empty()) memcpy(h.data() + o_map, map.data(), sizeof(StackRow) * map.size());
+    LVK_HIP(ctx, hipMemcpyAsync(d_in, h.data(), in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (h_rows > 0) {
+        LVK_HIP(ctx, hipMemcpyAsync(d_out + o_H, h_H, sizeof(double) * (size_t)h_rows * ldh, hipMemcpyHostToDevice, ctx->stream));
+        LVK_HIP(ctx, hipMemcpyAsync(d_out + o_r, h_r, sizeof(double) * h_rows, hipMemcpyHostToDevice, ctx->stream));
+    }
+    LVK_HIP(ctx, hipMemsetAsync(d_out + o_fo, 0, out_bytes - o_fo, ctx->stream));      // results and both triangulation result arrays
+    FilterFlags fl; fl.leg_dim = leg_dim; fl.if_fej = if_fej ? 1 : 0; fl.estimate_td = estimate_td ? 1 : 0; fl.pad = 0; fl.sigma2 = sigma2;
+    double* d_staging = (double*)d_st; int* d_ccols = (int*)(d_st + o_cc);
+    FeatResult* d_fout = (FeatResult*)(d_out + o_fo);
+    TriResult* d_tridev = (TriResult*)(d_out + o_tridev);
+    lvk_status st = LVK_OK;
+    if (n_tri) st = lvk_launch_triangulate(ctx, (const TriJob*)(d_in + o_tj), n_tri, (const CamPose*)(d_in + o_cam), (const int*)(d_in + o_crk), (const double*)(d_in + o_z),
+                                           (TriResult*)(d_out + o_tri), d_tridev);
+    if (st == LVK_OK)
+        st = lvk_launch_feature_rows(ctx, (const FeatJob*)(d_in + o_job), n_jobs, max_rows, (const CloneDev*)(d_in + o_cl), (const int*)(d_in + o_rk), (const double*)(d_in + o_z),
+                                     (const double*)(d_in + o_zv), (const double*)(d_in + o_P), ldp, fl, d_staging, d_ccols, d_fout, nullptr,
+                                     (mode & LVK_FR_DIRECT) ? (double*)(d_out + o_H) : nullptr, ldh, N, (mode & LVK_FR_DIRECT) ? (double*)(d_out + o_r) : nullptr,
+                                     stride, n_clones, n_tri ? d_tridev : nullptr);
+    if (st == LVK_OK && !map.empty())
+        st = lvk_launch_stack_rows(ctx, d_fout, (const StackRow*)(d_in + o_map), (int)map.size(), d_staging, d_ccols, (double*)(d_out + o_H), ldh, N, (double*)(d_out + o_r));
+    if (st != LVK_OK) return st;
+    LVK_HIP(ctx, hipMemcpyAsync(h_res, d_fout, sizeof(FeatResult) * n_jobs, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<double> hs(stage);
+    LVK_HIP(ctx, hipMemcpyAsync(hs.data(), d_staging, sizeof(double) * stage, hipMemcpyDeviceToHost, ctx->stream));
+    LVK_HIP(ctx, hipMemcpyAsync(h_ccols, d_ccols, sizeof(int) * ccols, hipMemcpyDeviceToHost, ctx->stream));
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // [G | r] of every job, from its staging slot G [rows x c] | T [rows x c] | r [rows]
+    size_t b_off = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const int rows = 2 * h_jobs[j].n_obs, c = h_res[j].c;
+        const double* G = hs.data() + hj[j].stage_off; const double* r = G + (size_t)2 * rows * c;
+        for (int a = 0; a < rows; ++a) { memcpy(h_blocks + b_off + (size_t)a * (c + 1), G + (size_t)a * c, sizeof(double) * c); h_blocks[b_off + (size_t)a * (c + 1) + c] = r[a]; }
+        b_off += (size_t)rows * (c + 1);
+    }
+    if (!slots) {
+        // the host reads the gate back and stacks the accepted jobs' rows only (larvio.cpp:2185-2201)
+        for (int j = 0; j < n_jobs; ++j) {
+            if (h_jobs[j].type == LVK_FJ_EKF_NEW || !h_res[j].accept) continue;
+            const int M = h_jobs[j].n_obs, c = h_res[j].c, first = h_jobs[j].type == LVK_FJ_MSCKF ? 3 : 0;
+            for (int k = 0; k < 2 * M - first; ++k) {
+                StackRow s; s.g_off = hj[j].stage_off; s.r_off = hj[j].stage_off + (long long)4 * M * c; s.src_row = first + k; s.c = c; s.ccol_off = hj[j].ccol_off;
+                s.dst_row = d0 + k; s.job = -1; s.pad = 0;
+                map.push_back(s);
+            }
+            d0 += 2 * M - first;
+        }
+        *rows_out = d0;                                                 // <= cand_rows <= h_rows, checked before the launches
+        if (d0 > 0) {
+            LVK_HIP(ctx, hipMemcpyAsync(d_in + o_map, map.data(), sizeof(StackRow) * map.size(), hipMemcpyHostToDevice, ctx->stream));
+            st = lvk_launch_stack_rows(ctx, d_fout, (const StackRow*)(d_in + o_map), (int)map.size(), d_staging, d_ccols, (double*)(d_out + o_H), ldh, N, (double*)(d_out + o_r));
+            if (st != LVK_OK) return st;
+        }
+    } else *rows_out = d0;
+    if (h_rows > 0) {
+        LVK_HIP(ctx, hipMemcpyAsync(h_H, d_out + o_H, sizeof(double) * (size_t)h_rows * ldh, hipMemcpyDeviceToHost, ctx->stream));
+        LVK_HIP(ctx, hipMemcpyAsync(h_r, d_out + o_r, sizeof(double) * h_rows, hipMemcpyDeviceToHost, ctx->stream));
+    }
     LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LVK_OK;
 }

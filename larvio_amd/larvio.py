@@ -77,6 +77,7 @@ def _L():
         L.lvk_ekf_shard_stats.argtypes = [vp, vp]; L.lvk_ekf_shard_stats.restype = None
         L.lvk_triangulate.argtypes = [vp, vp, vp, i, i, vp, pi, vp, vp, vp, vp]; L.lvk_triangulate.restype = i
         L.lvk_ekf_gate_and_stack.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp, i, i, i, d, vp, vp, i, pi, vp, vp]; L.lvk_ekf_gate_and_stack.restype = i
+        L.lvk_ekf_feature_rows.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp, i, vp, i, i, i, i, i, d, i, vp, vp, vp, vp, i, i, vp, pi]; L.lvk_ekf_feature_rows.restype = i
         _sig_done = True
     return L
 
@@ -109,6 +110,52 @@ def gate_and_stack(ctx, clones, feats, clone_rank, obs, obs_vel, P, sigma2, if_f
     ctx.check(_L().lvk_ekf_gate_and_stack(ctx.h, _p(clones), len(clones), _p(fa), len(fa), _p(cr), _p(obs), _p(ov), _p(P), N, int(if_fej), int(estimate_td),
                                           float(sigma2), _p(H), _p(r), cap, C.byref(rows), _p(gamma), _p(acc)))
     return H[:rows.value].copy(), r[:rows.value].copy(), gamma, acc.astype(bool)
+
+
+FEATURE_JOB = np.dtype([("type", np.int32), ("n_obs", np.int32), ("obs_off", np.int32), ("anchor_rank", np.int32), ("fcol", np.int32), ("gate", np.int32),
+                        ("tri_pending", np.int32), ("pad", np.int32), ("p_w", np.float64, 3), ("p_fej", np.float64, 3), ("inv_depth", np.float64),
+                        ("obs_anchor", np.float64, 3)])
+FEATURE_RESULT = np.dtype([("gamma", np.float64), ("h2", np.float64), ("rows", np.int32), ("first_row", np.int32), ("c", np.int32), ("accept", np.int32)])
+FJ_MSCKF, FJ_EKF_NEW, FJ_EKF_TRACKED = 0, 1, 2
+FR_GENERAL, FR_STRIDE, FR_DIRECT, FR_DEVICE_ZERO = 1, 2, 4, 8
+
+
+def feature_job_cols(job):
+    """compact columns of a job: 7 (extrinsics + td) + 6 per observing clone (+ the anchor's 6 and the feature column for EKF jobs)"""
+    M = int(job["n_obs"])
+    return 7 + 6 * M if job["type"] == FJ_MSCKF else 7 + 6 + 6 * M + 1
+
+
+def feature_rows(ctx, clones, jobs, clone_rank, obs, obs_vel, P, ldp=None, leg_dim=22, if_fej=1, estimate_td=1, sigma2=0.008 ** 2, mode=0,
+                 cams=None, H=None, r=None):
+    """lvk_ekf_feature_rows: the filter's per-feature row stage for a batch of FEATURE_JOB records.  P: N x N, or a whole row-major
+    buffer of ldp columns (its first N x N block is P).  H (rows x ldh) and r: the dense output buffers, read first and returned with
+    the written rows (default: one row per candidate row, ldh = N, NaN-filled).  Returns (results, blocks, ccols, H, r, rows_out):
+    blocks[j] = job j's compact [G | r] (2M x (c + 1)), ccols[j] = its column map."""
+    clones = np.ascontiguousarray(clones, CLONE); jobs = np.ascontiguousarray(jobs, FEATURE_JOB)
+    cr = np.ascontiguousarray(clone_rank, np.int32); obs = np.ascontiguousarray(obs, np.float64); ov = np.ascontiguousarray(obs_vel, np.float64)
+    P = np.ascontiguousarray(P, np.float64)
+    N = P.shape[0]
+    if ldp is None:
+        ldp = P.shape[1]
+    pose = np.ascontiguousarray(cams, POSE) if cams is not None else None
+    if H is None:
+        H = np.full((sum(2 * int(j["n_obs"]) - (3 if j["type"] == FJ_MSCKF else 0) for j in jobs if j["type"] != FJ_EKF_NEW), N), np.nan)
+    H = np.ascontiguousarray(H, np.float64)
+    r = np.full(H.shape[0], np.nan) if r is None else np.ascontiguousarray(r, np.float64)
+    res = np.zeros(len(jobs), FEATURE_RESULT)
+    cols = [feature_job_cols(j) for j in jobs]
+    blocks = np.zeros(sum(2 * int(j["n_obs"]) * (c + 1) for j, c in zip(jobs, cols)))
+    cc = np.zeros(sum(cols), np.int32); rows = C.c_int(0)
+    ctx.check(_L().lvk_ekf_feature_rows(ctx.h, _p(clones), len(clones), _p(jobs), len(jobs), _p(cr), _p(obs), _p(ov), _p(pose) if pose is not None else None, len(cr),
+                                        _p(P), N, int(ldp), int(leg_dim), int(if_fej), int(estimate_td), float(sigma2), int(mode), _p(res), _p(blocks), _p(cc),
+                                        _p(H), H.shape[1], H.shape[0], _p(r), C.byref(rows)))
+    bl, cl = [], []
+    bo = co = 0
+    for j, c in zip(jobs, cols):
+        n = 2 * int(j["n_obs"]) * (c + 1)
+        bl.append(blocks[bo:bo + n].reshape(2 * int(j["n_obs"]), c + 1)); cl.append(cc[co:co + c]); bo += n; co += c
+    return res, bl, cl, H, r, rows.value
 
 
 def _padded(X, ld, rows=None):

@@ -301,6 +301,82 @@ def test_triangulation_stage_bit_exact(gpu_ctx):
         assert ok_g == ok_o and np.array_equal(pos_g, pos_o)
 
 
+def _tri_views(seed, n, noise=0.002):
+    from tests import feature_rows_ref as F
+    from oracle import lvo_be
+    rng = np.random.default_rng(seed)
+    clones = F.window(seed, n); p_w = F.landmark(rng, clones)
+    poses = np.zeros(n, lvo_be.POSE); obs = np.zeros((n, 2))
+    for j in range(n):
+        R, t = F.cam_pose(clones[j]); poses[j]["R"] = R.ravel(); poses[j]["t"] = t
+        obs[j] = F.project(clones[j], p_w)[0] + rng.normal(0, noise, 2)
+    return poses, obs, p_w, rng
+
+
+def _tri_same(gpu_ctx, poses, obs, **kw):
+    """the same answer, and every output bit-identical when accepted (a rejected feature's outputs are never read)"""
+    from oracle import lvo_be
+    from larvio_amd import larvio as lv
+    o = lvo_be.triangulate(poses, obs, **kw); g = lv.triangulate(gpu_ctx, poses, obs, **kw)
+    assert g[0] == o[0]
+    for a, b in zip(g[1:], o[1:] if o[0] else ()):
+        assert np.array_equal(np.float64(a).view(np.uint64), np.float64(b).view(np.uint64)), (a, b)
+    return o[0]
+
+
+def _tri_cost(poses, obs, sol):
+    """for an inverse-depth solution (alpha, beta, rho) in the last view (feature.hpp:252-310): the normalized cost total / (2 n^2),
+    every view's reprojection error and every view's depth"""
+    n = len(poses); RL = poses[-1]["R"].reshape(3, 3); tL = poses[-1]["t"]
+    e = np.zeros(n); depth = np.zeros(n)
+    for i in range(n):
+        Ri = poses[i]["R"].reshape(3, 3)
+        h = Ri.T @ RL @ np.array([sol[0], sol[1], 1.0]) + sol[2] * (Ri.T @ (tL - poses[i]["t"]))
+        e[i] = np.hypot(h[0] / h[2] - obs[i, 0], h[1] / h[2] - obs[i, 1]); depth[i] = h[2] / sol[2]
+    return float(np.sum(e ** 2)) / (2 * n * n), e, depth
+
+
+@pytest.mark.parametrize("n", [2, 31, 32, 33, 63, 64])
+def test_triangulation_stage_bit_exact_wave_edges(gpu_ctx, n):
+    """k_triangulate's wave-wide sums and __shfl(., n - 1) at the wave's edges; outliers that take the Huber weight (a view whose
+    reprojection error exceeds 0.01 at the solution, so w != 1); use_position at n = 64"""
+    from oracle import lvo_be
+    poses, obs, p_w, rng = _tri_views(100 + n, n)
+    assert _tri_same(gpu_ctx, poses, obs)
+    bad = rng.choice(n, max(1, n // 8), replace=False)
+    out = obs.copy(); out[bad] += 0.03
+    assert _tri_same(gpu_ctx, poses, out)
+    _, e, _ = _tri_cost(poses, out, lvo_be.triangulate(poses, out)[2])
+    assert e[bad].max() > 0.01, e[bad]                                   # the Huber branch (d_tri_jacobian: w = sqrt(0.02 / e))
+    if n == 64:
+        assert _tri_same(gpu_ctx, poses, obs, use_position=True, position_in=p_w + 0.05)
+
+
+@pytest.mark.parametrize("n", [3, 12])
+def test_triangulation_cost_cut_bit_exact(gpu_ctx, n):
+    """scenes whose normalized cost lands just below and just above the 4.7673e-4 cut (the noise scale that flips the oracle's
+    answer, found by bisection).  Just below: the same answer and the same bits.  Just above: the same answer (the oracle, like
+    the reference, leaves a rejected feature's outputs unwritten); the kernel's own solution there shows that the cost cut decided
+    it: every depth positive, the normalized cost at the cut"""
+    from oracle import lvo_be
+    from larvio_amd import larvio as lv
+    poses, obs, p_w, rng = _tri_views(200 + n, n, noise=0.0)
+    d = rng.normal(0, 1, obs.shape)
+    lo, hi = 0.0, 1.0
+    assert lvo_be.triangulate(poses, obs + lo * d)[0] and not lvo_be.triangulate(poses, obs + hi * d)[0]
+    for _ in range(60):
+        mid = (lo + hi) / 2
+        if lvo_be.triangulate(poses, obs + mid * d)[0]:
+            lo = mid
+        else:
+            hi = mid
+    assert _tri_same(gpu_ctx, poses, obs + lo * d)
+    assert not _tri_same(gpu_ctx, poses, obs + hi * d)
+    for z, sol in ((obs + lo * d, lvo_be.triangulate(poses, obs + lo * d)[2]), (obs + hi * d, lv.triangulate(gpu_ctx, poses, obs + hi * d)[2])):
+        cost, _, depth = _tri_cost(poses, z, sol)
+        assert (depth > 0).all() and cost == pytest.approx(4.7673e-4, rel=1e-6), (cost, depth.min())
+
+
 def test_gate_and_stack_stage_matches_oracle(gpu_ctx):
     """lvk_ekf_gate_and_stack: per-feature Jacobian rows, null-space projection and chi-square gate vs the oracle's
     featureJacobian_msckf / gatingTest.  Both use the same Householder sequence: rows agree to 1e-10; gate decisions identical."""
