@@ -44,6 +44,10 @@ bool LarVio::initialize()
     if (!dir.empty() && !f_state) { f_state = std::fopen((dir + "msckf_2_state.txt").c_str(), "w"); f_takeoff = std::fopen((dir + "msckf_2_takeoff.txt").c_str(), "w"); }
     if (!ctx && lvk_context_create(0, &ctx) != LVK_OK) { std::printf("LarVio: no usable gfx950 device (there is no CPU fallback)\n"); return false; }
     if (lvk_ekf_create(ctx, &cfg, &ekf) != LVK_OK) { std::printf("LarVio: %s\n", lvk_last_error(ctx)); return false; }
+    // LVK_INDEFINITE_POLICY=ldlt: go on through an indefinite innovation covariance as the reference's S.ldlt().solve does
+    // (larvio.cpp:1456); otherwise the library's default (the update fails loudly)
+    const char* ip = std::getenv("LVK_INDEFINITE_POLICY");
+    if (ip && std::strcmp(ip, "ldlt") == 0 && lvk_ekf_set_indefinite_policy(ekf, LVK_INDEFINITE_LDLT) != LVK_OK) { std::printf("LarVio: %s\n", lvk_last_error(ctx)); return false; }
     return true;
 }
 

@@ -32,7 +32,8 @@ typedef int lvk_status;
 #define LVK_ERR_DEVICE      2   /* HIP runtime error / no device */
 #define LVK_ERR_CAPACITY    3   /* a fixed capacity was exceeded */
 #define LVK_ERR_UNSUPPORTED 4   /* configuration outside what the kernels are built for */
-#define LVK_ERR_NUMERIC     5   /* the measurement update met an innovation covariance that is not positive definite: the filter has diverged */
+#define LVK_ERR_NUMERIC     5   /* the measurement update met an innovation covariance that is not positive definite: the filter has diverged
+                                   (the default; lvk_ekf_set_indefinite_policy(LVK_INDEFINITE_LDLT) goes on as the reference does instead) */
 
 typedef struct lvk_context  lvk_context;
 typedef struct lvk_pyramid  lvk_pyramid;
@@ -214,10 +215,22 @@ lvk_status lvk_ekf_compress_qr_groups(lvk_context* ctx, double* d_H, int ld, int
 int        lvk_ekf_qr_plan(int N, int n_groups, const int* h_rows, const int* h_col_off, const int* h_cols, int* h_blocks, int cap_blocks,
                            int* h_block_cols, int cap_cols, int* h_level_blocks, int* h_level_cols, int cap_levels, int* final_rows);
 /* S = H P H^T + sigma2 I ; dx = P H^T S^-1 r ; P <- (I - K H) P symmetrised.  H is m x n (ldh), P n x n (ldp).
- * Replaces larvio.cpp:1453-1460, 1578-1594.  Waits for the update: LVK_ERR_NUMERIC when S is not positive definite (d_P is then
- * whatever the factorisation with that pivot replaced by 1 leaves; the reference's pivoted LDLT goes on silently). */
+ * Replaces larvio.cpp:1453-1460, 1578-1594.  Waits for the update: LVK_ERR_NUMERIC when S is not positive definite.  d_P and d_dx
+ * are then exactly what they were before the call (the launch that would write them reads the factorisation's report first), so
+ * the same arguments can go to lvk_ekf_update_ldlt, which goes on as the reference's pivoted LDLT does. */
 lvk_status lvk_ekf_update(lvk_context* ctx, double* d_P, int ldp, int n, const double* d_H, int ldh, int m,
                           const double* d_r, double sigma2, double* d_dx);
+/* The same update through an LDL^T factorisation of S with diagonal pivoting (at every step the remaining diagonal entry of largest
+ * magnitude, the first one on a tie), for an S that need not be positive definite - S.ldlt().solve(H P) of larvio.cpp:1456:
+ *     K = (S^-1 H P)^T ;  dx = K r ;  P <- (I - K H) P ;  P <- (P + P^T) / 2.
+ * A D entry of magnitude <= DBL_MIN gives a zero component of the solution instead of a division.  Always the pivoted route, also for
+ * a positive definite S.  h_info (host, 2 ints): [0] the number of negative, [1] of zero D entries.  Waits for its launch.
+ * LVK_ERR_ARG for bad arguments, LVK_ERR_CAPACITY (nothing launched) when m rows do not fit the factor kernel's LDS (m > ~1100). */
+lvk_status lvk_ekf_update_ldlt(lvk_context* ctx, double* d_P, int ldp, int n, const double* d_H, int ldh, int m,
+                               const double* d_r, double sigma2, double* d_dx, int* h_info);
+/* ... also returning the pivot order: h_perm (host, m ints), row i of the factor is row h_perm[i] of S (parity tests) */
+lvk_status lvk_ekf_update_ldlt_perm(lvk_context* ctx, double* d_P, int ldp, int n, const double* d_H, int ldh, int m,
+                                    const double* d_r, double sigma2, double* d_dx, int* h_info, int* h_perm);
 /* C = alpha op(A) op(B) + beta C on the FP64 matrix cores (v_mfma_f64_16x16x4_f64) — the P H^T-class contraction */
 lvk_status lvk_dgemm(lvk_context* ctx, int transa, int transb, int M, int N, int K, double alpha, const double* d_A, int lda,
                      const double* d_B, int ldb, double beta, double* d_C, int ldc);
@@ -317,6 +330,30 @@ lvk_status lvk_ekf_get_state(const lvk_ekf* e, double* h_out30);
 lvk_status lvk_ekf_get_imu_intrinsics(const lvk_ekf* e, double* h_out24);
 lvk_status lvk_ekf_set_imu_intrinsics(lvk_ekf* e, const double* h_in24);
 lvk_status lvk_ekf_get_cov(lvk_ekf* e, double* h_P);           /* N*N row-major, synchronises (getPpose/getPvel read blocks of it) */
+/* the counterpart: replace the covariance (n*n row-major, n == lvk_ekf_dim(); a prior, or a test's starting point).  Nothing is
+ * checked about the matrix itself.  LVK_ERR_ARG when n is not the state's dimension, or when an update queued with
+ * lvk_ekf_process_async has not been waited for yet - by lvk_ekf_wait or by any other call that waits for it (every getter does) -
+ * whether or not it has finished meanwhile: the answer does not depend on timing. */
+lvk_status lvk_ekf_set_cov(lvk_ekf* e, const double* h_P, int n);
+/* What a measurement update does when the Cholesky factorisation of S = H P H^T + sigma2 I meets a non-positive pivot:
+ *   LVK_INDEFINITE_FAIL (the default): the update fails with LVK_ERR_NUMERIC and the handle stays failed;
+ *   LVK_INDEFINITE_LDLT: that one update (after lost features, pruning or a zero-velocity update; queued with lvk_ekf_process_async or
+ *     not) runs again through the pivoted LDL^T of lvk_ekf_update_ldlt on the untouched covariance, as the reference does
+ *     (larvio.cpp:1456), and the filter continues.  lvk_ekf_indefinite_fallbacks counts how often this has happened.
+ *     If that update has more rows than the pivoted factor's LDS holds (m > ~1100) the call fails with LVK_ERR_CAPACITY instead of
+ *     LVK_ERR_NUMERIC; if the state's dimension is not the one the failed update ran on (no caller does that today) the default applies.
+ * The sharded update has no fallback yet: with a transport set (lvk_ekf_set_shard) LVK_INDEFINITE_LDLT is refused with
+ * LVK_ERR_UNSUPPORTED, and so is a transport once the policy is set. */
+#define LVK_INDEFINITE_FAIL 0
+#define LVK_INDEFINITE_LDLT 1
+lvk_status lvk_ekf_set_indefinite_policy(lvk_ekf* e, int policy);
+long       lvk_ekf_indefinite_fallbacks(const lvk_ekf* e);
+/* Test hook, meaningful ONLY directly after an update that failed with LVK_ERR_NUMERIC under LVK_INDEFINITE_FAIL (the one case in which
+ * it also answers on a failed handle): the stacked system that update read, after compression - H (m x n row-major), r (m) - and the
+ * covariance (n x n) and state (30 doubles, as lvk_ekf_get_state), which the failed update left exactly where it started.  In any other
+ * situation the row buffers may already hold a later stage's rows and covariance and state are simply the present ones: do not
+ * build on it.  Any output pointer may be null; with all four null only *m and *n are set. */
+lvk_status lvk_ekf_last_update(lvk_ekf* e, int* m, int* n, double* h_H, double* h_r, double* h_P, double* h_state30);
 /* the leading n x n block of the covariance (n <= 16: orientation 0..2, velocity 3..5, position 6..8, gyro bias 9..11, ...), row-major -
  * all that getPpose / getPvel read (larvio.cpp:2673-2690); served from a host-side mirror the update keeps, no transfer of the matrix */
 lvk_status lvk_ekf_get_cov_imu(lvk_ekf* e, int n, double* h_out);

@@ -118,6 +118,12 @@ public:
         if (updated) write_logs();
         return updated != 0;
     }
+    // What an update does with an innovation covariance that is not positive definite: LVK_INDEFINITE_FAIL (the default: the update
+    // fails and the handle stays failed) or LVK_INDEFINITE_LDLT (that update runs again through the pivoted LDL^T, as the reference's
+    // S.ldlt().solve does, and the filter goes on).  After initialize().
+    bool setIndefinitePolicy(int policy) { return ekf_ && lvk_ekf_set_indefinite_policy(ekf_, policy) == LVK_OK; }
+    // replace the covariance: n x n row-major, n == the state's dimension (lvk_ekf_dim); a prior to start from
+    bool setCov(const double* P, int n) { return ekf_ && lvk_ekf_set_cov(ekf_, P, n) == LVK_OK; }
     // getTbw (larvio.cpp:2644-2655): body-to-world pose as a row-major 4x4
     void getTbw(double T[16]) const
     {

@@ -35,8 +35,9 @@
 #define LEG_MAX 46
 #define GRAV 9.81
 
-struct UpdateWs { double* B; int ldb; double* S; int lds; int* info; hipEvent_t ev_a = nullptr, ev_b = nullptr; double* dx_host = nullptr; double* p00_host = nullptr; };   // ev_*: optional bracket around the H P GEMM; dx_host: host-mapped mirror of dx; p00_host: of the updated P's leading 16 x 16 block
+struct UpdateWs { double* B; int ldb; double* S; int lds; int* info; hipEvent_t ev_a = nullptr, ev_b = nullptr; double* dx_host = nullptr; double* p00_host = nullptr; int* info_host = nullptr; };   // info: the factorisation's report words in device memory, info_host: their mirror in device-mapped host memory (written only when one is set); ev_*: optional bracket around the H P GEMM; dx_host: host-mapped mirror of dx; p00_host: of the updated P's leading 16 x 16 block
 lvk_status lvk_update_core(lvk_context* ctx, double* P, int ldp, int n, const double* H, int ldh, int m, const double* r, double sigma2, double* dx, UpdateWs ws);
+lvk_status lvk_update_ldlt_core(lvk_context* ctx, double* P, int ldp, int n, const double* H, int ldh, int m, const double* r, double sigma2, double* dx, UpdateWs ws, int** d_cnt_out, int** d_perm_out);
 lvk_status lvk_cov_gather(lvk_context* ctx, const double* Pin, int ldin, double* Pout, int ldout, const int* d_idx, int n);
 lvk_status lvk_cov_propagate_augment(lvk_context* ctx, const double* Pin, int ldin, double* Pout, int ldout, int n_out, int pose_rows, int L,
                                      const double* h_phi, const double* h_q, const double* d_phiq);
@@ -263,6 +264,14 @@ struct lvk_ekf {
     size_t down_info = 0;                               // offset in h_down of the factorisation's report words (update_health)
     size_t down_p00 = 0; bool p00_valid = false;        // offset in h_down of the mirror of P[0:16, 0:16] (q v p bg ba[0]) the last update's final GEMM wrote; valid: nothing has touched that block since
     UpdateWs ws;
+    // what to do when the Cholesky meets a non-positive pivot (lvk_ekf_set_indefinite_policy).  The update's last launch leaves P
+    // and dx alone then (GemmRider::gate), so under LVK_INDEFINITE_LDLT update_health() runs that one update again through the
+    // pivoted LDL^T: `last` is the stacked system the failed update read (still in place: nothing writes d_H / d_r before the sync
+    // that looks at the report), `redo` what the caller had queued behind the update and has to be queued again behind the new one.
+    int indefinite_policy = LVK_INDEFINITE_FAIL; long indefinite_fallbacks = 0;
+    struct LastUpdate { const double* H = nullptr; const double* r = nullptr; int m = 0, n = 0; } last;
+    std::function<lvk_status()> redo;
+    bool fell_back = false;                             // set by update_health when it re-ran the update: d_dx has changed since the caller's copy was queued
     // pinned host arenas
     char* h_up = nullptr; size_t up_cap = 0, up_off = 0, up_flushed = 0;
     size_t up_lim = 0; int up_half = 0;                 // the arena is used in halves, alternating per call: kernels queued behind a call's last sync may still read its half while the next call stages into the other
@@ -297,10 +306,12 @@ struct lvk_ekf::Async {
     std::atomic<bool> stop{false};
     double ts = 0; std::vector<lvk_feature_obs> feats; std::vector<lvk_imu> imu; int expect_used = 0;
     lvk_status st = LVK_OK; int updated = 0; long n_deferred = 0;
+    bool unwaited = false;                              // an update was queued and no call has waited for it yet (caller's thread only)
 };
 static void ekf_quiesce(const lvk_ekf* e)
 {
     lvk_ekf::Async* a = e->async;
+    if (a) a->unwaited = false;
     if (!a || a->state.load(std::memory_order_acquire) == 0) return;
     for (int spin = 0; spin < 40000; ++spin) { if (a->state.load(std::memory_order_acquire) == 0) return; LVK_CPU_RELAX(); }
     std::unique_lock<std::mutex> lk(a->mu);
@@ -419,13 +430,29 @@ static lvk_status end_defer(lvk_ekf* e)
 }
 // The factorisation of S = H P H^T + sigma^2 I reports into device-mapped words (be_linalg.hip): a non-positive pivot means the
 // covariance has lost positive definiteness - the reference's pivoted LDLT (larvio.cpp:1456) would go on with an indefinite S and
-// produce a state nobody should fly on; here the update fails and the failure is sticky (ekf_process_guarded).  Called after a
-// stream sync that covers the update.
+// produce a state nobody should fly on; here, by default, the update fails and the failure is sticky (ekf_process_guarded).  Under
+// LVK_INDEFINITE_LDLT the update is run again through that pivoted LDLT instead (be_ldlt.hip) - the failed one has written neither P
+// nor dx - and the call goes on.  Called after a stream sync that covers the update.
 static lvk_status update_health(lvk_ekf* e)
 {
     int* w = (int*)(e->h_down + e->down_info);
     if (w[0] == 0 && w[1] == 0) return LVK_OK;
     const int piv = w[0], gave_up = w[1]; w[0] = 0; w[1] = 0;
+    EKF_HIP(hipMemsetAsync(e->ws.info, 0, 64, e->ctx->stream));
+    // (last.n == N always holds here - every caller syncs before it changes N; were it ever not so, the default applies.  A system of more
+    // rows than the factor kernel's LDS holds - m > ~1100, beyond what the filter's row capacity allows at the supported window sizes -
+    // ends in LVK_ERR_CAPACITY from lvk_update_ldlt_core: lvk_c.h says both.)
+    if (!gave_up && e->indefinite_policy == LVK_INDEFINITE_LDLT && e->last.m > 0 && e->last.n == e->N) {
+        // the reference's route (larvio.cpp:1456): P and dx are as they were before the failed update; this one update again, pivoted
+        UpdateWs ws = e->ws; ws.dx_host = (double*)(e->dh_down + e->down_dx);
+        int* d_cnt = nullptr;
+        lvk_status st = lvk_update_ldlt_core(e->ctx, e->dP[e->cur], e->ld, e->N, e->last.H, e->ld, e->last.m, e->last.r, e->sigma2, e->d_dx, ws, &d_cnt, nullptr);
+        if (st == LVK_OK && e->redo) st = e->redo();
+        if (st != LVK_OK) return st;
+        EKF_HIP(hipStreamSynchronize(e->ctx->stream)); e->n_sync++;
+        e->p00_valid = false; e->fell_back = true; e->indefinite_fallbacks++;
+        return LVK_OK;
+    }
     if (gave_up) return lvk_set_error(e->ctx, LVK_ERR_DEVICE, "measurement update: a solver workgroup waited for panel %d of the factorisation in vain", gave_up);
     return lvk_set_error(e->ctx, LVK_ERR_NUMERIC, "measurement update: the innovation covariance is not positive definite (pivot %d of %ld rows) - the filter has diverged", piv - 1, e->counters[2]);
 }
@@ -434,7 +461,13 @@ static lvk_status d2h_sync(lvk_ekf* e, void* dst, const void* src, size_t bytes)
     if (bytes) EKF_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->ctx->stream));
     EKF_HIP(hipStreamSynchronize(e->ctx->stream)); e->n_sync++;
     if (e->shard.fn) { int* f = (int*)(e->h_down + e->down_flag); if (*f) { const int mask = *f; *f = 0; return lvk_set_error(e->ctx, LVK_ERR_DEVICE, "sharded update: the block of a peer rank (mask 0x%x) arrived invalid - that rank failed before the exchange", mask); } }
-    return update_health(e);
+    e->fell_back = false;
+    lvk_status hs = update_health(e);
+    if (hs == LVK_OK && e->fell_back && bytes) {        // the copy above was queued behind the update that failed: fetch what the pivoted one wrote
+        EKF_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->ctx->stream));
+        EKF_HIP(hipStreamSynchronize(e->ctx->stream)); e->n_sync++;
+    }
+    return hs;
 }
 // P <- P[idx, idx] (ping-pong)
 static lvk_status cov_gather(lvk_ekf* e, const std::vector<int>& idx)
@@ -1370,6 +1403,7 @@ static lvk_status dense_update(lvk_ekf* e, int m, std::vector<double>& dx, int e
     UpdateWs ws = e->ws;
     ws.dx_host = (double*)(e->dh_down + e->down_dx);
     ws.p00_host = (double*)(e->dh_down + e->down_p00);
+    e->last.H = H; e->last.r = r; e->last.m = m; e->last.n = e->N; e->redo = nullptr;
     if (e->prof_on && m > 0) {
         auto take = [&]() { hipEvent_t ev; if (!e->prof_free.empty()) { ev = e->prof_free.back(); e->prof_free.pop_back(); } else hipEventCreate(&ev); return ev; };
         ws.ev_a = take(); ws.ev_b = take();
@@ -1751,7 +1785,9 @@ static lvk_status remove_lost_features(lvk_ekf* e)
                 memcpy(hh, h2.data(), sizeof(double) * n_acc);
                 st = flush_uploads(e);
                 if (N + n_acc > e->nmax) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "state dimension exceeds capacity");
-                if (st == LVK_OK) st = lvk_cov_append_features(e->ctx, e->dP[e->cur], e->ld, N, n_acc, e->d_H1, e->ld, dev(e, hh), e->d_r1, e->d_dx, e->sigma2, e->d_tmp, e->d_dx + N);
+                const double* d_hh = dev(e, hh);
+                e->redo = [e, N, n_acc, d_hh]() { return lvk_cov_append_features(e->ctx, e->dP[e->cur], e->ld, N, n_acc, e->d_H1, e->ld, d_hh, e->d_r1, e->d_dx, e->sigma2, e->d_tmp, e->d_dx + N); };
+                if (st == LVK_OK) st = e->redo();
                 if (st != LVK_OK) return st;
             }
             TR(TR_RLF_UPD);
@@ -2211,7 +2247,7 @@ void lvk_ekf_destroy(lvk_ekf* e)
         g_tr = EkfTrace();
     }
     void* ptrs[] = {e->dP[0], e->dP[1], e->d_idx, e->d_phiq, e->d_J, e->d_dx, e->d_tmp, e->d_tri, e->d_tridev, e->d_fj, e->d_fout, e->d_rank, e->d_z, e->d_zv,
-                    e->d_cams, e->d_clones, e->d_staging, e->d_ccols, e->d_map, e->d_H, e->d_r, e->d_Hb, e->d_rb, e->d_H1, e->d_H2, e->d_r1, e->ws.B, e->ws.S, e->zero_copy ? nullptr : (void*)e->d_up};
+                    e->d_cams, e->d_clones, e->d_staging, e->d_ccols, e->d_map, e->d_H, e->d_r, e->d_Hb, e->d_rb, e->d_H1, e->d_H2, e->d_r1, e->ws.B, e->ws.S, e->ws.info, e->zero_copy ? nullptr : (void*)e->d_up};
     for (void* p : ptrs) if (p) hipFree(p);
     if (e->h_up) hipHostFree(e->h_up);
     if (e->h_down) hipHostFree(e->h_down);
@@ -2303,7 +2339,8 @@ lvk_status lvk_ekf_create(lvk_context* ctx, const lvk_ekf_config* cfg, lvk_ekf**
         void* dd = nullptr;
         ok = ok && hipHostGetDevicePointer(&dd, e->h_down, 0) == hipSuccess && dd; e->dh_down = (char*)dd;
         e->d_triout = (TriResult*)e->dh_down;
-        e->ws.info = (int*)(e->dh_down + e->down_info); memset(e->h_down + e->down_info, 0, 256);
+        e->ws.info_host = (int*)(e->dh_down + e->down_info); memset(e->h_down + e->down_info, 0, 256);
+        ok = ok && hipMalloc((void**)&e->ws.info, 64) == hipSuccess && hipMemset(e->ws.info, 0, 64) == hipSuccess;
     }
     if (!ok) { lvk_ekf_destroy(e); return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_ekf_create: allocation failed"); }
     // initial covariance (larvio.cpp:163-186)
@@ -2408,7 +2445,7 @@ lvk_status lvk_ekf_process_async(lvk_ekf* e, double ts, const lvk_feature_obs* f
     *n_consumed = batch_imu_count(e, ts + e->td, imu, n_imu);
     *will_update = 1;
     a->ts = ts; a->feats.assign(feats, feats + n_feats); a->imu.assign(imu, imu + n_imu); a->expect_used = *n_consumed;
-    { std::lock_guard<std::mutex> lk(a->mu); a->st = LVK_OK; a->updated = 0; a->n_deferred += 1; a->state.store(1, std::memory_order_release); }
+    { std::lock_guard<std::mutex> lk(a->mu); a->st = LVK_OK; a->updated = 0; a->n_deferred += 1; a->unwaited = true; a->state.store(1, std::memory_order_release); }
     a->cv.notify_all();
     return LVK_OK;
 }
@@ -2532,6 +2569,7 @@ lvk_status lvk_ekf_set_shard(lvk_ekf* e, int rank, int world, lvk_exchange_fn fn
     if (!e || world < 1 || rank < 0 || rank >= world || (world > 1 && !fn)) return lvk_set_error(e ? e->ctx : nullptr, LVK_ERR_ARG, "lvk_ekf_set_shard: bad argument");
     auto& S = e->shard;
     ekf_quiesce(e);
+    if (fn && e->indefinite_policy == LVK_INDEFINITE_LDLT) return lvk_set_error(e->ctx, LVK_ERR_UNSUPPORTED, "lvk_ekf_set_shard: the sharded update has no pivoted fallback (LVK_INDEFINITE_LDLT is set)");
     EKF_HIP(hipStreamSynchronize(e->ctx->stream));
     if (S.d_send) hipFree(S.d_send); if (S.d_recv) hipFree(S.d_recv);
     S.d_send = S.d_recv = nullptr; S.cap = 0; S.xk_cap = 0;
@@ -2607,6 +2645,47 @@ lvk_status lvk_ekf_get_cov(lvk_ekf* e, double* h_P)
     EKF_HIP(hipStreamSynchronize(e->ctx->stream));       // (an update returns with its last covariance gather still queued)
     return LVK_OK;
 }
+lvk_status lvk_ekf_set_cov(lvk_ekf* e, const double* h_P, int n)
+{
+    if (!e || !h_P) return lvk_set_error(e ? e->ctx : nullptr, LVK_ERR_ARG, "lvk_ekf_set_cov: bad argument");
+    // "in flight" = queued and not yet waited for, whether or not the worker has finished meanwhile: the answer does not depend on timing
+    if (e->async && e->async->unwaited) return lvk_set_error(e->ctx, LVK_ERR_ARG, "lvk_ekf_set_cov: an update is in flight (lvk_ekf_wait first)");
+    ekf_quiesce(e);
+    if (e->failed != LVK_OK) return e->failed;
+    if (n != e->N) return lvk_set_error(e->ctx, LVK_ERR_ARG, "lvk_ekf_set_cov: n = %d, the state has %d dimensions", n, e->N);
+    EKF_HIP(hipStreamSynchronize(e->ctx->stream));
+    EKF_HIP(hipMemcpy2DAsync(e->dP[e->cur], sizeof(double) * e->ld, h_P, sizeof(double) * n, sizeof(double) * n, n, hipMemcpyHostToDevice, e->ctx->stream));
+    EKF_HIP(hipStreamSynchronize(e->ctx->stream));
+    e->p00_valid = false;
+    return LVK_OK;
+}
+lvk_status lvk_ekf_set_indefinite_policy(lvk_ekf* e, int policy)
+{
+    if (!e || (policy != LVK_INDEFINITE_FAIL && policy != LVK_INDEFINITE_LDLT)) return lvk_set_error(e ? e->ctx : nullptr, LVK_ERR_ARG, "lvk_ekf_set_indefinite_policy: bad argument");
+    ekf_quiesce(e);
+    if (policy == LVK_INDEFINITE_LDLT && e->shard.fn) return lvk_set_error(e->ctx, LVK_ERR_UNSUPPORTED, "lvk_ekf_set_indefinite_policy: the sharded update has no pivoted fallback");
+    e->indefinite_policy = policy;
+    return LVK_OK;
+}
+lvk_status lvk_ekf_last_update(lvk_ekf* e, int* m, int* n, double* h_H, double* h_r, double* h_P, double* h_state30)
+{
+    if (!e || !m || !n) return LVK_ERR_ARG;
+    ekf_quiesce(e);
+    *m = e->last.m; *n = e->last.n;
+    if (!h_H && !h_r && !h_P && !h_state30) return LVK_OK;
+    if (e->last.m <= 0 || e->last.n != e->N) return lvk_set_error(e->ctx, LVK_ERR_ARG, "lvk_ekf_last_update: no update on record for the present state");
+    (void)hipGetLastError();
+    hipStream_t st = e->ctx->stream;
+    const size_t row = sizeof(double) * (size_t)e->N;
+    if (h_H) EKF_HIP(hipMemcpy2DAsync(h_H, row, e->last.H, sizeof(double) * e->ld, row, e->last.m, hipMemcpyDeviceToHost, st));
+    if (h_r) EKF_HIP(hipMemcpyAsync(h_r, e->last.r, sizeof(double) * (size_t)e->last.m, hipMemcpyDeviceToHost, st));
+    if (h_P) EKF_HIP(hipMemcpy2DAsync(h_P, row, e->dP[e->cur], sizeof(double) * e->ld, row, e->N, hipMemcpyDeviceToHost, st));
+    EKF_HIP(hipStreamSynchronize(st));
+    if (h_state30) { double* o = h_state30; o[0] = e->s.t; memcpy(o + 1, e->s.q, 32); memcpy(o + 5, e->s.v, 24); memcpy(o + 8, e->s.p, 24); memcpy(o + 11, e->s.bg, 24); memcpy(o + 14, e->s.ba, 24);
+                     memcpy(o + 17, e->R_b2c, 72); memcpy(o + 26, e->t_c_b, 24); o[29] = e->td; }
+    return LVK_OK;
+}
+long lvk_ekf_indefinite_fallbacks(const lvk_ekf* e) { if (!e) return 0; ekf_quiesce(e); return e->indefinite_fallbacks; }
 // the leading n x n block (n <= 16: q v p bg ba[0]) - what getPpose / getPvel read (larvio.cpp:2673-2690) - without moving the
 // covariance: the update's last GEMM mirrors that tile into host-mapped memory, and the host waited for that launch when it read dx
 lvk_status lvk_ekf_get_cov_imu(lvk_ekf* e, int n, double* h_out)

@@ -19,7 +19,10 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 // D: col = l&15, row = (l>>4) + 4*reg  (f64 has its own C/D map, cdna_hip_programming.md §3).
 // Two optional riders save launches on the update's dependent chain: (xin, xin_col) copies a vector into column xin_col of C
 // ([HP | r] in one launch); (xout, xout_col) diverts output column xout_col to a vector, unscaled (W^T [W | w] -> P update and dx).
-struct GemmRider { const double* xin; int xin_col; double* xout; int xout_col; double* xout_host = nullptr; double* c00_host = nullptr; };   // xout_host: mirror of xout in device-mapped host memory; c00_host: mirror (16 x 16, row-major) of C's leading tile, likewise
+struct GemmRider { const double* xin; int xin_col; double* xout; int xout_col; double* xout_host = nullptr; double* c00_host = nullptr; const int* gate = nullptr; int* gate_host = nullptr; };   // xout_host: mirror of xout in device-mapped host memory; c00_host: mirror (16 x 16, row-major) of C's leading tile, likewise
+// gate: the factorisation's two report words (device memory).  When either is set the launch writes nothing - P and dx stay as they
+// were, so that a pivoted solve can redo the update (lvk_update_ldlt_core) - except that it forwards the words to gate_host (their
+// mirror in device-mapped host memory, optional).  Read up front with the operands, looked at before the first store.
 // Split-K: the four wavefronts of a workgroup share ONE 16x16 tile and take every fourth K-chunk (kc <= 64 consecutive k, a
 // multiple of 16) each.  The operands come from other XCDs' L2s / the memory side (they were written by the previous kernel), so a
 // dependent load costs microseconds and a tile's time is (number of load round trips) x latency, not bytes or flops: a tile of the
@@ -39,6 +42,8 @@ __global__ void __launch_bounds__(256) k_dgemm_sk(int M, int N, int K, int kc, c
     const int ar = row0 + i, bc = col0 + i;
     const bool a_ok = ar < M, b_ok = bc < N;
     d4 acc = {0., 0., 0., 0.};
+    int gate0 = 0, gate1 = 0;
+    if (rd.gate) { gate0 = rd.gate[0]; gate1 = rd.gate[1]; }
     // the current value of C (beta != 0: P -= W^T W, S22 -= L21 L21^T) is requested up front, in the shadow of the operand loads
     double cin[4] = {0., 0., 0., 0.};
     if (wave == 0 && beta != 0.) {
@@ -64,6 +69,10 @@ __global__ void __launch_bounds__(256) k_dgemm_sk(int M, int N, int K, int kc, c
     }
     __syncthreads();
     if (wave) return;
+    if (gate0 | gate1) {
+        if (rd.gate_host && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0) { rd.gate_host[0] = gate0; rd.gate_host[1] = gate1; }
+        return;
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const double sum = ((acc[r] + red[0][r][lane]) + red[1][r][lane]) + red[2][r][lane];
@@ -810,7 +819,7 @@ static lvk_status launch_chol_solve(lvk_context* ctx, double* S, int lds_, int m
 }
 
 // ------------------------------------------------------------------------- host drivers (internal + C ABI)
-struct UpdateWs { double* B; int ldb; double* S; int lds; int* info; hipEvent_t ev_a = nullptr, ev_b = nullptr; double* dx_host = nullptr; double* p00_host = nullptr; };   // ev_*: optional bracket around the H P GEMM; dx_host: host-mapped mirror of dx; p00_host: of the updated P's leading 16 x 16 block
+struct UpdateWs { double* B; int ldb; double* S; int lds; int* info; hipEvent_t ev_a = nullptr, ev_b = nullptr; double* dx_host = nullptr; double* p00_host = nullptr; int* info_host = nullptr; };   // info: the factorisation's report words, in DEVICE memory (the final GEMM reads them: GemmRider::gate); info_host: their mirror in device-mapped host memory, written only when one is set; ev_*: optional bracket around the H P GEMM; dx_host: host-mapped mirror of dx; p00_host: of the updated P's leading 16 x 16 block
 
 // dx (device, n) and P updated in place.  B: m x (n+1) workspace, S: m x m workspace.
 lvk_status lvk_update_core(lvk_context* ctx, double* P, int ldp, int n, const double* H, int ldh, int m, const double* r, double sigma2,
@@ -824,7 +833,35 @@ lvk_status lvk_update_core(lvk_context* ctx, double* P, int ldp, int n, const do
     launch_dgemm<false, true>(s, m, m, n, ws.B, ws.ldb, H, ldh, ws.S, ws.lds, 1.0, 0.0, sigma2);           // S = HP H^T + sigma2 I
     { lvk_status cs = launch_chol_solve(ctx, ws.S, ws.lds, m, ws.B, ws.ldb, n + 1, ws.info); if (cs != LVK_OK) return cs; }                                    // S = L L^T ; W = L^-1 [HP | r]
     // W^T [W | w]: columns 0..n-1 update P (P -= W^T W), column n is dx = W^T w
-    launch_dgemm<true, false>(s, n, n + 1, m, ws.B, ws.ldb, ws.B, ws.ldb, P, ldp, -1.0, 1.0, 0.0, GemmRider{nullptr, 0, dx, n, ws.dx_host, ws.p00_host});
+    launch_dgemm<true, false>(s, n, n + 1, m, ws.B, ws.ldb, ws.B, ws.ldb, P, ldp, -1.0, 1.0, 0.0, GemmRider{nullptr, 0, dx, n, ws.dx_host, ws.p00_host, ws.info, ws.info_host});
+    LVK_LAUNCH_CHECK(ctx);
+    return LVK_OK;
+}
+
+// The same update through the pivoted LDL^T (be_ldlt.hip), for an S that need not be positive definite - what the reference computes:
+//     K^T = X = S.ldlt().solve(H P) ;  dx = K r ;  P <- (I - K H) P = P - X^T (H P) ;  P <- (P + P^T) / 2      (larvio.cpp:1456-1460, 1578-1594)
+// ws.B / ws.S as for lvk_update_core; the pivot-order copies of [HP | r] and of X, D, the permutation and the two counters
+// (negative / zero D entries) live in context scratch slot 15.  *d_cnt_out = where the counters are (device).
+size_t lvk_ldlt_lds_bytes(int m);
+lvk_status lvk_ldlt_factor_solve(lvk_context* ctx, double* S, int ld, int m, const double* B, int ldb, int nbcols, double* Bp, double* X, double* Dg, int* perm, int* cnt);
+void lvk_cov_symmetrize(lvk_context* ctx, double* P, int ld, int n);
+lvk_status lvk_update_ldlt_core(lvk_context* ctx, double* P, int ldp, int n, const double* H, int ldh, int m, const double* r, double sigma2,
+                                double* dx, UpdateWs ws, int** d_cnt_out, int** d_perm_out)
+{
+    hipStream_t s = ctx->stream;
+    const size_t mat = sizeof(double) * (size_t)(m > 0 ? m : 1) * ws.ldb, vec = (sizeof(double) * (size_t)(m > 0 ? m : 1) + 63) & ~(size_t)63;
+    char* x = (char*)lvk_ctx_scratch(ctx, 15, 2 * mat + 2 * vec + 64);
+    if (!x) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
+    double* Bp = (double*)x; double* X = (double*)(x + mat); double* Dg = (double*)(x + 2 * mat); int* perm = (int*)(x + 2 * mat + vec); int* cnt = (int*)(x + 2 * mat + 2 * vec);
+    *d_cnt_out = cnt; if (d_perm_out) *d_perm_out = perm;
+    LVK_HIP(ctx, hipMemsetAsync(cnt, 0, 64, s));
+    if (m <= 0) { LVK_HIP(ctx, hipMemsetAsync(dx, 0, sizeof(double) * (size_t)n, s)); return LVK_OK; }
+    launch_dgemm<false, false>(s, m, n, n, H, ldh, P, ldp, ws.B, ws.ldb, 1.0, 0.0, 0.0, GemmRider{r, n, nullptr, 0, nullptr});   // [HP | r]
+    launch_dgemm<false, true>(s, m, m, n, ws.B, ws.ldb, H, ldh, ws.S, ws.lds, 1.0, 0.0, sigma2);           // S = HP H^T + sigma2 I
+    { lvk_status st = lvk_ldlt_factor_solve(ctx, ws.S, ws.lds, m, ws.B, ws.ldb, n + 1, Bp, X, Dg, perm, cnt); if (st != LVK_OK) return st; }
+    // X^T [HP | r] over the pivot-ordered rows: columns 0..n-1 update P, column n is dx = K r
+    launch_dgemm<true, false>(s, n, n + 1, m, X, ws.ldb, Bp, ws.ldb, P, ldp, -1.0, 1.0, 0.0, GemmRider{nullptr, 0, dx, n, ws.dx_host, nullptr});
+    lvk_cov_symmetrize(ctx, P, ldp, n);
     LVK_LAUNCH_CHECK(ctx);
     return LVK_OK;
 }
@@ -901,6 +938,39 @@ extern "C" lvk_status lvk_ekf_update(lvk_context* ctx, double* d_P, int ldp, int
     if (info[1]) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_ekf_update: a solver workgroup waited for panel %d of the factorisation in vain", info[1]);
     if (info[0]) return lvk_set_error(ctx, LVK_ERR_NUMERIC, "lvk_ekf_update: H P H^T + sigma2 I is not positive definite (pivot %d)", info[0] - 1);
     return LVK_OK;
+}
+
+static lvk_status ekf_update_ldlt_impl(lvk_context* ctx, double* d_P, int ldp, int n, const double* d_H, int ldh, int m, const double* d_r,
+                                       double sigma2, double* d_dx, int* h_info, int* h_perm)
+{
+    if (!ctx || !d_P || !d_dx || !h_info || n <= 0 || m < 0 || (m > 0 && (!d_H || !d_r)) || ldp < n || ldh < n)
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_update_ldlt: bad argument");
+    if (lvk_ldlt_lds_bytes(m) > 158 * 1024) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_ekf_update_ldlt: %d rows do not fit the factor kernel's LDS", m);
+    UpdateWs ws;
+    ws.ldb = (n + 1 + 7) & ~7; ws.lds = (m + 7) & ~7;
+    ws.B = (double*)lvk_ctx_scratch(ctx, 4, sizeof(double) * (size_t)(m > 0 ? m : 1) * ws.ldb);
+    ws.S = (double*)lvk_ctx_scratch(ctx, 5, sizeof(double) * (size_t)(m > 0 ? m : 1) * (ws.lds > 0 ? ws.lds : 8));
+    ws.info = nullptr;
+    if (!ws.B || !ws.S) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
+    int* d_cnt = nullptr; int* d_perm = nullptr;
+    lvk_status st = lvk_update_ldlt_core(ctx, d_P, ldp, n, d_H, ldh, m, d_r, sigma2, d_dx, ws, &d_cnt, &d_perm);
+    if (st != LVK_OK) return st;
+    LVK_HIP(ctx, hipMemcpyAsync(h_info, d_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (h_perm && m > 0) LVK_HIP(ctx, hipMemcpyAsync(h_perm, d_perm, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LVK_OK;
+}
+extern "C" lvk_status lvk_ekf_update_ldlt(lvk_context* ctx, double* d_P, int ldp, int n, const double* d_H, int ldh, int m, const double* d_r,
+                                          double sigma2, double* d_dx, int* h_info)
+{
+    return ekf_update_ldlt_impl(ctx, d_P, ldp, n, d_H, ldh, m, d_r, sigma2, d_dx, h_info, nullptr);
+}
+// the same, also returning the pivot order (h_perm: m ints; row i of the factor is row h_perm[i] of S) - for the stage tests
+extern "C" lvk_status lvk_ekf_update_ldlt_perm(lvk_context* ctx, double* d_P, int ldp, int n, const double* d_H, int ldh, int m, const double* d_r,
+                                               double sigma2, double* d_dx, int* h_info, int* h_perm)
+{
+    if (!h_perm) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_update_ldlt_perm: bad argument");
+    return ekf_update_ldlt_impl(ctx, d_P, ldp, n, d_H, ldh, m, d_r, sigma2, d_dx, h_info, h_perm);
 }
 
 extern "C" lvk_status lvk_dgemm(lvk_context* ctx, int transa, int transb, int M, int N, int K, double alpha, const double* d_A, int lda,

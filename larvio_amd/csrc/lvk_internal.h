@@ -49,7 +49,7 @@ static inline void* lvk_bar_alloc(int device, size_t bytes)
 #define LVK_MAX_LEVELS 8
 #define LVK_ORB_BORDER 32
 
-#define LVK_SCRATCH_SLOTS 15
+#define LVK_SCRATCH_SLOTS 16
 struct lvk_context {
     int device;
     hipStream_t stream;

@@ -66,6 +66,12 @@ def _L():
         L.lvk_ekf_get_state.argtypes = [vp, vp]; L.lvk_ekf_get_state.restype = i
         L.lvk_ekf_get_cov.argtypes = [vp, vp]; L.lvk_ekf_get_cov.restype = i
         L.lvk_ekf_get_cov_imu.argtypes = [vp, i, vp]; L.lvk_ekf_get_cov_imu.restype = i
+        L.lvk_ekf_set_cov.argtypes = [vp, vp, i]; L.lvk_ekf_set_cov.restype = i
+        L.lvk_ekf_set_indefinite_policy.argtypes = [vp, i]; L.lvk_ekf_set_indefinite_policy.restype = i
+        L.lvk_ekf_indefinite_fallbacks.argtypes = [vp]; L.lvk_ekf_indefinite_fallbacks.restype = C.c_long
+        L.lvk_ekf_last_update.argtypes = [vp, pi, pi, vp, vp, vp, vp]; L.lvk_ekf_last_update.restype = i
+        L.lvk_ekf_update_ldlt.argtypes = [vp, vp, i, i, vp, i, i, vp, d, vp, vp]; L.lvk_ekf_update_ldlt.restype = i
+        L.lvk_ekf_update_ldlt_perm.argtypes = [vp, vp, i, i, vp, i, i, vp, d, vp, vp, vp]; L.lvk_ekf_update_ldlt_perm.restype = i
         L.lvk_ekf_get_imu_intrinsics.argtypes = [vp, vp]; L.lvk_ekf_get_imu_intrinsics.restype = i
         L.lvk_ekf_set_imu_intrinsics.argtypes = [vp, vp]; L.lvk_ekf_set_imu_intrinsics.restype = i
         L.lvk_ekf_get_clones.argtypes = [vp, vp, i]; L.lvk_ekf_get_clones.restype = i
@@ -180,6 +186,9 @@ def dgemm(ctx, A, B, transa=False, transb=False, alpha=1.0, beta=0.0, Cin=None, 
     return ctx.to_host(dC, np.float64, Cm.shape)
 
 
+INDEFINITE_FAIL, INDEFINITE_LDLT = 0, 1
+
+
 def ekf_update(ctx, P, H, r, sigma2, ld=None):
     """ld: P and H stored with that leading dimension (NaN padding, as the filter's buffers); the whole P buffer (n x ld) is then
     returned, padding included."""
@@ -190,6 +199,23 @@ def ekf_update(ctx, P, H, r, sigma2, ld=None):
     dP, dH, dr, ddx = ctx.to_device(P), ctx.to_device(H), ctx.to_device(r), ctx.alloc(8 * n)
     ctx.check(_L().lvk_ekf_update(ctx.h, _p(dP), P.shape[1], n, _p(dH), H.shape[1], m, _p(dr), sigma2, _p(ddx)))
     return ctx.to_host(ddx, np.float64, (n,)), ctx.to_host(dP, np.float64, P.shape)
+
+
+def ekf_update_ldlt(ctx, P, H, r, sigma2, ld=None, with_perm=False):
+    """lvk_ekf_update_ldlt: the same update through the pivoted LDL^T (S need not be positive definite).  Arguments as ekf_update;
+    -> dx, P, (negative D entries, zero D entries) and, with_perm, the pivot order (row i of the factor = row perm[i] of S)."""
+    P = np.array(P, np.float64, order="C"); H = np.ascontiguousarray(H, np.float64); r = np.ascontiguousarray(r, np.float64)
+    n, m = P.shape[0], H.shape[0]
+    if ld is not None:
+        P, H = _padded(P, ld), _padded(H, ld)
+    dP, dH, dr, ddx = ctx.to_device(P), ctx.to_device(H), ctx.to_device(r), ctx.alloc(8 * n)
+    info = np.zeros(2, np.int32); perm = np.zeros(max(m, 1), np.int32)
+    if with_perm:
+        ctx.check(_L().lvk_ekf_update_ldlt_perm(ctx.h, _p(dP), P.shape[1], n, _p(dH), H.shape[1], m, _p(dr), sigma2, _p(ddx), _p(info), _p(perm)))
+    else:
+        ctx.check(_L().lvk_ekf_update_ldlt(ctx.h, _p(dP), P.shape[1], n, _p(dH), H.shape[1], m, _p(dr), sigma2, _p(ddx), _p(info)))
+    out = (ctx.to_host(ddx, np.float64, (n,)), ctx.to_host(dP, np.float64, P.shape), (int(info[0]), int(info[1])))
+    return out + (perm[:m].copy(),) if with_perm else out
 
 
 # The structural covariance operations (lvk_ekf_cov_*).  Matrices are passed as whole row-major buffers: the leading dimension is
@@ -402,6 +428,30 @@ class LarVio:
 
     def cov(self):
         N = self.dim; P = np.zeros((N, N)); self.ctx.check(_L().lvk_ekf_get_cov(self._h, _p(P))); return P
+
+    def set_cov(self, P):
+        """lvk_ekf_set_cov: replace the covariance (dim x dim); refused while a deferred update is in flight"""
+        P = np.ascontiguousarray(P, np.float64)
+        if P.ndim != 2 or P.shape[0] != P.shape[1]:
+            raise ValueError("set_cov: a square matrix is expected")
+        self.ctx.check(_L().lvk_ekf_set_cov(self._h, _p(P), P.shape[0]))
+
+    def set_indefinite_policy(self, policy):
+        """lvk_ekf_set_indefinite_policy: INDEFINITE_FAIL (0, the default: LVK_ERR_NUMERIC, the handle stays failed) or INDEFINITE_LDLT
+        (1: that update runs again through the pivoted LDL^T, as the reference does, and the filter goes on)"""
+        self.ctx.check(_L().lvk_ekf_set_indefinite_policy(self._h, int(policy)))
+
+    def last_update(self):
+        """lvk_ekf_last_update: (H, r, P, state30) - the stacked system the most recent update read, with covariance and state as they
+        are now; also on a handle that failed with LVK_ERR_NUMERIC (then: what that update started from)"""
+        m, n = C.c_int(0), C.c_int(0)
+        self.ctx.check(_L().lvk_ekf_last_update(self._h, C.byref(m), C.byref(n), None, None, None, None))
+        H = np.zeros((m.value, n.value)); r = np.zeros(m.value); P = np.zeros((n.value, n.value)); s = np.zeros(30)
+        self.ctx.check(_L().lvk_ekf_last_update(self._h, C.byref(m), C.byref(n), _p(H), _p(r), _p(P), _p(s)))
+        return H, r, P, s
+
+    def indefinite_fallbacks(self):
+        return int(_L().lvk_ekf_indefinite_fallbacks(self._h))
 
     def cov_imu(self, n=9):
         """the covariance's leading n x n block (n <= 16): what getPpose / getPvel read, served without moving the matrix"""
