@@ -253,13 +253,25 @@ def cov_append_features(ctx, P, n, H1, H2, r1, dx, sigma2):
     return ctx.to_host(dP, np.float64, P.shape), ctx.to_host(dxn, np.float64, (nn,))
 
 
-def compress_qr(ctx, H, r):
+def _padded_qr(H, r, ld):
+    """[H | r] as the filter hands it to a compression: H with leading dimension ld in a buffer of rows + 2 rows, r in one of rows + 2
+    entries, NaN everywhere outside"""
+    return _padded(H, ld, H.shape[0] + 2), np.concatenate([r, np.full(2, np.nan)])
+
+
+def compress_qr(ctx, H, r, ld=None):
+    """lvk_ekf_compress_qr on host arrays -> (H', r').  ld: the buffers of _padded_qr; the whole buffers are then returned with the
+    number of rows the call left: (H buffer, r buffer, rows_out)."""
     H = np.array(H, np.float64, order="C"); r = np.array(r, np.float64)
     rows, cols = H.shape
+    if ld is not None:
+        H, r = _padded_qr(H, r, ld)
     dH, dr = ctx.to_device(H), ctx.to_device(r)
     out = C.c_int(0)
-    ctx.check(_L().lvk_ekf_compress_qr(ctx.h, _p(dH), cols, rows, cols, _p(dr), C.byref(out)))
+    ctx.check(_L().lvk_ekf_compress_qr(ctx.h, _p(dH), H.shape[1], rows, cols, _p(dr), C.byref(out)))
     k = out.value
+    if ld is not None:
+        return ctx.to_host(dH, np.float64, H.shape), ctx.to_host(dr, np.float64, r.shape), k
     return ctx.to_host(dH, np.float64, (rows, cols))[:k].copy(), ctx.to_host(dr, np.float64, (rows,))[:k].copy()
 
 
@@ -290,15 +302,20 @@ def qr_plan(N, groups):
     return levels, fin.value
 
 
-def compress_qr_groups(ctx, H, r, groups):
-    """lvk_ekf_compress_qr_groups on host arrays: H (rows x cols), r, groups = [(rows, ascending column list), ...] -> (H', r')"""
+def compress_qr_groups(ctx, H, r, groups, ld=None):
+    """lvk_ekf_compress_qr_groups on host arrays: H (rows x cols), r, groups = [(rows, ascending column list), ...] -> (H', r').
+    ld: as compress_qr."""
     H = np.ascontiguousarray(H, np.float64); r = np.ascontiguousarray(r, np.float64)
     rows, cols = H.shape
+    if ld is not None:
+        H, r = _padded_qr(H, r, ld)
     gr, off, gc = _group_arrays(groups)
     dH = ctx.to_device(H); dr = ctx.to_device(r)
     out = C.c_int(0)
-    ctx.check(_L().lvk_ekf_compress_qr_groups(ctx.h, _p(dH), cols, rows, cols, _p(dr), len(groups), _p(gr), _p(off), _p(gc), C.byref(out)))
+    ctx.check(_L().lvk_ekf_compress_qr_groups(ctx.h, _p(dH), H.shape[1], rows, cols, _p(dr), len(groups), _p(gr), _p(off), _p(gc), C.byref(out)))
     k = out.value
+    if ld is not None:
+        return ctx.to_host(dH, np.float64, H.shape), ctx.to_host(dr, np.float64, r.shape), k
     return ctx.to_host(dH, np.float64, (rows, cols))[:k].copy(), ctx.to_host(dr, np.float64, (rows,))[:k].copy()
 
 

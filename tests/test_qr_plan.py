@@ -5,6 +5,8 @@ to, and every node's column union must fit the Gram a workgroup holds in LDS.  t
 import numpy as np
 import pytest
 
+from tests.qr_ref import emulate, lds_bytes
+
 
 def _msckf_like(seed, n_feat, n_clones, leg=22, track=6, n_state_feat=0, burst=False):
     """groups and a matching random H for `n_feat` MSCKF features (2 M - 3 rows, columns 15..21 + 6-blocks of M consecutive clones
@@ -29,32 +31,6 @@ def _msckf_like(seed, n_feat, n_clones, leg=22, track=6, n_state_feat=0, burst=F
     return N, groups, H, r
 
 
-def _lds_bytes(rows, ncols, N):
-    return 8 * ((ncols + 1) * (rows | 1) + ncols + 2) + 4 * N + 16
-
-
-def emulate(levels, H, r):
-    """what k_qr_sparse has to compute, node by node"""
-    N = H.shape[1]
-    for L in levels:
-        out_rows = sum(b["out_rows"] for b in L["blocks"])
-        Ho = np.zeros((out_rows, N)); ro = np.zeros(out_rows)
-        for b in L["blocks"]:
-            A = H[b["in_start"]:b["in_start"] + b["in_rows"]]; a = r[b["in_start"]:b["in_start"] + b["in_rows"]]
-            if b["copy"]:
-                Ho[b["out_start"]:b["out_start"] + b["out_rows"]] = A; ro[b["out_start"]:b["out_start"] + b["out_rows"]] = a
-                continue
-            cols = L["cols"][b["col_off"]:b["col_off"] + b["ncols"]]
-            rest = np.setdiff1d(np.arange(N), cols)
-            assert not np.any(A[:, rest]), "a node's rows are non-zero outside its column union"
-            Q, R = np.linalg.qr(np.column_stack([A[:, cols], a]), mode="reduced")
-            k = b["out_rows"]
-            assert k == min(b["in_rows"], b["ncols"])
-            Ho[b["out_start"]:b["out_start"] + k][:, cols] = R[:k, :-1]; ro[b["out_start"]:b["out_start"] + k] = R[:k, -1]
-        H, r = Ho, ro
-    return H, r
-
-
 @pytest.mark.parametrize("case", ["steady_A", "burst_5", "steady_5", "long_tracks"])
 def test_plan_preserves_the_information_and_fits_the_lds(case):
     from larvio_amd import larvio as lv
@@ -75,7 +51,7 @@ def test_plan_preserves_the_information_and_fits_the_lds(case):
             assert b["in_start"] == start and b["out_start"] == out         # consecutive, nothing skipped
             start += b["in_rows"]; out += b["out_rows"]
             if not b["copy"]:
-                assert b["in_rows"] > b["ncols"] and _lds_bytes(b["in_rows"], b["ncols"], N) <= 152 * 1024
+                assert b["in_rows"] > b["ncols"] and lds_bytes(b["in_rows"], b["ncols"], N) <= 152 * 1024
                 c = L["cols"][b["col_off"]:b["col_off"] + b["ncols"]]
                 assert np.all(np.diff(c) > 0) and c[-1] < N
         assert start == rows and out * 5 <= rows * 4                        # a level removes at least a fifth of the rows
