@@ -12,6 +12,7 @@
 // calib_imu = 0 or 1 (LEG_DIM 22 / 46) — config/euroc.yaml:8-10,105,108 and its calibration variant; anything else is refused.
 #include "lvk_internal.h"
 #include "be_dev.h"
+#include "be_host.h"
 #include "be_host_math.h"
 #include "be_qr.h"
 #include "be_init.h"
@@ -34,31 +35,6 @@
 #define LEG (e->leg)           // LEG_DIM: 22, or 46 with online IMU-intrinsics calibration (larvio.cpp:158-161)
 #define LEG_MAX 46
 #define GRAV 9.81
-
-struct UpdateWs { double* B; int ldb; double* S; int lds; int* info; hipEvent_t ev_a = nullptr, ev_b = nullptr; double* dx_host = nullptr; double* p00_host = nullptr; int* info_host = nullptr; };   // info: the factorisation's report words in device memory, info_host: their mirror in device-mapped host memory (written only when one is set); ev_*: optional bracket around the H P GEMM; dx_host: host-mapped mirror of dx; p00_host: of the updated P's leading 16 x 16 block
-lvk_status lvk_update_core(lvk_context* ctx, double* P, int ldp, int n, const double* H, int ldh, int m, const double* r, double sigma2, double* dx, UpdateWs ws);
-lvk_status lvk_update_ldlt_core(lvk_context* ctx, double* P, int ldp, int n, const double* H, int ldh, int m, const double* r, double sigma2, double* dx, UpdateWs ws, int** d_cnt_out, int** d_perm_out);
-lvk_status lvk_cov_gather(lvk_context* ctx, const double* Pin, int ldin, double* Pout, int ldout, const int* d_idx, int n);
-lvk_status lvk_cov_propagate_augment(lvk_context* ctx, const double* Pin, int ldin, double* Pout, int ldout, int n_out, int pose_rows, int L,
-                                     const double* h_phi, const double* h_q, const double* d_phiq);
-lvk_status lvk_cov_reanchor(lvk_context* ctx, double* P, int ld, int n, const double* d_J, int fc);
-lvk_status lvk_stage_copy2(lvk_context* ctx, void* d_dst0, const void* d_src0, size_t bytes0, void* d_dst1, const void* d_src1, size_t bytes1);
-lvk_status lvk_cov_append_features(lvk_context* ctx, double* P, int ld, int n, int nn, const double* H1, int ldh, const double* H2, const double* r1,
-                                   const double* dx, double sigma2, double* tmp, double* dx_new);
-lvk_status lvk_launch_triangulate(lvk_context* ctx, const TriJob* d_jobs, int n_jobs, const CamPose* d_cams, const int* d_rank, const double* d_z, TriResult* d_out, TriResult* d_out_dev);
-lvk_status lvk_launch_feature_rows(lvk_context* ctx, const FeatJob* d_jobs, int n_jobs, int max_rows, const CloneDev* d_clones, const int* d_rank,
-                                   const double* d_z, const double* d_zv, const double* d_P, int ldp, FilterFlags fl, double* d_staging, int* d_ccols, FeatResult* d_out, FeatResult* d_out_host,
-                                   double* d_Hout, int ldh, int ncols_out, double* d_rout, int obs_stride, int n_clones, const TriResult* d_tri);
-lvk_status lvk_launch_stack_rows(lvk_context* ctx, const FeatResult* d_fout, const StackRow* d_map, int n_rows, const double* d_staging, const int* d_ccols, double* d_H, int ldh, int ncols, double* d_r);
-int lvk_feature_rows_route(int max_rows, int gate_rows_max);
-lvk_status lvk_qr_compress_dev(lvk_context* ctx, double* d_H, int ldh, int rows, int cols, double* d_r, int* rows_out);
-
-double lvk_chi2_005(int dof);
-struct ShardMeta { int job_lo, job_n, k, row_off; };
-#define LVK_SHARD_HDR 256
-lvk_status lvk_shard_pack(lvk_context* ctx, const FeatResult* d_res, int n_res, const double* d_X, int ld, const double* d_rX, int k, int ncols, char* d_send, size_t res_bytes, int rank);
-lvk_status lvk_shard_unpack(lvk_context* ctx, const char* d_recv, size_t bytes_per_rank, size_t res_bytes, const ShardMeta* d_meta, int world, int ncols, int k_max,
-                            FeatResult* d_fout, FeatResult* d_fout_host, double* d_H, int ld, double* d_r, int* d_peer_fail);
 
 // ------------------------------------------------------------------------- host records
 struct Obs { long long sid; double z[2], zv[2]; };
@@ -308,6 +284,7 @@ struct lvk_ekf::Async {
     lvk_status st = LVK_OK; int updated = 0; long n_deferred = 0;
     bool unwaited = false;                              // an update was queued and no call has waited for it yet (caller's thread only)
 };
+// every entry point that reads or changes the filter first waits for the queued update
 static void ekf_quiesce(const lvk_ekf* e)
 {
     lvk_ekf::Async* a = e->async;
@@ -349,9 +326,6 @@ static EkfTrace g_tr;
 #define TRS(k) g_tr.sub(k)
 static const char* const TRS_NAMES[8] = {"update w/o new feature: jobs staged (launch_feature_rows)", "  row slots + groups (push_rows)", "  uploads flushed, row kernel launched (end_defer)",
     "  compression planned / launched", "  update core launched (4 kernels)", "batch_imu: (unused)", "(unused)", "(unused)"};
-
-// Deferred updates (lvk_ekf_process_async): every entry point that reads or changes the filter first waits for the queued update.
-static void ekf_quiesce(const lvk_ekf* e);
 
 // ------------------------------------------------------------------------- small helpers
 // rank of a clone in the window by state id: direct-address table over [first id, last id] (ids only grow; the window spans a few
@@ -481,6 +455,13 @@ static lvk_status cov_gather(lvk_ekf* e, const std::vector<int>& idx)
     if (st != LVK_OK) return st;
     e->cur ^= 1; e->N = n;
     return LVK_OK;
+}
+// P loses the rows / columns marked in drop (N flags)
+static lvk_status cov_drop(lvk_ekf* e, const std::vector<char>& drop)
+{
+    std::vector<int> idx; idx.reserve(e->N);
+    for (int i = 0; i < e->N; ++i) if (!drop[i]) idx.push_back(i);
+    return cov_gather(e, idx);
 }
 static lvk_status cov_delete(lvk_ekf* e, int start, int len)
 {
@@ -1109,7 +1090,7 @@ static lvk_status launch_feature_rows(lvk_ekf* e, std::vector<RowJob>& jobs, con
     const FeatJob* d_j = dev(e, hj); const int* d_r = dev(e, hr); const double* d_z = dev(e, hz); const double* d_v = dev(e, hv);
     const int nj = (int)jobs.size(); const CloneDev* d_cl = e->dv_clones; double* P = e->dP[e->cur];
     FeatResult* d_fh = (FeatResult*)(e->dh_down + e->down_feat);
-    double* Ho = e->d_H; double* ro = e->d_r; const int ldh = e->ld, ncols_out = e->N;       // direct output of the jobs that carry a destination row (set_direct_rows)
+    double* Ho = e->d_H; double* ro = e->d_r; const int ldh = e->ld, ncols_out = e->N;       // direct output of the jobs that carry a destination row (FeatJob::dst_row1, patched by gated_update)
     const int n_cl = (int)e->clones.size();
     const TriResult* d_tri = any_pending ? e->d_tridev : nullptr;      // results of the triangulation queued ahead, by job index (whole-batch launches only)
     if (any_pending && ranges) return lvk_set_error(e->ctx, LVK_ERR_ARG, "internal: device-consumed triangulation in a ranged launch");
@@ -1229,18 +1210,40 @@ static double qr_level_flops(const QrPlanLevel& L)
     }
     return f;
 }
+// a HIP event for a profiling bracket: recycled (prof_free) once its bracket has been read
+static hipEvent_t prof_take_event(lvk_ekf* e)
+{
+    hipEvent_t ev;
+    if (!e->prof_free.empty()) { ev = e->prof_free.back(); e->prof_free.pop_back(); } else hipEventCreate(&ev);
+    return ev;
+}
 // one level of the compression, bracketed by HIP events on the filter's stream when profiling is on (bench: roofline of the TSQR)
 static lvk_status qr_level_launch(lvk_ekf* e, const QrPlanLevel& L, const double* Hin, const double* rin, double* Hout, double* rout, const QrBlock* d_blocks, const int* d_cols, int ncols)
 {
     hipEvent_t a = nullptr, b = nullptr;
     if (e->prof_on) {
-        auto take = [&]() { hipEvent_t ev; if (!e->prof_free.empty()) { ev = e->prof_free.back(); e->prof_free.pop_back(); } else hipEventCreate(&ev); return ev; };
-        a = take(); b = take();
+        a = prof_take_event(e); b = prof_take_event(e);
         hipEventRecord(a, e->ctx->stream);
     }
     lvk_status st = lvk_qr_sparse_level(e->ctx, Hin, e->ld, rin, Hout, e->ld, rout, d_blocks, (int)L.blocks.size(), d_cols, ncols, L.lds, L.max_rows, L.max_cols);
     if (a) { hipEventRecord(b, e->ctx->stream); e->prof_pending.push_back({a, b, qr_level_flops(L), 1, (double)L.in_rows}); }
     return st;
+}
+// all levels of a plan: each level's blocks and column lists go up, the level reads *H / *r and writes their ping-pong partner
+// (d_H <-> d_Hb, d_r <-> d_rb); on return *H / *r name the result
+static lvk_status run_qr_levels(lvk_ekf* e, const std::vector<QrPlanLevel>& levels, double** H, double** r, int ncols)
+{
+    for (const QrPlanLevel& L : levels) {
+        QrBlock* hb = up_alloc<QrBlock>(e, L.blocks.size()); int* hc = up_alloc<int>(e, L.cols.size() + 1);
+        if (!hb || !hc) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "upload arena exhausted");
+        memcpy(hb, L.blocks.data(), sizeof(QrBlock) * L.blocks.size()); memcpy(hc, L.cols.data(), sizeof(int) * L.cols.size());
+        lvk_status st = flush_uploads(e);
+        double* Ho = (*H == e->d_H) ? e->d_Hb : e->d_H; double* ro = (*r == e->d_r) ? e->d_rb : e->d_r;
+        if (st == LVK_OK) st = qr_level_launch(e, L, *H, *r, Ho, ro, dev(e, hb), dev(e, hc), ncols);
+        if (st != LVK_OK) return st;
+        *H = Ho; *r = ro;
+    }
+    return LVK_OK;
 }
 // A rank that fails locally BEFORE the exchange's size is known to it (the layout of an update that admits new in-state features
 // depends on gate results it could not read) cannot post a poisoned block; it tells the transport to break the collective instead:
@@ -1307,17 +1310,8 @@ static lvk_status shard_stage1(lvk_ekf* e, const std::vector<StackRow>& map, std
     double* X = e->d_H; double* rX = e->d_r;
     auto local = [&]() -> lvk_status {
         lvk_status st = stack_rows(e, lmap, e->d_H, ncols, e->d_r);
+        if (st == LVK_OK) st = run_qr_levels(e, my_levels, &X, &rX, ncols);
         if (st != LVK_OK) return st;
-        for (QrPlanLevel& L : my_levels) {
-            QrBlock* hb = up_alloc<QrBlock>(e, L.blocks.size()); int* hc = up_alloc<int>(e, L.cols.size() + 1);
-            if (!hb || !hc) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "upload arena exhausted");
-            memcpy(hb, L.blocks.data(), sizeof(QrBlock) * L.blocks.size()); memcpy(hc, L.cols.data(), sizeof(int) * L.cols.size());
-            st = flush_uploads(e);
-            double* Ho = (X == e->d_H) ? e->d_Hb : e->d_H; double* ro = (rX == e->d_r) ? e->d_rb : e->d_r;
-            if (st == LVK_OK) st = qr_level_launch(e, L, X, rX, Ho, ro, dev(e, hb), dev(e, hc), ncols);
-            if (st != LVK_OK) return st;
-            X = Ho; rX = ro;
-        }
         st = flush_uploads(e);
         if (st == LVK_OK) st = lvk_shard_pack(e->ctx, e->d_fout + hm[me].job_lo, hm[me].job_n, X, e->ld, rX, kk[(size_t)me], ncols, S.d_send, res_bytes, me);
         return st;
@@ -1378,18 +1372,9 @@ static lvk_status dense_update(lvk_ekf* e, int m, std::vector<double>& dx, int e
         }
         if (take && g_tr.on) g_tr.cnt[2]++;
         if (take) {
-            for (QrPlanLevel& L : levels) {
-                QrBlock* hb = up_alloc<QrBlock>(e, L.blocks.size()); int* hc = up_alloc<int>(e, L.cols.size() + 1);
-                if (!hb || !hc) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "upload arena exhausted");
-                memcpy(hb, L.blocks.data(), sizeof(QrBlock) * L.blocks.size()); memcpy(hc, L.cols.data(), sizeof(int) * L.cols.size());
-                st = flush_uploads(e);
-                double* Ho = (H == e->d_H) ? e->d_Hb : e->d_H; double* ro = (r == e->d_r) ? e->d_rb : e->d_r;
-                if (st == LVK_OK) st = qr_level_launch(e, L, H, r, Ho, ro, dev(e, hb), dev(e, hc), e->N);
-                if (st != LVK_OK) return st;
-                H = Ho; r = ro;
-                e->qr_stats[1]++;
-            }
-            e->qr_stats[0]++; e->qr_stats[2] += m; e->qr_stats[3] += m2;
+            st = run_qr_levels(e, levels, &H, &r, e->N);
+            if (st != LVK_OK) return st;
+            e->qr_stats[0]++; e->qr_stats[1] += (long)levels.size(); e->qr_stats[2] += m; e->qr_stats[3] += m2;
             m = m2;
         }
     }
@@ -1405,8 +1390,7 @@ static lvk_status dense_update(lvk_ekf* e, int m, std::vector<double>& dx, int e
     ws.p00_host = (double*)(e->dh_down + e->down_p00);
     e->last.H = H; e->last.r = r; e->last.m = m; e->last.n = e->N; e->redo = nullptr;
     if (e->prof_on && m > 0) {
-        auto take = [&]() { hipEvent_t ev; if (!e->prof_free.empty()) { ev = e->prof_free.back(); e->prof_free.pop_back(); } else hipEventCreate(&ev); return ev; };
-        ws.ev_a = take(); ws.ev_b = take();
+        ws.ev_a = prof_take_event(e); ws.ev_b = prof_take_event(e);
         e->prof_pending.push_back({ws.ev_a, ws.ev_b, 2.0 * m * (double)e->N * (double)e->N, 0, 0.0});
     }
 #ifdef LVK_NPD_DEBUG   // debug builds only: the stacked system of every small update, as the update kernels are about to read it
@@ -1450,6 +1434,60 @@ static inline void grid_add(lvk_ekf* e, int code, int cells)
     if (code >= 0 && code < cells) e->grid_count[(size_t)code]++;
     else if (e->reference_grid) e->grid_phantom[code]++;
 }
+// The gated update in one sync.  No feature enters the state, so nothing on the host depends on a gate result before the update is
+// launched: every candidate row gets its slot, the device zeroes the rows of rejected jobs (a zero row with a zero residual leaves
+// the update unchanged), and gate results (jobs[].res), pending triangulation answers and dx come back in ONE sync.
+// order: the job index ranges in stacking order - MSCKF jobs first, then the tracked in-state features' two rows each:
+// H_o = [H_msckf ; H_ekf], the reference's order (larvio.cpp:1612-1626).  Unsharded, the row kernel (held back by begin_defer until
+// the slots are known) writes its rows straight into H_o (FeatJob::dst_row1); sharded, this rank builds the rows of its slice of
+// the jobs and shard_stage1 exchanges the compressed blocks.  tr: the trace slots that close after the row launch is staged (-1:
+// none), after the update is launched and after the sync.  retire: state ids whose observations leave every feature once the jobs
+// are staged (pruning: the clones about to go) - host work done here, while the device still runs what was queued ahead.
+static void drop_observations(lvk_ekf* e, const long long* sids, int n) { for (auto kv : e->map) for (int k = 0; k < n; ++k) kv.second.erase(sids[k]); }
+static lvk_status gated_update(lvk_ekf* e, std::vector<RowJob>& jobs, const size_t (&order)[2][2], const int (&tr)[3], std::vector<double>& dx,
+                               const long long* retire = nullptr, int n_retire = 0)
+{
+    const int N = e->N;
+    const bool sharded = e->shard.fn != nullptr;
+    std::vector<size_t> jb; JobRanges own;
+    if (sharded) { shard_bounds(jobs, 0, jobs.size(), e->shard.world, jb); own.push_back({jb[(size_t)e->shard.rank], jb[(size_t)e->shard.rank + 1]}); }
+    begin_defer(e);                                     // the jobs (and their row slots) go up in one copy
+    lvk_status st = launch_feature_rows(e, jobs, sharded ? &own : nullptr);
+    if (tr[0] >= 0) TR(tr[0]);
+    TRS(0);
+    if (st != LVK_OK && !sharded) { end_defer(e); return st; }      // sharded: a local failure still goes through the exchange (shard_stage1, pre_fail)
+    std::vector<StackRow> map_o; std::vector<RowGroup> grp;
+    int m = 0;
+    for (const auto& rg : order)
+        for (size_t k = rg[0]; k < rg[1]; ++k) {
+            const int r = job_rows(jobs[k]);
+            push_rows(map_o, jobs[k], job_first_row(jobs[k]), r, m, (int)k, &grp, e, N, sharded ? shard_owner(jb, k) : 0);
+            if (!sharded) jobs[k].hdev->dst_row1 = m + 1;
+            m += r;
+        }
+    // k_feature_rows does not bound dst_row1 itself: no job may keep a slot beyond the hrows rows of d_H (the same on every rank)
+    if (m > e->hrows) { for (RowJob& j : jobs) if (j.hdev) j.hdev->dst_row1 = 0; end_defer(e); return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "too many measurement rows (%d)", m); }
+    TRS(1);
+    drop_observations(e, retire, n_retire);
+    { lvk_status s2 = end_defer(e); if (st == LVK_OK) st = s2; }
+    TRS(2);
+    if (sharded) { st = shard_stage1(e, map_o, grp, N, &jb, &m, st); e->shard.stats[2]++; }
+    if (st == LVK_OK) st = dense_update(e, m, dx, 0, &grp);
+    TR(tr[1]);
+    if (st == LVK_OK) st = fetch_feature_results(e, jobs, dx.data(), (size_t)N);
+    if (st != LVK_OK) return st;
+    TR(tr[2]);
+    return LVK_OK;
+}
+// ... and its effect on the host state, when any row passed its gate; counter: 0 feature update, 1 pruning update
+static void gated_update_apply(lvk_ekf* e, const std::vector<double>& dx, int accepted, int counter)
+{
+    if (accepted <= 0) return;
+    inject(e, dx.data());
+    e->last_update_time = e->s.t;
+    e->counters[counter]++;
+    e->counters[2] = accepted;
+}
 // removeLostFeatures when no feature can enter the state in this update (the usual message: the augmentation grid is full, or no
 // track has reached max_track_len in a free cell) and the update is not sharded: NOTHING on the host depends on a device result
 // before the update is launched.  The triangulations of the features that need one are queued and consumed ON THE DEVICE by the row
@@ -1487,7 +1525,6 @@ static lvk_status remove_lost_fast(lvk_ekf* e, const std::vector<long long>& ekf
         for (const Pick& pk : picks) { bound += 2L * (long)pk.f->obs.size() - 3; pending |= pk.tri >= 0; }
         if (bound > (long)e->hrows && pending) { *fall_back = true; return LVK_OK; }
     }
-    const int N = e->N;
     std::vector<RowJob> jobs; jobs.reserve(ekf_ids.size() + picks.size());
     for (long long id : ekf_ids) { Feature& f = e->map[id]; RowJob r; r.f = &f; r.type = JOB_EKF_TRACKED; r.sids = {e->imu_id}; r.want_gate = true; r.dof = 2; jobs.push_back(r); }
     for (const Pick& pk : picks) {
@@ -1500,25 +1537,9 @@ static lvk_status remove_lost_fast(lvk_ekf* e, const std::vector<long long>& ekf
     if (st != LVK_OK) return st;
     TR(TR_RLF_TRI);
     TR(TR_RLF_TRIAGE);
-    begin_defer(e);                                     // the jobs go up in one copy; the row kernel writes its rows straight into H_o
-    st = launch_feature_rows(e, jobs);
-    TRS(0);
-    if (st != LVK_OK) { end_defer(e); return st; }
-    std::vector<StackRow> map_o; std::vector<RowGroup> grp;
-    int rows_m = 0, rows_e = 0;
-    for (size_t k = (size_t)n_ekf; k < jobs.size(); ++k) { const int r = job_rows(jobs[k]); push_rows(map_o, jobs[k], job_first_row(jobs[k]), r, rows_m, (int)k, &grp, e, N, 0); jobs[k].hdev->dst_row1 = rows_m + 1; rows_m += r; }
-    for (size_t k = 0; k < (size_t)n_ekf; ++k) { push_rows(map_o, jobs[k], 0, 2, rows_m + rows_e, (int)k, &grp, e, N, 0); jobs[k].hdev->dst_row1 = rows_m + rows_e + 1; rows_e += 2; }
-    const int m = rows_m + rows_e;
-    if (m > e->hrows) { for (RowJob& j : jobs) if (j.hdev) j.hdev->dst_row1 = 0; end_defer(e); return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "too many measurement rows (%d)", m); }
-    TRS(1);
-    st = end_defer(e);
-    TRS(2);
     std::vector<double> dx;
-    if (st == LVK_OK) st = dense_update(e, m, dx, 0, &grp);
-    TR(TR_RLF_UPD);
-    if (st == LVK_OK) st = fetch_feature_results(e, jobs, dx.data(), (size_t)N);
+    st = gated_update(e, jobs, {{(size_t)n_ekf, jobs.size()}, {0, (size_t)n_ekf}}, {-1, TR_RLF_UPD, TR_RLF_DX}, dx);
     if (st != LVK_OK) return st;
-    TR(TR_RLF_DX);
     int accepted = 0;
     for (size_t k = (size_t)n_ekf; k < jobs.size(); ++k) {
         const Pick& pk = picks[k - (size_t)n_ekf];
@@ -1531,12 +1552,7 @@ static lvk_status remove_lost_fast(lvk_ekf* e, const std::vector<long long>& ekf
         e->map.erase(pk.f->id);                          // used (:2240-2246)
     }
     for (size_t k = 0; k < (size_t)n_ekf; ++k) if (gate_ok(e, jobs[k])) accepted += 2;
-    if (accepted > 0) {
-        inject(e, dx.data());
-        e->last_update_time = e->s.t;
-        e->counters[0]++;
-        e->counters[2] = accepted;
-    }
+    gated_update_apply(e, dx, accepted, 0);
     TR(TR_RLF_INJ);
     return LVK_OK;
 }
@@ -1556,9 +1572,7 @@ static lvk_status remove_lost_features(lvk_ekf* e)
     if (!ekf_lost.empty()) {                                     // rmLostFeaturesCov (:3296-3348): all lost columns in one gather
         std::vector<char> drop(e->N, 0);
         for (long long id : ekf_lost) drop[LEG + 6 * (int)e->clones.size() + fs_rank(e, id)] = 1;
-        std::vector<int> idx; idx.reserve(e->N);
-        for (int i = 0; i < e->N; ++i) if (!drop[i]) idx.push_back(i);
-        st = cov_gather(e, idx);
+        st = cov_drop(e, drop);
         if (st != LVK_OK) return st;
         for (long long id : ekf_lost) {
             const Feature& f = e->map.at(id);                    // lost_slam_features (:3342): kept for getStableMapPointPositions
@@ -1684,46 +1698,13 @@ static lvk_status remove_lost_features(lvk_ekf* e)
         // it is not used by JOB_EKF_NEW rows (the feature column never reaches H_o), so any value works here.
         TR(TR_RLF_TRIAGE);
         if (ekf_new.empty()) {
-            // No feature enters the state in this update, so nothing on the host depends on the gate before the update is
-            // launched: every candidate row gets its slot, the device zeroes the rows of rejected features, and gate results and
-            // dx come back in ONE sync.
-            const bool sharded = e->shard.fn != nullptr;
-            std::vector<size_t> jb; JobRanges own;
-            if (sharded) { shard_bounds(jobs, 0, jobs.size(), e->shard.world, jb); own.push_back({jb[(size_t)e->shard.rank], jb[(size_t)e->shard.rank + 1]}); }
-            begin_defer(e);                             // the jobs and the stacking map go up in one copy
-            st = launch_feature_rows(e, jobs, sharded ? &own : nullptr);
-            TRS(0);
-            if (st != LVK_OK && !sharded) { end_defer(e); return st; }
-            lvk_status st_rows = st;                    // sharded: a local failure still goes through the exchange (shard_stage1, pre_fail)
-            std::vector<StackRow> map_o; std::vector<RowGroup> grp;
-            int rows_m = 0, rows_e = 0;
-            auto own_of = [&](size_t k) { return sharded ? shard_owner(jb, k) : 0; };
-            // unsharded: the row kernel (still held back by begin_defer) writes its rows straight into H_o - the slots are known now
-            const bool direct = !sharded;
-            for (size_t k = j_msckf; k < jobs.size(); ++k) { const int r = job_rows(jobs[k]); push_rows(map_o, jobs[k], job_first_row(jobs[k]), r, rows_m, (int)k, &grp, e, N, own_of(k)); if (direct) jobs[k].hdev->dst_row1 = rows_m + 1; rows_m += r; }
-            for (size_t k = j_ekf; k < j_msckf; ++k) { push_rows(map_o, jobs[k], 0, 2, rows_m + rows_e, (int)k, &grp, e, N, own_of(k)); if (direct) jobs[k].hdev->dst_row1 = rows_m + rows_e + 1; rows_e += 2; }
-            int m = rows_m + rows_e;
-            if (m > e->hrows) { for (RowJob& j : jobs) if (j.hdev) j.hdev->dst_row1 = 0; end_defer(e); return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "too many measurement rows (%d)", m); }   // (the same on every rank)
-            TRS(1);
-            if (!sharded && !direct) st = stack_rows(e, map_o, e->d_H, N, e->d_r);
-            { lvk_status s2 = end_defer(e); if (st == LVK_OK) st = s2; }
-            TRS(2);
-            if (sharded) { st = shard_stage1(e, map_o, grp, N, &jb, &m, st_rows != LVK_OK ? st_rows : st); e->shard.stats[2]++; }
-            std::vector<double> dx;
-            if (st == LVK_OK) st = dense_update(e, m, dx, 0, &grp);
-            TR(TR_RLF_UPD);
-            if (st == LVK_OK) st = fetch_feature_results(e, jobs, dx.data(), (size_t)N);
+            std::vector<double> dx;                     // no feature enters the state: gate results and dx in one sync (j_ekf == 0)
+            st = gated_update(e, jobs, {{j_msckf, jobs.size()}, {j_ekf, j_msckf}}, {-1, TR_RLF_UPD, TR_RLF_DX}, dx);
             if (st != LVK_OK) return st;
-            TR(TR_RLF_DX);
             int accepted = 0;
             for (size_t k = j_msckf; k < jobs.size(); ++k) if (gate_ok(e, jobs[k])) accepted += job_rows(jobs[k]);
             for (size_t k = j_ekf; k < j_msckf; ++k) if (gate_ok(e, jobs[k])) accepted += 2;
-            if (accepted > 0) {
-                inject(e, dx.data());
-                e->last_update_time = e->s.t;
-                e->counters[0]++;
-                e->counters[2] = accepted;
-            }
+            gated_update_apply(e, dx, accepted, 0);
             for (long long id : msckf) e->map.erase(id);
             TR(TR_RLF_INJ);
             return LVK_OK;
@@ -1902,6 +1883,13 @@ static lvk_status update_feature_cov_1d(lvk_ekf* e, const Feature& f, long long 
     return st;
 }
 
+// the feature seen from its new anchor clone: pn = R_cam^T (p - p_cam), inv_depth = 1 / pn.z
+static void reanchor_depth(Feature& f, const Clone& cn, double* pn)
+{
+    double R[9], d[3] = {f.position[0] - cn.p_cam[0], f.position[1] - cn.p_cam[1], f.position[2] - cn.p_cam[2]};
+    quat_to_rot(cn.q_cam, R); m3t_v(R, d, pn);
+    f.inv_depth = 1 / pn[2];
+}
 static lvk_status prune_imu_state_buffer(lvk_ekf* e)
 {
     long long rm[2]; int nrm = 0;
@@ -1925,10 +1913,7 @@ static lvk_status prune_imu_state_buffer(lvk_ekf* e)
         if (f.in_state) {
             if (anchor_involved) {
                 const long long new_id = get_new_anchor_id(e, f, inv.data(), (int)inv.size());
-                const Clone* cn = &e->clones[clone_rank(e, new_id)];
-                double R[9], d[3] = {f.position[0] - cn->p_cam[0], f.position[1] - cn->p_cam[1], f.position[2] - cn->p_cam[2]}, pn[3];
-                quat_to_rot(cn->q_cam, R); m3t_v(R, d, pn);
-                f.inv_depth = 1 / pn[2];
+                double pn[3]; reanchor_depth(f, e->clones[clone_rank(e, new_id)], pn);
                 f.obs_anchor[0] = pn[0] / pn[2]; f.obs_anchor[1] = pn[1] / pn[2];
                 st = update_feature_cov_1d(e, f, f.id_anchor, new_id);
                 if (st != LVK_OK) return st;
@@ -1937,10 +1922,7 @@ static lvk_status prune_imu_state_buffer(lvk_ekf* e)
         } else {
             if (f.is_initialized && anchor_involved) {
                 const long long new_id = get_new_anchor_id(e, f, inv.data(), (int)inv.size());
-                const Clone* cn = &e->clones[clone_rank(e, new_id)];
-                double R[9], d[3] = {f.position[0] - cn->p_cam[0], f.position[1] - cn->p_cam[1], f.position[2] - cn->p_cam[2]}, pn[3];
-                quat_to_rot(cn->q_cam, R); m3t_v(R, d, pn);
-                f.inv_depth = 1 / pn[2];
+                double pn[3]; reanchor_depth(f, e->clones[clone_rank(e, new_id)], pn);
                 const int oi = f.find(new_id);
                 if (oi >= 0) { f.obs_anchor[0] = f.obs[oi].z[0]; f.obs_anchor[1] = f.obs[oi].z[1]; } else { f.obs_anchor[0] = 0; f.obs_anchor[1] = 0; }
                 f.id_anchor = new_id;
@@ -1993,48 +1975,21 @@ static lvk_status prune_imu_state_buffer(lvk_ekf* e)
         if (!clones_uploaded) { st = upload_clones(e); if (st != LVK_OK) return st; }
         std::vector<RowJob> jobs;
         for (Use* u : used) { RowJob r; r.f = u->f; r.type = JOB_MSCKF; r.sids = u->inv; r.want_gate = true; r.dof = 2 * (int)u->inv.size() - 3; r.tri_pending = tri_on_device && u->tri >= 0 && !u->f->is_initialized; jobs.push_back(r); }
-        // measurementUpdate_msckf (:1420-1602), gate decided on the device (see remove_lost_features): one sync for gate + dx
-        const bool sharded = e->shard.fn != nullptr;
-        std::vector<size_t> jb; JobRanges own;
-        if (sharded) { shard_bounds(jobs, 0, jobs.size(), e->shard.world, jb); own.push_back({jb[(size_t)e->shard.rank], jb[(size_t)e->shard.rank + 1]}); }
-        begin_defer(e);
-        st = launch_feature_rows(e, jobs, sharded ? &own : nullptr);
-        if (st != LVK_OK && !sharded) { end_defer(e); return st; }
-        const lvk_status st_rows = st;                       // sharded: a local failure still goes through the exchange (shard_stage1, pre_fail)
-        TR(TR_PR_ROWS);
-        std::vector<StackRow> map_o; std::vector<RowGroup> grp; int rows = 0;
-        const bool direct = !sharded;      // as in remove_lost_features: the row kernel writes H_o itself
-        for (size_t k = 0; k < jobs.size(); ++k) { const int r = job_rows(jobs[k]); push_rows(map_o, jobs[k], job_first_row(jobs[k]), r, rows, (int)k, &grp, e, e->N, sharded ? shard_owner(jb, k) : 0); if (direct) jobs[k].hdev->dst_row1 = rows + 1; rows += r; }
-        for (auto kv : e->map) for (int k = 0; k < nrm; ++k) kv.second.erase(rm[k]);
-        {
-            if (!sharded && !direct) st = stack_rows(e, map_o, e->d_H, e->N, e->d_r);
-            { lvk_status s2 = end_defer(e); if (st == LVK_OK) st = s2; }
-            if (sharded) { st = shard_stage1(e, map_o, grp, e->N, &jb, &rows, st_rows != LVK_OK ? st_rows : st); e->shard.stats[2]++; }
-            std::vector<double> dx;
-            if (st == LVK_OK) st = dense_update(e, rows, dx, 0, &grp);
-            TR(TR_PR_UPD);
-            if (st == LVK_OK) st = fetch_feature_results(e, jobs, dx.data(), (size_t)e->N);
-            if (st != LVK_OK) return st;
-            TR(TR_PR_DX);
-            int accepted = 0;
-            for (size_t k = 0; k < jobs.size(); ++k) {
-                if (jobs[k].tri_pending) {               // initializePosition_AssignAnchor's result (:2420-2440), read now
-                    const TriAns a = tri_answer(e, reqs[(size_t)used[k]->tri], k);
-                    apply_tri(used[k]->f, 1, a);
-                    if (!a.ok) continue;                  // not used in this update (its rows were zeroed on the device)
-                }
-                if (gate_ok(e, jobs[k])) accepted += job_rows(jobs[k]);
+        // measurementUpdate_msckf (:1420-1602), gate decided on the device (gated_update): one sync for gate + dx
+        std::vector<double> dx;
+        st = gated_update(e, jobs, {{0, jobs.size()}, {0, 0}}, {TR_PR_ROWS, TR_PR_UPD, TR_PR_DX}, dx, rm, nrm);
+        if (st != LVK_OK) return st;
+        int accepted = 0;
+        for (size_t k = 0; k < jobs.size(); ++k) {
+            if (jobs[k].tri_pending) {                   // initializePosition_AssignAnchor's result (:2420-2440), read now
+                const TriAns a = tri_answer(e, reqs[(size_t)used[k]->tri], k);
+                apply_tri(used[k]->f, 1, a);
+                if (!a.ok) continue;                      // not used in this update (its rows were zeroed on the device)
             }
-            if (accepted > 0) {
-                inject(e, dx.data());
-                e->last_update_time = e->s.t;
-                e->counters[1]++;
-                e->counters[2] = accepted;
-            }
+            if (gate_ok(e, jobs[k])) accepted += job_rows(jobs[k]);
         }
-    } else {
-        for (auto kv : e->map) for (int k = 0; k < nrm; ++k) kv.second.erase(rm[k]);
-    }
+        gated_update_apply(e, dx, accepted, 1);
+    } else drop_observations(e, rm, nrm);
     {   // both clones' rows/columns leave P in ONE gather (the reference deletes them one after the other, :2563-2638)
         std::vector<char> drop(e->N, 0);
         bool any = false;
@@ -2045,9 +2000,7 @@ static lvk_status prune_imu_state_buffer(lvk_ekf* e)
             any = true;
         }
         if (any) {
-            std::vector<int> idx; idx.reserve(e->N);
-            for (int i = 0; i < e->N; ++i) if (!drop[i]) idx.push_back(i);
-            st = cov_gather(e, idx);
+            st = cov_drop(e, drop);
             if (st != LVK_OK) return st;
             for (int k = 0; k < nrm; ++k) { const int seq = clone_rank(e, rm[k]); if (seq >= 0) { e->clones.erase(e->clones.begin() + seq); e->ranks_dirty = true; e->rcam_valid = false; } }
         }
@@ -2305,7 +2258,10 @@ lvk_status lvk_ekf_create(lvk_context* ctx, const lvk_ekf_config* cfg, lvk_ekf**
     const int max_c = 7 + 6 + 6 * (c.sw_size + 2) + 1;
     e->staging_cap = std::min((size_t)2 * e->feat_cap * ((size_t)2 * (c.sw_size + 2) * max_c * 2 + 2 * (c.sw_size + 2)), (size_t)48 << 20);   // doubles; checked per batch
     e->ccols_cap = (size_t)2 * e->feat_cap * max_c;
-    // stacked rows before compression: every feature of a message can contribute 2M-3 rows (18,000 at 2000 tracks, M = 6)
+    // stacked rows before compression: every feature of a message can contribute 2M-3 rows (18,000 at 2000 tracks, M = 6).
+    // The row kernel's direct output relies on it: d_H / d_r have hrows rows and k_feature_rows does not bound FeatJob::dst_row1,
+    // so gated_update refuses a layout of more rows.  (A pruning update cannot get there: one row per job, at most 2 * feat_cap jobs
+    // per batch, and 2 * feat_cap = max(2048, 8 * max_features) <= hrows.)
     e->hrows = std::max(8 * e->rows_cap, 12 * c.max_features);
     const size_t hrows = (size_t)e->hrows;
     bool ok = dalloc(&e->dP[0], (size_t)e->ld * e->ld) && dalloc(&e->dP[1], (size_t)e->ld * e->ld) && dalloc(&e->d_idx, e->ld) && dalloc(&e->d_phiq, 2 * LEG_MAX * LEG_MAX) &&
@@ -2786,7 +2742,7 @@ lvk_status lvk_vio_process_deferred(lvk_frontend* fe, lvk_ekf* ekf, const lvk_im
 // caller's head is put right at once); (2) submit() only guesses while td is quiet: the largest |td step| of the last eight updates,
 // times the updates that can be in flight, must stay well inside the margin - while td is still converging from a bad initial value
 // every frame waits for its count.
-static double now_us_fwd();
+static double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 struct lvk_vio_pipe {
     lvk_frontend* fe; lvk_ekf* ekf;
     std::vector<lvk_imu> imu; size_t head = 0;          // the driver's imu_msg_buffer = imu[head..) as the CALLER's thread sees it (early counts applied)
@@ -2816,7 +2772,7 @@ struct lvk_vio_pipe {
     double t_busy = 0, t_idle = 0, t_submit_wait = 0, t_fe = 0;
     struct Ev { double t; int what; };                    // LVK_PIPE_LOG=<file>: event log (0 submit begin, 1 wait done, 2 front-end done,
     std::vector<Ev> log; bool logging = false;            //  3 job queued [4 precounted], 5 job start, 6 job end)
-    void ev(int what) { if (logging) log.push_back({now_us_fwd(), what}); }   // LVK_EKF_TRACE: where the two threads spend their time (us)
+    void ev(int what) { if (logging) log.push_back({now_us(), what}); }   // LVK_EKF_TRACE: where the two threads spend their time (us)
     bool td_quiet() const
     {   // may submit() trust the published td for a count?  (depth + 1) updates can move td before the counted one starts
         // The largest |td step| of the last TD_HIST updates, times td_factor, times the updates in flight, must stay inside the margin.
@@ -2832,8 +2788,6 @@ struct lvk_vio_pipe {
         return td_factor * (depth + 1) * mx < td_margin;
     }
 };
-static double now_us_fwd() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-static double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 static void pipe_on_consumed(void* user, int n)
 {   // fired by the filter once per call, when the number of samples it erases is final (before any GPU work)

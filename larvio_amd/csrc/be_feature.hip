@@ -13,6 +13,7 @@
 // blocks that are ~85 % zeros and multiplies them against the full P for every gate.
 #include "lvk_internal.h"
 #include "be_dev.h"
+#include "be_host.h"
 #include "lvk_wave.h"
 #include <vector>
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -533,8 +534,6 @@ lvk_status lvk_launch_stack_rows(lvk_context* ctx, const FeatResult* d_fout, con
 }
 
 // ========================================================================= stage-level C ABI (parity tests, single-stage callers)
-double lvk_chi2_005(int dof);
-
 extern "C" lvk_status lvk_triangulate(lvk_context* ctx, const lvk_cam_pose* h_poses, const double* h_obs, int n, int use_position,
                                       const double* h_position_in, int* ok_out, double* h_position, double* h_solution, double* h_inv_depth,
                                       double* h_obs_anchor)

@@ -1,0 +1,44 @@
+// be_host.h — what the back-end's translation units call in one another (host side): the records they pass by value and the
+// prototype of every lvk_* function that one be_*.hip / backend.hip defines and another calls.  Definers include it as well, so
+// the compiler checks each definition against the prototype its callers see.  (The structure-aware compression has be_qr.h.)
+#pragma once
+#include "lvk_internal.h"
+#include "be_dev.h"
+
+// Workspace of one measurement update, passed by value.  B: m x (n+1), S: m x m.  info: the factorisation's report words, in DEVICE
+// memory (the final GEMM reads them: GemmRider::gate); info_host: their mirror in device-mapped host memory, written only when one
+// is set; ev_*: optional bracket around the H P GEMM; dx_host: host-mapped mirror of dx; p00_host: of the updated P's leading
+// 16 x 16 block
+struct UpdateWs { double* B; int ldb; double* S; int lds; int* info; hipEvent_t ev_a = nullptr, ev_b = nullptr; double* dx_host = nullptr; double* p00_host = nullptr; int* info_host = nullptr; };
+// sharded update: rank g's jobs [job_lo, job_lo + job_n) and its k compressed rows, stacked from row_off (host writes, k_shard_unpack reads)
+struct ShardMeta { int job_lo, job_n, k, row_off; };
+#define LVK_SHARD_HDR 256                // bytes of the header every rank's block starts with (be_shard.hip)
+
+// be_linalg.hip
+lvk_status lvk_stage_copy2(lvk_context* ctx, void* d_dst0, const void* d_src0, size_t bytes0, void* d_dst1, const void* d_src1, size_t bytes1);
+lvk_status lvk_update_core(lvk_context* ctx, double* P, int ldp, int n, const double* H, int ldh, int m, const double* r, double sigma2, double* dx, UpdateWs ws);
+lvk_status lvk_update_ldlt_core(lvk_context* ctx, double* P, int ldp, int n, const double* H, int ldh, int m, const double* r, double sigma2, double* dx, UpdateWs ws, int** d_cnt_out, int** d_perm_out);
+lvk_status lvk_cov_gather(lvk_context* ctx, const double* Pin, int ldin, double* Pout, int ldout, const int* d_idx, int n);
+lvk_status lvk_cov_propagate_augment(lvk_context* ctx, const double* Pin, int ldin, double* Pout, int ldout, int n_out, int pose_rows, int L,
+                                     const double* h_phi, const double* h_q, const double* d_phiq);
+lvk_status lvk_cov_reanchor(lvk_context* ctx, double* P, int ld, int n, const double* d_J, int fc);
+lvk_status lvk_cov_append_features(lvk_context* ctx, double* P, int ld, int n, int nn, const double* H1, int ldh, const double* H2, const double* r1,
+                                   const double* dx, double sigma2, double* tmp, double* dx_new);
+// be_ldlt.hip
+size_t lvk_ldlt_lds_bytes(int m);
+lvk_status lvk_ldlt_factor_solve(lvk_context* ctx, double* S, int ld, int m, const double* B, int ldb, int nbcols, double* Bp, double* X, double* Dg, int* perm, int* cnt);
+void lvk_cov_symmetrize(lvk_context* ctx, double* P, int ld, int n);
+// be_feature.hip
+int lvk_feature_rows_route(int max_rows, int gate_rows_max);
+lvk_status lvk_launch_triangulate(lvk_context* ctx, const TriJob* d_jobs, int n_jobs, const CamPose* d_cams, const int* d_rank, const double* d_z, TriResult* d_out, TriResult* d_out_dev);
+lvk_status lvk_launch_feature_rows(lvk_context* ctx, const FeatJob* d_jobs, int n_jobs, int max_rows, const CloneDev* d_clones, const int* d_rank,
+                                   const double* d_z, const double* d_zv, const double* d_P, int ldp, FilterFlags fl, double* d_staging, int* d_ccols, FeatResult* d_out, FeatResult* d_out_host,
+                                   double* d_Hout, int ldh, int ncols_out, double* d_rout, int obs_stride, int n_clones, const TriResult* d_tri);
+lvk_status lvk_launch_stack_rows(lvk_context* ctx, const FeatResult* d_fout, const StackRow* d_map, int n_rows, const double* d_staging, const int* d_ccols, double* d_H, int ldh, int ncols, double* d_r);
+// be_qr.hip, be_qr_dense.hip
+double lvk_chi2_005(int dof);
+lvk_status lvk_qr_compress_dev(lvk_context* ctx, double* d_H, int ldh, int rows, int cols, double* d_r, int* rows_out);
+// be_shard.hip
+lvk_status lvk_shard_pack(lvk_context* ctx, const FeatResult* d_res, int n_res, const double* d_X, int ld, const double* d_rX, int k, int ncols, char* d_send, size_t res_bytes, int rank);
+lvk_status lvk_shard_unpack(lvk_context* ctx, const char* d_recv, size_t bytes_per_rank, size_t res_bytes, const ShardMeta* d_meta, int world, int ncols, int k_max,
+                            FeatResult* d_fout, FeatResult* d_fout_host, double* d_H, int ld, double* d_r, int* d_peer_fail);

@@ -16,6 +16,7 @@
 //     D^-1 with the zero rule, backward substitution.  The result stays in pivot order (row i belongs to row perm[i] of S) next to
 //     the equally permuted copy of B: every product the update needs is a sum over rows, which the order does not change.
 #include "lvk_internal.h"
+#include "be_host.h"
 #include "lvk_wave.h"
 #include <cfloat>
 

@@ -9,6 +9,7 @@
 // matrices are <= ~2 MB and the update is latency-, not bandwidth-bound at N ~ 232).
 // All matrices are ROW-MAJOR with a leading dimension in doubles.
 #include "lvk_internal.h"
+#include "be_host.h"
 #include "lvk_wave.h"
 
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -819,8 +820,6 @@ static lvk_status launch_chol_solve(lvk_context* ctx, double* S, int lds_, int m
 }
 
 // ------------------------------------------------------------------------- host drivers (internal + C ABI)
-struct UpdateWs { double* B; int ldb; double* S; int lds; int* info; hipEvent_t ev_a = nullptr, ev_b = nullptr; double* dx_host = nullptr; double* p00_host = nullptr; int* info_host = nullptr; };   // info: the factorisation's report words, in DEVICE memory (the final GEMM reads them: GemmRider::gate); info_host: their mirror in device-mapped host memory, written only when one is set; ev_*: optional bracket around the H P GEMM; dx_host: host-mapped mirror of dx; p00_host: of the updated P's leading 16 x 16 block
-
 // dx (device, n) and P updated in place.  B: m x (n+1) workspace, S: m x m workspace.
 lvk_status lvk_update_core(lvk_context* ctx, double* P, int ldp, int n, const double* H, int ldh, int m, const double* r, double sigma2,
                            double* dx, UpdateWs ws)
@@ -842,9 +841,6 @@ lvk_status lvk_update_core(lvk_context* ctx, double* P, int ldp, int n, const do
 //     K^T = X = S.ldlt().solve(H P) ;  dx = K r ;  P <- (I - K H) P = P - X^T (H P) ;  P <- (P + P^T) / 2      (larvio.cpp:1456-1460, 1578-1594)
 // ws.B / ws.S as for lvk_update_core; the pivot-order copies of [HP | r] and of X, D, the permutation and the two counters
 // (negative / zero D entries) live in context scratch slot 15.  *d_cnt_out = where the counters are (device).
-size_t lvk_ldlt_lds_bytes(int m);
-lvk_status lvk_ldlt_factor_solve(lvk_context* ctx, double* S, int ld, int m, const double* B, int ldb, int nbcols, double* Bp, double* X, double* Dg, int* perm, int* cnt);
-void lvk_cov_symmetrize(lvk_context* ctx, double* P, int ld, int n);
 lvk_status lvk_update_ldlt_core(lvk_context* ctx, double* P, int ldp, int n, const double* H, int ldh, int m, const double* r, double sigma2,
                                 double* dx, UpdateWs ws, int** d_cnt_out, int** d_perm_out)
 {

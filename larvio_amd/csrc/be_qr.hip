@@ -7,6 +7,7 @@
 //     structure and for the stage-level entry point.
 #include "lvk_internal.h"
 #include "be_qr.h"
+#include "be_host.h"
 #include <unordered_map>
 #include "lvk_wave.h"
 #include "chi2_table.inc"
@@ -398,8 +399,6 @@ void lvk_qr_sparse_plan(const std::vector<RowGroup>& groups, int N, std::vector<
         }
     }
 }
-
-lvk_status lvk_qr_compress_dev(lvk_context* ctx, double* d_H, int ldh, int rows, int cols, double* d_r, int* rows_out);   // be_qr_dense.hip
 
 // stage-level C ABI: compress a device matrix in place (rows x cols, leading dimension ld), d_r likewise
 extern "C" lvk_status lvk_ekf_compress_qr(lvk_context* ctx, double* d_H, int ld, int rows, int cols, double* d_r, int* rows_out)

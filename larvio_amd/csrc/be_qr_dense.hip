@@ -17,6 +17,7 @@
 // whole trailing matrix once per column with a stride of one row per lane), the panel work runs on all chunks in parallel, and the
 // O(rows cols^2) flops are MFMA GEMMs.  NB = 32 for rows <= 8192, NB = 16 up to 65536 rows.
 #include "lvk_internal.h"
+#include "be_host.h"
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 

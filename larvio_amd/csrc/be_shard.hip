@@ -7,16 +7,14 @@
 // in the same order).
 #include "lvk_internal.h"
 #include "be_dev.h"
+#include "be_host.h"
 #include <dlfcn.h>
 #include <limits.h>
 #include <stdlib.h>
 #include <string>
 
-struct ShardMeta { int job_lo, job_n, k, row_off; };
-
 // Every rank's block starts with a header the receivers check: a rank that failed locally after the (symmetric) capacity checks
 // still enters the collective - with a poisoned header - so that its peers return an error instead of waiting for it forever.
-#define LVK_SHARD_HDR 256
 #define LVK_SHARD_MAGIC 0x4c564b58u      // "LVKX"
 struct ShardHeader { unsigned magic; int rank; int k; int n_res; };
 

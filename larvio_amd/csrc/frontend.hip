@@ -18,11 +18,6 @@
 #include <new>
 #include <vector>
 
-lvk_status lvk_gftt_run(lvk_context* ctx, const float* d_eig, const uint8_t* d_mask, int w, int h, int max_corners,
-                        double quality, double min_distance, unsigned* d_scratch, unsigned long long* d_cands, int cand_cap,
-                        lvk_pt2f* d_out, int cap, int* d_n_out, const int* d_sub, bool prepared, bool max_done);
-lvk_status lvk_mask_and_max(lvk_context* ctx, const lvk_pt2f* d_pts, const int* d_n, int w, int h, int md, const float* d_eig, uint8_t* d_mask, unsigned* d_scratch);
-
 // =========================================================================== runtime environment, BAR self-test
 // plain loads, as the product kernels do them
 __global__ void k_bar_probe(const unsigned* __restrict__ src, unsigned* __restrict__ dst, int n, int stride)
@@ -1104,7 +1099,6 @@ static lvk_status fe_read_dev(lvk_frontend* fe)
 // findNewFeaturesToBeTracked (:1005-1037).  Nothing in this frame's message depends on it, so it runs on side[0] behind the
 // commit and overlaps the message read-back, the filter update and the next frame's pyramid; the next frame's LK of the new
 // points is queued on the same stream, right behind it.
-extern "C" lvk_status lvk_frontend_fetch_msg(lvk_frontend* fe, int slot, lvk_feature_obs* h_out, int cap, int* n_out);
 static lvk_status fe_detect_new(lvk_frontend* fe, int dst)
 {
     lvk_context* cx = fe->side[0];
