@@ -2,8 +2,10 @@
 // Pangolin): same command line, same loop, same log files (msckf_2_state.txt / msckf_2_takeoff.txt in the configuration's
 // output_dir, written by lvk::LarVio as larvio.cpp:388,446-453 does), running on liblvk_hip.so.
 //
-//   larvio_euroc path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined]
+//   larvio_euroc path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png]
 //
+// --mask restricts corner detection to the non-zero pixels of an 8-bit PNG of the configured resolution (ImageProcessor::setMask:
+// a fisheye vignette, the vehicle's own body); a mask of another size is an error.
 // --tum writes "t x y z qx qy qz qw" (body in world, absolute stamps, 17 significant digits) for tools/traj_rmse.py.
 // --pipelined runs the same loop through lvk::VioPipeline: the filter update of a message overlaps the front-end of the next
 // frames on a second HIP stream; the trajectory is the same, written from the filter thread's odometry callback.
@@ -69,14 +71,15 @@ static int run_pipelined(const char* image_dir, const std::vector<lvk::ImuData>&
 int main(int argc, char** argv)
 {
     if (argc < 5) {
-        std::fprintf(stderr, "Usage: %s path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined]\n", argv[0]);
+        std::fprintf(stderr, "Usage: %s path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png]\n", argv[0]);
         return 1;
     }
-    std::string tum_path; long max_frames = -1; bool pipelined = false;
+    std::string tum_path, mask_path; long max_frames = -1; bool pipelined = false;
     for (int a = 5; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--tum") && a + 1 < argc) tum_path = argv[++a];
         else if (!std::strcmp(argv[a], "--max-frames") && a + 1 < argc) max_frames = std::atol(argv[++a]);
         else if (!std::strcmp(argv[a], "--pipelined")) pipelined = true;
+        else if (!std::strcmp(argv[a], "--mask") && a + 1 < argc) mask_path = argv[++a];
         else { std::fprintf(stderr, "unknown option %s\n", argv[a]); return 1; }
     }
 
@@ -85,11 +88,24 @@ int main(int argc, char** argv)
     if (!lvk::loadImuFile(argv[1], allImuData) || allImuData.empty()) { std::fprintf(stderr, "cannot read IMU samples from %s\n", argv[1]); return 1; }
     if (!lvk::loadImageList(argv[2], allImgInfo) || allImgInfo.empty()) { std::fprintf(stderr, "cannot read the image list %s\n", argv[2]); return 1; }
     const std::string config_file(argv[4]);
+    // the mask is checked against the configuration before any device is touched
+    lvk::GreyImage mask;
+    if (!mask_path.empty()) {
+        std::string err; lvk::ConfigFile f; lvk_fe_config fcfg = lvk_fe_config();
+        if (!lvk::read_png_grey(mask_path, &mask, &err)) { std::fprintf(stderr, "%s: %s\n", mask_path.c_str(), err.c_str()); return 1; }
+        if (!f.open(config_file)) { std::fprintf(stderr, "config_file error: %s\n", f.error().c_str()); return 1; }
+        if (!lvk::load_fe_config(f, &fcfg, &err)) { std::fprintf(stderr, "config_file error: %s\n", err.c_str()); return 1; }
+        if (mask.width != fcfg.width || mask.height != fcfg.height) {
+            std::fprintf(stderr, "%s: the mask is %dx%d, the configuration says %dx%d\n", mask_path.c_str(), mask.width, mask.height, fcfg.width, fcfg.height);
+            return 1;
+        }
+    }
 
     lvk::Context ctx(0);
     if (!ctx.ok()) { std::fprintf(stderr, "larvio_euroc: %s\n", ctx.error()); return 3; }
     lvk::ImageProcessor ImgProcesser(config_file, ctx.get());                                      // :42-48
     if (!ImgProcesser.initialize()) { std::fprintf(stderr, "Image Processer initialization failed!\n"); return 1; }
+    if (!mask_path.empty() && !ImgProcesser.setMask(mask.data.data(), mask.width, mask.height, mask.width)) return 1;
     lvk::Context ctx2(0);                                                                           // the filter's own stream when pipelined
     if (pipelined && !ctx2.ok()) { std::fprintf(stderr, "larvio_euroc: %s\n", ctx2.error()); return 3; }
     lvk::LarVio Estimator(config_file, pipelined ? ctx2.get() : ctx.get());                         // :50-56

@@ -176,6 +176,19 @@ lvk_status lvk_frontend_tracks(lvk_frontend* fe, uint64_t* h_ids, lvk_pt2f* h_pt
                                lvk_pt2f* h_init, uint8_t* h_desc, int cap, int* n_out);
 lvk_status lvk_frontend_new_pts(lvk_frontend* fe, lvk_pt2f* h_pts, int cap, int* n_out);
 int        lvk_frontend_state(const lvk_frontend* fe);   /* 1 FIRST_IMAGE 2 SECOND_IMAGE 3 OTHER_IMAGES */
+/* Region mask for corner detection - OpenCV's mask argument of goodFeaturesToTrack.  No reference counterpart: the reference's
+ * ImageProcessor detects with its own keep-out mask only (image_processor.cpp:1005-1037) and with none on the first frame (:337-352).
+ * nonzero = corners may be detected here; NULL clears.  mask->width/height must equal the configured resolution and mask->stride >=
+ * width (LVK_ERR_ARG otherwise, as lvk_frontend_process; the mask in force stays); is_device 0 and 1 are both accepted.  The call waits
+ * for the front-end's own streams, so a detection already queued keeps the mask it was queued with, then stores a packed 0/255 copy in
+ * a device buffer the front-end owns (the caller's buffer is free on return).  The mask holds from the next processed frame on: it is
+ * ANDed with the reference's keep-out mask on re-detection and takes the place of "no mask" on the first frame, and it governs the
+ * maximum behind the quality threshold as well as the candidates.  It restricts detection only: a track that moves into a masked
+ * area is kept.  Budget, quality level, min_distance and ordering are unchanged, and with no mask set the front-end launches exactly
+ * the kernels it launches without this call.  With a lvk_vio_pipe attached, call it before the first lvk_vio_pipe_submit or after
+ * lvk_vio_pipe_drain - never between a submit and the drain that follows. */
+lvk_status lvk_frontend_set_mask(lvk_frontend* fe, const lvk_image* mask);
+int        lvk_frontend_has_mask(const lvk_frontend* fe);
 /* cumulative LK work: point-levels processed and iterations executed (SURVEY §8d byte model) */
 lvk_status lvk_frontend_lk_stats(lvk_frontend* fe, uint64_t* point_levels, uint64_t* iterations);
 /* feature messages published so far (getFeatureMsg, image_processor.cpp:1076-1128) and the features they carried in total:

@@ -77,6 +77,16 @@ public:
         features->features.assign(out_.begin(), out_.begin() + n);
         return true;
     }
+    // region mask for corner detection (lvk_frontend_set_mask; the reference has no such call): non-zero = corners may be detected
+    // there.  With a VioPipeline: before the first processImage or after drain().
+    bool setMask(const uint8_t* data, int w, int h, int stride)
+    {
+        if (!fe_) return false;
+        const lvk_image im = {data, w, h, stride, /*is_device=*/0};
+        if (lvk_frontend_set_mask(fe_, &im) != LVK_OK) { std::fprintf(stderr, "ImageProcessor::setMask: %s\n", lvk_last_error(ctx_)); return false; }
+        return true;
+    }
+    bool clearMask() { return fe_ && lvk_frontend_set_mask(fe_, nullptr) == LVK_OK; }
     lvk_frontend* handle() const { return fe_; }
 private:
     ImageProcessor(const ImageProcessor&); ImageProcessor& operator=(const ImageProcessor&);

@@ -23,6 +23,7 @@ ABI_SYMBOLS = [
     "lvk_lk_track", "lvk_orb_describe", "lvk_hamming256_rows", "lvk_undistort_points", "lvk_find_fundamental_mask", "lvk_find_fundamental",
     "lvk_ransac_fundamental", "lvk_predict_homography",
     "lvk_frontend_create", "lvk_frontend_destroy", "lvk_frontend_process", "lvk_frontend_tracks", "lvk_frontend_new_pts",
+    "lvk_frontend_set_mask", "lvk_frontend_has_mask",
     "lvk_frontend_state", "lvk_frontend_lk_stats", "lvk_frontend_msg_stats", "lvk_frontend_profile_enable", "lvk_frontend_profile_read",
     "lvk_frontend_stage_name",
     "lvk_ekf_compress_qr", "lvk_ekf_compress_qr_groups", "lvk_ekf_qr_plan", "lvk_ekf_update", "lvk_ekf_update_ldlt", "lvk_ekf_update_ldlt_perm", "lvk_dgemm", "lvk_ekf_cov_propagate_augment", "lvk_ekf_cov_gather", "lvk_ekf_cov_reanchor", "lvk_ekf_cov_append_features", "lvk_ekf_create", "lvk_ekf_destroy", "lvk_ekf_process", "lvk_ekf_process_async", "lvk_ekf_wait", "lvk_ekf_set_state",
@@ -99,6 +100,7 @@ def lib():
             "lvk_frontend_process": ([vp, C.POINTER(Image), d, vp, i, vp, i, pi, pi], i),
             "lvk_frontend_tracks": ([vp, vp, vp, vp, vp, vp, i, pi], i),
             "lvk_frontend_new_pts": ([vp, vp, i, pi], i), "lvk_frontend_state": ([vp], i),
+            "lvk_frontend_set_mask": ([vp, C.POINTER(Image)], i), "lvk_frontend_has_mask": ([vp], i),
             "lvk_frontend_lk_stats": ([vp, vp, vp], i),
             "lvk_frontend_msg_stats": ([vp, vp, vp], i),
             "lvk_frontend_profile_enable": ([vp, C.c_uint], i), "lvk_frontend_profile_read": ([vp, vp, vp, i], i),

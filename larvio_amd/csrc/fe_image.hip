@@ -462,8 +462,14 @@ __global__ void __launch_bounds__(256) k_masked_max(const float* __restrict__ ei
 // frame's new-point tracking.  The strip's response values are requested before the mask is built (they do not depend on it).
 #define MM_ROWS 4
 #define MM_PRE 8
+// USER: the strip starts from the rows of a caller-supplied region mask (lvk_frontend_set_mask: w x h bytes, tightly packed, 0 / 255,
+// read-only) instead of the 255 fill, so what is written out - and what governs the maximum - is the reference's mask ANDed with the
+// caller's; launched only while a mask is set.  USER = false is the kernel as it was (umask unused, nullptr): the template argument
+// only chooses between the fill and the load.
+template <bool USER>
 __global__ void __launch_bounds__(256) k_mask_max(const lvk_pt2f* __restrict__ pts, const int* __restrict__ n_pts, int w, int h, int md,
-                                                 const float* __restrict__ eig, uint8_t* __restrict__ mask, unsigned* __restrict__ scratch)
+                                                 const float* __restrict__ eig, uint8_t* __restrict__ mask, unsigned* __restrict__ scratch,
+                                                 const uint8_t* __restrict__ umask)
 {
     extern __shared__ unsigned mm_sh[];                     // MM_ROWS x wp bytes, wp = w rounded up to 4
     uint8_t* mb = (uint8_t*)mm_sh;
@@ -477,6 +483,18 @@ __global__ void __launch_bounds__(256) k_mask_max(const lvk_pt2f* __restrict__ p
 #pragma unroll
         for (int u = 0; u < MM_PRE; ++u) { const int i = t + 256 * u; if (i < nq) { const int r = i / wq, q = i - r * wq; pre[u] = ((const float4*)(eig + (size_t)(y0 + r) * w))[q]; } }
     }
+    if (USER) {
+        // the strip's rows are contiguous in the packed user mask, and with w % 4 == 0 they start on a 16-byte boundary (MM_ROWS = 4
+        // rows of a multiple of 4 bytes) and fill the LDS rows without gaps (wp == w): 16-byte loads, then the words that are left
+        const uint8_t* us = umask + (size_t)y0 * w;
+        if ((w & 3) == 0 && (((size_t)umask) & 15) == 0) {
+            const int nv = nq >> 2;
+            for (int i = t; i < nv; i += 256) { const uint4 v = ((const uint4*)us)[i]; mm_sh[4 * i] = v.x; mm_sh[4 * i + 1] = v.y; mm_sh[4 * i + 2] = v.z; mm_sh[4 * i + 3] = v.w; }
+            for (int i = (nv << 2) + t; i < nq; i += 256) mm_sh[i] = ((const unsigned*)us)[i];
+        } else {
+            for (int i = t; i < rows * w; i += 256) { const int r = i / w, x = i - r * w; mb[r * wp + x] = us[i]; }
+        }
+    } else
     for (int i = t; i < MM_ROWS * wq; i += 256) mm_sh[i] = 0xFFFFFFFFu;
     __syncthreads();
     const int n = *n_pts;
@@ -526,6 +544,12 @@ __global__ void __launch_bounds__(256) k_mask_max(const lvk_pt2f* __restrict__ p
     if ((t & 63) == 0) wmax[t >> 6] = best;
     __syncthreads();
     if (t == 0) { best = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])); if (best) atomicMax(&scratch[0], best); }
+}
+// a caller's region mask (any stride, any non-zero value = allowed) -> the packed 0 / 255 copy the front-end keeps
+__global__ void __launch_bounds__(256) k_mask_normalise(const uint8_t* __restrict__ src, int stride, int w, int h, uint8_t* __restrict__ dst)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x < w && y < h) dst[(size_t)y * w + x] = src[(size_t)y * stride + x] ? 255 : 0;
 }
 
 // 3x3 non-maximum suppression above quality*max, inside the mask.  One workgroup scans 256 columns x GC_ROWS rows, collects its
@@ -1085,7 +1109,23 @@ lvk_status lvk_mask_and_max(lvk_context* ctx, const lvk_pt2f* d_pts, const int* 
 {
     const size_t shm = (size_t)MM_ROWS * (((size_t)w + 3) & ~(size_t)3);
     if (shm > 60 * 1024) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "image width %d too large for the mask kernel", w);
-    hipLaunchKernelGGL(k_mask_max, dim3((h + MM_ROWS - 1) / MM_ROWS), dim3(256), shm, ctx->stream, d_pts, d_n, w, h, md, d_eig, d_mask, d_scratch);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mask_max<false>), dim3((h + MM_ROWS - 1) / MM_ROWS), dim3(256), shm, ctx->stream, d_pts, d_n, w, h, md, d_eig, d_mask, d_scratch, (const uint8_t*)nullptr);
+    LVK_LAUNCH_CHECK(ctx);
+    return LVK_OK;
+}
+// the same with a caller's region mask (packed w x h, 0 / 255) in place of the 255 fill: k_mask_max<true>
+lvk_status lvk_mask_and_max_user(lvk_context* ctx, const lvk_pt2f* d_pts, const int* d_n, int w, int h, int md, const float* d_eig, uint8_t* d_mask, unsigned* d_scratch,
+                                 const uint8_t* d_user_mask)
+{
+    const size_t shm = (size_t)MM_ROWS * (((size_t)w + 3) & ~(size_t)3);
+    if (shm > 60 * 1024) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "image width %d too large for the mask kernel", w);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mask_max<true>), dim3((h + MM_ROWS - 1) / MM_ROWS), dim3(256), shm, ctx->stream, d_pts, d_n, w, h, md, d_eig, d_mask, d_scratch, d_user_mask);
+    LVK_LAUNCH_CHECK(ctx);
+    return LVK_OK;
+}
+lvk_status lvk_mask_normalise(lvk_context* ctx, const uint8_t* d_src, int stride, int w, int h, uint8_t* d_dst)
+{
+    hipLaunchKernelGGL(k_mask_normalise, dim3((w + 255) / 256, h), dim3(256), 0, ctx->stream, d_src, stride, w, h, d_dst);
     LVK_LAUNCH_CHECK(ctx);
     return LVK_OK;
 }

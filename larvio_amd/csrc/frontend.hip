@@ -785,6 +785,9 @@ struct lvk_frontend {
     uint8_t *w_status, *wn_status;
     unsigned long long* wn_desc;
     float* eig; uint8_t* mask; unsigned* gf_scratch; unsigned long long* gf_cands; int gf_cand_cap;
+    // caller's region mask (lvk_frontend_set_mask; no reference counterpart): packed w x h, 0 / 255, allocated on first use and read-only to
+    // every kernel; has_user_mask chooses k_mask_max<true> over k_mask_max<false> and hands the bootstrap detection a mask
+    uint8_t* user_mask = nullptr; bool has_user_mask = false;
     // The message buffer: pinned host memory (h_msg) and its device-mapped view (d_msg), and its length, same arrangement - a ring
     // of LVK_MSG_SLOTS messages so that a pipelined driver can let the GPU run ahead: processImage returns as soon as the frame is
     // queued and the filter's thread picks the message up when ev_msg[slot] has fired (lvk_frontend_fetch_msg).
@@ -1009,7 +1012,7 @@ void lvk_frontend_destroy(lvk_frontend* fe)
         if (i < 2) set_free(fe->set[i]);
     }
     void* ptrs[] = {fe->d_img, fe->w_curr, fe->wn_curr, fe->w_und, fe->wn_und, fe->new_pts, fe->w_status, fe->wn_status, fe->wn_desc, fe->eig, fe->mask,
-                    fe->gf_scratch, fe->gf_cands, fe->dev};
+                    fe->gf_scratch, fe->gf_cands, fe->dev, fe->user_mask};
     for (void* p : ptrs) if (p) hipFree(p);
     for (int i = 0; i < 3; ++i) { if (fe->h_stage[i]) hipHostFree(fe->h_stage[i]); if (fe->d_ring[i]) hipFree(fe->d_ring[i]); if (fe->ev_img[i]) hipEventDestroy(fe->ev_img[i]); }
     for (int i = 0; i < LVK_MSG_SLOTS; ++i) if (fe->ev_msg[i]) hipEventDestroy(fe->ev_msg[i]);
@@ -1113,7 +1116,8 @@ static lvk_status fe_detect_new(lvk_frontend* fe, int dst)
     //  and starts behind the commit, without the message kernel in front of it)
     hipStreamWaitEvent(cx->stream, (fe->ev_trim && !fe->frame_early && fe->last_msg_slot >= 0) ? fe->ev_msg[fe->last_msg_slot] : fe->ev_commit, 0);
     ProfScope ps(fe, 7, cx->stream);
-    st = lvk_mask_and_max(cx, fe->set[dst].pts, &fe->dev->n_tracks[dst], c.width, c.height, c.min_distance, fe->eig, fe->mask, fe->gf_scratch);
+    if (fe->has_user_mask) st = lvk_mask_and_max_user(cx, fe->set[dst].pts, &fe->dev->n_tracks[dst], c.width, c.height, c.min_distance, fe->eig, fe->mask, fe->gf_scratch, fe->user_mask);
+    else st = lvk_mask_and_max(cx, fe->set[dst].pts, &fe->dev->n_tracks[dst], c.width, c.height, c.min_distance, fe->eig, fe->mask, fe->gf_scratch);
     if (st == LVK_OK) st = lvk_gftt_run(cx, fe->eig, fe->mask, c.width, c.height, c.max_features_num, 0.01, (double)c.min_distance, fe->gf_scratch,
                                         fe->gf_cands, fe->gf_cand_cap, fe->new_pts, fe->cap, &fe->dev->n_new, &fe->dev->n_tracks[dst], true, true);
     if (st != LVK_OK) return lvk_set_error(fe->ctx, st, "%s", cx->err);
@@ -1368,9 +1372,9 @@ static lvk_status frontend_process(lvk_frontend* fe, const lvk_image* img, doubl
         hipStreamWaitEvent(S1, fe->ev_tail, 0);
     }
     if (fe->image_state == 1) {
-        // initializeFirstFrame (:337-352): goodFeaturesToTrack(max_features_num, 0.01, min_distance), no mask
+        // initializeFirstFrame (:337-352): goodFeaturesToTrack(max_features_num, 0.01, min_distance), no mask - or the caller's
         { ProfScope ps(fe, 6); st = lvk_min_eigen_map(ctx, fe->pyr[1], fe->eig); }
-        if (st == LVK_OK) st = lvk_gftt_run(ctx, fe->eig, nullptr, c.width, c.height, c.max_features_num, 0.01, (double)c.min_distance, fe->gf_scratch,
+        if (st == LVK_OK) st = lvk_gftt_run(ctx, fe->eig, fe->has_user_mask ? fe->user_mask : nullptr, c.width, c.height, c.max_features_num, 0.01, (double)c.min_distance, fe->gf_scratch,
                                             fe->gf_cands, fe->gf_cand_cap, fe->new_pts, fe->cap, &fe->dev->n_new, nullptr, false, false);
         if (st == LVK_OK) st = fe_read_dev(fe);
         if (st != LVK_OK) return st;
@@ -1488,6 +1492,41 @@ lvk_status lvk_frontend_new_pts(lvk_frontend* fe, lvk_pt2f* h_pts, int cap, int*
 }
 
 int lvk_frontend_state(const lvk_frontend* fe) { return fe ? fe->image_state : 0; }
+
+// A caller's region mask for corner detection (OpenCV's mask argument; no reference counterpart).  Everything queued so far is waited
+// for first, so a detection already in flight keeps the mask it was queued with; the mask is then stored packed and 0 / 255.
+lvk_status lvk_frontend_set_mask(lvk_frontend* fe, const lvk_image* mask)
+{
+    if (!fe) return LVK_ERR_ARG;
+    lvk_context* ctx = fe->ctx;
+    const int w = fe->cfg.width, h = fe->cfg.height;
+    if (mask) {
+        if (!mask->data) return lvk_set_error(ctx, LVK_ERR_ARG, "mask: null pointer");
+        if (mask->width != w || mask->height != h)
+            return lvk_set_error(ctx, LVK_ERR_ARG, "mask is %dx%d, the front-end is configured for %dx%d", mask->width, mask->height, w, h);
+        if (mask->stride < w) return lvk_set_error(ctx, LVK_ERR_ARG, "mask stride %d is smaller than the width %d", mask->stride, w);
+    }
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < 2; ++i) LVK_HIP(ctx, hipStreamSynchronize(fe->side[i]->stream));
+    if (!mask) { fe->has_user_mask = false; return LVK_OK; }
+    const size_t n = (size_t)w * h;
+    if (!fe->user_mask && !dalloc(&fe->user_mask, n)) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_frontend_set_mask: allocation failed");
+    if (mask->is_device) {
+        lvk_status st = lvk_mask_normalise(ctx, mask->data, mask->stride, w, h, fe->user_mask);
+        if (st != LVK_OK) return st;
+        LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    } else {
+        std::vector<uint8_t> packed(n);
+        for (int y = 0; y < h; ++y) {
+            const uint8_t* src = mask->data + (size_t)y * mask->stride; uint8_t* dst = packed.data() + (size_t)y * w;
+            for (int x = 0; x < w; ++x) dst[x] = src[x] ? 255 : 0;
+        }
+        LVK_HIP(ctx, hipMemcpy(fe->user_mask, packed.data(), n, hipMemcpyHostToDevice));
+    }
+    fe->has_user_mask = true;
+    return LVK_OK;
+}
+int lvk_frontend_has_mask(const lvk_frontend* fe) { return fe && fe->has_user_mask ? 1 : 0; }
 
 lvk_status lvk_frontend_profile_enable(lvk_frontend* fe, unsigned stage_mask)
 {

@@ -84,6 +84,9 @@ lvk_status lvk_gftt_run(lvk_context* ctx, const float* d_eig, const uint8_t* d_m
                         double quality, double min_distance, unsigned* d_scratch, unsigned long long* d_cands, int cand_cap,
                         lvk_pt2f* d_out, int cap, int* d_n_out, const int* d_sub, bool prepared, bool max_done);
 lvk_status lvk_mask_and_max(lvk_context* ctx, const lvk_pt2f* d_pts, const int* d_n, int w, int h, int md, const float* d_eig, uint8_t* d_mask, unsigned* d_scratch);
+lvk_status lvk_mask_and_max_user(lvk_context* ctx, const lvk_pt2f* d_pts, const int* d_n, int w, int h, int md, const float* d_eig, uint8_t* d_mask, unsigned* d_scratch,
+                                 const uint8_t* d_user_mask);      // d_user_mask: packed w x h, 0 / 255 (lvk_frontend_set_mask)
+lvk_status lvk_mask_normalise(lvk_context* ctx, const uint8_t* d_src, int stride, int w, int h, uint8_t* d_dst);
 struct lvk_frontend;
 lvk_context* lvk_frontend_context(lvk_frontend* fe);      // frontend.hip
 extern "C" lvk_status lvk_frontend_begin(lvk_frontend* fe, const lvk_image* img, double ts);   // image stage only (internal)

@@ -89,6 +89,27 @@ class ImageProcessor:
         self.ctx.check(lib().lvk_frontend_new_pts(self._h, _p(p), self._cap, C.byref(n)))
         return p[:n.value].copy()
 
+    def set_mask(self, mask, device_ptr=None, stride=None, shape=None):
+        """Region mask for corner detection (lvk_frontend_set_mask; the reference has no such call): non-zero = corners may be
+        detected there, None clears.  mask: (H,W) uint8 array of the configured resolution (strided views are passed as they are), or
+        a device tensor (anything with data_ptr()) - or pass device_ptr/stride/shape as processImage does.  Holds from the next
+        processed frame on; with a VioPipeline call it before the first step or after drain()."""
+        if self._h is None:
+            raise LvkError("ImageProcessor.initialize() has not succeeded")
+        if mask is None and device_ptr is None:
+            self.ctx.check(lib().lvk_frontend_set_mask(self._h, None))
+            return
+        if mask is not None and hasattr(mask, "data_ptr"):
+            if mask.dim() != 2 or mask.element_size() != 1 or mask.stride(1) != 1:
+                raise ValueError("a device mask must be a 2-D uint8 tensor with unit column stride")
+            device_ptr, stride, shape, mask = mask.data_ptr(), mask.stride(0), tuple(mask.shape), None
+        im, keep = make_image(mask, device_ptr, stride, shape if shape is not None else (self.config["height"], self.config["width"]))
+        self.ctx.check(lib().lvk_frontend_set_mask(self._h, C.byref(im)))
+
+    @property
+    def has_mask(self):
+        return bool(lib().lvk_frontend_has_mask(self._h))
+
     @property
     def state(self):
         return lib().lvk_frontend_state(self._h)
