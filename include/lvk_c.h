@@ -244,9 +244,39 @@ lvk_status lvk_ekf_update_ldlt(lvk_context* ctx, double* d_P, int ldp, int n, co
 /* ... also returning the pivot order: h_perm (host, m ints), row i of the factor is row h_perm[i] of S (parity tests) */
 lvk_status lvk_ekf_update_ldlt_perm(lvk_context* ctx, double* d_P, int ldp, int n, const double* d_H, int ldh, int m,
                                     const double* d_r, double sigma2, double* d_dx, int* h_info, int* h_perm);
-/* C = alpha op(A) op(B) + beta C on the FP64 matrix cores (v_mfma_f64_16x16x4_f64) — the P H^T-class contraction */
+/* C = alpha op(A) op(B) + beta C on the FP64 matrix cores (v_mfma_f64_16x16x4_f64) — the P H^T-class contraction.  Row-major; A is stored
+ * M x K (K x M when transa), B K x N (N x K when transb), C M x N.  LVK_ERR_ARG (nothing launched) for a negative dimension or a leading
+ * dimension below the stored row length of its operand.  K = 0 is legal and gives C = beta C; beta = 0 never reads C. */
 lvk_status lvk_dgemm(lvk_context* ctx, int transa, int transb, int M, int N, int K, double alpha, const double* d_A, int lda,
                      const double* d_B, int ldb, double beta, double* d_C, int ldc);
+/* ... with the riders the measurement update hangs on its products (nothing else differs from lvk_dgemm):
+ *   diag_add          added to the entries with row == col;
+ *   d_xin, xin_col    (optional) M doubles copied into column xin_col of C's buffer, 0 <= xin_col < ldc ([H P | r] in one launch; the
+ *                     column may lie outside the N computed ones, and must when both are wanted);
+ *   d_xout, xout_col  (optional) output column xout_col (0 <= xout_col < N) goes to d_xout (M doubles) as the plain sum - no alpha, beta
+ *                     or diag_add - and that column of C is left as it was (dx = W^T w next to P -= W^T W);
+ *   d_gate            (optional) two ints in device memory: when either is non-zero the products write neither C nor d_xout (the
+ *                     d_xin column is still copied). */
+lvk_status lvk_dgemm_ex(lvk_context* ctx, int transa, int transb, int M, int N, int K, double alpha, const double* d_A, int lda,
+                        const double* d_B, int ldb, double beta, double* d_C, int ldc, double diag_add, const double* d_xin, int xin_col,
+                        double* d_xout, int xout_col, const int* d_gate);
+/* The factor-and-solve of lvk_ekf_update on caller-owned device buffers: S = L L^T (m x m, lds) and B <- W = L^-1 B (m x nbcols, ldb),
+ * both in place, in 32-row panels inside 160-row super-blocks [S11 . ; . S22]: each super-block is one fused launch (factor S11, solve
+ * its rows of B, and L21^T = L11^-1 S12), followed by S22 -= L21 L21^T and B2 -= L21 W1.  Waits for its launches.
+ * READ of S: the super-block's diagonal part and everything to its RIGHT, never what lies below-left of a super-block.  Inside a
+ *   super-block: the 32 x 32 blocks below the diagonal ones; of a diagonal 32 x 32 block its two 16 x 16 diagonal tiles' UPPER triangles
+ *   (diagonal included; the kernel takes row j for column j) and the 16 x 16 tile below-left of them.  For an exactly symmetric S this
+ *   is its lower triangle inside a super-block plus the blocks to the right.  Everything else - the rest of the diagonal blocks, the
+ *   blocks above them inside a super-block, the part below-left of a super-block, columns >= m - may hold anything, NaN included.
+ * DEFINED in S afterwards: the 32 x 32 blocks of L below the diagonal blocks of their super-block (rows < m), and L21^T in S12 (the
+ *   rows of a super-block, the columns right of it).  The diagonal blocks of L are NOT stored (the solves multiply with their inverses,
+ *   which stay in scratch memory); the rest of S holds intermediate values.  Columns >= m of S and >= nbcols of B are not written.
+ * h_info (host, 2 ints): [0] = 1 + the first row whose pivot was not positive (it is replaced by 1 and the launch goes on), 0 for a
+ *   positive definite S; [1] = non-zero when a solver workgroup gave up waiting for a panel (a broken device).  Neither is an error here.
+ * LVK_ERR_ARG unless m >= 0, nbcols >= 0, lds >= m, ldb >= nbcols, lds is a multiple of 4 and d_S is 32-byte aligned: rows of S are
+ *   read and written as 32-byte vectors of 4 doubles starting at columns that are multiples of 4, so every row must start 32-byte
+ *   aligned, and a row length that is no multiple of 4 would cut the last vector of a row short.  B is accessed by scalars. */
+lvk_status lvk_chol_solve(lvk_context* ctx, double* d_S, int lds, int m, double* d_B, int ldb, int nbcols, int* h_info);
 
 /* The structural covariance operations the filter runs on its device-resident P between updates, one call each (parity tests;
  * callers that want a single stage).  P is row-major with an explicit leading dimension; Pin and Pout are different buffers.  Each

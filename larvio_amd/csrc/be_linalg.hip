@@ -645,7 +645,7 @@ __global__ void __launch_bounds__(256) k_chol_fused(double* __restrict__ S, int 
 #pragma unroll
                 for (int bj = 0; bj <= bi; ++bj) {
                     const int gr = 32 * bi + row, gc = 32 * bj + c4;
-                    v[cf_idx(bi, bj)] = (bi < nblk && gr < m && gc + 3 < lds_) ? *(const d4*)(S + (size_t)gr * lds_ + gc) : zero4;
+                    v[cf_idx(bi, bj)] = (bi < nblk && gr < m && row0 + gc + 3 < lds_) ? *(const d4*)(S + (size_t)gr * lds_ + gc) : zero4;   // S starts at column row0 of its buffer's rows
                 }
 #pragma unroll
             for (int bi = 0; bi < CF_MAXB; ++bi)
@@ -969,16 +969,58 @@ extern "C" lvk_status lvk_ekf_update_ldlt_perm(lvk_context* ctx, double* d_P, in
     return ekf_update_ldlt_impl(ctx, d_P, ldp, n, d_H, ldh, m, d_r, sigma2, d_dx, h_info, h_perm);
 }
 
+// what both GEMM entries ask of their arguments: no negative dimension, and every leading dimension at least the stored row length of
+// its operand (A is M x K, or K x M when transposed; B is K x N, or N x K when transposed; C is M x N).  K = 0 is legal: C = beta C.
+static bool dgemm_args_ok(const lvk_context* ctx, int transa, int transb, int M, int N, int K, const double* d_A, int lda, const double* d_B, int ldb,
+                          const double* d_C, int ldc)
+{
+    return ctx && d_A && d_B && d_C && M >= 0 && N >= 0 && K >= 0 && lda >= (transa ? M : K) && ldb >= (transb ? K : N) && ldc >= N;
+}
+static void dgemm_dispatch(hipStream_t s, int transa, int transb, int M, int N, int K, double alpha, const double* d_A, int lda, const double* d_B, int ldb,
+                           double beta, double* d_C, int ldc, double diag_add, GemmRider rd)
+{
+    if (!transa && !transb) launch_dgemm<false, false>(s, M, N, K, d_A, lda, d_B, ldb, d_C, ldc, alpha, beta, diag_add, rd);
+    else if (!transa && transb) launch_dgemm<false, true>(s, M, N, K, d_A, lda, d_B, ldb, d_C, ldc, alpha, beta, diag_add, rd);
+    else if (transa && !transb) launch_dgemm<true, false>(s, M, N, K, d_A, lda, d_B, ldb, d_C, ldc, alpha, beta, diag_add, rd);
+    else launch_dgemm<true, true>(s, M, N, K, d_A, lda, d_B, ldb, d_C, ldc, alpha, beta, diag_add, rd);
+}
+
 extern "C" lvk_status lvk_dgemm(lvk_context* ctx, int transa, int transb, int M, int N, int K, double alpha, const double* d_A, int lda,
                                 const double* d_B, int ldb, double beta, double* d_C, int ldc)
 {
-    if (!ctx || !d_A || !d_B || !d_C) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_dgemm: bad argument");
-    hipStream_t s = ctx->stream;
-    if (!transa && !transb) launch_dgemm<false, false>(s, M, N, K, d_A, lda, d_B, ldb, d_C, ldc, alpha, beta, 0.0);
-    else if (!transa && transb) launch_dgemm<false, true>(s, M, N, K, d_A, lda, d_B, ldb, d_C, ldc, alpha, beta, 0.0);
-    else if (transa && !transb) launch_dgemm<true, false>(s, M, N, K, d_A, lda, d_B, ldb, d_C, ldc, alpha, beta, 0.0);
-    else launch_dgemm<true, true>(s, M, N, K, d_A, lda, d_B, ldb, d_C, ldc, alpha, beta, 0.0);
+    if (!dgemm_args_ok(ctx, transa, transb, M, N, K, d_A, lda, d_B, ldb, d_C, ldc)) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_dgemm: bad argument");
+    dgemm_dispatch(ctx->stream, transa, transb, M, N, K, alpha, d_A, lda, d_B, ldb, beta, d_C, ldc, 0.0, GemmRider{nullptr, 0, nullptr, 0, nullptr});
     LVK_LAUNCH_CHECK(ctx);
+    return LVK_OK;
+}
+
+// lvk_dgemm with the riders the update uses (GemmRider above): nothing here that the kernel does not already do for lvk_update_core
+extern "C" lvk_status lvk_dgemm_ex(lvk_context* ctx, int transa, int transb, int M, int N, int K, double alpha, const double* d_A, int lda,
+                                   const double* d_B, int ldb, double beta, double* d_C, int ldc, double diag_add, const double* d_xin, int xin_col,
+                                   double* d_xout, int xout_col, const int* d_gate)
+{
+    if (!dgemm_args_ok(ctx, transa, transb, M, N, K, d_A, lda, d_B, ldb, d_C, ldc) || (d_xin && (xin_col < 0 || xin_col >= ldc)) ||
+        (d_xout && (xout_col < 0 || xout_col >= N)))
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_dgemm_ex: bad argument");
+    GemmRider rd{d_xin, xin_col, d_xout, xout_col, nullptr};
+    rd.gate = d_gate;
+    dgemm_dispatch(ctx->stream, transa, transb, M, N, K, alpha, d_A, lda, d_B, ldb, beta, d_C, ldc, diag_add, rd);
+    LVK_LAUNCH_CHECK(ctx);
+    return LVK_OK;
+}
+
+// The factor-and-solve of the default update route on caller-owned buffers (include/lvk_c.h): launch_chol_solve, one wait, the two
+// report words handed back as they are.
+extern "C" lvk_status lvk_chol_solve(lvk_context* ctx, double* d_S, int lds, int m, double* d_B, int ldb, int nbcols, int* h_info)
+{
+    if (!ctx || !h_info || m < 0 || nbcols < 0 || lds < m || ldb < nbcols || (m > 0 && (!d_S || (nbcols > 0 && !d_B))) || (lds & 3) || ((uintptr_t)d_S & 31))
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_chol_solve: bad argument");
+    int* d_info = (int*)lvk_ctx_scratch(ctx, 6, 64);
+    if (!d_info) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
+    LVK_HIP(ctx, hipMemsetAsync(d_info, 0, 64, ctx->stream));
+    if (m > 0) { lvk_status st = launch_chol_solve(ctx, d_S, lds, m, d_B, ldb, nbcols, d_info); if (st != LVK_OK) return st; }
+    LVK_HIP(ctx, hipMemcpyAsync(h_info, d_info, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LVK_OK;
 }
 

@@ -51,6 +51,8 @@ def _L():
         L.lvk_ekf_compress_qr_groups.argtypes = [vp, vp, i, i, i, vp, i, vp, vp, vp, pi]; L.lvk_ekf_compress_qr_groups.restype = i
         L.lvk_ekf_qr_plan.argtypes = [i, i, vp, vp, vp, vp, i, vp, i, vp, vp, i, pi]; L.lvk_ekf_qr_plan.restype = i
         L.lvk_dgemm.argtypes = [vp, i, i, i, i, i, d, vp, i, vp, i, d, vp, i]; L.lvk_dgemm.restype = i
+        L.lvk_dgemm_ex.argtypes = [vp, i, i, i, i, i, d, vp, i, vp, i, d, vp, i, d, vp, i, vp, i, vp]; L.lvk_dgemm_ex.restype = i
+        L.lvk_chol_solve.argtypes = [vp, vp, i, i, vp, i, i, vp]; L.lvk_chol_solve.restype = i
         L.lvk_ekf_cov_propagate_augment.argtypes = [vp, vp, i, vp, i, i, i, i, vp, vp]; L.lvk_ekf_cov_propagate_augment.restype = i
         L.lvk_ekf_cov_gather.argtypes = [vp, vp, i, vp, i, vp, i]; L.lvk_ekf_cov_gather.restype = i
         L.lvk_ekf_cov_reanchor.argtypes = [vp, vp, i, i, vp, i]; L.lvk_ekf_cov_reanchor.restype = i
@@ -184,6 +186,30 @@ def dgemm(ctx, A, B, transa=False, transb=False, alpha=1.0, beta=0.0, Cin=None, 
     dA, dB, dC = ctx.to_device(A), ctx.to_device(B), ctx.to_device(Cm)
     ctx.check(_L().lvk_dgemm(ctx.h, int(transa), int(transb), M, N, K, alpha, _p(dA), A.shape[1], _p(dB), B.shape[1], beta, _p(dC), Cm.shape[1]))
     return ctx.to_host(dC, np.float64, Cm.shape)
+
+
+def dgemm_ex(ctx, A, B, Cbuf, M, N, K, transa=False, transb=False, alpha=1.0, beta=0.0, diag_add=0.0, xin=None, xin_col=0, xout=None, xout_col=0,
+             gate=None):
+    """lvk_dgemm_ex on whole row-major buffers (leading dimension = row length; contents go to the device as they are).  xin: M doubles;
+    xout: the M doubles the diverted column's buffer holds before the call; gate: two ints.  -> (C buffer, xout buffer or None)"""
+    A = np.ascontiguousarray(A, np.float64); B = np.ascontiguousarray(B, np.float64); Cbuf = np.ascontiguousarray(Cbuf, np.float64)
+    dA, dB, dC = ctx.to_device(A), ctx.to_device(B), ctx.to_device(Cbuf)
+    dxi = ctx.to_device(np.ascontiguousarray(xin, np.float64)) if xin is not None else None
+    dxo = ctx.to_device(np.ascontiguousarray(xout, np.float64)) if xout is not None else None
+    dg = ctx.to_device(np.ascontiguousarray(gate, np.int32)) if gate is not None else None
+    ctx.check(_L().lvk_dgemm_ex(ctx.h, int(transa), int(transb), M, N, K, alpha, _p(dA), A.shape[1], _p(dB), B.shape[1], beta, _p(dC), Cbuf.shape[1],
+                                diag_add, _p(dxi), int(xin_col), _p(dxo), int(xout_col), _p(dg)))
+    return ctx.to_host(dC, np.float64, Cbuf.shape), (ctx.to_host(dxo, np.float64, (len(xout),)) if xout is not None else None)
+
+
+def chol_solve(ctx, Sbuf, m, Bbuf, nbcols):
+    """lvk_chol_solve on whole row-major buffers (Sbuf: >= m rows, its row length is lds; Bbuf likewise with ldb).
+    -> (S buffer, B buffer, (info[0], info[1])) after the call"""
+    Sbuf = np.ascontiguousarray(Sbuf, np.float64); Bbuf = np.ascontiguousarray(Bbuf, np.float64)
+    dS, dB = ctx.to_device(Sbuf), ctx.to_device(Bbuf)
+    info = np.full(2, -1, np.int32)
+    ctx.check(_L().lvk_chol_solve(ctx.h, _p(dS), Sbuf.shape[1], int(m), _p(dB), Bbuf.shape[1], int(nbcols), _p(info)))
+    return ctx.to_host(dS, np.float64, Sbuf.shape), ctx.to_host(dB, np.float64, Bbuf.shape), (int(info[0]), int(info[1]))
 
 
 INDEFINITE_FAIL, INDEFINITE_LDLT = 0, 1

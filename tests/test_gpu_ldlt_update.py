@@ -95,10 +95,7 @@ def test_update_ldlt_matches_the_restatement_within_the_derived_bound(gpu_ctx, N
     _check_against_bound(dx, Pn, P, H, r, ref, f"indefinite N {N} m {m} bad {bad}{' padded' if padded else ''}")
 
 
-@pytest.mark.parametrize("N,m", [(232, 262), (118, 40), (46, 9), (232, 530), (250, 1), (232, 160), (232, 161), (232, 192), (240, 320), (330, 321), (460, 450), (470, 485)])
-def test_update_ldlt_agrees_with_the_cholesky_route_on_definite_problems(gpu_ctx, N, m):
-    """the twelve shapes of test_ekf_update_matches_oracle; both routes within the bound of the restatement, hence within twice the
-    bound of each other.  m = 485 and 530 need more than 64 KB of dynamic LDS in the factor kernel (its opt-in), N reaches 470."""
+def _both_routes_within_the_bound(gpu_ctx, N, m):
     from larvio_amd import larvio as lv
     P, H, r, ref = _definite_problem(N, m)
     assert ref["info"] == (0, 0)
@@ -109,6 +106,20 @@ def test_update_ldlt_agrees_with_the_cholesky_route_on_definite_problems(gpu_ctx
     _check_against_bound(dx_l, P_l, P, H, r, ref, f"definite N {N} m {m}")
     bdx, bP = R.forward_bound(P, H, r, S2, ref)
     assert (np.abs(np.asarray(dx_l, R.LD) - dx_c) <= 2 * bdx).all() and (np.abs(np.asarray(P_l, R.LD) - P_c) <= 2 * bP).all()
+
+
+@pytest.mark.parametrize("N,m", [(232, 262), (118, 40), (46, 9), (232, 530), (250, 1), (232, 160), (232, 161), (232, 192), (240, 320), (330, 321), (460, 450), (470, 485)])
+def test_update_ldlt_agrees_with_the_cholesky_route_on_definite_problems(gpu_ctx, N, m):
+    """the twelve shapes of test_ekf_update_matches_oracle; both routes within the bound of the restatement, hence within twice the
+    bound of each other.  m = 485 and 530 need more than 64 KB of dynamic LDS in the factor kernel (its opt-in), N reaches 470."""
+    _both_routes_within_the_bound(gpu_ctx, N, m)
+
+
+@pytest.mark.parametrize("N,m", [(47, 33), (48, 32), (63, 64), (64, 65), (127, 96), (128, 129), (232, 159)])
+def test_update_routes_agree_at_the_solver_and_panel_edges(gpu_ctx, N, m):
+    """the same assertions with the right-hand side's width N + 1 on the 16-column wavefront edges (48, 49) and the 64-column workgroup
+    edges (64, 65, 128, 129) of the Cholesky route's solver, and m on its 32-row panel edges and at 159 - through the real lvk_ekf_update"""
+    _both_routes_within_the_bound(gpu_ctx, N, m)
 
 
 @pytest.mark.parametrize("N,m,bad", [(120, 40, 7), (232, 150, 149), (232, 200, 170), (232, 330, 5)])
