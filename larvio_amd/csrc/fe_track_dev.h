@@ -156,165 +156,40 @@ __device__ __forceinline__ int lk_point_generic(const PyrView& prev, const PyrVi
     return total_it;
 }
 
-// ---- row-segment variant for WIN = 21 (every configuration of the reference uses patch_size 21).
+// ---- row-segment layout for WIN = 21 (every configuration of the reference uses patch_size 21).
 // Lane l owns SEVEN CONSECUTIVE pixels of window row l / 3 (segment l % 3): 63 lanes cover the 21 x 21 window.  The bilinear taps
 // of 7 neighbouring pixels are 8 consecutive bytes of two image rows, so a lane's share of the template is 2 eight-byte loads (I)
 // + 4 sixteen-byte loads ((Ix, Iy) pairs) instead of 84 one- and two-byte loads, and an iteration is 2 eight-byte loads instead
 // of 28 byte loads - all of a phase's loads in flight at once.  (gfx950 runs with unaligned access enabled: a dwordx2 load at any
 // byte address is one instruction.)  The per-pixel integer arithmetic is exactly that of the generic path and the 2x2 system is
 // made of exact integer sums, so which lane holds which pixel changes no bit of the result.
+// The building blocks below (fetch, blend, sums, level test, level iteration) are written ONCE; the two kernels that use the layout
+// (lk_point_rs21_lds: one wavefront does everything; lk_tpl_build21 + lk_pass_iterate21: the work spread over four) only arrange them.
+#define LK_RS_WIN 21
 #define LK_RS_SEG 7
-__device__ __forceinline__ int lk_point_rs21(const PyrView& prev, const PyrView& next, int n_levels, lvk_pt2f prev_pt, lvk_pt2f& next_pt,
-                                             int& status, int max_count, double epsilon, int* __restrict__ iters_out)
+static constexpr float LK_RS_HALF = (LK_RS_WIN - 1) * 0.5f;
+static constexpr float LK_FLT_SCALE = 1.f / (1 << 20);
+struct LkRsLane { int wrow, x0; bool act; };      // window row, first window column and "owns pixels" (lane 63 does not) of this lane
+__device__ __forceinline__ LkRsLane lk_rs_lane()
 {
-    constexpr int WIN = 21;
-    int total_it = 0;
     const int lane = threadIdx.x & 63;
-    const float half = (WIN - 1) * 0.5f;
-    const float FLT_SCALE = 1.f / (1 << 20);
-    const int max_level = n_levels - 1;
-    const int wrow = lane / 3, x0 = (lane - 3 * wrow) * LK_RS_SEG;
-    const bool act = lane < 3 * WIN;
-    // The template of a level depends on prev_pt alone, not on what the iterations of the coarser level find: its raw bytes are
-    // requested ONE LEVEL AHEAD (before the coarser level's iterations start) and sit in registers when that level begins - the
-    // first-touch round trip of levels max-1..0 disappears from the dependent chain.
-    struct Raw { unsigned long long i0, i1; uint4 d00, d01, d10, d11; int ipx, ipy; bool ok; };
-    auto fetch = [&](int level) {
-        Raw r; r.i0 = 0; r.i1 = 0; r.d00 = r.d01 = r.d10 = r.d11 = uint4{0, 0, 0, 0};
-        const float lscale = (float)(1. / (1 << level));
-        const float prx = prev_pt.x * lscale - half, pry = prev_pt.y * lscale - half;
-        r.ipx = d_cv_floor(prx); r.ipy = d_cv_floor(pry);
-        const int cols = prev.w[level], rows = prev.h[level];
-        r.ok = !(r.ipx < -WIN || r.ipx >= cols || r.ipy < -WIN || r.ipy >= rows);
-        if (r.ok && act) {
-            const int stepI = prev.istride[level], dstep = prev.dstride[level];
-            const uint8_t* src = prev.img[level] + (ptrdiff_t)(wrow + r.ipy) * stepI + (x0 + r.ipx);
-            const int16_t* ds = prev.der[level] + (ptrdiff_t)(wrow + r.ipy) * dstep + 2 * (x0 + r.ipx);
-            __builtin_memcpy(&r.i0, src, 8); __builtin_memcpy(&r.i1, src + stepI, 8);
-            __builtin_memcpy(&r.d00, ds, 16); __builtin_memcpy(&r.d01, ds + 8, 16);
-            __builtin_memcpy(&r.d10, ds + dstep, 16); __builtin_memcpy(&r.d11, ds + dstep + 8, 16);
-        }
-        return r;
-    };
-    Raw cur = fetch(max_level);
-
-    for (int level = max_level; level >= 0; --level) {
-        const Raw raw = cur;
-        if (level > 0) cur = fetch(level - 1);
-        const int cols = prev.w[level], rows = prev.h[level];
-        const int stepJ = next.istride[level];
-        const uint8_t* __restrict__ Jbase = next.img[level];
-        const float lscale = (float)(1. / (1 << level));
-        float prx = prev_pt.x * lscale, pry = prev_pt.y * lscale;
-        float nx, ny;
-        if (level == max_level) { nx = next_pt.x * lscale; ny = next_pt.y * lscale; }
-        else { nx = next_pt.x * 2.f; ny = next_pt.y * 2.f; }
-        next_pt.x = nx; next_pt.y = ny;
-        int n_it = 0;
-
-        prx -= half; pry -= half;
-        const int ipx = raw.ipx, ipy = raw.ipy;               // = cvFloor(prx), cvFloor(pry): the same expressions as in fetch()
-        if (!raw.ok) {
-            if (level == 0) status = 0;
-            if (iters_out && lane == 0) iters_out[level] = 0;
-            continue;
-        }
-        float a = prx - ipx, b = pry - ipy;
-        int iw00 = d_cv_round((1.f - a) * (1.f - b) * (1 << LK_W_BITS));
-        int iw01 = d_cv_round(a * (1.f - b) * (1 << LK_W_BITS));
-        int iw10 = d_cv_round((1.f - a) * b * (1 << LK_W_BITS));
-        int iw11 = (1 << LK_W_BITS) - iw00 - iw01 - iw10;
-
-        short Iv[LK_RS_SEG], Ixv[LK_RS_SEG], Iyv[LK_RS_SEG];
-        int pA11 = 0, pA12 = 0, pA22 = 0;
-        {
-            const unsigned long long i0 = raw.i0, i1 = raw.i1;
-            const uint4 d00 = raw.d00, d01 = raw.d01, d10 = raw.d10, d11 = raw.d11;
-            const unsigned dr0[8] = {d00.x, d00.y, d00.z, d00.w, d01.x, d01.y, d01.z, d01.w};
-            const unsigned dr1[8] = {d10.x, d10.y, d10.z, d10.w, d11.x, d11.y, d11.z, d11.w};
-#pragma unroll
-            for (int j = 0; j < LK_RS_SEG; ++j) {
-                const int s00 = (int)((i0 >> (8 * j)) & 0xFF), s01 = (int)((i0 >> (8 * j + 8)) & 0xFF);
-                const int s10 = (int)((i1 >> (8 * j)) & 0xFF), s11 = (int)((i1 >> (8 * j + 8)) & 0xFF);
-                const int x00 = (short)(dr0[j] & 0xFFFF), y00 = (short)(dr0[j] >> 16), x01 = (short)(dr0[j + 1] & 0xFFFF), y01 = (short)(dr0[j + 1] >> 16);
-                const int x10 = (short)(dr1[j] & 0xFFFF), y10 = (short)(dr1[j] >> 16), x11 = (short)(dr1[j + 1] & 0xFFFF), y11 = (short)(dr1[j + 1] >> 16);
-                int ival = (lk_blend_u8(s00, s01, s10, s11, iw00, iw01, iw10, iw11) + (1 << (LK_W_BITS - 5 - 1))) >> (LK_W_BITS - 5);
-                int ixval = (lk_blend_i16(x00, x01, x10, x11, iw00, iw01, iw10, iw11) + (1 << (LK_W_BITS - 1))) >> LK_W_BITS;
-                int iyval = (lk_blend_i16(y00, y01, y10, y11, iw00, iw01, iw10, iw11) + (1 << (LK_W_BITS - 1))) >> LK_W_BITS;
-                if (!act) { ival = 0; ixval = 0; iyval = 0; }
-                Iv[j] = (short)ival; Ixv[j] = (short)ixval; Iyv[j] = (short)iyval;
-                pA11 += ixval * ixval; pA12 += ixval * iyval; pA22 += iyval * iyval;
-            }
-        }
-        const long long sA11 = wave_sum_i64(pA11), sA12 = wave_sum_i64(pA12), sA22 = wave_sum_i64(pA22);
-        const float A11 = (float)sA11 * FLT_SCALE, A12 = (float)sA12 * FLT_SCALE, A22 = (float)sA22 * FLT_SCALE;
-        float D = A11 * A22 - A12 * A12;
-        const float min_eig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * WIN * WIN);
-        if (min_eig < (float)1e-4 || D < FLT_EPSILON) {      // float against float: LKTrackerInvoker keeps minEigThreshold as a float member
-            if (level == 0) status = 0;
-            if (iters_out && lane == 0) iters_out[level] = 0;
-            continue;
-        }
-        D = 1.f / D;
-        nx -= half; ny -= half;
-        float pdx = 0.f, pdy = 0.f;
-        for (int j = 0; j < max_count; ++j) {
-            const int inx = d_cv_floor(nx), iny = d_cv_floor(ny);
-            if (inx < -WIN || inx >= cols || iny < -WIN || iny >= rows) {
-                if (level == 0) status = 0;
-                break;
-            }
-            ++n_it;
-            a = nx - inx; b = ny - iny;
-            iw00 = d_cv_round((1.f - a) * (1.f - b) * (1 << LK_W_BITS));
-            iw01 = d_cv_round(a * (1.f - b) * (1 << LK_W_BITS));
-            iw10 = d_cv_round((1.f - a) * b * (1 << LK_W_BITS));
-            iw11 = (1 << LK_W_BITS) - iw00 - iw01 - iw10;
-            int pb1 = 0, pb2 = 0;
-            unsigned long long j0 = 0, j1 = 0;
-            if (act) {
-                const uint8_t* Jp = Jbase + (ptrdiff_t)(wrow + iny) * stepJ + (x0 + inx);
-                __builtin_memcpy(&j0, Jp, 8); __builtin_memcpy(&j1, Jp + stepJ, 8);
-            }
-#pragma unroll
-            for (int k = 0; k < LK_RS_SEG; ++k) {
-                const int s00 = (int)((j0 >> (8 * k)) & 0xFF), s01 = (int)((j0 >> (8 * k + 8)) & 0xFF);
-                const int s10 = (int)((j1 >> (8 * k)) & 0xFF), s11 = (int)((j1 >> (8 * k + 8)) & 0xFF);
-                int diff = ((lk_blend_u8(s00, s01, s10, s11, iw00, iw01, iw10, iw11) + (1 << (LK_W_BITS - 5 - 1))) >> (LK_W_BITS - 5)) - Iv[k];
-                if (!act) diff = 0;
-                pb1 += diff * Ixv[k]; pb2 += diff * Iyv[k];
-            }
-            const long long sb1 = wave_sum_i64(pb1), sb2 = wave_sum_i64(pb2);
-            const float b1 = (float)sb1 * FLT_SCALE, b2 = (float)sb2 * FLT_SCALE;
-            const float dx = (A12 * b2 - A22 * b1) * D;
-            const float dy = (A12 * b1 - A11 * b2) * D;
-            nx += dx; ny += dy;
-            next_pt.x = nx + half; next_pt.y = ny + half;
-            if ((double)dx * dx + (double)dy * dy <= epsilon) break;
-            if (j > 0 && fabs((double)(dx + pdx)) < 0.01 && fabs((double)(dy + pdy)) < 0.01) {
-                next_pt.x -= dx * 0.5f; next_pt.y -= dy * 0.5f;
-                break;
-            }
-            pdx = dx; pdy = dy;
-        }
-        if (iters_out && lane == 0) iters_out[level] = n_it;
-        total_it += n_it;
-    }
-    return total_it;
+    LkRsLane g; g.wrow = lane / 3; g.x0 = (lane - 3 * g.wrow) * LK_RS_SEG; g.act = lane < 3 * LK_RS_WIN;
+    return g;
 }
+// every lane holds the same value: say so (v_readfirstlane), the level / iteration control flow then compiles to scalar branches
+__device__ __forceinline__ float lk_uni(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
 
-// ---- the same row-segment layout with the reductions through LDS (round 6).
-// What an iteration of lk_point_rs21 costs is instruction issue of ONE wavefront (~280 instructions, ~5.8 cycles each), and a third
-// of them are the two exact 64-bit wave sums: 16 DPP adds + 16 v_readlane + the scalar carry chain + two int64 -> float conversions
-// with find-first-bit.  Here: three DPP rotations leave the sum of each aligned group of 8 lanes in the group's last lane (7 pixels x
+// ---- the reductions through LDS.
+// What an iteration costs is instruction issue of ONE wavefront (~5.8 cycles per instruction), and with wave-wide sums by DPP +
+// v_readlane a third of its ~280 instructions were the two exact 64-bit sums: 16 DPP adds + 16 v_readlane + the scalar carry chain +
+// two int64 -> float conversions with find-first-bit (profiles/r6_b_lk_lds_sums_ab.json: 31.6 against 28.5 us per launch).  Here: three DPP
+// rotations leave the sum of each aligned group of 8 lanes in the group's last lane (7 pixels x
 // 8 lanes x |diff * Ix| <= 8 * 7 * 8160 * 4080 = 1.86e9 < 2^31: still an exact int32), the eight group leaders add theirs,
 // sign-extended, to a 64-bit LDS accumulator (ds_add_u64) that is NEVER reset - a running total modulo 2^64 whose difference to the
 // previous reading is this reduction's sum, exactly - and every lane reads the accumulators back.  LDS instructions of one wavefront
 // execute in issue order, so the read follows the adds without a barrier.  The int64 -> float conversion goes through double
 // (hi * 2^32 + lo is exact below 2^53, and (float)(double) rounds to nearest-even like (float)(int64)): three instructions.
-// Integer sums in a different order: the same bits.  Second change: the 16 bytes of the next image a lane holds are reloaded only
-// when the window's integer origin moved - after the first step of a level it usually has not (the update is sub-pixel), and the
-// L2 round trip leaves the iteration's dependent chain.
+// Integer sums in a different order: the same bits.
 struct LkLdsAcc {
     unsigned off;                   // LDS byte address of 4 x u64 owned by this wavefront (3 running totals + pad, 16-byte aligned; zeroed once at kernel start)
     unsigned long long prev[3];
@@ -327,7 +202,7 @@ __device__ __forceinline__ int lk_group8_sum(int v)
     return v;
 }
 // LDS instructions as written.  ds_add_u64: through atomicAdd the compiler's atomic optimiser turns a same-address LDS atomic into a
-// per-active-lane v_readlane loop (8 trips x 21 instructions here) - the very chain this variant removes.  The reads: through a
+// per-active-lane v_readlane loop (8 trips x 21 instructions here) - the very chain these sums remove.  The reads: through a
 // generic pointer they become flat loads with system-scope cache bits.
 __device__ __forceinline__ void lds_add_u64(unsigned off, unsigned long long v)
 {
@@ -364,28 +239,48 @@ __device__ __forceinline__ void lk_lds_sums(LkLdsAcc& A, const int (&part)[NV], 
         const long long s = (long long)(now[k] - A.prev[k]);
         A.prev[k] = now[k];
         // every lane read the same totals: say so, the loop control around this stays scalar
-        out[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lk_i64_to_f32_scaled(s, scale))));
+        out[k] = lk_uni(lk_i64_to_f32_scaled(s, scale));
     }
 }
+// zero the wavefront's LDS accumulators (4 x u64, 16-byte aligned; call once, by the wavefront that will use them)
+__device__ __forceinline__ LkLdsAcc lk_acc_init(unsigned long long* lds4)
+{
+    LkLdsAcc a; a.prev[0] = a.prev[1] = a.prev[2] = 0;
+    a.off = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned long long*)lds4;
+    if ((threadIdx.x & 63) < 4) lds4[threadIdx.x & 63] = 0;
+    __builtin_amdgcn_wave_barrier();
+    return a;
+}
+
+// ---- debug builds
 #ifdef LVK_LK_TIMING
-static __device__ unsigned long long g_lk_tick[4096][12];    // -DLVK_LK_TIMING=1: the kernel's spans only (g_lk_span, frontend.hip); =2: this phase account too
+static __device__ unsigned long long g_lk_tick[4096][12];    // -DLVK_LK_TIMING=1: the kernel's spans only (LkSpan, frontend.hip); =2: this phase account too
 #endif
-#if defined(LVK_LK_TIMING) && LVK_LK_TIMING >= 2
-// per-block phase account of the LK wavefront (variants/lkt.so, tools/gpu/lk_ticks.py): shader-clock cycles by category
+// per-block phase account of the LK wavefront of k_fe_lk_both (variants/lkt.so, tools/gpu/lk_ticks.py): shader-clock cycles by category
 // 0 level set-up (template blends incl. the wait for the fetched bytes)  1 A sums  2 eigen test / inverse  3 iteration: origin, weights,
 // load (when the origin moved), blends  4 iteration: b sums  5 iteration: solve + stop tests  6 iterations  7 levels entered  8 loads issued
-#define LKT_DECL unsigned long long lkt_prev = clock64(); unsigned long long lkt_acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define LKT(k) do { const unsigned long long lkt_now = clock64(); lkt_acc[k] += lkt_now - lkt_prev; lkt_prev = lkt_now; } while (0)
-#define LKT_COUNT(k) do { lkt_acc[k] += 1; } while (0)
-#define LKT_FLUSH(pass) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 4096) { for (int q = 0; q < 9; ++q) { if (pass == 0) g_lk_tick[blockIdx.x][q] = lkt_acc[q]; else g_lk_tick[blockIdx.x][q] += lkt_acc[q]; } } } while (0)
+// An empty object in every other build: the shared level code below carries its calls at no cost.
+#if defined(LVK_LK_TIMING) && LVK_LK_TIMING >= 2
+struct LkTicks {
+    unsigned long long prev = clock64(), acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    __device__ __forceinline__ void lap(int k) { const unsigned long long now = clock64(); acc[k] += now - prev; prev = now; }
+    __device__ __forceinline__ void count(int k) { acc[k] += 1; }
+    __device__ __forceinline__ void flush(int pass) const      // pass 0 (forward) sets the block's row, pass 1 (reverse) adds to it
+    {
+        if ((threadIdx.x & 63) != 0 || blockIdx.x >= 4096) return;
+#pragma unroll
+        for (int q = 0; q < 9; ++q) { if (pass == 0) g_lk_tick[blockIdx.x][q] = acc[q]; else g_lk_tick[blockIdx.x][q] += acc[q]; }
+    }
+};
 #else
-#define LKT_DECL do { } while (0)
-#define LKT(k) do { } while (0)
-#define LKT_COUNT(k) do { } while (0)
-#define LKT_FLUSH(pass) do { } while (0)
+struct LkTicks {
+    __device__ __forceinline__ void lap(int) { }
+    __device__ __forceinline__ void count(int) { }
+    __device__ __forceinline__ void flush(int) const { }
+};
 #endif
-// -DLVK_LK_BOUNDS (debug builds only): every window load of variants 1 / 2 is checked against the level's padded plane; the first
-// violation is recorded (frontend.hip prints it when the front-end is destroyed) and the load skipped
+// -DLVK_LK_BOUNDS (debug builds only): every window load of the row-segment kernels is checked against the level's padded plane; the
+// first violation is recorded (frontend.hip prints it when the front-end is destroyed) and the load skipped
 #ifdef LVK_LK_BOUNDS
 static __device__ int g_lk_oob[16];
 __device__ __forceinline__ bool lk_in_bounds(const PyrView& V, int level, int row, int col, int tag, float fx, float fy)
@@ -401,167 +296,199 @@ __device__ __forceinline__ bool lk_in_bounds(const PyrView& V, int level, int ro
 #else
 #define LK_INB(V, level, row, col, tag, fx, fy) true
 #endif
+
+// ---- the building blocks
+// The raw template bytes of one level: this lane's 8 bytes of two image rows and 8 (Ix, Iy) pairs of two derivative rows, with the
+// window's integer origin, the origin's fractional part and the in-range verdict.  A function of the point in the FIRST image alone.
+struct LkRsRaw { unsigned long long i0, i1; uint4 d00, d01, d10, d11; int ipx, ipy; float a, b; bool ok; };
+__device__ __forceinline__ LkRsRaw lk_rs_fetch(const PyrView& I, int level, lvk_pt2f prev_pt, int inb_tag)
+{
+    constexpr int WIN = LK_RS_WIN;
+    const LkRsLane g = lk_rs_lane();
+    LkRsRaw r; r.i0 = 0; r.i1 = 0; r.d00 = r.d01 = r.d10 = r.d11 = uint4{0, 0, 0, 0};
+    const float lscale = (float)(1. / (1 << level));
+    const float prx = prev_pt.x * lscale - LK_RS_HALF, pry = prev_pt.y * lscale - LK_RS_HALF;
+    r.ipx = d_cv_floor(prx); r.ipy = d_cv_floor(pry);
+    r.a = prx - r.ipx; r.b = pry - r.ipy;
+    const int cols = I.w[level], rows = I.h[level];
+    r.ok = !(r.ipx < -WIN || r.ipx >= cols || r.ipy < -WIN || r.ipy >= rows);
+    if (r.ok && g.act && LK_INB(I, level, g.wrow + r.ipy, g.x0 + r.ipx, inb_tag, prev_pt.x, prev_pt.y)) {
+        const int stepI = I.istride[level], dstep = I.dstride[level];
+        const uint8_t* src = I.img[level] + (ptrdiff_t)(g.wrow + r.ipy) * stepI + (g.x0 + r.ipx);
+        const int16_t* ds = I.der[level] + (ptrdiff_t)(g.wrow + r.ipy) * dstep + 2 * (g.x0 + r.ipx);
+        __builtin_memcpy(&r.i0, src, 8); __builtin_memcpy(&r.i1, src + stepI, 8);
+        __builtin_memcpy(&r.d00, ds, 16); __builtin_memcpy(&r.d01, ds + 8, 16);
+        __builtin_memcpy(&r.d10, ds + dstep, 16); __builtin_memcpy(&r.d11, ds + dstep + 8, 16);
+    }
+    return r;
+}
+// the four 14-bit bilinear weights of a window whose origin has the fractional part (a, b)
+struct LkWeights { int w00, w01, w10, w11; };
+__device__ __forceinline__ LkWeights lk_weights(float a, float b)
+{
+    LkWeights w;
+    w.w00 = d_cv_round((1.f - a) * (1.f - b) * (1 << LK_W_BITS));
+    w.w01 = d_cv_round(a * (1.f - b) * (1 << LK_W_BITS));
+    w.w10 = d_cv_round((1.f - a) * b * (1 << LK_W_BITS));
+    w.w11 = (1 << LK_W_BITS) - w.w00 - w.w01 - w.w10;
+    return w;
+}
+// the 7 blended intensities of a lane's segment from its 8 bytes of two rows
+__device__ __forceinline__ int lk_rs_pixel(unsigned long long r0, unsigned long long r1, int k, const LkWeights& w)
+{
+    const int s00 = (int)((r0 >> (8 * k)) & 0xFF), s01 = (int)((r0 >> (8 * k + 8)) & 0xFF);
+    const int s10 = (int)((r1 >> (8 * k)) & 0xFF), s11 = (int)((r1 >> (8 * k + 8)) & 0xFF);
+    return (lk_blend_u8(s00, s01, s10, s11, w.w00, w.w01, w.w10, w.w11) + (1 << (LK_W_BITS - 5 - 1))) >> (LK_W_BITS - 5);
+}
+// raw bytes -> this lane's template (I, Ix, Iy of its seven pixels) and its share of the three sums of the 2x2 matrix
+__device__ __forceinline__ void lk_rs_blend(const LkRsRaw& raw, const LkWeights& w, short (&Iv)[LK_RS_SEG], short (&Ixv)[LK_RS_SEG], short (&Iyv)[LK_RS_SEG], int (&pA)[3])
+{
+    const bool act = lk_rs_lane().act;
+    const unsigned dr0[8] = {raw.d00.x, raw.d00.y, raw.d00.z, raw.d00.w, raw.d01.x, raw.d01.y, raw.d01.z, raw.d01.w};
+    const unsigned dr1[8] = {raw.d10.x, raw.d10.y, raw.d10.z, raw.d10.w, raw.d11.x, raw.d11.y, raw.d11.z, raw.d11.w};
+    pA[0] = 0; pA[1] = 0; pA[2] = 0;
+#pragma unroll
+    for (int j = 0; j < LK_RS_SEG; ++j) {
+        const int x00 = (short)(dr0[j] & 0xFFFF), y00 = (short)(dr0[j] >> 16), x01 = (short)(dr0[j + 1] & 0xFFFF), y01 = (short)(dr0[j + 1] >> 16);
+        const int x10 = (short)(dr1[j] & 0xFFFF), y10 = (short)(dr1[j] >> 16), x11 = (short)(dr1[j + 1] & 0xFFFF), y11 = (short)(dr1[j + 1] >> 16);
+        int ival = lk_rs_pixel(raw.i0, raw.i1, j, w);
+        int ixval = (lk_blend_i16(x00, x01, x10, x11, w.w00, w.w01, w.w10, w.w11) + (1 << (LK_W_BITS - 1))) >> LK_W_BITS;
+        int iyval = (lk_blend_i16(y00, y01, y10, y11, w.w00, w.w01, w.w10, w.w11) + (1 << (LK_W_BITS - 1))) >> LK_W_BITS;
+        if (!act) { ival = 0; ixval = 0; iyval = 0; }
+        Iv[j] = (short)ival; Ixv[j] = (short)ixval; Iyv[j] = (short)iyval;
+        pA[0] += ixval * ixval; pA[1] += ixval * iyval; pA[2] += iyval * iyval;
+    }
+}
+// the level's 2x2 matrix from its three exact sums, 1 / det, and the verdict of the eigenvalue / determinant test (false: no
+// iterations at this level, status 0 at level 0; Dinv is 0 then)
+__device__ __forceinline__ bool lk_level_test(const float (&fA)[3], float& A11, float& A12, float& A22, float& Dinv)
+{
+    constexpr int WIN = LK_RS_WIN;
+    A11 = fA[0]; A12 = fA[1]; A22 = fA[2];
+    const float D = A11 * A22 - A12 * A12;
+    const float min_eig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * WIN * WIN);
+    const bool bad = min_eig < (float)1e-4 || D < FLT_EPSILON;      // float against float: LKTrackerInvoker keeps minEigThreshold as a float member
+    Dinv = bad ? 0.f : 1.f / D;
+    return !bad;
+}
+// where a level starts: the caller's guess scaled down to the coarsest level, the coarser level's result doubled below it
+__device__ __forceinline__ void lk_level_start(lvk_pt2f& next_pt, int level, int max_level)
+{
+    const float lscale = (float)(1. / (1 << level));
+    float nx, ny;
+    if (level == max_level) { nx = next_pt.x * lscale; ny = next_pt.y * lscale; }
+    else { nx = next_pt.x * 2.f; ny = next_pt.y * 2.f; }
+    next_pt.x = nx; next_pt.y = ny;
+}
+// The iterations of one level, from next_pt (level coordinates) on; returns how many ran.  The 16 bytes of the next image a lane
+// holds are reloaded only when the window's integer origin moved - after the first step of a level it usually has not (the update is
+// sub-pixel), and the L2 round trip leaves the iteration's dependent chain.
+__device__ __forceinline__ int lk_rs_iterate(const short (&Iv)[LK_RS_SEG], const short (&Ixv)[LK_RS_SEG], const short (&Iyv)[LK_RS_SEG],
+                                             float A11, float A12, float A22, float Dinv, const PyrView& next, int level, int max_count, double epsilon,
+                                             lvk_pt2f& next_pt, int& status, LkLdsAcc& acc, LkTicks& tk, int inb_tag)
+{
+    constexpr int WIN = LK_RS_WIN;
+    const LkRsLane g = lk_rs_lane();
+    const int cols = next.w[level], rows = next.h[level];
+    const int stepJ = next.istride[level];
+    const uint8_t* __restrict__ Jbase = next.img[level];
+    float nx = next_pt.x - LK_RS_HALF, ny = next_pt.y - LK_RS_HALF;
+    int n_it = 0;
+    float pdx = 0.f, pdy = 0.f;
+    unsigned long long j0 = 0, j1 = 0;
+    int held_x = INT_MIN, held_y = INT_MIN;            // window origin the bytes in j0 / j1 were loaded for
+    for (int j = 0; j < max_count; ++j) {
+        const int inx = d_cv_floor(nx), iny = d_cv_floor(ny);
+        if (inx < -WIN || inx >= cols || iny < -WIN || iny >= rows) {
+            if (level == 0) status = 0;
+            break;
+        }
+        ++n_it;
+        if (inx != held_x || iny != held_y) {
+            held_x = inx; held_y = iny; tk.count(8);
+            if (g.act && LK_INB(next, level, g.wrow + iny, g.x0 + inx, inb_tag, nx, ny)) {
+                const uint8_t* Jp = Jbase + (ptrdiff_t)(g.wrow + iny) * stepJ + (g.x0 + inx);
+                __builtin_memcpy(&j0, Jp, 8); __builtin_memcpy(&j1, Jp + stepJ, 8);
+            }
+        }
+        const LkWeights w = lk_weights(nx - inx, ny - iny);
+        int pb[2] = {0, 0};
+#pragma unroll
+        for (int k = 0; k < LK_RS_SEG; ++k) {
+            const int diff = lk_rs_pixel(j0, j1, k, w) - Iv[k];
+            pb[0] += diff * Ixv[k]; pb[1] += diff * Iyv[k];          // lane 63 (no pixels): Ixv = Iyv = 0, j0 = j1 = 0
+        }
+        tk.lap(3); tk.count(6);
+        float fb[2];
+        lk_lds_sums<2>(acc, pb, fb, LK_FLT_SCALE);
+        tk.lap(4);
+        const float b1 = fb[0], b2 = fb[1];
+        const float dx = (A12 * b2 - A22 * b1) * Dinv;
+        const float dy = (A12 * b1 - A11 * b2) * Dinv;
+        nx += dx; ny += dy;
+        next_pt.x = nx + LK_RS_HALF; next_pt.y = ny + LK_RS_HALF;
+        if ((double)dx * dx + (double)dy * dy <= epsilon) break;
+        if (j > 0 && fabs((double)(dx + pdx)) < 0.01 && fabs((double)(dy + pdy)) < 0.01) {
+            next_pt.x -= dx * 0.5f; next_pt.y -= dy * 0.5f;
+            break;
+        }
+        pdx = dx; pdy = dy;
+        tk.lap(5);
+    }
+    tk.lap(5);
+    return n_it;
+}
+
+// ---- one wavefront per pass (k_lk_track<21>, k_fe_lk_both<21>): per level fetch, blend, sums, test, iterate.
+// The template of a level depends on prev_pt alone, not on what the iterations of the coarser level find: its raw bytes are
+// requested ONE LEVEL AHEAD (before the coarser level's iterations start) and sit in registers when that level begins - the
+// first-touch round trip of levels max-1..0 disappears from the dependent chain.
 template <int LKT_PASS = 0>
 __device__ __forceinline__ int lk_point_rs21_lds(const PyrView& prev, const PyrView& next, int n_levels, lvk_pt2f prev_pt, lvk_pt2f& next_pt,
                                                  int& status, int max_count, double epsilon, int* __restrict__ iters_out, LkLdsAcc& acc)
 {
-    // every lane holds the same points: say so (v_readfirstlane), the level / iteration control flow below then compiles to scalar branches
-    auto uni = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-    prev_pt.x = uni(prev_pt.x); prev_pt.y = uni(prev_pt.y); next_pt.x = uni(next_pt.x); next_pt.y = uni(next_pt.y);
-    constexpr int WIN = 21;
+    prev_pt.x = lk_uni(prev_pt.x); prev_pt.y = lk_uni(prev_pt.y); next_pt.x = lk_uni(next_pt.x); next_pt.y = lk_uni(next_pt.y);
     int total_it = 0;
     const int lane = threadIdx.x & 63;
-    const float half = (WIN - 1) * 0.5f;
-    const float FLT_SCALE = 1.f / (1 << 20);
     const int max_level = n_levels - 1;
-    const int wrow = lane / 3, x0 = (lane - 3 * wrow) * LK_RS_SEG;
-    const bool act = lane < 3 * WIN;
-    struct Raw { unsigned long long i0, i1; uint4 d00, d01, d10, d11; int ipx, ipy; bool ok; };
-    auto fetch = [&](int level) {
-        Raw r; r.i0 = 0; r.i1 = 0; r.d00 = r.d01 = r.d10 = r.d11 = uint4{0, 0, 0, 0};
-        const float lscale = (float)(1. / (1 << level));
-        const float prx = prev_pt.x * lscale - half, pry = prev_pt.y * lscale - half;
-        r.ipx = d_cv_floor(prx); r.ipy = d_cv_floor(pry);
-        const int cols = prev.w[level], rows = prev.h[level];
-        r.ok = !(r.ipx < -WIN || r.ipx >= cols || r.ipy < -WIN || r.ipy >= rows);
-        if (r.ok && act && LK_INB(prev, level, wrow + r.ipy, x0 + r.ipx, 1, prev_pt.x, prev_pt.y)) {
-            const int stepI = prev.istride[level], dstep = prev.dstride[level];
-            const uint8_t* src = prev.img[level] + (ptrdiff_t)(wrow + r.ipy) * stepI + (x0 + r.ipx);
-            const int16_t* ds = prev.der[level] + (ptrdiff_t)(wrow + r.ipy) * dstep + 2 * (x0 + r.ipx);
-            __builtin_memcpy(&r.i0, src, 8); __builtin_memcpy(&r.i1, src + stepI, 8);
-            __builtin_memcpy(&r.d00, ds, 16); __builtin_memcpy(&r.d01, ds + 8, 16);
-            __builtin_memcpy(&r.d10, ds + dstep, 16); __builtin_memcpy(&r.d11, ds + dstep + 8, 16);
-        }
-        return r;
-    };
-    Raw cur = fetch(max_level);
-    LKT_DECL;
+    LkRsRaw cur = lk_rs_fetch(prev, max_level, prev_pt, 1);
+    LkTicks tk;
 
     for (int level = max_level; level >= 0; --level) {
-        const Raw raw = cur;
-        if (level > 0) cur = fetch(level - 1);
-        const int cols = prev.w[level], rows = prev.h[level];
-        const int stepJ = next.istride[level];
-        const uint8_t* __restrict__ Jbase = next.img[level];
-        const float lscale = (float)(1. / (1 << level));
-        float prx = prev_pt.x * lscale, pry = prev_pt.y * lscale;
-        float nx, ny;
-        if (level == max_level) { nx = next_pt.x * lscale; ny = next_pt.y * lscale; }
-        else { nx = next_pt.x * 2.f; ny = next_pt.y * 2.f; }
-        next_pt.x = nx; next_pt.y = ny;
+        const LkRsRaw raw = cur;
+        if (level > 0) cur = lk_rs_fetch(prev, level - 1, prev_pt, 1);
+        lk_level_start(next_pt, level, max_level);
         int n_it = 0;
-
-        prx -= half; pry -= half;
-        const int ipx = raw.ipx, ipy = raw.ipy;
-        if (!raw.ok) {
-            if (level == 0) status = 0;
-            if (iters_out && lane == 0) iters_out[level] = 0;
-            continue;
-        }
-        float a = prx - ipx, b = pry - ipy;
-        int iw00 = d_cv_round((1.f - a) * (1.f - b) * (1 << LK_W_BITS));
-        int iw01 = d_cv_round(a * (1.f - b) * (1 << LK_W_BITS));
-        int iw10 = d_cv_round((1.f - a) * b * (1 << LK_W_BITS));
-        int iw11 = (1 << LK_W_BITS) - iw00 - iw01 - iw10;
-
         short Iv[LK_RS_SEG], Ixv[LK_RS_SEG], Iyv[LK_RS_SEG];
-        int pA[3] = {0, 0, 0};
-        {
-            const unsigned long long i0 = raw.i0, i1 = raw.i1;
-            const uint4 d00 = raw.d00, d01 = raw.d01, d10 = raw.d10, d11 = raw.d11;
-            const unsigned dr0[8] = {d00.x, d00.y, d00.z, d00.w, d01.x, d01.y, d01.z, d01.w};
-            const unsigned dr1[8] = {d10.x, d10.y, d10.z, d10.w, d11.x, d11.y, d11.z, d11.w};
-#pragma unroll
-            for (int j = 0; j < LK_RS_SEG; ++j) {
-                const int s00 = (int)((i0 >> (8 * j)) & 0xFF), s01 = (int)((i0 >> (8 * j + 8)) & 0xFF);
-                const int s10 = (int)((i1 >> (8 * j)) & 0xFF), s11 = (int)((i1 >> (8 * j + 8)) & 0xFF);
-                const int x00 = (short)(dr0[j] & 0xFFFF), y00 = (short)(dr0[j] >> 16), x01 = (short)(dr0[j + 1] & 0xFFFF), y01 = (short)(dr0[j + 1] >> 16);
-                const int x10 = (short)(dr1[j] & 0xFFFF), y10 = (short)(dr1[j] >> 16), x11 = (short)(dr1[j + 1] & 0xFFFF), y11 = (short)(dr1[j + 1] >> 16);
-                int ival = (lk_blend_u8(s00, s01, s10, s11, iw00, iw01, iw10, iw11) + (1 << (LK_W_BITS - 5 - 1))) >> (LK_W_BITS - 5);
-                int ixval = (lk_blend_i16(x00, x01, x10, x11, iw00, iw01, iw10, iw11) + (1 << (LK_W_BITS - 1))) >> LK_W_BITS;
-                int iyval = (lk_blend_i16(y00, y01, y10, y11, iw00, iw01, iw10, iw11) + (1 << (LK_W_BITS - 1))) >> LK_W_BITS;
-                if (!act) { ival = 0; ixval = 0; iyval = 0; }
-                Iv[j] = (short)ival; Ixv[j] = (short)ixval; Iyv[j] = (short)iyval;
-                pA[0] += ixval * ixval; pA[1] += ixval * iyval; pA[2] += iyval * iyval;
-            }
+        float A11, A12, A22, Dinv;
+        bool good = raw.ok;
+        if (good) {
+            int pA[3];
+            lk_rs_blend(raw, lk_weights(raw.a, raw.b), Iv, Ixv, Iyv, pA);
+            tk.lap(0); tk.count(7);
+            float fA[3];
+            lk_lds_sums<3>(acc, pA, fA, LK_FLT_SCALE);
+            tk.lap(1);
+            good = lk_level_test(fA, A11, A12, A22, Dinv);
         }
-        LKT(0); LKT_COUNT(7);
-        float fA[3];
-        lk_lds_sums<3>(acc, pA, fA, FLT_SCALE);
-        LKT(1);
-        const float A11 = fA[0], A12 = fA[1], A22 = fA[2];
-        float D = A11 * A22 - A12 * A12;
-        const float min_eig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * WIN * WIN);
-        if (min_eig < (float)1e-4 || D < FLT_EPSILON) {      // float against float: LKTrackerInvoker keeps minEigThreshold as a float member
-            if (level == 0) status = 0;
-            if (iters_out && lane == 0) iters_out[level] = 0;
-            continue;
-        }
-        D = 1.f / D;
-        nx -= half; ny -= half;
-        LKT(2);
-        float pdx = 0.f, pdy = 0.f;
-        unsigned long long j0 = 0, j1 = 0;
-        int held_x = INT_MIN, held_y = INT_MIN;            // window origin the bytes in j0 / j1 were loaded for
-        for (int j = 0; j < max_count; ++j) {
-            const int inx = d_cv_floor(nx), iny = d_cv_floor(ny);
-            if (inx < -WIN || inx >= cols || iny < -WIN || iny >= rows) {
-                if (level == 0) status = 0;
-                break;
-            }
-            ++n_it;
-            if (inx != held_x || iny != held_y) {
-                held_x = inx; held_y = iny; LKT_COUNT(8);
-                if (act && LK_INB(next, level, wrow + iny, x0 + inx, 2, nx, ny)) {
-                    const uint8_t* Jp = Jbase + (ptrdiff_t)(wrow + iny) * stepJ + (x0 + inx);
-                    __builtin_memcpy(&j0, Jp, 8); __builtin_memcpy(&j1, Jp + stepJ, 8);
-                }
-            }
-            a = nx - inx; b = ny - iny;
-            iw00 = d_cv_round((1.f - a) * (1.f - b) * (1 << LK_W_BITS));
-            iw01 = d_cv_round(a * (1.f - b) * (1 << LK_W_BITS));
-            iw10 = d_cv_round((1.f - a) * b * (1 << LK_W_BITS));
-            iw11 = (1 << LK_W_BITS) - iw00 - iw01 - iw10;
-            int pb[2] = {0, 0};
-#pragma unroll
-            for (int k = 0; k < LK_RS_SEG; ++k) {
-                const int s00 = (int)((j0 >> (8 * k)) & 0xFF), s01 = (int)((j0 >> (8 * k + 8)) & 0xFF);
-                const int s10 = (int)((j1 >> (8 * k)) & 0xFF), s11 = (int)((j1 >> (8 * k + 8)) & 0xFF);
-                const int diff = ((lk_blend_u8(s00, s01, s10, s11, iw00, iw01, iw10, iw11) + (1 << (LK_W_BITS - 5 - 1))) >> (LK_W_BITS - 5)) - Iv[k];
-                pb[0] += diff * Ixv[k]; pb[1] += diff * Iyv[k];          // lane 63 (no pixels): Ixv = Iyv = 0, j0 = j1 = 0
-            }
-            LKT(3); LKT_COUNT(6);
-            float fb[2];
-            lk_lds_sums<2>(acc, pb, fb, FLT_SCALE);
-            LKT(4);
-            const float b1 = fb[0], b2 = fb[1];
-            const float dx = (A12 * b2 - A22 * b1) * D;
-            const float dy = (A12 * b1 - A11 * b2) * D;
-            nx += dx; ny += dy;
-            next_pt.x = nx + half; next_pt.y = ny + half;
-            if ((double)dx * dx + (double)dy * dy <= epsilon) break;
-            if (j > 0 && fabs((double)(dx + pdx)) < 0.01 && fabs((double)(dy + pdy)) < 0.01) {
-                next_pt.x -= dx * 0.5f; next_pt.y -= dy * 0.5f;
-                break;
-            }
-            pdx = dx; pdy = dy;
-            LKT(5);
-        }
-        LKT(5);
+        if (good) {
+            tk.lap(2);
+            n_it = lk_rs_iterate(Iv, Ixv, Iyv, A11, A12, A22, Dinv, next, level, max_count, epsilon, next_pt, status, acc, tk, 2);
+        } else if (level == 0) status = 0;
         if (iters_out && lane == 0) iters_out[level] = n_it;
         total_it += n_it;
     }
-    LKT_FLUSH(LKT_PASS);
+    tk.flush(LKT_PASS);
     return total_it;
 }
 
-// ---- variant 2: the same arithmetic, the levels' templates built by OTHER wavefronts of the block (k_fe_lk_pipe, frontend.hip).
+// ---- the levels' templates built by OTHER wavefronts of the block (k_fe_lk_pipe, frontend.hip).
 // What a track costs is one wavefront's dependent instruction stream (profiles/r6_e_*: fewer instructions in one phase did not make it
 // shorter), and a third of that stream - per level: six loads, 21 bilinear blends, three exact sums, a square root and two divisions,
 // ~1.7 us - does not depend on what the iterations find: the template of a level is a function of the point in the FIRST image alone.
 // So the wavefront that iterates no longer builds it: three builder wavefronts (levels l, l + 3, ...) do, at once, before the pass
 // starts, and leave per lane the 21 shorts (I, Ix, Iy of its seven pixels) and per level A11, A12, A22, 1 / D and the verdict of the
-// eigenvalue test in LDS.  Same loads, same integer blends, same exact sums, same float expressions: the same bits.
+// eigenvalue test in LDS.  The same building blocks as above, so the same bits.
 #define LK_PIPE_MAX_LEVELS 4
 struct LkTplLevel {
     unsigned long long px[64][6];       // per lane: Iv[7], Ixv[7], Iyv[7] (21 shorts, 48 bytes)
@@ -569,94 +496,45 @@ struct LkTplLevel {
     int state;                          // 0 the window's origin lies outside the image, 1 the eigenvalue / determinant test failed (either: no iterations, status 0 at level 0), 2 iterate
     int pad_[3];
 };
+// fetch, blend, sums, test, pack to LDS
 __device__ __forceinline__ void lk_tpl_build21(const PyrView& I, int level, lvk_pt2f prev_pt, LkTplLevel& T, LkLdsAcc& acc)
 {
-    constexpr int WIN = 21;
-    auto uni = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-    prev_pt.x = uni(prev_pt.x); prev_pt.y = uni(prev_pt.y);
+    prev_pt.x = lk_uni(prev_pt.x); prev_pt.y = lk_uni(prev_pt.y);
     const int lane = threadIdx.x & 63;
-    const float half = (WIN - 1) * 0.5f;
-    const float FLT_SCALE = 1.f / (1 << 20);
-    const int wrow = lane / 3, x0 = (lane - 3 * wrow) * LK_RS_SEG;
-    const bool act = lane < 3 * WIN;
-    const float lscale = (float)(1. / (1 << level));
-    const float prx = prev_pt.x * lscale - half, pry = prev_pt.y * lscale - half;
-    const int ipx = d_cv_floor(prx), ipy = d_cv_floor(pry);
-    const int cols = I.w[level], rows = I.h[level];
-    if (ipx < -WIN || ipx >= cols || ipy < -WIN || ipy >= rows) {
+    const LkRsRaw raw = lk_rs_fetch(I, level, prev_pt, 3);
+    if (!raw.ok) {
         if (lane == 0) T.state = 0;
         return;
     }
-    unsigned long long i0 = 0, i1 = 0; uint4 d00 = {0, 0, 0, 0}, d01 = d00, d10 = d00, d11 = d00;
-    if (act && LK_INB(I, level, wrow + ipy, x0 + ipx, 3, prev_pt.x, prev_pt.y)) {
-        const int stepI = I.istride[level], dstep = I.dstride[level];
-        const uint8_t* src = I.img[level] + (ptrdiff_t)(wrow + ipy) * stepI + (x0 + ipx);
-        const int16_t* ds = I.der[level] + (ptrdiff_t)(wrow + ipy) * dstep + 2 * (x0 + ipx);
-        __builtin_memcpy(&i0, src, 8); __builtin_memcpy(&i1, src + stepI, 8);
-        __builtin_memcpy(&d00, ds, 16); __builtin_memcpy(&d01, ds + 8, 16);
-        __builtin_memcpy(&d10, ds + dstep, 16); __builtin_memcpy(&d11, ds + dstep + 8, 16);
-    }
-    const float a = prx - ipx, b = pry - ipy;
-    const int iw00 = d_cv_round((1.f - a) * (1.f - b) * (1 << LK_W_BITS));
-    const int iw01 = d_cv_round(a * (1.f - b) * (1 << LK_W_BITS));
-    const int iw10 = d_cv_round((1.f - a) * b * (1 << LK_W_BITS));
-    const int iw11 = (1 << LK_W_BITS) - iw00 - iw01 - iw10;
+    short Iv[LK_RS_SEG], Ixv[LK_RS_SEG], Iyv[LK_RS_SEG];
+    int pA[3];
+    lk_rs_blend(raw, lk_weights(raw.a, raw.b), Iv, Ixv, Iyv, pA);
+    float fA[3];
+    lk_lds_sums<3>(acc, pA, fA, LK_FLT_SCALE);
+    float A11, A12, A22, Dinv;
+    const bool good = lk_level_test(fA, A11, A12, A22, Dinv);
     unsigned short q[24];
 #pragma unroll
-    for (int j = 21; j < 24; ++j) q[j] = 0;
-    int pA[3] = {0, 0, 0};
-    {
-        const unsigned dr0[8] = {d00.x, d00.y, d00.z, d00.w, d01.x, d01.y, d01.z, d01.w};
-        const unsigned dr1[8] = {d10.x, d10.y, d10.z, d10.w, d11.x, d11.y, d11.z, d11.w};
+    for (int j = 0; j < LK_RS_SEG; ++j) { q[j] = (unsigned short)Iv[j]; q[7 + j] = (unsigned short)Ixv[j]; q[14 + j] = (unsigned short)Iyv[j]; }
 #pragma unroll
-        for (int j = 0; j < LK_RS_SEG; ++j) {
-            const int s00 = (int)((i0 >> (8 * j)) & 0xFF), s01 = (int)((i0 >> (8 * j + 8)) & 0xFF);
-            const int s10 = (int)((i1 >> (8 * j)) & 0xFF), s11 = (int)((i1 >> (8 * j + 8)) & 0xFF);
-            const int x00 = (short)(dr0[j] & 0xFFFF), y00 = (short)(dr0[j] >> 16), x01 = (short)(dr0[j + 1] & 0xFFFF), y01 = (short)(dr0[j + 1] >> 16);
-            const int x10 = (short)(dr1[j] & 0xFFFF), y10 = (short)(dr1[j] >> 16), x11 = (short)(dr1[j + 1] & 0xFFFF), y11 = (short)(dr1[j + 1] >> 16);
-            int ival = (lk_blend_u8(s00, s01, s10, s11, iw00, iw01, iw10, iw11) + (1 << (LK_W_BITS - 5 - 1))) >> (LK_W_BITS - 5);
-            int ixval = (lk_blend_i16(x00, x01, x10, x11, iw00, iw01, iw10, iw11) + (1 << (LK_W_BITS - 1))) >> LK_W_BITS;
-            int iyval = (lk_blend_i16(y00, y01, y10, y11, iw00, iw01, iw10, iw11) + (1 << (LK_W_BITS - 1))) >> LK_W_BITS;
-            if (!act) { ival = 0; ixval = 0; iyval = 0; }
-            q[j] = (unsigned short)(short)ival; q[7 + j] = (unsigned short)(short)ixval; q[14 + j] = (unsigned short)(short)iyval;
-            pA[0] += ixval * ixval; pA[1] += ixval * iyval; pA[2] += iyval * iyval;
-        }
-    }
-    float fA[3];
-    lk_lds_sums<3>(acc, pA, fA, FLT_SCALE);
-    const float A11 = fA[0], A12 = fA[1], A22 = fA[2];
-    const float D = A11 * A22 - A12 * A12;
-    const float min_eig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * WIN * WIN);
-    const bool bad = min_eig < (float)1e-4 || D < FLT_EPSILON;
+    for (int j = 21; j < 24; ++j) q[j] = 0;
 #pragma unroll
     for (int j = 0; j < 6; ++j)
         T.px[lane][j] = (unsigned long long)q[4 * j] | ((unsigned long long)q[4 * j + 1] << 16) | ((unsigned long long)q[4 * j + 2] << 32) | ((unsigned long long)q[4 * j + 3] << 48);
-    if (lane == 0) { T.A11 = A11; T.A12 = A12; T.A22 = A22; T.Dinv = bad ? 0.f : 1.f / D; T.state = bad ? 1 : 2; }
+    if (lane == 0) { T.A11 = A11; T.A12 = A12; T.A22 = A22; T.Dinv = Dinv; T.state = good ? 2 : 1; }
 }
-// the iterations of one pass over all levels, by the wavefront that owns the track; T[level] was filled by lk_tpl_build21 (and a barrier)
+// the iterations of one pass over all levels, by the wavefront that owns the track; T[level] was filled by lk_tpl_build21 (and a
+// barrier): per level unpack, iterate
 __device__ __forceinline__ int lk_pass_iterate21(const PyrView& next, int n_levels, const LkTplLevel* T, lvk_pt2f& next_pt, int& status,
                                                  int max_count, double epsilon, LkLdsAcc& acc)
 {
-    constexpr int WIN = 21;
-    auto uni = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-    next_pt.x = uni(next_pt.x); next_pt.y = uni(next_pt.y);
+    next_pt.x = lk_uni(next_pt.x); next_pt.y = lk_uni(next_pt.y);
     int total_it = 0;
     const int lane = threadIdx.x & 63;
-    const float half = (WIN - 1) * 0.5f;
-    const float FLT_SCALE = 1.f / (1 << 20);
     const int max_level = n_levels - 1;
-    const int wrow = lane / 3, x0 = (lane - 3 * wrow) * LK_RS_SEG;
-    const bool act = lane < 3 * WIN;
+    LkTicks tk;                         // the phase account is k_fe_lk_both's: never flushed here
     for (int level = max_level; level >= 0; --level) {
-        const int cols = next.w[level], rows = next.h[level];
-        const int stepJ = next.istride[level];
-        const uint8_t* __restrict__ Jbase = next.img[level];
-        const float lscale = (float)(1. / (1 << level));
-        float nx, ny;
-        if (level == max_level) { nx = next_pt.x * lscale; ny = next_pt.y * lscale; }
-        else { nx = next_pt.x * 2.f; ny = next_pt.y * 2.f; }
-        next_pt.x = nx; next_pt.y = ny;
-        int n_it = 0;
+        lk_level_start(next_pt, level, max_level);
         const LkTplLevel& L = T[level];
         const int state = __builtin_amdgcn_readfirstlane(L.state);
         if (state != 2) {
@@ -675,83 +553,27 @@ __device__ __forceinline__ int lk_pass_iterate21(const PyrView& next, int n_leve
                 Iyv[j] = (short)(w[(14 + j) >> 2] >> (16 * ((14 + j) & 3)));
             }
         }
-        const float A11 = uni(L.A11), A12 = uni(L.A12), A22 = uni(L.A22), D = uni(L.Dinv);
-        nx -= half; ny -= half;
-        float pdx = 0.f, pdy = 0.f;
-        unsigned long long j0 = 0, j1 = 0;
-        int held_x = INT_MIN, held_y = INT_MIN;
-        for (int j = 0; j < max_count; ++j) {
-            const int inx = d_cv_floor(nx), iny = d_cv_floor(ny);
-            if (inx < -WIN || inx >= cols || iny < -WIN || iny >= rows) {
-                if (level == 0) status = 0;
-                break;
-            }
-            ++n_it;
-            if (inx != held_x || iny != held_y) {
-                held_x = inx; held_y = iny;
-                if (act && LK_INB(next, level, wrow + iny, x0 + inx, 4, nx, ny)) {
-                    const uint8_t* Jp = Jbase + (ptrdiff_t)(wrow + iny) * stepJ + (x0 + inx);
-                    __builtin_memcpy(&j0, Jp, 8); __builtin_memcpy(&j1, Jp + stepJ, 8);
-                }
-            }
-            const float a = nx - inx, b = ny - iny;
-            const int iw00 = d_cv_round((1.f - a) * (1.f - b) * (1 << LK_W_BITS));
-            const int iw01 = d_cv_round(a * (1.f - b) * (1 << LK_W_BITS));
-            const int iw10 = d_cv_round((1.f - a) * b * (1 << LK_W_BITS));
-            const int iw11 = (1 << LK_W_BITS) - iw00 - iw01 - iw10;
-            int pb[2] = {0, 0};
-#pragma unroll
-            for (int k = 0; k < LK_RS_SEG; ++k) {
-                const int s00 = (int)((j0 >> (8 * k)) & 0xFF), s01 = (int)((j0 >> (8 * k + 8)) & 0xFF);
-                const int s10 = (int)((j1 >> (8 * k)) & 0xFF), s11 = (int)((j1 >> (8 * k + 8)) & 0xFF);
-                const int diff = ((lk_blend_u8(s00, s01, s10, s11, iw00, iw01, iw10, iw11) + (1 << (LK_W_BITS - 5 - 1))) >> (LK_W_BITS - 5)) - Iv[k];
-                pb[0] += diff * Ixv[k]; pb[1] += diff * Iyv[k];
-            }
-            float fb[2];
-            lk_lds_sums<2>(acc, pb, fb, FLT_SCALE);
-            const float b1 = fb[0], b2 = fb[1];
-            const float dx = (A12 * b2 - A22 * b1) * D;
-            const float dy = (A12 * b1 - A11 * b2) * D;
-            nx += dx; ny += dy;
-            next_pt.x = nx + half; next_pt.y = ny + half;
-            if ((double)dx * dx + (double)dy * dy <= epsilon) break;
-            if (j > 0 && fabs((double)(dx + pdx)) < 0.01 && fabs((double)(dy + pdy)) < 0.01) {
-                next_pt.x -= dx * 0.5f; next_pt.y -= dy * 0.5f;
-                break;
-            }
-            pdx = dx; pdy = dy;
-        }
-        total_it += n_it;
+        total_it += lk_rs_iterate(Iv, Ixv, Iyv, lk_uni(L.A11), lk_uni(L.A12), lk_uni(L.A22), lk_uni(L.Dinv), next, level, max_count, epsilon, next_pt, status, acc, tk, 4);
     }
     return total_it;
 }
 
-// LK variants (run-time: LVK_LK_VARIANT, read once per process; A/B records in profiles/):
-//   0  lk_point_rs21      wave-wide sums by DPP + v_readlane + scalar carry chain (rounds 3-5)
-//   1  lk_point_rs21_lds  sums through LDS accumulators, next-image bytes kept while the window origin stands
-//   2  k_fe_lk_pipe (frontend.hip): variant 1's arithmetic with the levels' templates built by three more wavefronts of the block
+// The LK kernels (A/B records in profiles/; the wave-wide sums by DPP + v_readlane of rounds 3-5, once variant 0, are gone):
+//   lk_point_rs21_lds  one wavefront per pass: k_lk_track<21>, k_fe_lk_both<21> (LVK_LK_VARIANT=1, and 0 selects it too)
+//   lk_tpl_build21 + lk_pass_iterate21  the same arithmetic with the levels' templates built by three more wavefronts of the block:
+//                      k_fe_lk_pipe (frontend.hip; LVK_LK_VARIANT=2)
 // (tried and dropped, profiles/r6_e_*: sums by DPP + one FP64 MFMA; touching the next image's lines of all levels at the start of a pass)
+// Which of the two a frame uses when LVK_LK_VARIANT is unset: lvk_lk_variant(), lvk_internal.h.
 // LVK_LK_GENERIC (compile-time): the one-pixel-per-lane-slot path for every window size
-#define LVK_LK_VARIANTS 3
-template <int WIN, int VAR, int PASS = 0>
+template <int WIN, int PASS = 0>
 __device__ __forceinline__ int lk_point(const PyrView& prev, const PyrView& next, int n_levels, lvk_pt2f prev_pt, lvk_pt2f& next_pt,
                                         int& status, int max_count, double epsilon, int* __restrict__ iters_out, LkLdsAcc& acc)
 {
 #ifndef LVK_LK_GENERIC
-    if constexpr (WIN == 21 && VAR >= 1) return lk_point_rs21_lds<PASS>(prev, next, n_levels, prev_pt, next_pt, status, max_count, epsilon, iters_out, acc);
-    else if constexpr (WIN == 21) return lk_point_rs21(prev, next, n_levels, prev_pt, next_pt, status, max_count, epsilon, iters_out);
+    if constexpr (WIN == 21) return lk_point_rs21_lds<PASS>(prev, next, n_levels, prev_pt, next_pt, status, max_count, epsilon, iters_out, acc);
     else
 #endif
     return lk_point_generic<WIN>(prev, next, n_levels, prev_pt, next_pt, status, max_count, epsilon, iters_out);
-}
-// zero the wavefront's LDS accumulators (4 x u64, 16-byte aligned; call once, by the wavefront that will use them)
-__device__ __forceinline__ LkLdsAcc lk_acc_init(unsigned long long* lds4)
-{
-    LkLdsAcc a; a.prev[0] = a.prev[1] = a.prev[2] = 0;
-    a.off = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned long long*)lds4;
-    if ((threadIdx.x & 63) < 4) lds4[threadIdx.x & 63] = 0;
-    __builtin_amdgcn_wave_barrier();
-    return a;
 }
 
 // ------------------------------------------------------------------------- ORB

@@ -380,6 +380,93 @@ __device__ __forceinline__ lvk_pt2f apply_h(const HMat& H, lvk_pt2f p)
 #define ST_REV   2
 #define ST_ORB   3
 
+// ---- what the two frame kernels below share; none of these pieces contains a block barrier
+// per-block spans (-DLVK_LK_TIMING, tools/gpu/lk_ticks.py); an empty object in every other build
+#ifdef LVK_LK_TIMING
+static __device__ unsigned long long g_lk_span[4096][4];     // per block: cycles entry -> forward done, -> reverse done, -> end; 100 MHz ticks entry -> end
+struct LkSpan {
+    unsigned long long c0, w0, c1 = 0, c2 = 0;
+    __device__ __forceinline__ LkSpan() : c0(clock64()), w0(wall_clock64()) { }
+    __device__ __forceinline__ void fwd_done() { c1 = clock64(); }
+    __device__ __forceinline__ void rev_done() { c2 = clock64(); }
+    __device__ __forceinline__ void write(int p) const
+    {
+        if (p < 4096) { g_lk_span[p][0] = c1 - c0; g_lk_span[p][1] = c2 - c0; g_lk_span[p][2] = clock64() - c0; g_lk_span[p][3] = wall_clock64() - w0; }
+    }
+};
+#else
+struct LkSpan {
+    __device__ __forceinline__ void fwd_done() { }
+    __device__ __forceinline__ void rev_done() { }
+    __device__ __forceinline__ void write(int) const { }
+};
+#endif
+// -DLVK_LK_BOUNDS: is a point handed to the LK / ORB wavefronts inside the image?  The first one that is not is recorded by `reporter`
+// (one thread of the callers) as site 5 (the source point) or 6 (the forward result).  Always true in every other build.
+__device__ __forceinline__ bool fe_lk_point_ok(lvk_pt2f pt, int width, int height, bool reporter, int site, int n, int p, int is_new)
+{
+#ifdef LVK_LK_BOUNDS
+    if (!(pt.x >= 0 && pt.x <= width - 1 && pt.y >= 0 && pt.y <= height - 1)) {
+        if (reporter && atomicAdd(&g_lk_oob[0], 1) == 0) { g_lk_oob[1] = site; g_lk_oob[2] = n; g_lk_oob[3] = p; g_lk_oob[4] = is_new; g_lk_oob[7] = __builtin_bit_cast(int, pt.x); g_lk_oob[8] = __builtin_bit_cast(int, pt.y); g_lk_oob[9] = blockIdx.x; }
+        return false;
+    }
+#endif
+    return true;
+}
+__device__ __forceinline__ bool fe_outside_image(lvk_pt2f p, int width, int height) { return p.y < 0 || p.y > height - 1 || p.x < 0 || p.x > width - 1; }
+// the LK wavefront after the forward pass: the in-image test, then the point and the verdict for the block
+__device__ __forceinline__ void fe_lk_forward_done(lvk_pt2f np, int& st, int width, int height, lvk_pt2f& s_np, int& s_st)
+{
+    if (st && fe_outside_image(np, width, height)) st = 0;
+    if ((threadIdx.x & 63) == 0) { s_np = np; s_st = st; }
+}
+// the LK wavefront after the reverse pass: the status code of a point that came back at `back` (:616-642)
+__device__ __forceinline__ int fe_lk_round_trip(lvk_pt2f pp, lvk_pt2f back, int sr, int width, int height)
+{
+    if (sr) {
+        if (fe_outside_image(back, width, height)) sr = 0;
+        else {
+            float dx = back.x - pp.x, dy = back.y - pp.y;
+            float dis = (float)sqrt((double)dx * dx + (double)dy * dy);      // cv::norm(Point2f) is double
+            if (dis > 1) sr = 0;
+        }
+    }
+    return sr ? ST_ALIVE : ST_REV;
+}
+// the descriptor / undistortion wavefront, during the forward pass: the previous-image descriptor of a new point (kept in dp and
+// written out), the undistorted source point
+__device__ __forceinline__ void fe_desc_before(const uint8_t* __restrict__ prv_ext, const uint8_t* __restrict__ prv_blur, int step, lvk_pt2f pp, int p, int is_new,
+                                               unsigned long long (&dp)[4], unsigned long long* __restrict__ w_desc, const CamParams& cam, lvk_pt2f* __restrict__ w_und)
+{
+    const int lane = threadIdx.x & 63;
+    if (is_new) {
+        orb_point(prv_ext, prv_blur, step, pp, dp);
+        if (lane == 0) { unsigned long long* o = w_desc + (size_t)p * 4; o[0] = dp[0]; o[1] = dp[1]; o[2] = dp[2]; o[3] = dp[3]; }
+    }
+    if (lane == 0) w_und[2 * (size_t)p] = undistort_point(pp, cam, cam.intr);
+}
+// ... and once the forward pass has produced the point np (in_plane: fe_lk_point_ok of it): the current-image descriptor, its distance to
+// the previous-image one (new points) or the stored first-seen one (old tracks) for the block, the undistorted np
+__device__ __forceinline__ void fe_desc_after(const uint8_t* __restrict__ cur_ext, const uint8_t* __restrict__ cur_blur, int step, lvk_pt2f np, bool in_plane, int p, int is_new,
+                                              const unsigned long long (&dp)[4], const unsigned long long* __restrict__ stored_desc, const CamParams& cam,
+                                              lvk_pt2f* __restrict__ w_und, int& s_dist)
+{
+    unsigned long long dc[4];
+    if (in_plane) orb_point(cur_ext, cur_blur, step, np, dc);
+    const int dist = is_new ? hamming256_u64(dc, dp) : hamming256_u64(dc, stored_desc + (size_t)p * 4);
+    if ((threadIdx.x & 63) == 0) { s_dist = dist; w_und[2 * (size_t)p + 1] = undistort_point(np, cam, cam.intr); }
+}
+// one thread, after the last barrier: the descriptor gate (:677-699 / :909-930), then point, status code, counters and span
+__device__ __forceinline__ void fe_lk_finish(int p, lvk_pt2f np, int code, const int& s_dist, int passes, int n_levels, int its,
+                                             lvk_pt2f* __restrict__ w_curr, uint8_t* __restrict__ w_status, FeDev* __restrict__ dev, const LkSpan& span, bool span_on)
+{
+    if (code == ST_ALIVE && s_dist > 58) code = ST_ORB;
+    w_curr[p] = np; w_status[p] = (uint8_t)code;
+    atomicAdd(&dev->lk_point_levels, (unsigned long long)(passes * n_levels));
+    atomicAdd(&dev->lk_iterations, (unsigned long long)its);
+    if (span_on) span.write(p);
+}
+
 // Forward LK (prev -> curr, seeded with the gyro-predicted point, :558-590 / :830-860), reverse LK (curr -> prev, seeded with the
 // original point; in-image and <= 1 px tests, :616-642) and the ORB descriptor gate (:677-699 old tracks: descriptor at the current
 // point vs the stored first-seen one; :909-930 new points: descriptor in the previous image vs in the current one, the previous one is
@@ -390,10 +477,7 @@ __device__ __forceinline__ lvk_pt2f apply_h(const HMat& H, lvk_pt2f p)
 // wavefront also undistorts the point pair (K -> K, what findFundamentalMat is fed, :701-712 / :932-943) into w_und[2p], [2p+1]:
 // two sequential double-precision fixed-point loops per point that the one-workgroup commit kernel would otherwise run for
 // every point of its set (24 us of its 120 at 2000 tracks).
-#ifdef LVK_LK_TIMING
-static __device__ unsigned long long g_lk_span[4096][4];     // per block: cycles entry -> forward done, -> reverse done, -> end; 100 MHz ticks entry -> end
-#endif
-template <int WIN, int VAR>
+template <int WIN>
 __global__ void __launch_bounds__(128) k_fe_lk_both(PyrView prev, PyrView next, const lvk_pt2f* __restrict__ src_pts, const int* __restrict__ n_ptr,
                                                    HMat H, int width, int height, int max_count, double epsilon,
                                                    lvk_pt2f* __restrict__ w_curr, uint8_t* __restrict__ w_status, FeDev* __restrict__ dev,
@@ -406,12 +490,9 @@ __global__ void __launch_bounds__(128) k_fe_lk_both(PyrView prev, PyrView next, 
     __shared__ int s_st, s_dist;
     __shared__ __attribute__((aligned(16))) unsigned long long s_acc[4];
     const int p = blockIdx.x;
-#ifdef LVK_LK_TIMING
-    const unsigned long long lkt_c0 = clock64(), lkt_w0 = wall_clock64();
-    unsigned long long lkt_c1 = 0, lkt_c2 = 0;
-#endif
+    LkSpan span;
     if (p >= *n_ptr) return;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
     const int n_levels = prev.n_levels < next.n_levels ? prev.n_levels : next.n_levels;
     const int step = width + 2 * LVK_ORB_BORDER;
     const lvk_pt2f pp = src_pts[p];
@@ -422,61 +503,31 @@ __global__ void __launch_bounds__(128) k_fe_lk_both(PyrView prev, PyrView next, 
     if (wave == 0) {
         acc = lk_acc_init(s_acc);
         np = apply_h(H, pp);
-        its = lk_point<WIN, VAR>(prev, next, n_levels, pp, np, st, max_count, epsilon, nullptr, acc);
-        if (st && (np.y < 0 || np.y > height - 1 || np.x < 0 || np.x > width - 1)) st = 0;
-        if (lane == 0) { s_np = np; s_st = st; }
-#ifdef LVK_LK_TIMING
-        lkt_c1 = clock64();
-#endif
-    } else {
-        if (is_new) {
-            orb_point(prv_ext, prv_blur, step, pp, dp);
-            if (lane == 0) { unsigned long long* o = w_desc + (size_t)p * 4; o[0] = dp[0]; o[1] = dp[1]; o[2] = dp[2]; o[3] = dp[3]; }
-        }
-        if (lane == 0) w_und[2 * (size_t)p] = undistort_point(pp, cam, cam.intr);
-    }
+        its = lk_point<WIN>(prev, next, n_levels, pp, np, st, max_count, epsilon, nullptr, acc);
+        fe_lk_forward_done(np, st, width, height, s_np, s_st);
+        span.fwd_done();
+    } else fe_desc_before(prv_ext, prv_blur, step, pp, p, is_new, dp, w_desc, cam, w_und);
     __syncthreads();
     int code = ST_FWD, passes = 1;
     if (wave == 0) {
-        code = st ? ST_ALIVE : ST_FWD;
         if (st) {
             lvk_pt2f back = pp;
             int sr = 1;
-            its += lk_point<WIN, VAR, 1>(next, prev, n_levels, np, back, sr, max_count, epsilon, nullptr, acc);
+            its += lk_point<WIN, 1>(next, prev, n_levels, np, back, sr, max_count, epsilon, nullptr, acc);
             passes = 2;
-            if (sr) {
-                if (back.y < 0 || back.y > height - 1 || back.x < 0 || back.x > width - 1) sr = 0;
-                else {
-                    float dx = back.x - pp.x, dy = back.y - pp.y;
-                    float dis = (float)sqrt((double)dx * dx + (double)dy * dy);      // cv::norm(Point2f) is double
-                    if (dis > 1) sr = 0;
-                }
-            }
-            if (!sr) code = ST_REV;
+            code = fe_lk_round_trip(pp, back, sr, width, height);
         }
-#ifdef LVK_LK_TIMING
-        lkt_c2 = clock64();
-#endif
+        span.rev_done();
     } else if (s_st) {
-        unsigned long long dc[4];
-        orb_point(cur_ext, cur_blur, step, s_np, dc);
-        const int dist = is_new ? hamming256_u64(dc, dp) : hamming256_u64(dc, stored_desc + (size_t)p * 4);
-        if (lane == 0) { s_dist = dist; w_und[2 * (size_t)p + 1] = undistort_point(s_np, cam, cam.intr); }
+        const lvk_pt2f fnp = s_np;
+        fe_desc_after(cur_ext, cur_blur, step, fnp, fe_lk_point_ok(fnp, width, height, (threadIdx.x & 63) == 0, 6, *n_ptr, p, is_new), p, is_new, dp, stored_desc, cam, w_und, s_dist);
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        if (code == ST_ALIVE && s_dist > 58) code = ST_ORB;
-        w_curr[p] = np; w_status[p] = (uint8_t)code;
-        atomicAdd(&dev->lk_point_levels, (unsigned long long)(passes * n_levels));
-        atomicAdd(&dev->lk_iterations, (unsigned long long)its);
-#ifdef LVK_LK_TIMING
-        if (p < 4096) { g_lk_span[p][0] = lkt_c1 - lkt_c0; g_lk_span[p][1] = lkt_c2 - lkt_c0; g_lk_span[p][2] = clock64() - lkt_c0; g_lk_span[p][3] = wall_clock64() - lkt_w0; }
-#endif
-    }
+    if (threadIdx.x == 0) fe_lk_finish(p, np, code, s_dist, passes, n_levels, its, w_curr, w_status, dev, span, true);
 }
 
-// The same stages with the track's work spread over FIVE wavefronts (LK variant 2, fe_track_dev.h): wavefront 0 owns the track and
-// only iterates; wavefronts 1-3 build the levels' templates of a pass at once (level w - 1, w + 2, ...) before it starts - forward: from
+// The same stages with the track's work spread over FIVE wavefronts (lk_tpl_build21 + lk_pass_iterate21, fe_track_dev.h): wavefront 0 owns the
+// track and only iterates; wavefronts 1-3 build the levels' templates of a pass at once (level w - 1, w + 2, ...) before it starts - forward: from
 // the point in the previous image, known at launch; reverse: from the forward result - and wavefront 4 is the descriptor / undistortion
 // wavefront of k_fe_lk_both.  Four block barriers, every wavefront passes each of them.
 // One track set of a launch: the old tracks (trackFeatures) or the new points (trackNewFeatures).  The kernel can carry BOTH in one launch
@@ -509,12 +560,9 @@ __global__ void __launch_bounds__(320) k_fe_lk_pipe(PyrView prev, PyrView next, 
     lvk_pt2f* __restrict__ w_curr = S.w_curr; uint8_t* __restrict__ w_status = S.w_status;
     const unsigned long long* __restrict__ stored_desc = S.stored_desc; unsigned long long* __restrict__ w_desc = S.w_desc;
     lvk_pt2f* __restrict__ w_und = S.w_und; const int is_new = S.is_new;
-#ifdef LVK_LK_TIMING
-    const unsigned long long lkt_c0 = clock64(), lkt_w0 = wall_clock64();
-    unsigned long long lkt_c1 = 0, lkt_c2 = 0;
-#endif
+    LkSpan span;
     if (p >= *n_ptr) return;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
     const int n_levels = prev.n_levels < next.n_levels ? prev.n_levels : next.n_levels;
     const int step = width + 2 * LVK_ORB_BORDER;
     const lvk_pt2f pp = src_pts[p];
@@ -523,30 +571,16 @@ __global__ void __launch_bounds__(320) k_fe_lk_pipe(PyrView prev, PyrView next, 
     unsigned long long dp[4] = {0, 0, 0, 0};
     LkLdsAcc acc; acc.off = 0; acc.prev[0] = acc.prev[1] = acc.prev[2] = 0;
     if (wave < 4) acc = lk_acc_init(s_acc[wave]);
-#ifdef LVK_LK_BOUNDS
-    if (!(pp.x >= 0 && pp.x <= width - 1 && pp.y >= 0 && pp.y <= height - 1)) {
-        if (threadIdx.x == 0 && atomicAdd(&g_lk_oob[0], 1) == 0) { g_lk_oob[1] = 5; g_lk_oob[2] = *n_ptr; g_lk_oob[3] = p; g_lk_oob[4] = is_new; g_lk_oob[7] = __builtin_bit_cast(int, pp.x); g_lk_oob[8] = __builtin_bit_cast(int, pp.y); g_lk_oob[9] = blockIdx.x; }
-        return;
-    }
-#endif
+    if (!fe_lk_point_ok(pp, width, height, threadIdx.x == 0, 5, *n_ptr, p, is_new)) return;
     // ---- before the forward pass: its templates, the gyro-predicted start, the previous-image descriptor of a new point
     if (wave == 0) np = apply_h(H, pp);
     else if (wave < 4) { for (int level = wave - 1; level < n_levels; level += 3) lk_tpl_build21(prev, level, pp, s_tpl[level], acc); }
-    else {
-        if (is_new) {
-            orb_point(prv_ext, prv_blur, step, pp, dp);
-            if (lane == 0) { unsigned long long* o = w_desc + (size_t)p * 4; o[0] = dp[0]; o[1] = dp[1]; o[2] = dp[2]; o[3] = dp[3]; }
-        }
-        if (lane == 0) w_und[2 * (size_t)p] = undistort_point(pp, cam, cam.intr);
-    }
+    else fe_desc_before(prv_ext, prv_blur, step, pp, p, is_new, dp, w_desc, cam, w_und);
     __syncthreads();
     if (wave == 0) {
         its = lk_pass_iterate21(next, n_levels, s_tpl, np, st, max_count, epsilon, acc);
-        if (st && (np.y < 0 || np.y > height - 1 || np.x < 0 || np.x > width - 1)) st = 0;
-        if (lane == 0) { s_np = np; s_st = st; }
-#ifdef LVK_LK_TIMING
-        lkt_c1 = clock64();
-#endif
+        fe_lk_forward_done(np, st, width, height, s_np, s_st);
+        span.fwd_done();
     }
     __syncthreads();
     const int fwd_ok = s_st;
@@ -556,46 +590,18 @@ __global__ void __launch_bounds__(320) k_fe_lk_pipe(PyrView prev, PyrView next, 
     __syncthreads();
     int code = ST_FWD, passes = 1;
     if (wave == 0) {
-        code = st ? ST_ALIVE : ST_FWD;
         if (st) {
             lvk_pt2f back = pp;
             int sr = 1;
             its += lk_pass_iterate21(prev, n_levels, s_tpl, back, sr, max_count, epsilon, acc);
             passes = 2;
-            if (sr) {
-                if (back.y < 0 || back.y > height - 1 || back.x < 0 || back.x > width - 1) sr = 0;
-                else {
-                    float dx = back.x - pp.x, dy = back.y - pp.y;
-                    float dis = (float)sqrt((double)dx * dx + (double)dy * dy);      // cv::norm(Point2f) is double
-                    if (dis > 1) sr = 0;
-                }
-            }
-            if (!sr) code = ST_REV;
+            code = fe_lk_round_trip(pp, back, sr, width, height);
         }
-#ifdef LVK_LK_TIMING
-        lkt_c2 = clock64();
-#endif
-    } else if (wave == 4 && fwd_ok) {
-        unsigned long long dc[4];
-#ifdef LVK_LK_BOUNDS
-        if (!(fnp.x >= 0 && fnp.x <= width - 1 && fnp.y >= 0 && fnp.y <= height - 1)) {
-            if (lane == 0 && atomicAdd(&g_lk_oob[0], 1) == 0) { g_lk_oob[1] = 6; g_lk_oob[2] = *n_ptr; g_lk_oob[3] = p; g_lk_oob[4] = is_new; g_lk_oob[7] = __builtin_bit_cast(int, fnp.x); g_lk_oob[8] = __builtin_bit_cast(int, fnp.y); g_lk_oob[9] = blockIdx.x; }
-        } else
-#endif
-        orb_point(cur_ext, cur_blur, step, fnp, dc);
-        const int dist = is_new ? hamming256_u64(dc, dp) : hamming256_u64(dc, stored_desc + (size_t)p * 4);
-        if (lane == 0) { s_dist = dist; w_und[2 * (size_t)p + 1] = undistort_point(fnp, cam, cam.intr); }
-    }
+        span.rev_done();
+    } else if (wave == 4 && fwd_ok)
+        fe_desc_after(cur_ext, cur_blur, step, fnp, fe_lk_point_ok(fnp, width, height, (threadIdx.x & 63) == 0, 6, *n_ptr, p, is_new), p, is_new, dp, stored_desc, cam, w_und, s_dist);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        if (code == ST_ALIVE && s_dist > 58) code = ST_ORB;
-        w_curr[p] = np; w_status[p] = (uint8_t)code;
-        atomicAdd(&dev->lk_point_levels, (unsigned long long)(passes * n_levels));
-        atomicAdd(&dev->lk_iterations, (unsigned long long)its);
-#ifdef LVK_LK_TIMING
-        if (!second && p < 4096) { g_lk_span[p][0] = lkt_c1 - lkt_c0; g_lk_span[p][1] = lkt_c2 - lkt_c0; g_lk_span[p][2] = clock64() - lkt_c0; g_lk_span[p][3] = wall_clock64() - lkt_w0; }
-#endif
-    }
+    if (threadIdx.x == 0) fe_lk_finish(p, np, code, s_dist, passes, n_levels, its, w_curr, w_status, dev, span, !second);
 }
 
 // One workgroup of NT threads: count survivors per stage, order-preserving compaction of the alive points (wavefront ballots), the
@@ -885,23 +891,21 @@ static void launch_track_chain(lvk_frontend* fe, hipStream_t s, const PyrView& p
     const int W = fe->cfg.width, Hh = fe->cfg.height;
     if (fe->pyr_event) hipStreamWaitEvent(s, fe->ev_orb, 0);      // the frame start waited for the pyramid only: the ORB planes (read by the kernel's second wavefront) follow it on the image stream
     ProfScope ps(fe, 2, s);
-#define LVK_LK_LAUNCH(V) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fe_lk_both<WIN, V>), dim3(grid), dim3(128), 0, s, pv, cv, src_pts, n_ptr, H, W, Hh, max_count, epsilon, w_curr, w_status, fe->dev, \
-                           (const uint8_t*)fe->ext[1], (const uint8_t*)fe->blur[1], (const uint8_t*)fe->ext[0], (const uint8_t*)fe->blur[0], stored_desc, w_desc, is_new, \
-                           fe->cam, w_curr == fe->w_curr ? fe->w_und : fe->wn_und)
-    int var = WIN == 21 ? lvk_lk_variant() : 1;
-    if (var < 0) var = grid <= LVK_LK_PIPE_MAX_TRACKS ? 2 : 1;
+    lvk_pt2f* const w_und = w_curr == fe->w_curr ? fe->w_und : fe->wn_und;
     if constexpr (WIN == 21) {
+        int var = lvk_lk_variant();
+        if (var < 0) var = grid <= LVK_LK_PIPE_MAX_TRACKS ? 2 : 1;
         if (var == 2 && pv.n_levels <= LK_PIPE_MAX_LEVELS && cv.n_levels <= LK_PIPE_MAX_LEVELS) {
             LkSet a; a.src_pts = src_pts; a.n_ptr = n_ptr; a.w_curr = w_curr; a.w_status = w_status; a.stored_desc = stored_desc; a.w_desc = w_desc;
-            a.w_und = w_curr == fe->w_curr ? fe->w_und : fe->wn_und; a.is_new = is_new; a.pad_ = 0;
+            a.w_und = w_und; a.is_new = is_new; a.pad_ = 0;
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fe_lk_pipe<21>), dim3(grid), dim3(320), 0, s, pv, cv, a, a, grid, H, W, Hh, max_count, epsilon, fe->dev,
                                (const uint8_t*)fe->ext[1], (const uint8_t*)fe->blur[1], (const uint8_t*)fe->ext[0], (const uint8_t*)fe->blur[0], fe->cam);
             return;
         }
     }
-    if (var == 0) LVK_LK_LAUNCH(0);
-    else LVK_LK_LAUNCH(1);
-#undef LVK_LK_LAUNCH
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fe_lk_both<WIN>), dim3(grid), dim3(128), 0, s, pv, cv, src_pts, n_ptr, H, W, Hh, max_count, epsilon, w_curr, w_status, fe->dev,
+                       (const uint8_t*)fe->ext[1], (const uint8_t*)fe->blur[1], (const uint8_t*)fe->ext[0], (const uint8_t*)fe->blur[0], stored_desc, w_desc, is_new,
+                       fe->cam, w_und);
 }
 
 static lvk_status track_chain(lvk_frontend* fe, hipStream_t stream, const lvk_pt2f* src_pts, const int* n_ptr, const HMat& H, lvk_pt2f* w_curr, uint8_t* w_status,

@@ -90,6 +90,21 @@ def test_odd_image_sizes(gpu_ctx, w, h, levels):
     assert states[-1] == 3 and n_tracks[-1] > 40 and n_msgs >= 5
 
 
+@pytest.mark.parametrize("over", [dict(max_features_num=601, min_distance=12),
+                                  dict(max_features_num=120, min_distance=12, patch_size=15),
+                                  dict(max_features_num=120, min_distance=12, patch_size=31)],
+                         ids=["601_slots", "patch_15", "patch_31"])
+def test_two_wavefront_kernel_by_track_count_and_by_window(gpu_ctx, over):
+    """The frame path's two-wavefront LK kernel, reached through configuration alone: 601 track slots is the smallest budget above the
+    five-wavefront kernel's limit of 600 (21 x 21 window, row-segment code); patch_size 15 and 31 take its one-pixel-per-lane-slot
+    path, which no other frame-level test runs."""
+    w, h = 320, 240
+    tex = _texture(8, h + 120, w + 160)
+    frames = _crops(tex, w, h, _walk(14))
+    states, n_tracks, n_msgs = _run(gpu_ctx, frames, _cfg(w, h, pyramid_levels=2, **over))
+    assert states[-1] == 3 and n_msgs >= 5 and n_tracks[-1] > 40
+
+
 def test_featureless_frames_at_the_start_and_in_the_middle(gpu_ctx):
     w, h = 320, 240
     tex = _texture(2, h + 120, w + 160)
