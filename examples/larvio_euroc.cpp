@@ -2,10 +2,12 @@
 // Pangolin): same command line, same loop, same log files (msckf_2_state.txt / msckf_2_takeoff.txt in the configuration's
 // output_dir, written by lvk::LarVio as larvio.cpp:388,446-453 does), running on liblvk_hip.so.
 //
-//   larvio_euroc path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png]
+//   larvio_euroc path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE]
 //
 // --mask restricts corner detection to the non-zero pixels of an 8-bit PNG of the configured resolution (ImageProcessor::setMask:
 // a fisheye vignette, the vehicle's own body); a mask of another size is an error.
+// --map-out turns the filter's lost-point covariances on (LarVio::setLostFeatureCov) and writes, at the end of the run, one line per
+// stable map point: "id x y z sxx sxy sxz syy syz szz" - its last world position and the upper triangle of its 3 x 3 position covariance.
 // --tum writes "t x y z qx qy qz qw" (body in world, absolute stamps, 17 significant digits) for tools/traj_rmse.py.
 // --pipelined runs the same loop through lvk::VioPipeline: the filter update of a message overlaps the front-end of the next
 // frames on a second HIP stream; the trajectory is the same, written from the filter thread's odometry callback.
@@ -25,6 +27,24 @@ static void write_tum(FILE* tum, const lvk::LarVio& Estimator)
     std::fprintf(tum, "%.9f %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", s[0], s[8], s[9], s[10], s[1], s[2], s[3], s[4]);
 }
 
+// --map-out: the stable points collected so far (the filter hands each one out once)
+struct MapOut {
+    FILE* f; long n;
+    void drain(lvk::LarVio& Estimator)
+    {
+        if (!f) return;
+        std::vector<int64_t> ids; std::vector<double> xyz, cov;
+        do {
+            Estimator.takeLostFeaturesCov(ids, xyz, cov);
+            for (size_t i = 0; i < ids.size(); ++i, ++n) {
+                const double* p = &xyz[3 * i]; const double* c = &cov[9 * i];
+                std::fprintf(f, "%lld %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", (long long)ids[i], p[0], p[1], p[2], c[0], c[1], c[2], c[4], c[5], c[8]);
+            }
+        } while (!ids.empty());
+    }
+    void close() { if (f) { std::fclose(f); f = nullptr; } }
+};
+
 struct OdometrySink { FILE* tum; long n_odo; };
 static void on_odometry(void* user, double, const lvk::LarVio& Estimator)
 {
@@ -34,7 +54,7 @@ static void on_odometry(void* user, double, const lvk::LarVio& Estimator)
 }
 
 static int run_pipelined(const char* image_dir, const std::vector<lvk::ImuData>& allImuData, const std::vector<lvk::ImgInfo>& allImgInfo, long max_frames,
-                         lvk::ImageProcessor& ImgProcesser, lvk::LarVio& Estimator, FILE* tum)
+                         lvk::ImageProcessor& ImgProcesser, lvk::LarVio& Estimator, FILE* tum, MapOut& map_out)
 {
     typedef std::chrono::steady_clock Clock;
     lvk::VioPipeline pipe(ImgProcesser, Estimator);
@@ -62,6 +82,7 @@ static int run_pipelined(const char* image_dir, const std::vector<lvk::ImuData>&
     if (!pipe.drain(&n_upd, &n_msgs)) { std::fprintf(stderr, "pipeline: %s\n", "an update failed"); return 1; }
     t_proc += std::chrono::duration<double>(Clock::now() - t2).count();
     if (tum) std::fclose(tum);
+    map_out.drain(Estimator); map_out.close();
     std::printf("frames %zu  feature messages %ld  odometry updates %ld  state dim %d\n", n_frames, n_msgs, sink.n_odo, lvk_ekf_dim(Estimator.handle()));
     std::printf("pipelined: %.3f ms/frame in the driver thread   image read+decode %.3f ms/frame\n", n_frames ? 1e3 * t_proc / n_frames : 0.0, n_frames ? 1e3 * t_io / n_frames : 0.0);
     if (t_proc > 0) std::printf("processing rate %.1f frames/s (pipelined, host buffers)\n", n_frames / t_proc);
@@ -71,15 +92,16 @@ static int run_pipelined(const char* image_dir, const std::vector<lvk::ImuData>&
 int main(int argc, char** argv)
 {
     if (argc < 5) {
-        std::fprintf(stderr, "Usage: %s path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png]\n", argv[0]);
+        std::fprintf(stderr, "Usage: %s path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE]\n", argv[0]);
         return 1;
     }
-    std::string tum_path, mask_path; long max_frames = -1; bool pipelined = false;
+    std::string tum_path, mask_path, map_path; long max_frames = -1; bool pipelined = false;
     for (int a = 5; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--tum") && a + 1 < argc) tum_path = argv[++a];
         else if (!std::strcmp(argv[a], "--max-frames") && a + 1 < argc) max_frames = std::atol(argv[++a]);
         else if (!std::strcmp(argv[a], "--pipelined")) pipelined = true;
         else if (!std::strcmp(argv[a], "--mask") && a + 1 < argc) mask_path = argv[++a];
+        else if (!std::strcmp(argv[a], "--map-out") && a + 1 < argc) map_path = argv[++a];
         else { std::fprintf(stderr, "unknown option %s\n", argv[a]); return 1; }
     }
 
@@ -113,7 +135,12 @@ int main(int argc, char** argv)
 
     FILE* tum = nullptr;
     if (!tum_path.empty() && !(tum = std::fopen(tum_path.c_str(), "w"))) { std::perror(tum_path.c_str()); return 1; }
-    if (pipelined) return run_pipelined(argv[3], allImuData, allImgInfo, max_frames, ImgProcesser, Estimator, tum);
+    MapOut map_out = {nullptr, 0};
+    if (!map_path.empty()) {
+        if (!(map_out.f = std::fopen(map_path.c_str(), "w"))) { std::perror(map_path.c_str()); return 1; }
+        if (!Estimator.setLostFeatureCov(true)) { std::fprintf(stderr, "larvio_euroc: %s\n", ctx.error()); return 1; }
+    }
+    if (pipelined) return run_pipelined(argv[3], allImuData, allImgInfo, max_frames, ImgProcesser, Estimator, tum, map_out);
 
     typedef std::chrono::steady_clock Clock;
     double t_fe = 0, t_be = 0, t_io = 0; long n_fe = 0, n_be = 0, n_odo = 0;
@@ -148,6 +175,7 @@ int main(int argc, char** argv)
         }
     }
     if (tum) std::fclose(tum);
+    map_out.drain(Estimator); map_out.close();
     std::printf("frames %ld  feature messages %ld  odometry updates %ld  state dim %d\n", n_fe, n_be, n_odo, lvk_ekf_dim(Estimator.handle()));
     std::printf("front-end %.3f ms/frame   back-end %.3f ms/message   image read+decode %.3f ms/frame\n", n_fe ? 1e3 * t_fe / n_fe : 0.0,
                 n_be ? 1e3 * t_be / n_be : 0.0, n_fe ? 1e3 * t_io / n_fe : 0.0);

@@ -303,6 +303,29 @@ lvk_status lvk_ekf_cov_reanchor(lvk_context* ctx, double* d_P, int ld, int n, co
 lvk_status lvk_ekf_cov_append_features(lvk_context* ctx, double* d_P, int ld, int n, int nn, const double* d_H1, int ldh, const double* h_H2,
                                        const double* d_r1, const double* d_dx, double sigma2, double* d_dx_new);
 
+/* Position covariance of anchored inverse-depth landmarks, one 3 x 3 matrix per job, read off a device-resident covariance (n x n,
+ * row-major, leading dimension ldp) without moving it.  Sigma is the first-order covariance of the landmark's world position
+ *   p_w = R_c2w [u/rho, v/rho, 1/rho] + p_cam,   R_c2w = R(q_anchor) R_b2c^T,   p_cam = p_anchor + R(q_anchor) t_c_b
+ * (R_c2w goes through Eigen's matrix -> quaternion -> matrix conversions, as the filter keeps a clone's camera attitude: with an
+ * R_b2c that is orthonormal to the digits of a configuration file only, that is the matrix Feature::position was formed with)
+ * under an error state delta ~ N(0, P) applied exactly as the filter's state injection applies a correction (larvio.cpp:1476-1575):
+ *   anchor clone attitude   q <- small_angle_quat(d_theta) * q          (Hamilton, [x y z w]; R(q) maps body to world)
+ *   anchor clone position   p <- p + d_p
+ *   extrinsic rotation      R_b2c <- R_b2c R(small_angle_quat(d_theta_e))^T
+ *   extrinsic translation   t_c_b <- t_c_b + d_t
+ *   inverse depth           rho <- rho + d_rho
+ * Thirteen columns of P matter: the extrinsics' 15..20 (d_theta_e, d_t), the anchor clone's six from anchor_col (d_theta, d_p) and the
+ * feature's feat_col; Sigma = J P[those, those] J^T with, for R = R(q_anchor), r_c = p_w - p_cam and r = p_w - p_anchor,
+ *   J = [ -[r_c]x R | R | -[r]x | I | -r_c / rho ].
+ * Nothing outside those 13 rows and columns of P is read; every sum runs in a fixed order (the same input gives the same bits) and
+ * the lower triangle is a copy of the upper one.  h_cov9: 9 doubles per job, row-major.  The call waits for its launch.
+ * LVK_ERR_ARG, with nothing launched and the context still usable, when a pointer is null, n_jobs < 0, ldp < n, a job's column range
+ * (15..20, anchor_col..anchor_col+5, feat_col) leaves [0, n), or its inv_depth is 0.  n_jobs == 0 is LVK_OK. */
+typedef struct { int anchor_col, feat_col, pad0, pad1;      /* first of the anchor clone's 6 columns; the feature's column */
+                 double q_anchor[4], R_b2c[9], t_c_b[3];    /* the anchor clone's IMU attitude as lvk_clone.q; extrinsics as lvk_ekf_get_state */
+                 double obs_anchor[2], inv_depth; } lvk_landmark_job;
+lvk_status lvk_ekf_landmark_cov(lvk_context* ctx, const double* d_P, int ldp, int n, const lvk_landmark_job* h_jobs, int n_jobs, double* h_cov9);
+
 typedef struct {
     /* names and meaning as LarVio::loadParameters reads them (larvio.cpp:58-311, config/euroc.yaml) */
     int if_fej, estimate_extrin, estimate_td, if_zupt_valid;
@@ -405,6 +428,26 @@ int        lvk_ekf_get_features(const lvk_ekf* e, int64_t* h_ids, double* h_inv_
 /* getStableMapPointPositions (larvio.cpp:2717-2722): in-state features that were lost since the last call, with their last world
  * position; the entries handed out are removed, as the reference clears lost_slam_features on read.  Returns the count (<= cap). */
 int        lvk_ekf_take_lost_features(lvk_ekf* e, int64_t* h_ids, double* h_pos_w, int cap);
+/* How well each map point is known: the 3 x 3 position covariance of lvk_ekf_landmark_cov (the conventions are stated there), read
+ * off the filter's device-resident covariance by one kernel launch - the matrix itself is not transferred.
+ * lvk_ekf_get_feature_cov: the in-state features in the order of lvk_ekf_get_features - id, anchor clone id, world position and Sigma
+ *   (9 doubles each, row-major, exactly symmetric) - up to cap of them; *n_out = how many.  The jobs are built from the host state
+ *   (anchor clone attitude, current extrinsics, anchor observation, inverse depth), the kernel runs on the context's stream behind
+ *   whatever the last update left queued, and the call waits for it.  Any output pointer except n_out may be null.  A feature whose
+ *   anchor clone is not in the window gets nine NaNs (the state injection skips the same case).  A failed handle answers as
+ *   lvk_ekf_get_cov does.
+ * lvk_ekf_set_lost_feature_cov: off by default.  While on, an update that drops lost in-state features from the covariance first runs
+ *   the same kernel for them, on the covariance as it is BEFORE their columns go (after this message's propagation and clone
+ *   augmentation, which leave the 13 rows and columns involved untouched); the results land in the filter's pinned download
+ *   buffer and are attached to the queued points once the update has waited for its stream.  An update that drops features and
+ *   would otherwise return without any wait behind that launch makes one more stream wait - only while the switch is on.  With it
+ *   off the filter launches exactly the kernels it launched before this entry point existed.  Under the sharded update
+ *   (lvk_ekf_set_shard) every rank runs the kernel for all lost points on its own replica of the covariance: identical bits everywhere.
+ * lvk_ekf_take_lost_features_cov: drains the same list as lvk_ekf_take_lost_features, with each point's Sigma (9 doubles; nine NaNs
+ *   for a point queued while the switch was off, or whose anchor had left the window).  h_ids, h_pos_w, h_cov9 may each be null. */
+lvk_status lvk_ekf_get_feature_cov(lvk_ekf* e, int64_t* h_ids, int64_t* h_anchor_ids, double* h_pos_w, double* h_cov9, int cap, int* n_out);
+lvk_status lvk_ekf_set_lost_feature_cov(lvk_ekf* e, int on);
+int        lvk_ekf_take_lost_features_cov(lvk_ekf* e, int64_t* h_ids, double* h_pos_w, double* h_cov9, int cap);
 /* What the moving-start initialiser (FlexibleInitializer.cpp:11-25 -> DynamicInitializer.cpp) handed to the filter, with the intermediate
  * results of the successful attempt - for parity tests against an independent restatement fed the same messages:
  *   valid        1 once the dynamic initialiser has succeeded on this handle (0: never ran, or the static one fired)

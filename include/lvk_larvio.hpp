@@ -171,6 +171,25 @@ public:
         const int n = lvk_ekf_take_lost_features(ekf_, ids.data(), xyz.data(), 4096);
         ids.resize((size_t)n); xyz.resize((size_t)3 * n);
     }
+    // Position covariances of the map points (lvk_ekf_get_feature_cov / lvk_ekf_take_lost_features_cov; conventions in lvk_c.h):
+    // cov holds 9 doubles per point, row-major, NaN where the filter has none.  setLostFeatureCov(true), after initialize(), makes
+    // the filter compute a lost point's covariance before its column leaves the state.
+    bool getFeatureCov(std::vector<int64_t>& ids, std::vector<int64_t>& anchor_ids, std::vector<double>& xyz, std::vector<double>& cov) const
+    {
+        ids.resize(1024); anchor_ids.resize(1024); xyz.resize(3 * 1024); cov.resize(9 * 1024);
+        int n = 0;
+        const bool ok = ekf_ && lvk_ekf_get_feature_cov(ekf_, ids.data(), anchor_ids.data(), xyz.data(), cov.data(), 1024, &n) == LVK_OK;
+        if (!ok) n = 0;
+        ids.resize((size_t)n); anchor_ids.resize((size_t)n); xyz.resize((size_t)3 * n); cov.resize((size_t)9 * n);
+        return ok;
+    }
+    bool setLostFeatureCov(bool on) { return ekf_ && lvk_ekf_set_lost_feature_cov(ekf_, on ? 1 : 0) == LVK_OK; }
+    void takeLostFeaturesCov(std::vector<int64_t>& ids, std::vector<double>& xyz, std::vector<double>& cov)
+    {
+        ids.resize(4096); xyz.resize(3 * 4096); cov.resize(9 * 4096);
+        const int n = lvk_ekf_take_lost_features_cov(ekf_, ids.data(), xyz.data(), cov.data(), 4096);
+        ids.resize((size_t)n); xyz.resize((size_t)3 * n); cov.resize((size_t)9 * n);
+    }
     lvk_ekf* handle() const { return ekf_; }
 private:
     friend class VioPipeline;

@@ -190,8 +190,13 @@ struct lvk_ekf {
     bool is_gravity_set = false, b_first_features = false, if_fej = false, if_zupt = false;
     double m_gyro_old[3], m_acc_old[3];
     double take_off_stamp = 0, last_update_time = 0, last_zupt_time = 0, tracking_rate = 0;
-    struct LostPoint { long long id; double p[3]; };
+    struct LostPoint { long long id; double p[3]; double cov[9]; };
     std::vector<LostPoint> lost_slam;                   // in-state features that were lost, with their last world position (drained on read)
+    // lvk_ekf_set_lost_feature_cov: the position covariance of every lost point, computed (k_landmark_cov) before its column leaves P.
+    // lost_cov_slot: for the last lost_cov_slot.size() entries of lost_slam, where in the download buffer (down_lm) the kernel puts
+    // their Sigma (-1: no job, the anchor is outside the window); attached at the end of the call, behind a stream sync
+    // (lost_cov_mark = n_sync when the launch was queued: one more sync only if none has followed)
+    bool lost_cov_on = false; std::vector<int> lost_cov_slot; int lost_cov_mark = 0; size_t down_lm = 0; int lm_cap = 0;
     double sigma2, zupt_v2, zupt_p2, zupt_q2, imu_img_time_th, Qc[12];
     double x_min, y_min, grid_w, grid_h;
     std::vector<int> grid_count;
@@ -454,6 +459,43 @@ static lvk_status cov_gather(lvk_ekf* e, const std::vector<int>& idx)
     lvk_status st = run_or_defer(e, [=]() { return lvk_cov_gather(e->ctx, src, e->ld, dst, e->ld, d_idx, n); });
     if (st != LVK_OK) return st;
     e->cur ^= 1; e->N = n;
+    return LVK_OK;
+}
+// the landmark-covariance job of in-state feature f (state column LEG + 6 clones + fs_index) from the host state, as inject() reads it;
+// false when the injection would skip the feature (anchor not in the window) or the depth is degenerate
+static bool landmark_job(const lvk_ekf* e, const Feature& f, int fs_index, lvk_landmark_job* j)
+{
+    const int ar = clone_rank(e, f.id_anchor);
+    if (ar < 0) return false;
+    memset(j, 0, sizeof *j);
+    j->anchor_col = LEG + 6 * ar; j->feat_col = LEG + 6 * (int)e->clones.size() + fs_index;
+    memcpy(j->q_anchor, e->clones[(size_t)ar].q, 32); memcpy(j->R_b2c, e->R_b2c, 72); memcpy(j->t_c_b, e->t_c_b, 24);
+    j->obs_anchor[0] = f.obs_anchor[0]; j->obs_anchor[1] = f.obs_anchor[1]; j->inv_depth = f.inv_depth;
+    return lvk_landmark_job_ok(j, e->N);
+}
+// lvk_ekf_set_lost_feature_cov: queue k_landmark_cov for the lost in-state features on the covariance as it is now (their columns
+// still in place); the results go to the pinned download buffer and are attached by lost_cov_attach()
+static lvk_status lost_cov_queue(lvk_ekf* e, const std::vector<long long>& ekf_lost)
+{
+    e->lost_cov_slot.assign(ekf_lost.size(), -1);
+    lvk_landmark_job* hj = up_alloc<lvk_landmark_job>(e, ekf_lost.size());
+    if (!hj) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "upload arena exhausted");
+    int n = 0;
+    for (size_t k = 0; k < ekf_lost.size(); ++k)
+        if (n < e->lm_cap && landmark_job(e, e->map.at(ekf_lost[k]), fs_rank(e, ekf_lost[k]), hj + n)) e->lost_cov_slot[k] = n++;
+    e->lost_cov_mark = e->n_sync;
+    if (n == 0) return LVK_OK;
+    const double* P = e->dP[e->cur]; const lvk_landmark_job* d_jobs = dev(e, hj); double* out = (double*)(e->dh_down + e->down_lm);
+    return run_or_defer(e, [=]() { return lvk_launch_landmark_cov(e->ctx, P, e->ld, d_jobs, n, out); });
+}
+static lvk_status lost_cov_attach(lvk_ekf* e)
+{
+    if (e->lost_cov_slot.empty()) return LVK_OK;
+    if (e->n_sync == e->lost_cov_mark) { EKF_HIP(hipStreamSynchronize(e->ctx->stream)); e->n_sync++; }
+    const size_t k = e->lost_cov_slot.size(), base = e->lost_slam.size() - k;
+    const double* src = (const double*)(e->h_down + e->down_lm);
+    for (size_t i = 0; i < k; ++i) if (e->lost_cov_slot[i] >= 0) memcpy(e->lost_slam[base + i].cov, src + 9 * (size_t)e->lost_cov_slot[i], 72);
+    e->lost_cov_slot.clear();
     return LVK_OK;
 }
 // P loses the rows / columns marked in drop (N flags)
@@ -1572,12 +1614,15 @@ static lvk_status remove_lost_features(lvk_ekf* e)
     if (!ekf_lost.empty()) {                                     // rmLostFeaturesCov (:3296-3348): all lost columns in one gather
         std::vector<char> drop(e->N, 0);
         for (long long id : ekf_lost) drop[LEG + 6 * (int)e->clones.size() + fs_rank(e, id)] = 1;
+        if (e->lost_cov_on) { st = lost_cov_queue(e, ekf_lost); if (st != LVK_OK) return st; }
         st = cov_drop(e, drop);
         if (st != LVK_OK) return st;
         for (long long id : ekf_lost) {
             const Feature& f = e->map.at(id);                    // lost_slam_features (:3342): kept for getStableMapPointPositions
             if (e->lost_slam.size() >= (size_t)1 << 16) e->lost_slam.erase(e->lost_slam.begin(), e->lost_slam.begin() + (1 << 15));
-            e->lost_slam.push_back({id, {f.position[0], f.position[1], f.position[2]}});
+            lvk_ekf::LostPoint lp = {id, {f.position[0], f.position[1], f.position[2]}, {}};
+            for (double& v : lp.cov) v = NAN;
+            e->lost_slam.push_back(lp);
             e->feature_states.erase(e->feature_states.begin() + fs_rank(e, id)); e->map.erase(id);
         }
     }
@@ -2278,7 +2323,9 @@ lvk_status lvk_ekf_create(lvk_context* ctx, const lvk_ekf_config* cfg, lvk_ekf**
     e->down_flag = (e->down_dx + sizeof(double) * (size_t)(e->ld + 64) + 255) & ~(size_t)255;
     e->down_info = e->down_flag + 256;                  // [0] first non-positive Cholesky pivot (+1), [1] a solver workgroup gave up waiting: written by k_chol_fused
     e->down_p00 = e->down_info + 256;                   // 16 x 16 doubles
-    e->down_cap = e->down_p00 + 2048;
+    e->down_lm = e->down_p00 + 2048;                    // lvk_ekf_set_lost_feature_cov: 9 doubles per lost in-state feature of one update
+    e->lm_cap = max_feat_state + 8;
+    e->down_cap = e->down_lm + ((sizeof(double) * 9 * (size_t)e->lm_cap + 255) & ~(size_t)255);
     ok = ok && hipHostMalloc((void**)&e->h_up, e->up_cap) == hipSuccess && hipHostMalloc((void**)&e->h_down, e->down_cap) == hipSuccess;
     if (ok) {
         // No copy commands on the filter's chain (each ~8 us of API + copy + barrier; ten of them were 385 -> 336 us per update):
@@ -2446,6 +2493,7 @@ static lvk_status ekf_process_impl(lvk_ekf* e, double ts, const lvk_feature_obs*
     e->up_half ^= 1; e->n_sync = 0;
     e->up_off = e->up_flushed = e->up_half ? e->up_cap / 2 : 0; e->up_lim = e->up_off + e->up_cap / 2;
     e->colcache.cols.reset();                           // column lists depend on the clones' ranks, which this call changes
+    e->lost_cov_slot.clear();
     if (!e->b_first_features) {
         if (n_imu > 0 && imu[0].t - ts - e->td <= 0.0) e->b_first_features = true;
         else return LVK_OK;
@@ -2492,6 +2540,8 @@ static lvk_status ekf_process_impl(lvk_ekf* e, double ts, const lvk_feature_obs*
     // it reads the half of the upload arena the NEXT call leaves alone: the call returns without waiting for it.  The call after
     // that reuses this half - behind at least one stream sync of the call in between, which is why a call that had none ends with one.
     if (e->n_sync == 0) { EKF_HIP(hipStreamSynchronize(e->ctx->stream)); e->n_sync++; }
+    st = lost_cov_attach(e);
+    if (st != LVK_OK) return st;
     prof_harvest(e, false);
 #ifdef LVK_MSG_HASH_LOG   // debugging aid, compiled out of the product (make CXXFLAGS+=-DLVK_MSG_HASH_LOG); bounded: the first 65536 messages
     {   // LVK_MSG_HASH=<file>: one line per processed message (time stamp, size, FNV-1a of its bytes, IMU samples used + their hash, td
@@ -2689,6 +2739,53 @@ int lvk_ekf_take_lost_features(lvk_ekf* e, int64_t* ids, double* pos_w, int cap)
     for (int i = 0; i < n; ++i) { ids[i] = e->lost_slam[i].id; memcpy(pos_w + 3 * i, e->lost_slam[i].p, 24); }
     e->lost_slam.erase(e->lost_slam.begin(), e->lost_slam.begin() + n);
     return n;
+}
+int lvk_ekf_take_lost_features_cov(lvk_ekf* e, int64_t* ids, double* pos_w, double* cov9, int cap)
+{
+    if (!e || cap <= 0) return 0;
+    ekf_quiesce(e);
+    const int n = std::min((int)e->lost_slam.size(), cap);
+    for (int i = 0; i < n; ++i) {
+        const lvk_ekf::LostPoint& lp = e->lost_slam[i];
+        if (ids) ids[i] = lp.id;
+        if (pos_w) memcpy(pos_w + 3 * i, lp.p, 24);
+        if (cov9) memcpy(cov9 + 9 * i, lp.cov, 72);
+    }
+    e->lost_slam.erase(e->lost_slam.begin(), e->lost_slam.begin() + n);
+    return n;
+}
+lvk_status lvk_ekf_set_lost_feature_cov(lvk_ekf* e, int on)
+{
+    if (!e) return LVK_ERR_ARG;
+    ekf_quiesce(e);
+    e->lost_cov_on = on != 0;
+    return LVK_OK;
+}
+lvk_status lvk_ekf_get_feature_cov(lvk_ekf* e, int64_t* ids, int64_t* anchor_ids, double* pos_w, double* cov9, int cap, int* n_out)
+{
+    if (!e || !n_out || cap < 0) return lvk_set_error(e ? e->ctx : nullptr, LVK_ERR_ARG, "lvk_ekf_get_feature_cov: bad argument");
+    ekf_quiesce(e);
+    if (e->failed != LVK_OK) return e->failed;
+    const int n = std::min((int)e->feature_states.size(), cap);
+    std::vector<lvk_landmark_job> jobs; std::vector<int> slot((size_t)n, -1);
+    jobs.reserve((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const Feature& f = e->map.at(e->feature_states[i]);
+        if (ids) ids[i] = f.id;
+        if (anchor_ids) anchor_ids[i] = f.id_anchor;
+        if (pos_w) memcpy(pos_w + 3 * i, f.position, 24);
+        lvk_landmark_job j;
+        if (cov9 && landmark_job(e, f, i, &j)) { slot[(size_t)i] = (int)jobs.size(); jobs.push_back(j); }
+    }
+    *n_out = n;
+    if (!cov9) return LVK_OK;
+    for (int i = 0; i < 9 * n; ++i) cov9[i] = NAN;
+    if (jobs.empty()) return LVK_OK;
+    std::vector<double> out(9 * jobs.size());
+    lvk_status st = lvk_ekf_landmark_cov(e->ctx, e->dP[e->cur], e->ld, e->N, jobs.data(), (int)jobs.size(), out.data());
+    if (st != LVK_OK) return st;
+    for (int i = 0; i < n; ++i) if (slot[(size_t)i] >= 0) memcpy(cov9 + 9 * i, &out[9 * (size_t)slot[(size_t)i]], 72);
+    return LVK_OK;
 }
 void lvk_ekf_counters(const lvk_ekf* e, long* out8) { if (e && out8) { ekf_quiesce(e); memcpy(out8, e->counters, sizeof e->counters); } }
 

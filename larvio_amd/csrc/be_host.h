@@ -28,6 +28,9 @@ lvk_status lvk_cov_append_features(lvk_context* ctx, double* P, int ld, int n, i
 size_t lvk_ldlt_lds_bytes(int m);
 lvk_status lvk_ldlt_factor_solve(lvk_context* ctx, double* S, int ld, int m, const double* B, int ldb, int nbcols, double* Bp, double* X, double* Dg, int* perm, int* cnt);
 void lvk_cov_symmetrize(lvk_context* ctx, double* P, int ld, int n);
+// be_landmark.hip
+bool lvk_landmark_job_ok(const lvk_landmark_job* j, int n);
+lvk_status lvk_launch_landmark_cov(lvk_context* ctx, const double* d_P, int ldp, const lvk_landmark_job* d_jobs, int n_jobs, double* d_cov9);
 // be_feature.hip
 int lvk_feature_rows_route(int max_rows, int gate_rows_max);
 lvk_status lvk_launch_triangulate(lvk_context* ctx, const TriJob* d_jobs, int n_jobs, const CamPose* d_cams, const int* d_rank, const double* d_z, TriResult* d_out, TriResult* d_out_dev);

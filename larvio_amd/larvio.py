@@ -65,6 +65,9 @@ def _L():
         L.lvk_ekf_is_initialized.argtypes = [vp]; L.lvk_ekf_is_initialized.restype = i
         L.lvk_ekf_take_off_stamp.argtypes = [vp]; L.lvk_ekf_take_off_stamp.restype = C.c_double
         L.lvk_ekf_take_lost_features.argtypes = [vp, vp, vp, i]; L.lvk_ekf_take_lost_features.restype = i
+        L.lvk_ekf_get_feature_cov.argtypes = [vp, vp, vp, vp, vp, i, pi]; L.lvk_ekf_get_feature_cov.restype = i
+        L.lvk_ekf_set_lost_feature_cov.argtypes = [vp, i]; L.lvk_ekf_set_lost_feature_cov.restype = i
+        L.lvk_ekf_take_lost_features_cov.argtypes = [vp, vp, vp, vp, i]; L.lvk_ekf_take_lost_features_cov.restype = i
         L.lvk_ekf_get_state.argtypes = [vp, vp]; L.lvk_ekf_get_state.restype = i
         L.lvk_ekf_get_cov.argtypes = [vp, vp]; L.lvk_ekf_get_cov.restype = i
         L.lvk_ekf_get_cov_imu.argtypes = [vp, i, vp]; L.lvk_ekf_get_cov_imu.restype = i
@@ -437,6 +440,27 @@ class LarVio:
         ids = np.zeros(4096, np.int64); pos = np.zeros((4096, 3))
         n = _L().lvk_ekf_take_lost_features(self._h, _p(ids), _p(pos), 4096)
         return ids[:n].copy(), pos[:n].copy()
+
+    def get_feature_cov(self):
+        """lvk_ekf_get_feature_cov: (ids, anchor clone ids, world positions, Sigma (n, 3, 3)) of the in-state features, in the order of
+        features(); Sigma is all NaN for a feature whose anchor clone has left the window"""
+        cap = 4096
+        ids = np.zeros(cap, np.int64); anc = np.zeros(cap, np.int64); pos = np.zeros((cap, 3)); cov = np.zeros((cap, 3, 3)); n = C.c_int(0)
+        self.ctx.check(_L().lvk_ekf_get_feature_cov(self._h, _p(ids), _p(anc), _p(pos), _p(cov), cap, C.byref(n)))
+        n = n.value
+        return ids[:n].copy(), anc[:n].copy(), pos[:n].copy(), cov[:n].copy()
+
+    def set_lost_feature_cov(self, on=True):
+        """lvk_ekf_set_lost_feature_cov: while on, every in-state feature that is lost gets its position covariance computed before its
+        column leaves the covariance (take_lost_features_cov hands it out)"""
+        self.ctx.check(_L().lvk_ekf_set_lost_feature_cov(self._h, int(bool(on))))
+
+    def take_lost_features_cov(self):
+        """lvk_ekf_take_lost_features_cov: stable_map_points() with each point's Sigma: (ids, positions, Sigma (n, 3, 3)); NaN
+        matrices for points queued while the switch was off"""
+        ids = np.zeros(4096, np.int64); pos = np.zeros((4096, 3)); cov = np.zeros((4096, 3, 3))
+        n = _L().lvk_ekf_take_lost_features_cov(self._h, _p(ids), _p(pos), _p(cov), 4096)
+        return ids[:n].copy(), pos[:n].copy(), cov[:n].copy()
 
     def set_shard(self, rank, world, fn, user, keepalive=None):
         """lvk_ekf_set_shard: this filter does the per-feature device work of rank `rank` of `world`; fn/user = the all-gather

@@ -167,3 +167,21 @@ def predict_homography(imu, t_prev, t_curr, R_cam_imu, intr):
     if st != 0:
         raise LvkError("lvk_predict_homography")
     return H.reshape(3, 3)
+
+
+LANDMARK_JOB = np.dtype([("anchor_col", np.int32), ("feat_col", np.int32), ("pad0", np.int32), ("pad1", np.int32), ("q_anchor", np.float64, 4),
+                         ("R_b2c", np.float64, 9), ("t_c_b", np.float64, 3), ("obs_anchor", np.float64, 2), ("inv_depth", np.float64)])
+
+
+def landmark_cov(ctx, P, jobs, n=None):
+    """lvk_ekf_landmark_cov: the 3 x 3 position covariance of every LANDMARK_JOB record, read off the covariance P.  P: a whole
+    row-major buffer (its row length is the leading dimension, contents go to the device as they are) whose leading n x n block
+    (default: all rows) is the covariance.  -> (n_jobs, 3, 3)"""
+    P = np.ascontiguousarray(P, np.float64); jobs = np.ascontiguousarray(jobs, LANDMARK_JOB)
+    n = P.shape[0] if n is None else int(n)
+    out = np.full((len(jobs), 3, 3), np.nan)
+    L = lib()
+    L.lvk_ekf_landmark_cov.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]; L.lvk_ekf_landmark_cov.restype = C.c_int
+    dP = ctx.to_device(P)
+    ctx.check(L.lvk_ekf_landmark_cov(ctx.h, _p(dP), P.shape[1], n, _p(jobs), len(jobs), _p(out)))
+    return out
