@@ -555,6 +555,40 @@ lvk_status lvk_ekf_feature_rows(lvk_context* ctx, const lvk_clone* h_clones, int
                                 lvk_feature_result* h_res, double* h_blocks, int* h_ccols, double* h_H, int ldh, int h_rows, double* h_r,
                                 int* rows_out);
 
+/* ---- the two kernels around the exchange of the sharded update (lvk_ekf_set_shard), one call each (parity tests).  Host
+ * buffers; each call launches the production kernel through the launcher the filter uses, waits, and copies back.
+ * Wire layout of one rank's block (bytes_per_rank bytes, the same on every rank of an update; d_recv holds `world` of them in rank
+ * order):
+ *   [0, LVK_SHARD_HDR)        header; only its first 16 bytes are defined: unsigned magic (LVK_SHARD_MAGIC), int rank, int k, int n_res
+ *   [.., + res_bytes)         n_res lvk_feature_result records, the gate results of the rank's jobs (res_bytes: a multiple of 256,
+ *                             >= 32 * the largest job count of any rank)
+ *   [.., + k (ncols + 1) 8)   the rank's k compressed rows, ncols + 1 doubles each: the row of H, then its residual
+ * Whatever follows (rows k.. of a rank with fewer rows than the largest block, padding) is undefined and never read.
+ * The receiver accepts a block iff magic, rank, k and n_res are what ITS plan says about that rank (every rank plans every rank's
+ * share).  A block that fails the test - a rank that failed locally posts 0xFF over its header - contributes k zero rows with zero
+ * residuals, its results are not copied, and bit min(rank, 31) is raised in the peer-failure word.
+ *
+ * lvk_shard_pack_stage: k rows of h_X (row-major, ld >= ncols) and h_rX, n_res results -> the block of `rank`, in h_send.  The
+ *   device send buffer holds `fill` in every byte before the launch: bytes the kernel does not write come back as fill.
+ * lvk_shard_unpack_stage: h_recv (world * bytes_per_rank bytes) and the plan h_meta[world] -> rank g's rows to rows row_off.. of
+ *   H (rows x ld, columns [0, ncols)) and r, its results to [job_lo, job_lo + job_n) of both result arrays (n_fout entries each).
+ *   h_H, h_r, h_fout, h_fout_host are uploaded as given and read back after the kernel: what it does not write is unchanged.
+ *   h_fout_host may be NULL (the kernel then gets no mirror array), h_peer_fail may be NULL (the kernel then gets no word to raise);
+ *   otherwise *h_peer_fail is uploaded, OR-ed into by the kernel and read back.
+ * LVK_ERR_ARG, nothing launched: a negative size, ld < ncols, res_bytes no multiple of 256 or < 32 n_res (32 job_n of any meta),
+ * bytes_per_rank no multiple of 8 or < LVK_SHARD_HDR + res_bytes + 8 k (ncols + 1) (k_max for the unpack), a meta with k outside
+ * [0, k_max], with rows outside [0, rows) or jobs outside [0, n_fout). */
+#define LVK_SHARD_HDR   256
+#define LVK_SHARD_MAGIC 0x4c564b58u      /* "LVKX" */
+typedef struct { int job_lo, job_n, k, row_off; } lvk_shard_meta;
+lvk_status lvk_shard_pack_stage(lvk_context* ctx, int rank, const double* h_X, int ld, const double* h_rX, int k, int ncols,
+                                const lvk_feature_result* h_res, int n_res, size_t res_bytes, int fill,
+                                void* h_send, size_t bytes_per_rank);
+lvk_status lvk_shard_unpack_stage(lvk_context* ctx, const void* h_recv, size_t bytes_per_rank, const lvk_shard_meta* h_meta, int world,
+                                  int ncols, int k_max, size_t res_bytes, double* h_H, int ld, int rows, double* h_r,
+                                  lvk_feature_result* h_fout, lvk_feature_result* h_fout_host /* or NULL */, int n_fout,
+                                  int* h_peer_fail /* or NULL */);
+
 /* ==================================================================== the driver step
  * One camera frame through both halves, exactly the two calls the reference's drivers make per image
  * (app/larvioMain.cpp:104-116: processImage, then processFeatures when it returned true), with the driver's IMU buffer

@@ -11,8 +11,8 @@
 // 16 x 16 block
 struct UpdateWs { double* B; int ldb; double* S; int lds; int* info; hipEvent_t ev_a = nullptr, ev_b = nullptr; double* dx_host = nullptr; double* p00_host = nullptr; int* info_host = nullptr; };
 // sharded update: rank g's jobs [job_lo, job_lo + job_n) and its k compressed rows, stacked from row_off (host writes, k_shard_unpack reads)
+// LVK_SHARD_HDR, the bytes of the header every rank's block starts with, is part of the wire layout: include/lvk_c.h
 struct ShardMeta { int job_lo, job_n, k, row_off; };
-#define LVK_SHARD_HDR 256                // bytes of the header every rank's block starts with (be_shard.hip)
 
 // be_linalg.hip
 lvk_status lvk_stage_copy2(lvk_context* ctx, void* d_dst0, const void* d_src0, size_t bytes0, void* d_dst1, const void* d_src1, size_t bytes1);

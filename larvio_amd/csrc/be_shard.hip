@@ -12,10 +12,11 @@
 #include <limits.h>
 #include <stdlib.h>
 #include <string>
+#include <algorithm>
 
 // Every rank's block starts with a header the receivers check: a rank that failed locally after the (symmetric) capacity checks
 // still enters the collective - with a poisoned header - so that its peers return an error instead of waiting for it forever.
-#define LVK_SHARD_MAGIC 0x4c564b58u      // "LVKX"
+// (LVK_SHARD_MAGIC and the wire layout: include/lvk_c.h)
 struct ShardHeader { unsigned magic; int rank; int k; int n_res; };
 
 // send layout: [ header (256 B) | FeatResult x res_cap | k rows of (ncols + 1) doubles: H row, then the residual ]
@@ -163,6 +164,86 @@ void lvk_shard_comm_destroy(lvk_shard_comm* c)
     if (!c) return;
     if (c->comm) rccl_api()->comm_destroy(c->comm);
     delete c;
+}
+
+// ------------------------------------------------------------------------- stage entries (parity tests): host buffers in, the
+// launchers above on scratch slots 9 (inputs) and 10 (outputs), one wait, host buffers out
+lvk_status lvk_shard_pack_stage(lvk_context* ctx, int rank, const double* h_X, int ld, const double* h_rX, int k, int ncols,
+                                const lvk_feature_result* h_res, int n_res, size_t res_bytes, int fill, void* h_send, size_t bytes_per_rank)
+{
+    static_assert(sizeof(lvk_feature_result) == sizeof(FeatResult) && sizeof(FeatResult) == 32, "lvk_feature_result is FeatResult");
+    static_assert(sizeof(ShardHeader) == 16 && sizeof(ShardHeader) <= LVK_SHARD_HDR, "the defined part of the header");
+    if (!ctx) return LVK_ERR_ARG;
+    if (rank < 0 || k < 0 || ncols < 0 || n_res < 0 || n_res > INT_MAX / 4 || ld < ncols || !h_send || (k > 0 && (!h_X || !h_rX)) || (n_res > 0 && !h_res))
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_shard_pack_stage: bad argument");
+    if (res_bytes % 256 || res_bytes < sizeof(FeatResult) * (size_t)n_res)
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_shard_pack_stage: res_bytes %zu (a multiple of 256, >= 32 n_res)", res_bytes);
+    if (bytes_per_rank % 8 || bytes_per_rank < LVK_SHARD_HDR + res_bytes + sizeof(double) * (size_t)k * ((size_t)ncols + 1))
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_shard_pack_stage: bytes_per_rank %zu (a multiple of 8, >= header + res_bytes + 8 k (ncols + 1))", bytes_per_rank);
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
+    const size_t nX = sizeof(double) * (size_t)k * ld, nr = sizeof(double) * (size_t)k, nres = sizeof(FeatResult) * (size_t)n_res;
+    const size_t o_X = take(nX), o_r = take(nr), o_res = take(nres), in_bytes = std::max(o, (size_t)256);
+    char* d_in = (char*)lvk_ctx_scratch(ctx, 9, in_bytes);
+    char* d_send = (char*)lvk_ctx_scratch(ctx, 10, bytes_per_rank);
+    if (!d_in || !d_send) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
+    if (nX) LVK_HIP(ctx, hipMemcpyAsync(d_in + o_X, h_X, nX, hipMemcpyHostToDevice, ctx->stream));
+    if (nr) LVK_HIP(ctx, hipMemcpyAsync(d_in + o_r, h_rX, nr, hipMemcpyHostToDevice, ctx->stream));
+    if (nres) LVK_HIP(ctx, hipMemcpyAsync(d_in + o_res, h_res, nres, hipMemcpyHostToDevice, ctx->stream));
+    LVK_HIP(ctx, hipMemsetAsync(d_send, fill & 0xFF, bytes_per_rank, ctx->stream));
+    lvk_status st = lvk_shard_pack(ctx, (const FeatResult*)(d_in + o_res), n_res, (const double*)(d_in + o_X), ld, (const double*)(d_in + o_r), k, ncols, d_send, res_bytes, rank);
+    if (st != LVK_OK) return st;
+    LVK_HIP(ctx, hipMemcpyAsync(h_send, d_send, bytes_per_rank, hipMemcpyDeviceToHost, ctx->stream));
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LVK_OK;
+}
+
+lvk_status lvk_shard_unpack_stage(lvk_context* ctx, const void* h_recv, size_t bytes_per_rank, const lvk_shard_meta* h_meta, int world, int ncols, int k_max,
+                                  size_t res_bytes, double* h_H, int ld, int rows, double* h_r, lvk_feature_result* h_fout, lvk_feature_result* h_fout_host,
+                                  int n_fout, int* h_peer_fail)
+{
+    static_assert(sizeof(lvk_shard_meta) == sizeof(ShardMeta), "lvk_shard_meta is ShardMeta");
+    if (!ctx) return LVK_ERR_ARG;
+    if (!h_recv || !h_meta || world < 1 || world > 65535 || ncols < 0 || k_max < 0 || ld < ncols || rows < 0 || n_fout < 0 || (rows > 0 && (!h_H || !h_r)) || (n_fout > 0 && !h_fout))
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_shard_unpack_stage: bad argument");
+    if (res_bytes % 256) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_shard_unpack_stage: res_bytes %zu is no multiple of 256", res_bytes);
+    if (bytes_per_rank % 8 || bytes_per_rank < LVK_SHARD_HDR + res_bytes + sizeof(double) * (size_t)k_max * ((size_t)ncols + 1))
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_shard_unpack_stage: bytes_per_rank %zu (a multiple of 8, >= header + res_bytes + 8 k_max (ncols + 1))", bytes_per_rank);
+    for (int g = 0; g < world; ++g) {
+        const lvk_shard_meta& m = h_meta[g];
+        if (m.k < 0 || m.k > k_max || m.row_off < 0 || (long long)m.row_off + m.k > rows)
+            return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_shard_unpack_stage: rank %d's rows [%d, %d + %d) leave k_max %d or the %d rows of H", g, m.row_off, m.row_off, m.k, k_max, rows);
+        if (m.job_lo < 0 || m.job_n < 0 || (long long)m.job_lo + m.job_n > n_fout || sizeof(FeatResult) * (size_t)m.job_n > res_bytes)
+            return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_shard_unpack_stage: rank %d's jobs [%d, %d + %d) leave the %d results or res_bytes", g, m.job_lo, m.job_lo, m.job_n, n_fout);
+    }
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
+    const size_t n_recv = bytes_per_rank * (size_t)world, n_meta = sizeof(ShardMeta) * (size_t)world;
+    const size_t o_recv = take(n_recv), o_meta = take(n_meta), in_bytes = o;
+    o = 0;
+    const size_t nH = sizeof(double) * (size_t)rows * ld, nr = sizeof(double) * (size_t)rows, nf = sizeof(FeatResult) * (size_t)n_fout;
+    const size_t o_H = take(nH), o_r = take(nr), o_f = take(nf), o_fh = take(nf), o_flag = take(sizeof(int)), out_bytes = o;
+    char* d_in = (char*)lvk_ctx_scratch(ctx, 9, in_bytes);
+    char* d_out = (char*)lvk_ctx_scratch(ctx, 10, out_bytes);
+    if (!d_in || !d_out) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
+    LVK_HIP(ctx, hipMemcpyAsync(d_in + o_recv, h_recv, n_recv, hipMemcpyHostToDevice, ctx->stream));
+    LVK_HIP(ctx, hipMemcpyAsync(d_in + o_meta, h_meta, n_meta, hipMemcpyHostToDevice, ctx->stream));
+    if (nH) LVK_HIP(ctx, hipMemcpyAsync(d_out + o_H, h_H, nH, hipMemcpyHostToDevice, ctx->stream));
+    if (nr) LVK_HIP(ctx, hipMemcpyAsync(d_out + o_r, h_r, nr, hipMemcpyHostToDevice, ctx->stream));
+    if (nf) LVK_HIP(ctx, hipMemcpyAsync(d_out + o_f, h_fout, nf, hipMemcpyHostToDevice, ctx->stream));
+    if (nf && h_fout_host) LVK_HIP(ctx, hipMemcpyAsync(d_out + o_fh, h_fout_host, nf, hipMemcpyHostToDevice, ctx->stream));
+    if (h_peer_fail) LVK_HIP(ctx, hipMemcpyAsync(d_out + o_flag, h_peer_fail, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    lvk_status st = lvk_shard_unpack(ctx, d_in + o_recv, bytes_per_rank, res_bytes, (const ShardMeta*)(d_in + o_meta), world, ncols, k_max, (FeatResult*)(d_out + o_f),
+                                     h_fout_host ? (FeatResult*)(d_out + o_fh) : nullptr, (double*)(d_out + o_H), ld, (double*)(d_out + o_r),
+                                     h_peer_fail ? (int*)(d_out + o_flag) : nullptr);
+    if (st != LVK_OK) return st;
+    if (nH) LVK_HIP(ctx, hipMemcpyAsync(h_H, d_out + o_H, nH, hipMemcpyDeviceToHost, ctx->stream));
+    if (nr) LVK_HIP(ctx, hipMemcpyAsync(h_r, d_out + o_r, nr, hipMemcpyDeviceToHost, ctx->stream));
+    if (nf) LVK_HIP(ctx, hipMemcpyAsync(h_fout, d_out + o_f, nf, hipMemcpyDeviceToHost, ctx->stream));
+    if (nf && h_fout_host) LVK_HIP(ctx, hipMemcpyAsync(h_fout_host, d_out + o_fh, nf, hipMemcpyDeviceToHost, ctx->stream));
+    if (h_peer_fail) LVK_HIP(ctx, hipMemcpyAsync(h_peer_fail, d_out + o_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LVK_OK;
 }
 
 const char* lvk_shard_comm_error(const lvk_shard_comm* c) { return c ? c->err : "null communicator"; }

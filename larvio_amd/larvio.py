@@ -89,6 +89,8 @@ def _L():
         L.lvk_triangulate.argtypes = [vp, vp, vp, i, i, vp, pi, vp, vp, vp, vp]; L.lvk_triangulate.restype = i
         L.lvk_ekf_gate_and_stack.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp, i, i, i, d, vp, vp, i, pi, vp, vp]; L.lvk_ekf_gate_and_stack.restype = i
         L.lvk_ekf_feature_rows.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp, i, vp, i, i, i, i, i, d, i, vp, vp, vp, vp, i, i, vp, pi]; L.lvk_ekf_feature_rows.restype = i
+        L.lvk_shard_pack_stage.argtypes = [vp, i, vp, i, vp, i, i, vp, i, C.c_size_t, i, vp, C.c_size_t]; L.lvk_shard_pack_stage.restype = i
+        L.lvk_shard_unpack_stage.argtypes = [vp, vp, C.c_size_t, vp, i, i, i, C.c_size_t, vp, i, i, vp, vp, vp, i, vp]; L.lvk_shard_unpack_stage.restype = i
         _sig_done = True
     return L
 
@@ -167,6 +169,46 @@ def feature_rows(ctx, clones, jobs, clone_rank, obs, obs_vel, P, ldp=None, leg_d
         n = 2 * int(j["n_obs"]) * (c + 1)
         bl.append(blocks[bo:bo + n].reshape(2 * int(j["n_obs"]), c + 1)); cl.append(cc[co:co + c]); bo += n; co += c
     return res, bl, cl, H, r, rows.value
+
+
+# The exchange step of the sharded update (wire layout: include/lvk_c.h, next to lvk_shard_pack_stage).
+SHARD_HDR, SHARD_MAGIC = 256, 0x4c564b58
+SHARD_META = np.dtype([("job_lo", np.int32), ("job_n", np.int32), ("k", np.int32), ("row_off", np.int32)])
+
+
+def shard_pack(ctx, rank, X, rX, res, res_bytes, bytes_per_rank, fill=0, k=None, ncols=None):
+    """lvk_shard_pack_stage: k_shard_pack on k rows of the row-major buffer X (its row length is ld; k defaults to its rows, ncols to
+    ld), their residuals rX and the FEATURE_RESULT records res -> the rank's block (uint8, bytes_per_rank); bytes the kernel did not
+    write hold `fill`."""
+    X = np.ascontiguousarray(X, np.float64); rX = np.ascontiguousarray(rX, np.float64); res = np.ascontiguousarray(res, FEATURE_RESULT)
+    if X.ndim != 2:
+        raise ValueError("X must be a 2-D buffer (rows x ld)")
+    k = X.shape[0] if k is None else int(k); ncols = X.shape[1] if ncols is None else int(ncols)
+    if k > X.shape[0] or k > len(rX):
+        raise ValueError("k exceeds the rows given")
+    out = np.empty(max(int(bytes_per_rank), 0), np.uint8)
+    ctx.check(_L().lvk_shard_pack_stage(ctx.h, int(rank), _p(X), X.shape[1], _p(rX), k, ncols, _p(res), len(res), int(res_bytes), int(fill), _p(out), int(bytes_per_rank)))
+    return out
+
+
+def shard_unpack(ctx, recv, metas, ncols, k_max, res_bytes, H, r, fout, fout_host=None, peer_fail=0, bytes_per_rank=None):
+    """lvk_shard_unpack_stage: k_shard_unpack on the received image recv (world blocks) and the plan metas (SHARD_META).  H (rows x
+    ld), r, fout and fout_host (FEATURE_RESULT arrays of one length; fout_host None = the kernel gets no mirror array) go to the device
+    as given; peer_fail: the word's value before the launch, None = the kernel gets no word.
+    -> (H, r, fout, fout_host or None, peer_fail or None) after the kernel."""
+    recv = np.ascontiguousarray(recv, np.uint8); metas = np.ascontiguousarray(metas, SHARD_META)
+    H = np.array(H, np.float64, order="C"); r = np.array(r, np.float64); fout = np.array(fout, FEATURE_RESULT)
+    fh = None if fout_host is None else np.array(fout_host, FEATURE_RESULT)
+    if H.ndim != 2 or len(r) != H.shape[0] or (fh is not None and len(fh) != len(fout)):
+        raise ValueError("H must be rows x ld, r one entry per row, fout_host as long as fout")
+    world = len(metas)
+    bpr = recv.size // max(world, 1) if bytes_per_rank is None else int(bytes_per_rank)
+    if bpr < 0 or recv.size < world * bpr:
+        raise ValueError("recv is shorter than world * bytes_per_rank")
+    word = None if peer_fail is None else np.array([peer_fail], np.int32)
+    ctx.check(_L().lvk_shard_unpack_stage(ctx.h, _p(recv), bpr, _p(metas), world, int(ncols), int(k_max), int(res_bytes), _p(H), H.shape[1], H.shape[0], _p(r),
+                                          _p(fout), _p(fh), len(fout), _p(word)))
+    return H, r, fout, fh, (None if word is None else int(word[0]))
 
 
 def _padded(X, ld, rows=None):
