@@ -111,6 +111,17 @@ lvk_status lvk_min_eigen_map(lvk_context* ctx, const lvk_pyramid* p, float* d_ei
 lvk_status lvk_good_features(lvk_context* ctx, const lvk_pyramid* p, const uint8_t* d_mask,
                              int max_corners, double quality, double min_distance,
                              lvk_pt2f* d_out, int cap, int* d_n_out);
+/* Stage entry: the selection half of lvk_good_features (masked maximum, threshold at quality * max, 3x3 non-maximum suppression,
+ * greedy minDistance pass) on a caller's response map; lvk_good_features is lvk_min_eigen_map followed by this call.
+ * Reads d_eig: w * h packed floats (row stride w), and d_mask (may be NULL): w * h packed bytes, any non-zero byte = allowed; neither
+ * needs more than its type's alignment.  Writes min(found, cap) corners to d_out, strongest first, and that count to d_n_out.
+ * Refusals (the context stays usable): LVK_ERR_ARG for a null ctx / d_eig / d_out / d_n_out, w < 3 or h < 3 (no interior pixel), w * h
+ * beyond 2^31 - 1 or cap < 0; LVK_ERR_UNSUPPORTED for a min_distance that is not in 1 .. 32767 (a NaN included) or max_corners outside 1..4096; LVK_ERR_CAPACITY, with nothing
+ * launched, when the grid of rint(min_distance)-sized cells does not fit the selection kernel's LDS next to its survivor buffer
+ * (8 bytes per cell: about 11,000 cells, e.g. 1000 x 1000 at min_distance 2). */
+lvk_status lvk_good_features_from_map(lvk_context* ctx, const float* d_eig, const uint8_t* d_mask, int w, int h,
+                                      int max_corners, double quality, double min_distance,
+                                      lvk_pt2f* d_out, int cap, int* d_n_out);
 
 /* ------------------------------------------------------------------ per-point stages
  * replaces cv::calcOpticalFlowPyrLK(..., OPTFLOW_USE_INITIAL_FLOW) at

@@ -19,7 +19,7 @@ ABI_SYMBOLS = [
     "lvk_runtime_env", "lvk_context_create", "lvk_context_destroy", "lvk_context_set_stream", "lvk_context_get_stream", "lvk_sync", "lvk_last_error", "lvk_version",
     "lvk_malloc", "lvk_free", "lvk_memcpy_h2d", "lvk_memcpy_d2h", "lvk_memset",
     "lvk_clahe_u8", "lvk_pyramid_create", "lvk_pyramid_destroy", "lvk_pyramid_build", "lvk_pyramid_build_clahe",
-    "lvk_pyramid_levels", "lvk_pyramid_level", "lvk_orb_prepare", "lvk_min_eigen_map", "lvk_good_features",
+    "lvk_pyramid_levels", "lvk_pyramid_level", "lvk_orb_prepare", "lvk_min_eigen_map", "lvk_good_features", "lvk_good_features_from_map",
     "lvk_lk_track", "lvk_orb_describe", "lvk_hamming256_rows", "lvk_undistort_points", "lvk_find_fundamental_mask", "lvk_find_fundamental",
     "lvk_ransac_fundamental", "lvk_predict_homography",
     "lvk_frontend_create", "lvk_frontend_destroy", "lvk_frontend_process", "lvk_frontend_tracks", "lvk_frontend_new_pts",
@@ -88,6 +88,7 @@ def lib():
             "lvk_pyramid_level": ([vp, i, pi, pi, pi, pi, pi, C.POINTER(vp), C.POINTER(vp)], i),
             "lvk_orb_prepare": ([vp, vp, vp, vp], i), "lvk_min_eigen_map": ([vp, vp, vp], i),
             "lvk_good_features": ([vp, vp, vp, i, d, d, vp, i, vp], i),
+            "lvk_good_features_from_map": ([vp, vp, vp, i, i, i, d, d, vp, i, vp], i),
             "lvk_lk_track": ([vp, vp, vp, vp, vp, vp, i, i, d, vp], i),
             "lvk_orb_describe": ([vp, vp, vp, i, i, vp, i, vp, vp], i),
             "lvk_hamming256_rows": ([vp, vp, vp, i, vp], i),

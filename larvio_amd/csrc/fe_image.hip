@@ -425,7 +425,7 @@ __global__ void __launch_bounds__(256) k_min_eigen(const uint8_t* __restrict__ s
 __device__ __forceinline__ unsigned f2ord(float f) { unsigned b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 __device__ __forceinline__ float ord2f(unsigned k) { return k == 0 ? 0.f : __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
-// gftt scratch layout (uints): [0] max key, [1] n candidates, [2] overflow flag, [3] spare, [GF_HIST_OFF ...) strength histogram
+// gftt scratch layout (uints): [0] max key, [1] n candidates, [2] [3] spare, [GF_HIST_OFF ...) strength histogram
 #define GF_HIST_BITS 13
 #define GF_HIST_OFF 4
 #define GF_SCRATCH_UINTS 4
@@ -552,19 +552,21 @@ __global__ void __launch_bounds__(256) k_mask_normalise(const uint8_t* __restric
     if (x < w && y < h) dst[(size_t)y * w + x] = src[(size_t)y * stride + x] ? 255 : 0;
 }
 
-// 3x3 non-maximum suppression above quality*max, inside the mask.  One workgroup scans 256 columns x GC_ROWS rows, collects its
+// 3x3 non-maximum suppression above quality*max, inside the mask.  One workgroup (GC_COLS threads) scans GC_COLS columns x GC_ROWS rows, collects its
 // candidates in LDS and reserves space in the global list with ONE atomic (a per-wavefront atomic on a single counter serialises
-// ~2,000 L2 atomics per frame: 35 us).
+// ~2,000 L2 atomics per frame: 35 us).  The local list holds the whole tile (16 KB): on a plateau of equal response every pixel is
+// its own 3x3 maximum, and a list of half the tile silently dropped the rest.  Resident workgroups per CU stay at 8 (32 wavefronts).
+#define GC_COLS 256
 #define GC_ROWS 8
-__global__ void __launch_bounds__(256) k_gftt_candidates(const float* __restrict__ eig, const uint8_t* __restrict__ mask, int w, int h,
-                                                        float quality, unsigned* __restrict__ scratch,
+__global__ void __launch_bounds__(GC_COLS) k_gftt_candidates(const float* __restrict__ eig, const uint8_t* __restrict__ mask, int w, int h,
+                                                        double quality, unsigned* __restrict__ scratch,
                                                         unsigned long long* __restrict__ cands, int cap)
 {
-    __shared__ unsigned long long loc[256 * GC_ROWS / 2];
+    __shared__ unsigned long long loc[GC_COLS * GC_ROWS];
     __shared__ unsigned cnt, base;
     if (threadIdx.x == 0) cnt = 0;
     __syncthreads();
-    const int x = blockIdx.x * 256 + threadIdx.x + 1;
+    const int x = blockIdx.x * GC_COLS + threadIdx.x + 1;
     const int y0 = blockIdx.y * GC_ROWS + 1;
     // every value a thread will look at - its column and the two next to it over GC_ROWS + 2 rows, its mask bytes - is asked for
     // before the first one is used: the map was written by the previous kernel on other XCDs, and a row loop that loads, tests and
@@ -581,7 +583,7 @@ __global__ void __launch_bounds__(256) k_gftt_candidates(const float* __restrict
 #pragma unroll
     for (int r = 0; r < GC_ROWS; ++r) { const int y = y0 + r; mk[r] = (mask && xin && y < h - 1) ? mask[(size_t)y * w + x] : (uint8_t)1; }
     const float max_val = ord2f(scratch[0]);
-    const float thresh = (float)((double)max_val * (double)quality);
+    const float thresh = (float)((double)max_val * quality);   // quality stays a double: through a float, 0.01 moves the threshold by an ulp for some maxima
 #pragma unroll
     for (int ry = 0; ry < GC_ROWS; ++ry) {
         const int y = y0 + ry;
@@ -600,14 +602,15 @@ __global__ void __launch_bounds__(256) k_gftt_candidates(const float* __restrict
                 m = fmaxf(m, u);
             }
         if (v != m) continue;
-        const unsigned slot = atomicAdd(&cnt, 1u);
-        if (slot < 256 * GC_ROWS / 2) loc[slot] = ((unsigned long long)f2ord(v) << 32) | (unsigned)(y * w + x);
+        const unsigned slot = atomicAdd(&cnt, 1u);               // < GC_COLS * GC_ROWS: one per pixel of the tile at most
+        loc[slot] = ((unsigned long long)f2ord(v) << 32) | (unsigned)(y * w + x);
     }
     __syncthreads();
-    const unsigned n_loc = min(cnt, (unsigned)(256 * GC_ROWS / 2));
-    if (threadIdx.x == 0) { base = n_loc ? atomicAdd(&scratch[1], n_loc) : 0u; if (cnt > n_loc) scratch[2] = 1u; }
+    const unsigned n_loc = cnt;
+    if (threadIdx.x == 0) base = n_loc ? atomicAdd(&scratch[1], n_loc) : 0u;
     __syncthreads();
-    for (unsigned i = threadIdx.x; i < n_loc; i += 256) { const unsigned slot = base + i; if (slot < (unsigned)cap) cands[slot] = loc[i]; else scratch[2] = 1u; }
+    // cap = w * h at every call site, the tiles hold (w - 2) * (h - 2) pixels: the test never fails, it keeps the store inside the list
+    for (unsigned i = threadIdx.x; i < n_loc; i += GC_COLS) { const unsigned slot = base + i; if (slot < (unsigned)cap) cands[slot] = loc[i]; }
 }
 
 // single workgroup: the greedy min-distance pass of goodFeaturesToTrack ("visit candidates by descending strength, accept
@@ -618,7 +621,12 @@ __global__ void __launch_bounds__(256) k_gftt_candidates(const float* __restrict
 // conflicts live in the 3x3 cells around a candidate, <= 4 corners per cell), only the SURVIVORS are sorted (bitonic, LDS)
 // and wave 0 resolves them in order exactly like the sequential rule.  Rejections by the grid are final because the grid
 // only grows; buckets are visited in descending strength, survivors in descending (strength, index): identical result.
+// A bucket is a contiguous range of the 64-bit keys (strength order key | pixel index), [klo, sh_top]: whole histogram bins as a rule;
+// a bin that alone holds more than the survivor buffer (a plateau, a regular target: thousands of equal or nearly equal strengths)
+// is cut further by the key bits below the histogram's, ten at a time - the keys are unique, so some cut always fits - and the
+// histogram then counts what is left of that bin.  (Such a bin used to end the selection, silently, with the corners found so far.)
 #define GF_MAX_OUT 4096
+#define GF_MAX_MIN_DISTANCE 32767                            // accepted corners are kept as short2; beyond any image's diagonal anyway
 #define GF_SURV 8192
 __device__ __forceinline__ bool gf_grid_conflict(const unsigned short (*cells)[4], const short2* acc, int gw, int gh, int cell, float md2, int x, int y)
 {
@@ -633,6 +641,17 @@ __device__ __forceinline__ bool gf_grid_conflict(const unsigned short (*cells)[4
                 if (dx * dx + dy * dy < md2) return true;
             }
     return false;
+}
+
+// in-place suffix sums of 1024 counts, one per thread of the 1024-thread workgroup: v[i] = v[i] + v[i + 1] + ... + v[1023]
+__device__ __forceinline__ void gf_suffix_sum(unsigned* v, int t)
+{
+    for (int o = 1; o < 1024; o <<= 1) {
+        const unsigned add = t + o < 1024 ? v[t + o] : 0u;
+        __syncthreads();
+        v[t] += add;
+        __syncthreads();
+    }
 }
 
 #ifdef LVK_GF_TIMING
@@ -654,7 +673,8 @@ __global__ void __launch_bounds__(1024) k_gftt_select(const unsigned long long* 
     short2* acc = reinterpret_cast<short2*>(gf_sh + surv_cap + gw * gh);
     __shared__ unsigned coarse[1024];                        // histogram folded to 1024 groups (8 bins each at 13 bits)
     __shared__ unsigned hist[1 << GF_HIST_BITS];
-    __shared__ int sh_ns, sh_na, sh_done, sh_lo, sh_hi;
+    __shared__ int sh_ns, sh_na, sh_done, sh_lo, sh_hi, sh_cut, sh_part, sh_sub;
+    __shared__ unsigned long long sh_top;                    // while sh_part: the largest key not yet visited (bins >= sh_hi are done, bin sh_hi - 1 in part)
     unsigned* scan = reinterpret_cast<unsigned*>(surv);      // the survivor buffer is idle while the next bucket is being chosen
     const int t = threadIdx.x, lane = t & 63;
     if (d_sub) {   // image_processor.cpp:1034-1036: maxCorners = max_features_num - curr_pts_.size(), skipped when 0
@@ -667,7 +687,7 @@ __global__ void __launch_bounds__(1024) k_gftt_select(const unsigned long long* 
     // strength histogram of the candidates (LDS atomics; one pass over the candidate keys)
     for (int q = 0; q < GROUP; ++q) hist[t * GROUP + q] = 0u;
     for (int i = t; i < gw * gh; i += 1024) { cells[i][0] = cells[i][1] = cells[i][2] = cells[i][3] = 0xFFFF; }
-    if (t == 0) { sh_na = 0; sh_done = 0; sh_hi = 1 << GF_HIST_BITS; }
+    if (t == 0) { sh_na = 0; sh_done = 0; sh_hi = 1 << GF_HIST_BITS; sh_top = ~0ull; sh_cut = 0; sh_part = 0; }
     __syncthreads();
     // the candidate keys were written by the previous kernel on other XCDs: 8 loads in flight per thread, not one trip per key
     for (int i0 = t; i0 < n; i0 += 1024 * 8) {
@@ -689,7 +709,7 @@ __global__ void __launch_bounds__(1024) k_gftt_select(const unsigned long long* 
     // first bucket: a few times the corners still wanted (the publish-frame case asks for 10-50), later buckets double
     int target = 1024;
     if (max_corners > 0) { target = 64; while (target < 4 * max_corners && target < 1024) target <<= 1; }   // (any bucket boundaries give the same corners)
-    for (int bucket = 0; bucket < 4096; ++bucket) {
+    for (int bucket = 0; bucket < n + 2; ++bucket) {        // every bucket but the last holds a key: the bound only keeps the loop finite
         // next bucket = whole histogram groups [lo, hi) below the current top holding >= target candidates (or all that is left):
         // suffix sums of the 1024 group counts by a block scan, then ONE thread-parallel boundary test - a serial walk over
         // thousands of mostly empty bins by one thread was 26 us.  (Any bucket boundaries give the same corners.)
@@ -698,12 +718,7 @@ __global__ void __launch_bounds__(1024) k_gftt_select(const unsigned long long* 
             const int hg = sh_hi / GROUP;                   // groups >= hg are done
             scan[t] = t < hg ? coarse[t] : 0u;
             __syncthreads();
-            for (int o = 1; o < 1024; o <<= 1) {            // suffix sum: scan[g] = candidates in groups [g, hg)
-                const unsigned add = t + o < 1024 ? scan[t + o] : 0u;
-                __syncthreads();
-                scan[t] += add;
-                __syncthreads();
-            }
+            gf_suffix_sum(scan, t);                         // scan[g] = candidates in groups [g, hg)
             if (t == 0) { sh_lo = -1; sh_ns = 0; }
             __syncthreads();
             const unsigned mine = scan[t], above = t + 1 < 1024 ? scan[t + 1] : 0u;
@@ -726,14 +741,50 @@ __global__ void __launch_bounds__(1024) k_gftt_select(const unsigned long long* 
                 if (cnt >= (unsigned)target) break;
             }
             sh_lo = lo;
-            if (cnt > (unsigned)surv_cap) sh_done = 2;                 // one histogram bin alone exceeds the survivor buffer
+            sh_cut = cnt > (unsigned)surv_cap;                         // one histogram bin alone exceeds the survivor buffer (then lo is that bin)
         }
         __syncthreads();
         if (bucket == 0) GF_TICK(3);
         const int lo = sh_lo, hi = sh_hi;
-        if (sh_done == 2) break;
         if (hi == 0 || lo == hi) break;
-        const unsigned klo = (unsigned)lo << (32 - GF_HIST_BITS), khi_excl = hi >= (1 << GF_HIST_BITS) ? 0xFFFFFFFFu : ((unsigned)hi << (32 - GF_HIST_BITS));
+        const bool cut = sh_cut != 0, in_part = sh_part != 0;
+        const unsigned klo32 = (unsigned)lo << (32 - GF_HIST_BITS), khi_excl = hi >= (1 << GF_HIST_BITS) ? 0xFFFFFFFFu : ((unsigned)hi << (32 - GF_HIST_BITS));
+        unsigned long long klo = (unsigned long long)lo << (64 - GF_HIST_BITS);
+        const unsigned long long ktop = in_part ? sh_top : ((unsigned long long)hi << (64 - GF_HIST_BITS)) - 1ull;    // (hi = 8192 wraps to all ones)
+        if (cut) {
+            // the bucket becomes the top of bin lo: a histogram of the next ten key bits of what is left of the range [klo, klo + 2^s), its
+            // suffix sums, and the longest run of sub-ranges from the top that holds at most target keys; when the first sub-range that
+            // holds any is alone too many for the survivor buffer, the same again inside it (s = 51, 41, ... 1, 0: a range of one key fits)
+            for (int s = 64 - GF_HIST_BITS; ; ) {
+                const int s2 = s > 10 ? s - 10 : 0;
+                const unsigned long long kend = klo + ((1ull << s) - 1ull);
+                __syncthreads();
+                scan[t] = 0u;
+                __syncthreads();
+                for (int i0 = t; i0 < n; i0 += 1024 * 8) {
+                    unsigned long long kv[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) { const int i = i0 + 1024 * u; kv[u] = i < n ? cands[i] : 0ull; }
+#pragma unroll
+                    for (int u = 0; u < 8; ++u)
+                        if (i0 + 1024 * u < n && kv[u] >= klo && kv[u] <= kend && kv[u] <= ktop) atomicAdd(&scan[(unsigned)((kv[u] - klo) >> s2)], 1u);
+                }
+                __syncthreads();
+                gf_suffix_sum(scan, t);                     // scan[j] = keys left in sub-ranges [j, 2^(s - s2))
+                if (t == 0) {
+                    const int nb = 1 << (s - s2);
+                    int a = 0, z = nb;                      // smallest j with scan[j] <= target (scan is non-increasing; "scan[nb]" = 0)
+                    while (a < z) { const int m = (a + z) >> 1; if (scan[m] <= (unsigned)target) z = m; else a = m + 1; }
+                    int again = 0;
+                    if (a > 0 && (a == nb || scan[a] == 0u)) { --a; again = scan[a] > (unsigned)surv_cap; }   // nothing above fits: the first sub-range that holds any
+                    sh_sub = a; sh_cut = again ? 2 : 1;
+                }
+                __syncthreads();
+                klo += (unsigned long long)sh_sub << s2;
+                if (sh_cut != 2 || s == 0) break;           // (s == 0: one key value; only keeps the loop finite)
+                s = s2;
+            }
+        }
         for (int i0 = t; i0 < n; i0 += 1024 * 8) {
             unsigned long long kv[8];
 #pragma unroll
@@ -742,7 +793,8 @@ __global__ void __launch_bounds__(1024) k_gftt_select(const unsigned long long* 
             for (int u = 0; u < 8; ++u) {
                 const unsigned long long k = kv[u];
                 const unsigned sv = (unsigned)(k >> 32);
-                const bool keep = i0 + 1024 * u < n && !(sv < klo || (hi < (1 << GF_HIST_BITS) && sv >= khi_excl));
+                const bool keep = i0 + 1024 * u < n && ((cut || in_part) ? (k >= klo && k <= ktop)        // a bucket that ends inside a bin: whole keys
+                                                                      : !(sv < klo32 || (hi < (1 << GF_HIST_BITS) && sv >= khi_excl)));
                 // one LDS atomic per wavefront (a single-address atomic per survivor serialised: ~1000 x 16 ns)
                 const unsigned long long mk = __ballot(keep);
                 if (mk) {
@@ -864,7 +916,11 @@ __global__ void __launch_bounds__(1024) k_gftt_select(const unsigned long long* 
                 }
                 __threadfence_block();                      // the next batch's grid test reads what this one inserted
             }
-            if (lane == 0) { sh_na = na; if (done) sh_done = 1; sh_hi = lo; }
+            if (lane == 0) {
+                sh_na = na; if (done) sh_done = 1;
+                if (cut) { hist[lo] -= (unsigned)ns; coarse[lo / GROUP] -= (unsigned)ns; sh_hi = lo + 1; sh_cut = 0; sh_part = 1; sh_top = klo - 1ull; }   // the histogram counts what is left of bin lo
+                else { sh_hi = lo; if (in_part) sh_part = 0; }
+            }
         }
         __syncthreads();
         if (bucket == 0) GF_TICK(6);
@@ -1077,15 +1133,11 @@ lvk_status lvk_gftt_run(lvk_context* ctx, const float* d_eig, const uint8_t* d_m
                         lvk_pt2f* d_out, int cap, int* d_n_out, const int* d_sub, bool prepared, bool max_done)
 {   // max_done: scratch[0] already holds the masked maximum (lvk_mask_and_max)
    // prepared: the scratch words are zero (k_gftt_select leaves them so; a scratch of unknown content is cleared here) and the mask is final
-    if (min_distance < 1.0) return lvk_set_error(ctx, LVK_ERR_UNSUPPORTED, "goodFeaturesToTrack with minDistance < 1 is not supported");
+    if (!(min_distance >= 1.0 && min_distance <= GF_MAX_MIN_DISTANCE))      // written so that a NaN is refused too: rint() of it has no defined int
+        return lvk_set_error(ctx, LVK_ERR_UNSUPPORTED, "goodFeaturesToTrack with minDistance outside 1 .. %d is not supported", GF_MAX_MIN_DISTANCE);
     const int cell = (int)rint(min_distance);
     const int gw = (w + cell - 1) / cell, gh = (h + cell - 1) / cell;
     if (max_corners > GF_MAX_OUT || max_corners <= 0) return lvk_set_error(ctx, LVK_ERR_UNSUPPORTED, "maxCorners must be in 1..%d", GF_MAX_OUT);
-    if (!prepared) LVK_HIP(ctx, hipMemsetAsync(d_scratch, 0, GF_SCRATCH_UINTS * sizeof(unsigned), ctx->stream));
-    if (!max_done)
-    { int mb = (w * h / 4 + 2047) / 2048; mb = mb < 128 ? 128 : mb > 1024 ? 1024 : mb;      // ~8 four-pixel loads per lane
-      hipLaunchKernelGGL(k_masked_max, dim3(mb), dim3(256), 0, ctx->stream, d_eig, d_mask, w * h, d_scratch); }
-    hipLaunchKernelGGL(k_gftt_candidates, dim3((w - 2 + 255) / 256, (h - 2 + GC_ROWS - 1) / GC_ROWS), dim3(256), 0, ctx->stream, d_eig, d_mask, w, h, (float)quality, d_scratch, d_cands, cand_cap);
     // LDS of the selection kernel: survivors | one 8-byte cell per minDistance x minDistance square | the accepted corners (as many as can be
     // asked for), next to its static 36 KB (histogram).  A fine grid (minDistance 6 on 752 x 480: 10,080 cells; found by the whole-program fuzz
     // at 512 x 512 / 6, which asked for 177 KB and left the front-end in a failed state) takes the survivor buffer at half size - any
@@ -1097,6 +1149,11 @@ lvk_status lvk_gftt_run(lvk_context* ctx, const float* d_eig, const uint8_t* d_m
     size_t shm = (size_t)surv_cap * 8 + (size_t)gw * gh * 8 + (size_t)acc_cap * 4;
     if (shm > lds_avail) { surv_cap = GF_SURV / 2; shm = (size_t)surv_cap * 8 + (size_t)gw * gh * 8 + (size_t)acc_cap * 4; }
     if (shm > lds_avail) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "GFTT: a %dx%d grid of minDistance cells and %d corners need %zu bytes of LDS (%zu available)", gw, gh, max_corners, shm, lds_avail);
+    if (!prepared) LVK_HIP(ctx, hipMemsetAsync(d_scratch, 0, GF_SCRATCH_UINTS * sizeof(unsigned), ctx->stream));
+    if (!max_done)
+    { int mb = (w * h / 4 + 2047) / 2048; mb = mb < 128 ? 128 : mb > 1024 ? 1024 : mb;      // ~8 four-pixel loads per lane
+      hipLaunchKernelGGL(k_masked_max, dim3(mb), dim3(256), 0, ctx->stream, d_eig, d_mask, w * h, d_scratch); }
+    hipLaunchKernelGGL(k_gftt_candidates, dim3((w - 2 + GC_COLS - 1) / GC_COLS, (h - 2 + GC_ROWS - 1) / GC_ROWS), dim3(GC_COLS), 0, ctx->stream, d_eig, d_mask, w, h, quality, d_scratch, d_cands, cand_cap);
     LVK_LDS_OPTIN(ctx, 2, k_gftt_select, shm);   // the opt-in must leave room for the kernel's static LDS: ask for what is launched
     hipLaunchKernelGGL(k_gftt_select, dim3(1), dim3(1024), shm, ctx->stream, (const unsigned long long*)d_cands, cand_cap, w, h, max_corners, cell,
                        (float)(min_distance * min_distance), surv_cap, acc_cap, d_scratch, d_out, cap, d_n_out, d_sub);
@@ -1130,18 +1187,28 @@ lvk_status lvk_mask_normalise(lvk_context* ctx, const uint8_t* d_src, int stride
     return LVK_OK;
 }
 
+// stage entry: the selection half of goodFeaturesToTrack on a caller's response map (what lvk_good_features runs behind lvk_min_eigen_map)
+extern "C" lvk_status lvk_good_features_from_map(lvk_context* ctx, const float* d_eig, const uint8_t* d_mask, int w, int h, int max_corners,
+                                                 double quality, double min_distance, lvk_pt2f* d_out, int cap, int* d_n_out)
+{
+    if (!ctx || !d_eig || !d_out || !d_n_out || w < 3 || h < 3 || (long long)w * h > 0x7fffffffLL || cap < 0)
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_good_features_from_map: bad argument");
+    const int cand_cap = w * h;
+    size_t cand_alloc = 1; while (cand_alloc < (size_t)cand_cap) cand_alloc <<= 1;     // bitonic sort pads to a power of two in place
+    unsigned* scratch = (unsigned*)lvk_ctx_scratch(ctx, 2, GF_SCRATCH_UINTS * sizeof(unsigned));
+    unsigned long long* cands = (unsigned long long*)lvk_ctx_scratch(ctx, 3, sizeof(unsigned long long) * cand_alloc);
+    if (!scratch || !cands) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
+    return lvk_gftt_run(ctx, d_eig, d_mask, w, h, max_corners, quality, min_distance, scratch, cands, cand_cap, d_out, cap, d_n_out, nullptr, false, false);
+}
+
 extern "C" lvk_status lvk_good_features(lvk_context* ctx, const lvk_pyramid* p, const uint8_t* d_mask, int max_corners,
                                         double quality, double min_distance, lvk_pt2f* d_out, int cap, int* d_n_out)
 {
     if (!ctx || !p || !d_out || !d_n_out) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_good_features: bad argument");
     const int w = p->w[0], h = p->h[0];
-    const int cand_cap = w * h;
-    size_t cand_alloc = 1; while (cand_alloc < (size_t)cand_cap) cand_alloc <<= 1;     // bitonic sort pads to a power of two in place
     float* eig = (float*)lvk_ctx_scratch(ctx, 1, sizeof(float) * (size_t)w * h);
-    unsigned* scratch = (unsigned*)lvk_ctx_scratch(ctx, 2, GF_SCRATCH_UINTS * sizeof(unsigned));
-    unsigned long long* cands = (unsigned long long*)lvk_ctx_scratch(ctx, 3, sizeof(unsigned long long) * cand_alloc);
-    if (!eig || !scratch || !cands) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
+    if (!eig) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
     lvk_status st = lvk_min_eigen_map(ctx, p, eig);
-    if (st == LVK_OK) st = lvk_gftt_run(ctx, eig, d_mask, w, h, max_corners, quality, min_distance, scratch, cands, cand_cap, d_out, cap, d_n_out, nullptr, false, false);
+    if (st == LVK_OK) st = lvk_good_features_from_map(ctx, eig, d_mask, w, h, max_corners, quality, min_distance, d_out, cap, d_n_out);
     return st;
 }

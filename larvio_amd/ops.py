@@ -103,6 +103,23 @@ class Pyramid:
             pass
 
 
+def good_features_from_map(ctx, eig, max_corners, quality=0.01, min_distance=20.0, mask=None, cap=None):
+    """lvk_good_features_from_map: corner selection on a float32 response map (H, W); cap (default max_corners) = room in the output list"""
+    eig = np.ascontiguousarray(eig, np.float32)
+    assert eig.ndim == 2
+    h, w = eig.shape
+    cap = max_corners if cap is None else cap
+    d_eig = ctx.to_device(eig); d_out = ctx.alloc(8 * max(cap, 1)); d_n = ctx.alloc(4)
+    d_mask = None
+    if mask is not None:
+        mask = _u8(mask)
+        assert mask.shape == eig.shape
+        d_mask = ctx.to_device(mask)
+    ctx.check(lib().lvk_good_features_from_map(ctx.h, _p(d_eig), _p(d_mask), w, h, max_corners, quality, min_distance, _p(d_out), cap, _p(d_n)))
+    n = int(ctx.to_host(d_n, np.int32, (1,))[0])
+    return ctx.to_host(d_out, np.float32, (max(cap, 1), 2))[:n].copy()
+
+
 def lk_track(ctx, prev, nxt, prev_pts, init_pts, max_iter=30, eps=0.01):
     p0 = _pts(prev_pts); p1 = _pts(init_pts); n = len(p0)
     nl = min(prev.n_levels, nxt.n_levels)
