@@ -42,6 +42,11 @@ class LarVio {
     void getStableMapPointPositions(std::map<larvio::FeatureIDType, Eigen::Vector3d>& mMapPoints);       // :2719-2723 (clears on read)
     void getActiveeMapPointPositions(std::map<larvio::FeatureIDType, Eigen::Vector3d>& mMapPoints);      // :2726-2730 (clears on read)
 
+    // not in the reference: the MSCKF points the lost-feature updates triangulate, accept and erase, each with its 3 x 3 position
+    // covariance (lvk_ekf_set_msckf_points / lvk_ekf_take_msckf_points, lvk_c.h); cov9: 9 doubles per point, row-major (drained on read)
+    bool setMsckfPoints(bool on);
+    void takeMsckfPoints(std::vector<FeatureIDType>& ids, std::vector<Eigen::Vector3d>& positions, std::vector<double>& cov9, std::vector<int>& n_obs);
+
     typedef boost::shared_ptr<LarVio> Ptr;
     typedef boost::shared_ptr<const LarVio> ConstPtr;
 

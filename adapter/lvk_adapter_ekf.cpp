@@ -185,6 +185,28 @@ void LarVio::getStableMapPointPositions(std::map<larvio::FeatureIDType, Eigen::V
     }
 }
 
+bool LarVio::setMsckfPoints(bool on)
+{
+    finish();
+    return ekf && lvk_ekf_set_msckf_points(ekf, on ? 1 : 0) == LVK_OK;
+}
+
+void LarVio::takeMsckfPoints(std::vector<FeatureIDType>& ids, std::vector<Eigen::Vector3d>& positions, std::vector<double>& cov9, std::vector<int>& n_obs)
+{
+    finish();
+    ids.clear(); positions.clear(); cov9.clear(); n_obs.clear();
+    std::vector<int64_t> id(4096); std::vector<double> pos(3 * 4096), cov(9 * 4096); std::vector<int> no(4096);
+    for (;;) {
+        const int n = lvk_ekf_take_msckf_points(ekf, id.data(), pos.data(), cov.data(), no.data(), 4096);
+        for (int i = 0; i < n; ++i) {
+            ids.push_back((FeatureIDType)id[(size_t)i]); positions.push_back(Eigen::Vector3d(pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2]));
+            n_obs.push_back(no[(size_t)i]);
+        }
+        cov9.insert(cov9.end(), cov.begin(), cov.begin() + 9 * (size_t)n);
+        if (n < 4096) break;
+    }
+}
+
 void LarVio::getActiveeMapPointPositions(std::map<larvio::FeatureIDType, Eigen::Vector3d>& mMapPoints)
 {
     finish();

@@ -4,8 +4,12 @@
 //   host_tools png <in.png> <out.raw>      prints "width height", writes the 8-bit grey pixels
 //   host_tools imu <data.csv>              one "%.17g x7" line per sample
 //   host_tools images <data.csv>           one "stamp name" line per image
+//   host_tools euroc-args [options...]     the dataset driver's options as it parses them, one "name value" line each (exit 1 + the
+//                                          driver's message on an unknown option)
+//   host_tools msckf-line <id> <x y z> <9 covariance entries, row-major> <n_obs>      the --msckf-out line of that point
 #include "lvk_config.hpp"
 #include "lvk_dataset.hpp"
+#include "lvk_euroc_args.hpp"
 #include "lvk_png.hpp"
 #include <cstdio>
 #include <cstring>
@@ -59,6 +63,18 @@ int main(int argc, char** argv)
         for (size_t i = 0; i < v.size(); ++i) std::printf("%.17g %s\n", v[i].timeStampToSec, v[i].imgName.c_str());
         return 0;
     }
-    std::fprintf(stderr, "usage: host_tools config|png|imu|images ...\n");
+    if (argc >= 2 && !std::strcmp(argv[1], "euroc-args")) {
+        lvk::EurocArgs o; std::string bad;
+        if (!lvk::parse_euroc_args(argc, argv, 2, &o, &bad)) { std::fprintf(stderr, "unknown option %s\n", bad.c_str()); return 1; }
+        std::printf("tum %s\nmask %s\nmap_out %s\nmsckf_out %s\nmax_frames %ld\npipelined %d\n", o.tum.c_str(), o.mask.c_str(), o.map_out.c_str(), o.msckf_out.c_str(),
+                    o.max_frames, o.pipelined ? 1 : 0);
+        return 0;
+    }
+    if (argc == 16 && !std::strcmp(argv[1], "msckf-line")) {
+        double v[12]; for (int i = 0; i < 12; ++i) v[i] = std::strtod(argv[3 + i], nullptr);
+        lvk::write_msckf_point(stdout, std::atoll(argv[2]), v, v + 3, std::atoi(argv[15]));
+        return 0;
+    }
+    std::fprintf(stderr, "usage: host_tools config|png|imu|images|euroc-args|msckf-line ...\n");
     return 2;
 }

@@ -2,17 +2,21 @@
 // Pangolin): same command line, same loop, same log files (msckf_2_state.txt / msckf_2_takeoff.txt in the configuration's
 // output_dir, written by lvk::LarVio as larvio.cpp:388,446-453 does), running on liblvk_hip.so.
 //
-//   larvio_euroc path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE]
+//   larvio_euroc path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE]
 //
 // --mask restricts corner detection to the non-zero pixels of an 8-bit PNG of the configured resolution (ImageProcessor::setMask:
 // a fisheye vignette, the vehicle's own body); a mask of another size is an error.
 // --map-out turns the filter's lost-point covariances on (LarVio::setLostFeatureCov) and writes, at the end of the run, one line per
 // stable map point: "id x y z sxx sxy sxz syy syz szz" - its last world position and the upper triangle of its 3 x 3 position covariance.
+// --msckf-out turns the filter's MSCKF-point export on (LarVio::setMsckfPoints) and writes one line per point the lost-feature updates
+// triangulated, accepted and erased: "id x y z" + the nine entries of its 3 x 3 position covariance, row-major + its observation count.
+// The list is drained after every update; --pipelined drains it once, at the end (the filter keeps the newest 65536 points).
 // --tum writes "t x y z qx qy qz qw" (body in world, absolute stamps, 17 significant digits) for tools/traj_rmse.py.
 // --pipelined runs the same loop through lvk::VioPipeline: the filter update of a message overlaps the front-end of the next
 // frames on a second HIP stream; the trajectory is the same, written from the filter thread's odometry callback.
 // The filter starts with the static initializer (StaticInitializer.cpp); the dynamic (SfM) initializer is outside the hot path.
 #include "lvk_dataset.hpp"
+#include "lvk_euroc_args.hpp"
 #include "lvk_png.hpp"
 #include <chrono>
 #include <cstdio>
@@ -45,6 +49,21 @@ struct MapOut {
     void close() { if (f) { std::fclose(f); f = nullptr; } }
 };
 
+// --msckf-out: the MSCKF points collected so far (drained after every update, so the filter's list stays short)
+struct MsckfOut {
+    FILE* f; long n;
+    void drain(lvk::LarVio& Estimator)
+    {
+        if (!f) return;
+        std::vector<int64_t> ids; std::vector<double> xyz, cov; std::vector<int> n_obs;
+        do {
+            Estimator.takeMsckfPoints(ids, xyz, cov, n_obs);
+            for (size_t i = 0; i < ids.size(); ++i, ++n) lvk::write_msckf_point(f, (long long)ids[i], &xyz[3 * i], &cov[9 * i], n_obs[i]);
+        } while (!ids.empty());
+    }
+    void close() { if (f) { std::fclose(f); f = nullptr; } }
+};
+
 struct OdometrySink { FILE* tum; long n_odo; };
 static void on_odometry(void* user, double, const lvk::LarVio& Estimator)
 {
@@ -54,7 +73,7 @@ static void on_odometry(void* user, double, const lvk::LarVio& Estimator)
 }
 
 static int run_pipelined(const char* image_dir, const std::vector<lvk::ImuData>& allImuData, const std::vector<lvk::ImgInfo>& allImgInfo, long max_frames,
-                         lvk::ImageProcessor& ImgProcesser, lvk::LarVio& Estimator, FILE* tum, MapOut& map_out)
+                         lvk::ImageProcessor& ImgProcesser, lvk::LarVio& Estimator, FILE* tum, MapOut& map_out, MsckfOut& msckf_out)
 {
     typedef std::chrono::steady_clock Clock;
     lvk::VioPipeline pipe(ImgProcesser, Estimator);
@@ -83,6 +102,7 @@ static int run_pipelined(const char* image_dir, const std::vector<lvk::ImuData>&
     t_proc += std::chrono::duration<double>(Clock::now() - t2).count();
     if (tum) std::fclose(tum);
     map_out.drain(Estimator); map_out.close();
+    msckf_out.drain(Estimator); msckf_out.close();
     std::printf("frames %zu  feature messages %ld  odometry updates %ld  state dim %d\n", n_frames, n_msgs, sink.n_odo, lvk_ekf_dim(Estimator.handle()));
     std::printf("pipelined: %.3f ms/frame in the driver thread   image read+decode %.3f ms/frame\n", n_frames ? 1e3 * t_proc / n_frames : 0.0, n_frames ? 1e3 * t_io / n_frames : 0.0);
     if (t_proc > 0) std::printf("processing rate %.1f frames/s (pipelined, host buffers)\n", n_frames / t_proc);
@@ -92,18 +112,12 @@ static int run_pipelined(const char* image_dir, const std::vector<lvk::ImuData>&
 int main(int argc, char** argv)
 {
     if (argc < 5) {
-        std::fprintf(stderr, "Usage: %s path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE]\n", argv[0]);
+        std::fprintf(stderr, "Usage: %s path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE]\n", argv[0]);
         return 1;
     }
-    std::string tum_path, mask_path, map_path; long max_frames = -1; bool pipelined = false;
-    for (int a = 5; a < argc; ++a) {
-        if (!std::strcmp(argv[a], "--tum") && a + 1 < argc) tum_path = argv[++a];
-        else if (!std::strcmp(argv[a], "--max-frames") && a + 1 < argc) max_frames = std::atol(argv[++a]);
-        else if (!std::strcmp(argv[a], "--pipelined")) pipelined = true;
-        else if (!std::strcmp(argv[a], "--mask") && a + 1 < argc) mask_path = argv[++a];
-        else if (!std::strcmp(argv[a], "--map-out") && a + 1 < argc) map_path = argv[++a];
-        else { std::fprintf(stderr, "unknown option %s\n", argv[a]); return 1; }
-    }
+    lvk::EurocArgs opt; std::string bad;
+    if (!lvk::parse_euroc_args(argc, argv, 5, &opt, &bad)) { std::fprintf(stderr, "unknown option %s\n", bad.c_str()); return 1; }
+    const std::string &tum_path = opt.tum, &mask_path = opt.mask, &map_path = opt.map_out; const long max_frames = opt.max_frames; const bool pipelined = opt.pipelined;
 
     // Read sensors (larvioMain.cpp:33-37)
     std::vector<lvk::ImuData> allImuData; std::vector<lvk::ImgInfo> allImgInfo;
@@ -140,7 +154,12 @@ int main(int argc, char** argv)
         if (!(map_out.f = std::fopen(map_path.c_str(), "w"))) { std::perror(map_path.c_str()); return 1; }
         if (!Estimator.setLostFeatureCov(true)) { std::fprintf(stderr, "larvio_euroc: %s\n", ctx.error()); return 1; }
     }
-    if (pipelined) return run_pipelined(argv[3], allImuData, allImgInfo, max_frames, ImgProcesser, Estimator, tum, map_out);
+    MsckfOut msckf_out = {nullptr, 0};
+    if (!opt.msckf_out.empty()) {
+        if (!(msckf_out.f = std::fopen(opt.msckf_out.c_str(), "w"))) { std::perror(opt.msckf_out.c_str()); return 1; }
+        if (!Estimator.setMsckfPoints(true)) { std::fprintf(stderr, "larvio_euroc: %s\n", (pipelined ? ctx2 : ctx).error()); return 1; }
+    }
+    if (pipelined) return run_pipelined(argv[3], allImuData, allImgInfo, max_frames, ImgProcesser, Estimator, tum, map_out, msckf_out);
 
     typedef std::chrono::steady_clock Clock;
     double t_fe = 0, t_be = 0, t_io = 0; long n_fe = 0, n_be = 0, n_odo = 0;
@@ -173,9 +192,11 @@ int main(int argc, char** argv)
             ++n_odo;
             if (tum) write_tum(tum, Estimator);
         }
+        msckf_out.drain(Estimator);
     }
     if (tum) std::fclose(tum);
     map_out.drain(Estimator); map_out.close();
+    msckf_out.drain(Estimator); msckf_out.close();
     std::printf("frames %ld  feature messages %ld  odometry updates %ld  state dim %d\n", n_fe, n_be, n_odo, lvk_ekf_dim(Estimator.handle()));
     std::printf("front-end %.3f ms/frame   back-end %.3f ms/message   image read+decode %.3f ms/frame\n", n_fe ? 1e3 * t_fe / n_fe : 0.0,
                 n_be ? 1e3 * t_be / n_be : 0.0, n_fe ? 1e3 * t_io / n_fe : 0.0);

@@ -1,0 +1,35 @@
+// lvk_euroc_args.hpp — the options of examples/larvio_euroc after its four positional arguments, and the line format of its
+// --msckf-out file; host-only, so that examples/host_tools can show both on a machine without a GPU.
+#pragma once
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+namespace lvk {
+
+struct EurocArgs { std::string tum, mask, map_out, msckf_out; long max_frames; bool pipelined; EurocArgs() : max_frames(-1), pipelined(false) {} };
+
+// argv[first..]: false, with the offending word in *bad, on an unknown option or an option without its value
+inline bool parse_euroc_args(int argc, char** argv, int first, EurocArgs* o, std::string* bad)
+{
+    for (int a = first; a < argc; ++a) {
+        if (!std::strcmp(argv[a], "--tum") && a + 1 < argc) o->tum = argv[++a];
+        else if (!std::strcmp(argv[a], "--max-frames") && a + 1 < argc) o->max_frames = std::atol(argv[++a]);
+        else if (!std::strcmp(argv[a], "--pipelined")) o->pipelined = true;
+        else if (!std::strcmp(argv[a], "--mask") && a + 1 < argc) o->mask = argv[++a];
+        else if (!std::strcmp(argv[a], "--map-out") && a + 1 < argc) o->map_out = argv[++a];
+        else if (!std::strcmp(argv[a], "--msckf-out") && a + 1 < argc) o->msckf_out = argv[++a];
+        else { if (bad) *bad = argv[a]; return false; }
+    }
+    return true;
+}
+
+// one --msckf-out line: "id x y z s00 s01 s02 s10 s11 s12 s20 s21 s22 n_obs" (17 significant digits: the doubles round-trip)
+inline void write_msckf_point(FILE* f, long long id, const double* p, const double* c, int n_obs)
+{
+    std::fprintf(f, "%lld %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %d\n", id, p[0], p[1], p[2], c[0], c[1], c[2], c[3], c[4],
+                 c[5], c[6], c[7], c[8], n_obs);
+}
+
+}   // namespace lvk

@@ -459,6 +459,32 @@ int        lvk_ekf_take_lost_features(lvk_ekf* e, int64_t* h_ids, double* h_pos_
 lvk_status lvk_ekf_get_feature_cov(lvk_ekf* e, int64_t* h_ids, int64_t* h_anchor_ids, double* h_pos_w, double* h_cov9, int cap, int* n_out);
 lvk_status lvk_ekf_set_lost_feature_cov(lvk_ekf* e, int on);
 int        lvk_ekf_take_lost_features_cov(lvk_ekf* e, int64_t* h_ids, double* h_pos_w, double* h_cov9, int cap);
+/* The MSCKF points: every lost-feature update triangulates the features that never enter the state (hundreds to thousands per message),
+ * uses them once and forgets them.  lvk_ekf_set_msckf_points (off by default) keeps them, each with the covariance of
+ * lvk_ekf_msckf_point_cov (conventions there): while on, the lost-feature update queues that kernel for its MSCKF jobs ahead of its
+ * update, on the covariance the update starts from (after this message's propagation and augmentation - the one the gate reads), with
+ * the results going to the filter's pinned download buffer.  Once the update has waited for its stream and the gate results are known,
+ * every MSCKF feature that was used and erased - it triangulated, its gate accepted it, and the kernel reported ok - yields one record
+ * {id, world position, Sigma, number of observations} on a list that lvk_ekf_take_msckf_points drains (up to cap records per call;
+ * any output pointer may be null; returns the count).  The list holds at most 65536 records: the oldest half goes when it is full.
+ * Sigma is CONSERVATIVE: it is stated against the covariance before the update that consumes the point has been applied.
+ * One feature id can appear in SEVERAL records: a track that is still alive when it reaches max_track_len observations is used and
+ * erased like a lost one, and the tracker's next message starts it again under the same id - a long track is consumed in pieces, each
+ * piece a record of its own (its own observations, position and Sigma).  Do not key a map by id alone; only with max_track_len above
+ * the window (sw_size + 2) is every id handed out once.
+ * The kernel takes 2..64 observations per point, as the stage entry does: a feature seen from more than 64 clones (possible only with
+ * sw_size > 62) takes part in the update as always but is not exported.  Every MSCKF job of an update has a result slot (the download
+ * buffer holds as many as the update's batch may have jobs; a batch that broke that rule would fail the update with
+ * LVK_ERR_CAPACITY, not lose points).
+ * Gate-rejected points and the features of pruning updates (they stay in the map) are not exported.  The launch is queued ahead of the update,
+ * whose gate results and correction the host always waits for on the same stream before it reads the export: by that order of calls
+ * the export is meant to need no stream wait of its own (at most one more per update is its budget; the waits are not counted by a
+ * test).  With the switch off the filter launches exactly the kernels it launched
+ * before this entry point existed.  State, covariance and counters are the same bits with the switch on or off.
+ * The sharded update does not export: with a transport set (lvk_ekf_set_shard) switching on is refused with LVK_ERR_UNSUPPORTED, and so
+ * is a transport while the switch is on. */
+lvk_status lvk_ekf_set_msckf_points(lvk_ekf* e, int on);
+int        lvk_ekf_take_msckf_points(lvk_ekf* e, int64_t* h_ids, double* h_pos_w, double* h_cov9, int* h_n_obs, int cap);
 /* What the moving-start initialiser (FlexibleInitializer.cpp:11-25 -> DynamicInitializer.cpp) handed to the filter, with the intermediate
  * results of the successful attempt - for parity tests against an independent restatement fed the same messages:
  *   valid        1 once the dynamic initialiser has succeeded on this handle (0: never ran, or the static one fired)
@@ -565,6 +591,28 @@ lvk_status lvk_ekf_feature_rows(lvk_context* ctx, const lvk_clone* h_clones, int
                                 const double* h_P, int N, int ldp, int leg_dim, int if_fej, int estimate_td, double sigma2, int mode,
                                 lvk_feature_result* h_res, double* h_blocks, int* h_ccols, double* h_H, int ldh, int h_rows, double* h_r,
                                 int* rows_out);
+
+/* lvk_ekf_msckf_point_cov: first-order 3 x 3 position covariance of least-squares (MSCKF) points, one per job, read off a
+ * device-resident covariance (n x n, row-major, leading dimension ldp) without moving it.  A job is a point p_w with M = n_obs
+ * observations from DISTINCT clones; clone ranks, z and zv (2 doubles each) are indexed by obs_off + k, as in lvk_ekf_gate_and_stack:
+ * the three arrays carry no length, the caller supplies at least max(obs_off + n_obs) entries (2 doubles each for z and zv).
+ * With Hx_t (2 x 6, the observing clone), He_t (2 x 6, the extrinsics) and Hf_t (2 x 3, the point) of measurementJacobian_msckf
+ * (larvio.cpp:859-921, first-estimate form when if_fej) for observation t, and Hc (2M x c, c = 7 + 6M) the compact block the row stage
+ * builds before its null-space projection - columns 0..5 He_t, column 6 the observation's zv when estimate_td and 0 otherwise, columns
+ * 7+6t.. Hx_t; its column map cc is 15..21, then leg_dim + 6 rank_t + j -
+ *   A = sum_t Hf_t^T Hf_t,   G_t = A^-1 Hf_t^T,   B = sum_t G_t Hc[2t:2t+2, :],   Sigma = sigma2 A^-1 + B P[cc, cc] B^T :
+ * the covariance of the least-squares point under pixel noise sigma2 and a state error ~ N(0, P), cross terms between all observing
+ * clones included.  A is solved with an unpivoted 3 x 3 LDL^T; if one of its pivots is not positive the point gets nine NaNs and
+ * h_ok = 0 (h_ok = 1 otherwise) - a nearly singular A gives a correspondingly large Sigma, not a refusal.  Nothing of P outside rows and
+ * columns cc is read; every sum runs in a fixed order (the same input gives the same bits); the lower triangle is a copy of the upper
+ * one.  h_cov9: 9 doubles per job, row-major.  The call waits for its launch.
+ * LVK_ERR_ARG, with nothing launched and the context still usable: a null pointer, n_jobs < 0, n <= 0, ldp < n, leg_dim other than 22 / 46,
+ * n_obs outside 2..64, a negative obs_off, a rank outside [0, n_clones) or whose six columns leave [0, n), a rank that appears twice in
+ * one job.  n_jobs == 0 is LVK_OK. */
+typedef struct { int n_obs, obs_off; double p_w[3]; } lvk_msckf_point_job;
+lvk_status lvk_ekf_msckf_point_cov(lvk_context* ctx, const double* d_P, int ldp, int n, const lvk_clone* h_clones, int n_clones,
+                                   const lvk_msckf_point_job* h_jobs, int n_jobs, const int* h_clone_rank, const double* h_obs, const double* h_obs_vel,
+                                   int leg_dim, int if_fej, int estimate_td, double sigma2, double* h_cov9, int* h_ok);
 
 /* ---- the two kernels around the exchange of the sharded update (lvk_ekf_set_shard), one call each (parity tests).  Host
  * buffers; each call launches the production kernel through the launcher the filter uses, waits, and copies back.

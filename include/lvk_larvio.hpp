@@ -190,6 +190,16 @@ public:
         const int n = lvk_ekf_take_lost_features_cov(ekf_, ids.data(), xyz.data(), cov.data(), 4096);
         ids.resize((size_t)n); xyz.resize((size_t)3 * n); cov.resize((size_t)9 * n);
     }
+    // The MSCKF points (lvk_ekf_set_msckf_points / lvk_ekf_take_msckf_points; conventions in lvk_c.h): setMsckfPoints(true), after
+    // initialize(), makes every lost-feature update keep the features it triangulated, accepted and erased, each with its 3 x 3
+    // position covariance (9 doubles, row-major) and observation count; takeMsckfPoints hands out up to 4096 of them per call.
+    bool setMsckfPoints(bool on) { return ekf_ && lvk_ekf_set_msckf_points(ekf_, on ? 1 : 0) == LVK_OK; }
+    void takeMsckfPoints(std::vector<int64_t>& ids, std::vector<double>& xyz, std::vector<double>& cov, std::vector<int>& n_obs)
+    {
+        ids.resize(4096); xyz.resize(3 * 4096); cov.resize(9 * 4096); n_obs.resize(4096);
+        const int n = ekf_ ? lvk_ekf_take_msckf_points(ekf_, ids.data(), xyz.data(), cov.data(), n_obs.data(), 4096) : 0;
+        ids.resize((size_t)n); xyz.resize((size_t)3 * n); cov.resize((size_t)9 * n); n_obs.resize((size_t)n);
+    }
     lvk_ekf* handle() const { return ekf_; }
 private:
     friend class VioPipeline;

@@ -197,6 +197,12 @@ struct lvk_ekf {
     // their Sigma (-1: no job, the anchor is outside the window); attached at the end of the call, behind a stream sync
     // (lost_cov_mark = n_sync when the launch was queued: one more sync only if none has followed)
     bool lost_cov_on = false; std::vector<int> lost_cov_slot; int lost_cov_mark = 0; size_t down_lm = 0; int lm_cap = 0;
+    // lvk_ekf_set_msckf_points: the MSCKF features a lost-feature update used and erased, with the position covariance k_msckf_point_cov
+    // computed for them ahead of that update (drained on read).  The kernel covers jobs [mp_lo, mp_lo + mp_n) of the update's batch and
+    // writes job k's Sigma / ok word to slot k - mp_lo of the download buffer (down_mp / down_mpok)
+    struct MsckfPoint { long long id; double p[3]; double cov[9]; int n_obs; };
+    std::vector<MsckfPoint> msckf_points;
+    bool msckf_points_on = false; size_t down_mp = 0, down_mpok = 0, mp_lo = 0; int mp_cap = 0, mp_n = 0;
     double sigma2, zupt_v2, zupt_p2, zupt_q2, imu_img_time_th, Qc[12];
     double x_min, y_min, grid_w, grid_h;
     std::vector<int> grid_count;
@@ -1085,7 +1091,8 @@ static bool feat_check_motion(const lvk_ekf* e, const Feature& f, bool if_tracke
 struct RowJob { Feature* f; int type; std::vector<long long> sids; bool want_gate; int dof; FeatJob dev; FeatResult res; FeatJob* hdev = nullptr; bool tri_pending = false; };   // hdev: the job's record in the upload arena (patched until the launch is flushed)
 
 typedef std::vector<std::pair<size_t, size_t>> JobRanges;
-static lvk_status launch_feature_rows(lvk_ekf* e, std::vector<RowJob>& jobs, const JobRanges* ranges = nullptr)
+struct RowObs { const int* rank = nullptr; const double *z = nullptr, *zv = nullptr; };      // where a batch's observations lie on the device (FeatJob::obs_off indexes them)
+static lvk_status launch_feature_rows(lvk_ekf* e, std::vector<RowJob>& jobs, const JobRanges* ranges = nullptr, RowObs* obs_out = nullptr)
 {   // stages the jobs and queues k_feature_rows (for the given index ranges only, in the sharded update); nothing is read back
     // (fetch_feature_results does that)
     if (jobs.empty()) return LVK_OK;
@@ -1135,6 +1142,7 @@ static lvk_status launch_feature_rows(lvk_ekf* e, std::vector<RowJob>& jobs, con
     double* Ho = e->d_H; double* ro = e->d_r; const int ldh = e->ld, ncols_out = e->N;       // direct output of the jobs that carry a destination row (FeatJob::dst_row1, patched by gated_update)
     const int n_cl = (int)e->clones.size();
     const TriResult* d_tri = any_pending ? e->d_tridev : nullptr;      // results of the triangulation queued ahead, by job index (whole-batch launches only)
+    if (obs_out) { obs_out->rank = d_r; obs_out->z = d_z; obs_out->zv = d_v; }
     if (any_pending && ranges) return lvk_set_error(e->ctx, LVK_ERR_ARG, "internal: device-consumed triangulation in a ranged launch");
     if (!ranges) return run_or_defer(e, [=]() { return lvk_launch_feature_rows(e->ctx, d_j, nj, max_rows, d_cl, d_r, d_z, d_v, P, e->ld, fl, e->d_staging, e->d_ccols, e->d_fout, d_fh, Ho, ldh, ncols_out, ro, obs_stride, n_cl, d_tri); });
     for (const auto& rg : *ranges) {                    // jobs carry absolute offsets into the observation / staging / column arrays
@@ -1144,6 +1152,42 @@ static lvk_status launch_feature_rows(lvk_ekf* e, std::vector<RowJob>& jobs, con
         if (st != LVK_OK) return st;
     }
     return LVK_OK;
+}
+// lvk_ekf_set_msckf_points: queue k_msckf_point_cov for the MSCKF jobs [lo, hi) of the batch launch_feature_rows has just staged, on the
+// covariance as it is now (the one the update starts from), on the observations that launch staged (obs); the results go to the pinned
+// download buffer, msckf_point_record() reads them behind the wait the update makes for its gate results
+static lvk_status msckf_points_queue(lvk_ekf* e, const std::vector<RowJob>& jobs, size_t lo, size_t hi, const RowObs& obs)
+{
+    e->mp_n = 0;
+    if (!e->msckf_points_on || hi <= lo) return LVK_OK;
+    if (!obs.rank || !obs.z || !obs.zv) return lvk_set_error(e->ctx, LVK_ERR_ARG, "internal: MSCKF points queued without a staged batch");
+    if (hi - lo > (size_t)e->mp_cap) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "internal: %zu MSCKF jobs exceed the %d result slots of the point export", hi - lo, e->mp_cap);
+    const int n = (int)(hi - lo);
+    PointJob* hj = up_alloc<PointJob>(e, (size_t)n);
+    if (!hj) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "upload arena exhausted");
+    for (int k = 0; k < n; ++k) {
+        const RowJob& j = jobs[lo + (size_t)k];
+        hj[k].n_obs = j.dev.n_obs; hj[k].obs_off = j.dev.obs_off; hj[k].tri_slot1 = j.tri_pending ? (int)(lo + (size_t)k) + 1 : 0; hj[k].pad = 0;
+        memcpy(hj[k].p_w, j.dev.p_w, 24);
+    }
+    e->mp_lo = lo; e->mp_n = n;
+    FilterFlags fl; fl.leg_dim = LEG; fl.if_fej = e->if_fej ? 1 : 0; fl.estimate_td = e->cfg.estimate_td; fl.pad = 0; fl.sigma2 = e->sigma2;
+    const double* P = e->dP[e->cur]; const PointJob* d_jobs = dev(e, hj); const CloneDev* d_cl = e->dv_clones;
+    const int* d_r = obs.rank; const double* d_z = obs.z; const double* d_v = obs.zv; const TriResult* d_tri = e->d_tridev;
+    double* out = (double*)(e->dh_down + e->down_mp); int* ok = (int*)(e->dh_down + e->down_mpok);
+    return run_or_defer(e, [=]() { return lvk_launch_msckf_point_cov(e->ctx, P, e->ld, d_jobs, n, d_cl, d_r, d_z, d_v, fl, d_tri, out, ok); });
+}
+// job k of the batch was an MSCKF feature that triangulated and passed its gate, and is about to be erased: keep it (after the stream
+// wait that covers the launch above)
+static void msckf_point_record(lvk_ekf* e, const RowJob& j, size_t k)
+{
+    if (e->mp_n <= 0 || k < e->mp_lo || k >= e->mp_lo + (size_t)e->mp_n) return;
+    const size_t slot = k - e->mp_lo;
+    if (!((const int*)(e->h_down + e->down_mpok))[slot]) return;
+    if (e->msckf_points.size() >= (size_t)1 << 16) e->msckf_points.erase(e->msckf_points.begin(), e->msckf_points.begin() + (1 << 15));
+    lvk_ekf::MsckfPoint mp; mp.id = j.f->id; memcpy(mp.p, j.f->position, 24); mp.n_obs = (int)j.sids.size();
+    memcpy(mp.cov, (const double*)(e->h_down + e->down_mp) + 9 * slot, 72);
+    e->msckf_points.push_back(mp);
 }
 static lvk_status shard_peer_check(lvk_ekf* e);
 // results of the queued jobs (+ optionally n_dx doubles of d_dx in the same sync)
@@ -1487,14 +1531,16 @@ static inline void grid_add(lvk_ekf* e, int code, int cells)
 // are staged (pruning: the clones about to go) - host work done here, while the device still runs what was queued ahead.
 static void drop_observations(lvk_ekf* e, const long long* sids, int n) { for (auto kv : e->map) for (int k = 0; k < n; ++k) kv.second.erase(sids[k]); }
 static lvk_status gated_update(lvk_ekf* e, std::vector<RowJob>& jobs, const size_t (&order)[2][2], const int (&tr)[3], std::vector<double>& dx,
-                               const long long* retire = nullptr, int n_retire = 0)
+                               const long long* retire = nullptr, int n_retire = 0, size_t mp_lo = 0, size_t mp_hi = 0)
 {
     const int N = e->N;
     const bool sharded = e->shard.fn != nullptr;
     std::vector<size_t> jb; JobRanges own;
     if (sharded) { shard_bounds(jobs, 0, jobs.size(), e->shard.world, jb); own.push_back({jb[(size_t)e->shard.rank], jb[(size_t)e->shard.rank + 1]}); }
     begin_defer(e);                                     // the jobs (and their row slots) go up in one copy
-    lvk_status st = launch_feature_rows(e, jobs, sharded ? &own : nullptr);
+    RowObs obs;
+    lvk_status st = launch_feature_rows(e, jobs, sharded ? &own : nullptr, &obs);
+    if (st == LVK_OK && !sharded) st = msckf_points_queue(e, jobs, mp_lo, mp_hi, obs);      // [mp_lo, mp_hi): the MSCKF jobs of a lost-feature update (lvk_ekf_set_msckf_points)
     if (tr[0] >= 0) TR(tr[0]);
     TRS(0);
     if (st != LVK_OK && !sharded) { end_defer(e); return st; }      // sharded: a local failure still goes through the exchange (shard_stage1, pre_fail)
@@ -1580,7 +1626,7 @@ static lvk_status remove_lost_fast(lvk_ekf* e, const std::vector<long long>& ekf
     TR(TR_RLF_TRI);
     TR(TR_RLF_TRIAGE);
     std::vector<double> dx;
-    st = gated_update(e, jobs, {{(size_t)n_ekf, jobs.size()}, {0, (size_t)n_ekf}}, {-1, TR_RLF_UPD, TR_RLF_DX}, dx);
+    st = gated_update(e, jobs, {{(size_t)n_ekf, jobs.size()}, {0, (size_t)n_ekf}}, {-1, TR_RLF_UPD, TR_RLF_DX}, dx, nullptr, 0, (size_t)n_ekf, jobs.size());
     if (st != LVK_OK) return st;
     int accepted = 0;
     for (size_t k = (size_t)n_ekf; k < jobs.size(); ++k) {
@@ -1590,7 +1636,7 @@ static lvk_status remove_lost_fast(lvk_ekf* e, const std::vector<long long>& ekf
             apply_tri(pk.f, 0, a);
             if (!a.ok) { if (pk.lost) e->map.erase(pk.f->id); continue; }      // a lost feature that cannot be triangulated is invalid (:1921-1925); a tracked one waits for more views
         }
-        if (gate_ok(e, jobs[k])) accepted += job_rows(jobs[k]);
+        if (gate_ok(e, jobs[k])) { accepted += job_rows(jobs[k]); msckf_point_record(e, jobs[k], k); }
         e->map.erase(pk.f->id);                          // used (:2240-2246)
     }
     for (size_t k = 0; k < (size_t)n_ekf; ++k) if (gate_ok(e, jobs[k])) accepted += 2;
@@ -1744,10 +1790,10 @@ static lvk_status remove_lost_features(lvk_ekf* e)
         TR(TR_RLF_TRIAGE);
         if (ekf_new.empty()) {
             std::vector<double> dx;                     // no feature enters the state: gate results and dx in one sync (j_ekf == 0)
-            st = gated_update(e, jobs, {{j_msckf, jobs.size()}, {j_ekf, j_msckf}}, {-1, TR_RLF_UPD, TR_RLF_DX}, dx);
+            st = gated_update(e, jobs, {{j_msckf, jobs.size()}, {j_ekf, j_msckf}}, {-1, TR_RLF_UPD, TR_RLF_DX}, dx, nullptr, 0, j_msckf, jobs.size());
             if (st != LVK_OK) return st;
             int accepted = 0;
-            for (size_t k = j_msckf; k < jobs.size(); ++k) if (gate_ok(e, jobs[k])) accepted += job_rows(jobs[k]);
+            for (size_t k = j_msckf; k < jobs.size(); ++k) if (gate_ok(e, jobs[k])) { accepted += job_rows(jobs[k]); msckf_point_record(e, jobs[k], k); }
             for (size_t k = j_ekf; k < j_msckf; ++k) if (gate_ok(e, jobs[k])) accepted += 2;
             gated_update_apply(e, dx, accepted, 0);
             for (long long id : msckf) e->map.erase(id);
@@ -1767,7 +1813,12 @@ static lvk_status remove_lost_features(lvk_ekf* e)
             st = launch_feature_rows(e, jobs, &rgs);
             if (st == LVK_OK) st = fetch_feature_results(e, jobs);          // local sync: only jobs [0, j_ekf) are looked at before the exchange
             if (st != LVK_OK) shard_abort(e);                               // the exchange's size depends on those results: cannot post a poisoned block
-        } else st = run_feature_rows(e, jobs);
+        } else {
+            RowObs obs;
+            st = launch_feature_rows(e, jobs, nullptr, &obs);
+            if (st == LVK_OK) st = msckf_points_queue(e, jobs, j_msckf, jobs.size(), obs);
+            if (st == LVK_OK) st = fetch_feature_results(e, jobs);
+        }
         if (st != LVK_OK) return st;
         auto own_of = [&](size_t k) { return sharded ? shard_owner(jb, k) : 0; };
         TR(TR_RLF_ROWS);
@@ -1778,7 +1829,7 @@ static lvk_status remove_lost_features(lvk_ekf* e)
             for (size_t k = j_msckf; k < jobs.size(); ++k) { const int r = job_rows(jobs[k]); push_rows(map_o, jobs[k], job_first_row(jobs[k]), r, rows_m, (int)k, &grp, e, N, own_of(k)); rows_m += r; }
             for (size_t k = j_ekf; k < j_msckf; ++k) { push_rows(map_o, jobs[k], 0, 2, rows_m + rows_e, (int)k, &grp, e, N, own_of(k)); rows_e += 2; }
         } else {
-            for (size_t k = j_msckf; k < jobs.size(); ++k) if (gate_ok(e, jobs[k])) { push_rows(map_o, jobs[k], jobs[k].res.first_row, jobs[k].res.rows, rows_m, -1, &grp, e, N, own_of(k)); rows_m += jobs[k].res.rows; }
+            for (size_t k = j_msckf; k < jobs.size(); ++k) if (gate_ok(e, jobs[k])) { push_rows(map_o, jobs[k], jobs[k].res.first_row, jobs[k].res.rows, rows_m, -1, &grp, e, N, own_of(k)); rows_m += jobs[k].res.rows; msckf_point_record(e, jobs[k], k); }
             for (size_t k = j_ekf; k < j_msckf; ++k) if (gate_ok(e, jobs[k])) { push_rows(map_o, jobs[k], 0, 2, rows_m + rows_e, -1, &grp, e, N, own_of(k)); rows_e += 2; }
         }
         std::vector<long long> acc_ids; std::vector<double> h2;
@@ -2325,7 +2376,10 @@ lvk_status lvk_ekf_create(lvk_context* ctx, const lvk_ekf_config* cfg, lvk_ekf**
     e->down_p00 = e->down_info + 256;                   // 16 x 16 doubles
     e->down_lm = e->down_p00 + 2048;                    // lvk_ekf_set_lost_feature_cov: 9 doubles per lost in-state feature of one update
     e->lm_cap = max_feat_state + 8;
-    e->down_cap = e->down_lm + ((sizeof(double) * 9 * (size_t)e->lm_cap + 255) & ~(size_t)255);
+    e->down_mp = e->down_lm + ((sizeof(double) * 9 * (size_t)e->lm_cap + 255) & ~(size_t)255);     // lvk_ekf_set_msckf_points: 9 doubles + an ok word per MSCKF job of one update
+    e->mp_cap = 2 * e->feat_cap;
+    e->down_mpok = e->down_mp + ((sizeof(double) * 9 * (size_t)e->mp_cap + 255) & ~(size_t)255);
+    e->down_cap = e->down_mpok + ((sizeof(int) * (size_t)e->mp_cap + 255) & ~(size_t)255);
     ok = ok && hipHostMalloc((void**)&e->h_up, e->up_cap) == hipSuccess && hipHostMalloc((void**)&e->h_down, e->down_cap) == hipSuccess;
     if (ok) {
         // No copy commands on the filter's chain (each ~8 us of API + copy + barrier; ten of them were 385 -> 336 us per update):
@@ -2493,7 +2547,7 @@ static lvk_status ekf_process_impl(lvk_ekf* e, double ts, const lvk_feature_obs*
     e->up_half ^= 1; e->n_sync = 0;
     e->up_off = e->up_flushed = e->up_half ? e->up_cap / 2 : 0; e->up_lim = e->up_off + e->up_cap / 2;
     e->colcache.cols.reset();                           // column lists depend on the clones' ranks, which this call changes
-    e->lost_cov_slot.clear();
+    e->lost_cov_slot.clear(); e->mp_n = 0;
     if (!e->b_first_features) {
         if (n_imu > 0 && imu[0].t - ts - e->td <= 0.0) e->b_first_features = true;
         else return LVK_OK;
@@ -2576,6 +2630,7 @@ lvk_status lvk_ekf_set_shard(lvk_ekf* e, int rank, int world, lvk_exchange_fn fn
     auto& S = e->shard;
     ekf_quiesce(e);
     if (fn && e->indefinite_policy == LVK_INDEFINITE_LDLT) return lvk_set_error(e->ctx, LVK_ERR_UNSUPPORTED, "lvk_ekf_set_shard: the sharded update has no pivoted fallback (LVK_INDEFINITE_LDLT is set)");
+    if (fn && e->msckf_points_on) return lvk_set_error(e->ctx, LVK_ERR_UNSUPPORTED, "lvk_ekf_set_shard: the sharded update does not export MSCKF points (lvk_ekf_set_msckf_points is on)");
     EKF_HIP(hipStreamSynchronize(e->ctx->stream));
     if (S.d_send) hipFree(S.d_send); if (S.d_recv) hipFree(S.d_recv);
     S.d_send = S.d_recv = nullptr; S.cap = 0; S.xk_cap = 0;
@@ -2760,6 +2815,29 @@ lvk_status lvk_ekf_set_lost_feature_cov(lvk_ekf* e, int on)
     ekf_quiesce(e);
     e->lost_cov_on = on != 0;
     return LVK_OK;
+}
+lvk_status lvk_ekf_set_msckf_points(lvk_ekf* e, int on)
+{
+    if (!e) return LVK_ERR_ARG;
+    ekf_quiesce(e);
+    if (on && e->shard.fn) return lvk_set_error(e->ctx, LVK_ERR_UNSUPPORTED, "lvk_ekf_set_msckf_points: the sharded update does not export MSCKF points");
+    e->msckf_points_on = on != 0;
+    return LVK_OK;
+}
+int lvk_ekf_take_msckf_points(lvk_ekf* e, int64_t* ids, double* pos_w, double* cov9, int* n_obs, int cap)
+{
+    if (!e || cap <= 0) return 0;
+    ekf_quiesce(e);
+    const int n = std::min((int)e->msckf_points.size(), cap);
+    for (int i = 0; i < n; ++i) {
+        const lvk_ekf::MsckfPoint& mp = e->msckf_points[i];
+        if (ids) ids[i] = mp.id;
+        if (pos_w) memcpy(pos_w + 3 * i, mp.p, 24);
+        if (cov9) memcpy(cov9 + 9 * i, mp.cov, 72);
+        if (n_obs) n_obs[i] = mp.n_obs;
+    }
+    e->msckf_points.erase(e->msckf_points.begin(), e->msckf_points.begin() + n);
+    return n;
 }
 lvk_status lvk_ekf_get_feature_cov(lvk_ekf* e, int64_t* ids, int64_t* anchor_ids, double* pos_w, double* cov9, int cap, int* n_out)
 {

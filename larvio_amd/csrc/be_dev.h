@@ -22,6 +22,9 @@ struct FeatResult { double gamma, h2; int rows, first_row, c, accept; };   // ac
 // zero residual leaves the update unchanged) - the host then never has to read the gate back before launching the update
 struct StackRow { long long g_off, r_off; int src_row, c, ccol_off, dst_row, job, pad; };
 struct FilterFlags { int leg_dim, if_fej, estimate_td, pad; double sigma2; };
+// k_msckf_point_cov: one MSCKF point; observations at obs_off + k as in FeatJob; tri_slot1 > 0: its position is TriResult[tri_slot1 - 1]
+// of the triangulation queued ahead of the launch (what FJ_TRI_PENDING is to the row kernel), 0: p_w
+struct PointJob { int n_obs, obs_off, tri_slot1, pad; double p_w[3]; };
 
 #ifdef __HIPCC__
 __device__ __forceinline__ void d_m3_mul(const double* A, const double* B, double* C)

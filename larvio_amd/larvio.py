@@ -68,6 +68,8 @@ def _L():
         L.lvk_ekf_get_feature_cov.argtypes = [vp, vp, vp, vp, vp, i, pi]; L.lvk_ekf_get_feature_cov.restype = i
         L.lvk_ekf_set_lost_feature_cov.argtypes = [vp, i]; L.lvk_ekf_set_lost_feature_cov.restype = i
         L.lvk_ekf_take_lost_features_cov.argtypes = [vp, vp, vp, vp, i]; L.lvk_ekf_take_lost_features_cov.restype = i
+        L.lvk_ekf_set_msckf_points.argtypes = [vp, i]; L.lvk_ekf_set_msckf_points.restype = i
+        L.lvk_ekf_take_msckf_points.argtypes = [vp, vp, vp, vp, vp, i]; L.lvk_ekf_take_msckf_points.restype = i
         L.lvk_ekf_get_state.argtypes = [vp, vp]; L.lvk_ekf_get_state.restype = i
         L.lvk_ekf_get_cov.argtypes = [vp, vp]; L.lvk_ekf_get_cov.restype = i
         L.lvk_ekf_get_cov_imu.argtypes = [vp, i, vp]; L.lvk_ekf_get_cov_imu.restype = i
@@ -503,6 +505,24 @@ class LarVio:
         ids = np.zeros(4096, np.int64); pos = np.zeros((4096, 3)); cov = np.zeros((4096, 3, 3))
         n = _L().lvk_ekf_take_lost_features_cov(self._h, _p(ids), _p(pos), _p(cov), 4096)
         return ids[:n].copy(), pos[:n].copy(), cov[:n].copy()
+
+    def set_msckf_points(self, on=True):
+        """lvk_ekf_set_msckf_points: while on, every MSCKF feature a lost-feature update triangulates, accepts and erases is kept with
+        its position covariance (take_msckf_points hands it out); refused (LvkError) with a shard transport set"""
+        self.ctx.check(_L().lvk_ekf_set_msckf_points(self._h, int(bool(on))))
+
+    def take_msckf_points(self):
+        """lvk_ekf_take_msckf_points: (ids, world positions, Sigma (n, 3, 3), observation counts) of the MSCKF points collected since
+        the last call; Sigma is stated against the covariance before the update that consumed the point (conservative)"""
+        out = [[], [], [], []]
+        while True:
+            ids = np.zeros(4096, np.int64); pos = np.zeros((4096, 3)); cov = np.zeros((4096, 3, 3)); nob = np.zeros(4096, np.int32)
+            n = _L().lvk_ekf_take_msckf_points(self._h, _p(ids), _p(pos), _p(cov), _p(nob), 4096)
+            for o, a in zip(out, (ids, pos, cov, nob)):
+                o.append(a[:n].copy())
+            if n < 4096:
+                break
+        return tuple(np.concatenate(o) for o in out)
 
     def set_shard(self, rank, world, fn, user, keepalive=None):
         """lvk_ekf_set_shard: this filter does the per-feature device work of rank `rank` of `world`; fn/user = the all-gather

@@ -202,3 +202,25 @@ def landmark_cov(ctx, P, jobs, n=None):
     dP = ctx.to_device(P)
     ctx.check(L.lvk_ekf_landmark_cov(ctx.h, _p(dP), P.shape[1], n, _p(jobs), len(jobs), _p(out)))
     return out
+
+
+MSCKF_POINT_JOB = np.dtype([("n_obs", np.int32), ("obs_off", np.int32), ("p_w", np.float64, 3)])
+
+
+def msckf_point_cov(ctx, P, clones, jobs, clone_rank, obs, obs_vel, leg_dim=22, if_fej=False, estimate_td=False, sigma2=1.0, n=None):
+    """lvk_ekf_msckf_point_cov: the 3 x 3 position covariance of every MSCKF_POINT_JOB record (a least-squares point with its
+    observations at obs_off + k of clone_rank / obs / obs_vel), read off the covariance P.  P: a whole row-major buffer (its row
+    length is the leading dimension, contents go to the device as they are) whose leading n x n block (default: all rows) is the
+    covariance; clones: an array of larvio.CLONE records.  -> (Sigma (n_jobs, 3, 3), ok (n_jobs,))"""
+    from .larvio import CLONE
+    P = np.ascontiguousarray(P, np.float64); jobs = np.ascontiguousarray(jobs, MSCKF_POINT_JOB); clones = np.ascontiguousarray(clones, CLONE)
+    rk = np.ascontiguousarray(clone_rank, np.int32); z = np.ascontiguousarray(obs, np.float64); zv = np.ascontiguousarray(obs_vel, np.float64)
+    n = P.shape[0] if n is None else int(n)
+    out = np.full((len(jobs), 3, 3), np.nan); ok = np.full(len(jobs), -1, np.int32)
+    L = lib()
+    vp, i = C.c_void_p, C.c_int
+    L.lvk_ekf_msckf_point_cov.argtypes = [vp, vp, i, i, vp, i, vp, i, vp, vp, vp, i, i, i, C.c_double, vp, vp]; L.lvk_ekf_msckf_point_cov.restype = i
+    dP = ctx.to_device(P)
+    ctx.check(L.lvk_ekf_msckf_point_cov(ctx.h, _p(dP), P.shape[1], n, _p(clones), len(clones), _p(jobs), len(jobs), _p(rk), _p(z), _p(zv),
+                                        int(leg_dim), int(bool(if_fej)), int(bool(estimate_td)), float(sigma2), _p(out), _p(ok)))
+    return out, ok
