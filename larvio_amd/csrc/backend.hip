@@ -992,7 +992,7 @@ static lvk_status upload_clones(lvk_ekf* e)
     for (size_t i = 0; i < n; ++i) {
         const Clone& c = e->clones[i];
         quat_to_rot(c.q_cam, hc[i].R); memcpy(hc[i].t, c.p_cam, 24);
-        memcpy(hd[i].q, c.q, 32); memcpy(hd[i].p, c.p, 24); memcpy(hd[i].p_fej, c.p_fej, 24); memcpy(hd[i].R_b2c, c.R_b2c, 72); memcpy(hd[i].t_c_b, c.t_c_b, 24);
+        clone_dev_from(c, &hd[i]);
     }
     // (pinned-host arena only.)  The two tables are read by EVERY workgroup of the triangulation and row kernels that follow (40..2000 of them), and the arena is host
     // memory: each of those reads would cross PCIe (k_feature_rows spent 9 of its 29 us fetching 5 KB of clone poses per workgroup,
@@ -1110,7 +1110,6 @@ static lvk_status launch_feature_rows(lvk_ekf* e, std::vector<RowJob>& jobs, con
     for (size_t i = 0; i < jobs.size(); ++i) {
         RowJob& j = jobs[i]; Feature* f = j.f;
         const int M = (int)j.sids.size();
-        const int c = (j.type == JOB_MSCKF) ? 7 + 6 * M : 7 + 6 + 6 * M + 1;
         FeatJob& d = j.dev; memset(&d, 0, sizeof d);
         if (obs_stride) off = i * (size_t)obs_stride;
         d.type = j.type; d.n_obs = M; d.obs_off = (int)off; d.want_gate = (j.want_gate ? FJ_GATE : 0) | (j.tri_pending ? FJ_TRI_PENDING : 0);
@@ -1128,14 +1127,14 @@ static lvk_status launch_feature_rows(lvk_ekf* e, std::vector<RowJob>& jobs, con
         }
         if (obs_stride) for (int k = M; k < obs_stride; ++k) { hr[off + k] = 0; hz[2 * (off + k)] = hz[2 * (off + k) + 1] = hv[2 * (off + k)] = hv[2 * (off + k) + 1] = 0.; }
         off += M;
-        stage += (size_t)2 * M * c * 2 + 2 * M; ccols += c;
+        stage += (size_t)fj_stage_doubles(j.type, M); ccols += (size_t)fj_cols(j.type, M);
         max_rows = std::max(max_rows, 2 * M);
-        if (j.want_gate) gate_max = std::max(gate_max, 2 * M - (j.type == JOB_MSCKF ? 3 : j.type == JOB_EKF_NEW ? 1 : 0));
+        if (j.want_gate) gate_max = std::max(gate_max, fj_rows(j.type, M));
         hj[i] = d; j.hdev = &hj[i];
     }
     max_rows = lvk_feature_rows_route(max_rows, gate_max);
     if (stage > e->staging_cap || ccols > e->ccols_cap) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "staging buffer too small (%zu doubles needed)", stage);
-    FilterFlags fl; fl.leg_dim = LEG; fl.if_fej = e->if_fej ? 1 : 0; fl.estimate_td = e->cfg.estimate_td; fl.pad = 0; fl.sigma2 = e->sigma2;
+    const FilterFlags fl = filter_flags(LEG, e->if_fej, e->cfg.estimate_td, e->sigma2);
     const FeatJob* d_j = dev(e, hj); const int* d_r = dev(e, hr); const double* d_z = dev(e, hz); const double* d_v = dev(e, hv);
     const int nj = (int)jobs.size(); const CloneDev* d_cl = e->dv_clones; double* P = e->dP[e->cur];
     FeatResult* d_fh = (FeatResult*)(e->dh_down + e->down_feat);
@@ -1171,7 +1170,7 @@ static lvk_status msckf_points_queue(lvk_ekf* e, const std::vector<RowJob>& jobs
         memcpy(hj[k].p_w, j.dev.p_w, 24);
     }
     e->mp_lo = lo; e->mp_n = n;
-    FilterFlags fl; fl.leg_dim = LEG; fl.if_fej = e->if_fej ? 1 : 0; fl.estimate_td = e->cfg.estimate_td; fl.pad = 0; fl.sigma2 = e->sigma2;
+    const FilterFlags fl = filter_flags(LEG, e->if_fej, e->cfg.estimate_td, e->sigma2);
     const double* P = e->dP[e->cur]; const PointJob* d_jobs = dev(e, hj); const CloneDev* d_cl = e->dv_clones;
     const int* d_r = obs.rank; const double* d_z = obs.z; const double* d_v = obs.zv; const TriResult* d_tri = e->d_tridev;
     double* out = (double*)(e->dh_down + e->down_mp); int* ok = (int*)(e->dh_down + e->down_mpok);
@@ -1210,9 +1209,8 @@ static lvk_status run_feature_rows(lvk_ekf* e, std::vector<RowJob>& jobs)
 }
 // row layout of a job, known before it runs: MSCKF blocks lose the 3 rows of the null-space projection, a new in-state
 // feature's block keeps its range row first, a tracked in-state feature contributes its 2 rows as they are
-static int job_first_row(const RowJob& j) { return j.type == JOB_MSCKF ? 3 : j.type == JOB_EKF_NEW ? 1 : 0; }
-static int job_rows(const RowJob& j) { return 2 * (int)j.sids.size() - job_first_row(j); }
-static int job_cols(const RowJob& j) { const int M = (int)j.sids.size(); return j.type == JOB_MSCKF ? 7 + 6 * M : 7 + 6 + 6 * M + 1; }
+static int job_first_row(const RowJob& j) { return fj_first_row(j.type); }
+static int job_rows(const RowJob& j) { return fj_rows(j.type, (int)j.sids.size()); }
 static bool gate_ok(lvk_ekf* e, const RowJob& j)
 {
     const bool ok = j.res.gamma < lvk_chi2_005(j.dof);
@@ -1249,12 +1247,7 @@ static void push_rows(std::vector<StackRow>& map, const RowJob& j, int first, in
                       std::vector<RowGroup>* groups = nullptr, const lvk_ekf* e = nullptr, int ncols = 0, int owner = 0)
 {
     if (groups && count > 0) { groups->emplace_back(); RowGroup& g = groups->back(); g.start = dst; g.rows = count; g.owner = owner; g.cols = job_dense_cols(e, j, ncols); }
-    const int M = j.dev.n_obs, c = job_cols(j);
-    for (int k = 0; k < count; ++k) {
-        StackRow s; s.g_off = j.dev.stage_off; s.r_off = j.dev.stage_off + (long long)2 * M * c * 2; s.src_row = first + k; s.c = c; s.ccol_off = j.dev.ccol_off; s.dst_row = dst + k;
-        s.job = gate_job; s.pad = 0;
-        map.push_back(s);
-    }
+    for (int k = 0; k < count; ++k) map.push_back(fj_stack_row(j.dev, first + k, dst + k, gate_job));
 }
 static lvk_status stack_rows(lvk_ekf* e, const std::vector<StackRow>& map, double* dH, int ncols, double* dr)
 {
@@ -2351,9 +2344,8 @@ lvk_status lvk_ekf_create(lvk_context* ctx, const lvk_ekf_config* cfg, lvk_ekf**
     e->rows_cap = 1024;                                      // dense update up to this many stacked rows; taller blocks are QR-compressed first
     e->feat_cap = std::max(1024, 4 * c.max_features);        // jobs per batch: the map holds lost and young features besides the tracked ones
     e->obs_cap = 2 * e->feat_cap * (c.sw_size + 2);
-    const int max_c = 7 + 6 + 6 * (c.sw_size + 2) + 1;
-    e->staging_cap = std::min((size_t)2 * e->feat_cap * ((size_t)2 * (c.sw_size + 2) * max_c * 2 + 2 * (c.sw_size + 2)), (size_t)48 << 20);   // doubles; checked per batch
-    e->ccols_cap = (size_t)2 * e->feat_cap * max_c;
+    e->staging_cap = std::min((size_t)2 * e->feat_cap * (size_t)fj_stage_doubles(JOB_EKF_NEW, c.sw_size + 2), (size_t)48 << 20);   // doubles; checked per batch
+    e->ccols_cap = (size_t)2 * e->feat_cap * fj_cols(JOB_EKF_NEW, c.sw_size + 2);
     // stacked rows before compression: every feature of a message can contribute 2M-3 rows (18,000 at 2000 tracks, M = 6).
     // The row kernel's direct output relies on it: d_H / d_r have hrows rows and k_feature_rows does not bound FeatJob::dst_row1,
     // so gated_update refuses a layout of more rows.  (A pruning update cannot get there: one row per job, at most 2 * feat_cap jobs

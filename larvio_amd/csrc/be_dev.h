@@ -26,6 +26,40 @@ struct FilterFlags { int leg_dim, if_fej, estimate_td, pad; double sigma2; };
 // of the triangulation queued ahead of the launch (what FJ_TRI_PENDING is to the row kernel), 0: p_w
 struct PointJob { int n_obs, obs_off, tri_slot1, pad; double p_w[3]; };
 
+// ---- the layout of a feature-row job (type, M observations), defined here once for the host code that lays batches out and the kernels
+// that read them: compact columns (extrinsics + td 7, [the anchor's block 6,] 6 per observing clone [, the feature's own column]), the
+// first output row (an MSCKF block loses the 3 rows of its null-space projection, a new in-state feature keeps its range row first, a
+// tracked one contributes its rows as they are), and the staging slot G [2M x c] | T [2M x c] | r [2M]
+#ifdef __HIPCC__
+#define BE_HD __host__ __device__ inline
+#else
+#define BE_HD inline
+#endif
+#define BE_HDC BE_HD constexpr
+BE_HDC int fj_cols(int type, int M) { return type == JOB_MSCKF ? 7 + 6 * M : 7 + 6 + 6 * M + 1; }
+BE_HDC int fj_first_row(int type) { return type == JOB_MSCKF ? 3 : type == JOB_EKF_NEW ? 1 : 0; }
+BE_HDC int fj_rows(int type, int M) { return 2 * M - fj_first_row(type); }
+BE_HDC long long fj_r_off(int type, int M) { return (long long)4 * M * fj_cols(type, M); }           // of r inside the staging slot (doubles)
+BE_HDC long long fj_stage_doubles(int type, int M) { return fj_r_off(type, M) + 2 * M; }
+// row src_row of job j's compact block -> dense row dst_row; gate_job as StackRow::job
+BE_HD StackRow fj_stack_row(const FeatJob& j, int src_row, int dst_row, int gate_job)
+{
+    StackRow s;
+    s.g_off = j.stage_off; s.r_off = j.stage_off + fj_r_off(j.type, j.n_obs); s.src_row = src_row; s.c = fj_cols(j.type, j.n_obs); s.ccol_off = j.ccol_off;
+    s.dst_row = dst_row; s.job = gate_job; s.pad = 0;
+    return s;
+}
+// host only
+inline FilterFlags filter_flags(int leg_dim, int if_fej, int estimate_td, double sigma2)
+{
+    FilterFlags fl; fl.leg_dim = leg_dim; fl.if_fej = if_fej ? 1 : 0; fl.estimate_td = estimate_td ? 1 : 0; fl.pad = 0; fl.sigma2 = sigma2;
+    return fl;
+}
+template <class C> inline void clone_dev_from(const C& c, CloneDev* d)      // C: lvk_clone, or the filter's own clone record (the same five fields)
+{
+    memcpy(d->q, c.q, 32); memcpy(d->p, c.p, 24); memcpy(d->p_fej, c.p_fej, 24); memcpy(d->R_b2c, c.R_b2c, 72); memcpy(d->t_c_b, c.t_c_b, 24);
+}
+
 #ifdef __HIPCC__
 __device__ __forceinline__ void d_m3_mul(const double* A, const double* B, double* C)
 {

@@ -183,9 +183,9 @@ __global__ void __launch_bounds__(FR_THREADS) k_feature_rows(const FeatJob* __re
     const int M = job.n_obs;
     const int rows = 2 * M;
     const int nf = (job.type == JOB_MSCKF) ? 3 : 1;                  // columns of H_f
-    const int c = (job.type == JOB_MSCKF) ? 7 + 6 * M : 7 + 6 + 6 * M + 1;
+    const int c = (job.type == JOB_MSCKF) ? 7 + 6 * M : 7 + 6 + 6 * M + 1;      // fj_cols(job.type, M), written out: through the helper the compiler emits other code
     double* Gg = staging + job.stage_off;                             // staging slot: G [rows x c] | T [rows x c] | r [rows]
-    double* rrg = Gg + (size_t)2 * rows * c;
+    double* rrg = Gg + (size_t)2 * rows * c;                          // (fj_r_off)
     int* cc = ccols + job.ccol_off;
     // LDS: Hf [rows x 3] | v [rows] | S [k x k] | y [k] | scal[4]  (+ SMALL: G | T | r | P_cc)
     double* Hf = sh;
@@ -507,16 +507,16 @@ lvk_status lvk_launch_feature_rows(lvk_context* ctx, const FeatJob* d_jobs, int 
 {
     if (n_jobs <= 0) return LVK_OK;
     const size_t base = sizeof(double) * ((size_t)max_rows * 4 + (size_t)max_rows * max_rows + max_rows + 8);
-    // max_rows = 2 M_max; compact columns <= 7 + 6 + 6 M_max + 1
-    const bool small = max_rows <= FRS_ROWS && 14 + 3 * max_rows <= FRS_COLS;
+    // max_rows = 2 M_max; the widest block is an in-state feature's
+    const bool small = max_rows <= FRS_ROWS && fj_cols(JOB_EKF_NEW, (max_rows + 1) / 2) <= FRS_COLS;
     const size_t shmem = base + (small ? sizeof(double) * ((size_t)2 * FRS_ROWS * FRS_COLS + FRS_ROWS + (size_t)FRS_COLS * FRS_PLD + (size_t)n_clones * (sizeof(CloneDev) / sizeof(double)) + 8 + FRS_COLS / 2 + 8) : 0);     // + srank (16 ints) + scc (64 ints)
     if (shmem > 150 * 1024) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "feature block with %d rows exceeds the LDS budget", max_rows);
     if (small) {
-        if (shmem > 64 * 1024) LVK_LDS_OPTIN(ctx, 10, k_feature_rows<true>, shmem);
+        if (shmem > 64 * 1024) LVK_LDS_OPTIN(ctx, k_feature_rows<true>, shmem);
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_feature_rows<true>), dim3(n_jobs), dim3(FR_THREADS), shmem, ctx->stream, d_jobs, n_jobs, d_clones, d_rank, d_z, d_zv,
                            d_P, ldp, fl, d_staging, d_ccols, d_out, d_out_host, d_Hout, ldh, ncols_out, d_rout, obs_stride, n_clones, d_tri);
     } else {
-        LVK_LDS_OPTIN(ctx, 1, k_feature_rows<false>, shmem);
+        LVK_LDS_OPTIN(ctx, k_feature_rows<false>, shmem);
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_feature_rows<false>), dim3(n_jobs), dim3(FR_THREADS), shmem, ctx->stream, d_jobs, n_jobs, d_clones, d_rank, d_z, d_zv,
                            d_P, ldp, fl, d_staging, d_ccols, d_out, d_out_host, d_Hout, ldh, ncols_out, d_rout, 0, n_clones, d_tri);
     }
@@ -540,23 +540,22 @@ extern "C" lvk_status lvk_triangulate(lvk_context* ctx, const lvk_cam_pose* h_po
 {
     if (!ctx || !h_poses || !h_obs || n < 2 || n > 64 || !ok_out) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_triangulate: 2..64 views required");
     static_assert(sizeof(lvk_cam_pose) == sizeof(CamPose), "lvk_cam_pose is CamPose");
-    const size_t o_cams = 0, o_rank = o_cams + sizeof(CamPose) * n, o_z = (o_rank + sizeof(int) * n + 63) & ~(size_t)63, o_job = o_z + sizeof(double) * 2 * n,
-                 o_out = (o_job + sizeof(TriJob) + 63) & ~(size_t)63, total = o_out + sizeof(TriResult);
-    char* d = (char*)lvk_ctx_scratch(ctx, 9, total);
-    if (!d) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
-    std::vector<char> h(total, 0);
-    memcpy(h.data() + o_cams, h_poses, sizeof(CamPose) * n);
-    for (int i = 0; i < n; ++i) ((int*)(h.data() + o_rank))[i] = i;
-    memcpy(h.data() + o_z, h_obs, sizeof(double) * 2 * n);
-    TriJob* j = (TriJob*)(h.data() + o_job);
+    TriResult r;
+    Stage sg(ctx);
+    const size_t o_cams = sg.take(Stage::IN, sizeof(CamPose) * n), o_rank = sg.take(Stage::IN, sizeof(int) * n), o_z = sg.take(Stage::IN, sizeof(double) * 2 * n),
+                 o_job = sg.take(Stage::IN, sizeof(TriJob)), o_out = sg.take(Stage::OUT, sizeof(TriResult));
+    LVK_TRY(sg.alloc());
+    memcpy(sg.host<CamPose>(o_cams), h_poses, sizeof(CamPose) * n);
+    for (int i = 0; i < n; ++i) sg.host<int>(o_rank)[i] = i;
+    memcpy(sg.host<double>(o_z), h_obs, sizeof(double) * 2 * n);
+    TriJob* j = sg.host<TriJob>(o_job);
     j->n = n; j->use_position = use_position ? 1 : 0; j->obs_off = 0; j->out_slot1 = 0;
     if (h_position_in) memcpy(j->position_in, h_position_in, 24);
-    LVK_HIP(ctx, hipMemcpyAsync(d, h.data(), o_out, hipMemcpyHostToDevice, ctx->stream));
-    lvk_status st = lvk_launch_triangulate(ctx, (const TriJob*)(d + o_job), 1, (const CamPose*)(d + o_cams), (const int*)(d + o_rank), (const double*)(d + o_z), (TriResult*)(d + o_out), nullptr);
-    if (st != LVK_OK) return st;
-    TriResult r;
-    LVK_HIP(ctx, hipMemcpyAsync(&r, d + o_out, sizeof r, hipMemcpyDeviceToHost, ctx->stream));
-    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    LVK_TRY(sg.upload());
+    LVK_TRY(lvk_launch_triangulate(ctx, sg.at<TriJob>(Stage::IN, o_job), 1, sg.at<CamPose>(Stage::IN, o_cams), sg.at<int>(Stage::IN, o_rank), sg.at<double>(Stage::IN, o_z),
+                                   sg.at<TriResult>(Stage::OUT, o_out), nullptr));
+    LVK_TRY(sg.get(&r, Stage::OUT, o_out, sizeof r));
+    LVK_TRY(sg.wait());
     *ok_out = r.ok;
     if (h_position) memcpy(h_position, r.position, 24);
     if (h_solution) memcpy(h_solution, r.solution, 24);
@@ -565,98 +564,16 @@ extern "C" lvk_status lvk_triangulate(lvk_context* ctx, const lvk_cam_pose* h_po
     return LVK_OK;
 }
 
-extern "C" lvk_status lvk_ekf_gate_and_stack(lvk_context* ctx, const lvk_clone* h_clones, int n_clones, const lvk_msckf_feature* h_feats, int n_feats,
-                                             const int* h_clone_rank, const double* h_obs, const double* h_obs_vel, const double* h_P, int N,
-                                             int if_fej, int estimate_td, double sigma2, double* h_H, double* h_r, int rows_cap, int* rows_out,
-                                             double* h_gamma, int* h_accept)
-{
-    if (!ctx || !h_clones || n_clones <= 0 || !h_feats || n_feats <= 0 || !h_clone_rank || !h_obs || !h_obs_vel || !h_P || !h_H || !h_r || !rows_out ||
-        N < 22 + 6 * n_clones) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_gate_and_stack: bad argument");
-    size_t tot = 0, stage = 0, ccols = 0; int max_rows = 2, cand_rows = 0;
-    for (int f = 0; f < n_feats; ++f) {
-        const int M = h_feats[f].n_obs;
-        if (M < 2 || M > 64 || h_feats[f].obs_off < 0) return lvk_set_error(ctx, LVK_ERR_ARG, "feature %d: 2..64 observations required", f);
-        for (int k = 0; k < M; ++k) { const int cr = h_clone_rank[h_feats[f].obs_off + k]; if (cr < 0 || cr >= n_clones) return lvk_set_error(ctx, LVK_ERR_ARG, "clone rank out of range"); }
-        tot = std::max(tot, (size_t)h_feats[f].obs_off + M);
-        const int c = 7 + 6 * M;
-        stage += (size_t)2 * M * c * 2 + 2 * M; ccols += c; max_rows = std::max(max_rows, 2 * M); cand_rows += 2 * M - 3;
-    }
-    const int ld = (N + 7) & ~7;
-    // one input blob, one staging blob, one output blob
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = (o + bytes + 63) & ~(size_t)63; return at; };
-    const size_t o_cl = take(sizeof(CloneDev) * n_clones), o_job = take(sizeof(FeatJob) * n_feats), o_rk = take(sizeof(int) * tot), o_z = take(16 * tot),
-                 o_zv = take(16 * tot), o_P = take(sizeof(double) * (size_t)N * ld), o_map = take(sizeof(StackRow) * (size_t)std::max(cand_rows, 1)), in_bytes = o;
-    char* d_in = (char*)lvk_ctx_scratch(ctx, 9, in_bytes);
-    char* d_st = (char*)lvk_ctx_scratch(ctx, 10, sizeof(double) * stage + sizeof(int) * ccols + 64);
-    const size_t oH = 0, o_r = (sizeof(double) * (size_t)std::max(cand_rows, 1) * ld + 63) & ~(size_t)63, o_fo = (o_r + sizeof(double) * std::max(cand_rows, 1) + 63) & ~(size_t)63,
-                 out_bytes = o_fo + sizeof(FeatResult) * n_feats;
-    char* d_out = (char*)lvk_ctx_scratch(ctx, 11, out_bytes);
-    if (!d_in || !d_st || !d_out) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
-    std::vector<char> h(in_bytes, 0);
-    CloneDev* hc = (CloneDev*)(h.data() + o_cl);
-    for (int i = 0; i < n_clones; ++i) {
-        memcpy(hc[i].q, h_clones[i].q, 32); memcpy(hc[i].p, h_clones[i].p, 24); memcpy(hc[i].p_fej, h_clones[i].p_fej, 24);
-        memcpy(hc[i].R_b2c, h_clones[i].R_b2c, 72); memcpy(hc[i].t_c_b, h_clones[i].t_c_b, 24);
-    }
-    FeatJob* hj = (FeatJob*)(h.data() + o_job);
-    size_t s_off = 0, c_off = 0;
-    for (int f = 0; f < n_feats; ++f) {
-        const int M = h_feats[f].n_obs, c = 7 + 6 * M;
-        FeatJob& j = hj[f];
-        j.type = JOB_MSCKF; j.n_obs = M; j.obs_off = h_feats[f].obs_off; j.want_gate = 1; j.stage_off = (long long)s_off; j.ccol_off = (int)c_off;
-        memcpy(j.p_w, h_feats[f].p_w, 24); memcpy(j.p_fej, h_feats[f].p_w, 24);
-        j.gate_thr = lvk_chi2_005(2 * M - 3);
-        s_off += (size_t)2 * M * c * 2 + 2 * M; c_off += c;
-    }
-    memcpy(h.data() + o_rk, h_clone_rank, sizeof(int) * tot);
-    memcpy(h.data() + o_z, h_obs, 16 * tot); memcpy(h.data() + o_zv, h_obs_vel, 16 * tot);
-    for (int i = 0; i < N; ++i) memcpy(h.data() + o_P + sizeof(double) * (size_t)i * ld, h_P + (size_t)i * N, sizeof(double) * N);
-    LVK_HIP(ctx, hipMemcpyAsync(d_in, h.data(), o_map, hipMemcpyHostToDevice, ctx->stream));
-    FilterFlags fl; fl.leg_dim = 22; fl.if_fej = if_fej ? 1 : 0; fl.estimate_td = estimate_td ? 1 : 0; fl.pad = 0; fl.sigma2 = sigma2;
-    double* d_staging = (double*)d_st; int* d_ccols = (int*)(d_st + ((sizeof(double) * stage + 63) & ~(size_t)63));
-    FeatResult* d_fout = (FeatResult*)(d_out + o_fo);
-    lvk_status st = lvk_launch_feature_rows(ctx, (const FeatJob*)(d_in + o_job), n_feats, max_rows, (const CloneDev*)(d_in + o_cl), (const int*)(d_in + o_rk),
-                                            (const double*)(d_in + o_z), (const double*)(d_in + o_zv), (const double*)(d_in + o_P), ld, fl, d_staging, d_ccols, d_fout, nullptr, nullptr, 0, 0, nullptr, 0, n_clones, nullptr);
-    if (st != LVK_OK) return st;
-    std::vector<FeatResult> res(n_feats);
-    LVK_HIP(ctx, hipMemcpyAsync(res.data(), d_fout, sizeof(FeatResult) * n_feats, hipMemcpyDeviceToHost, ctx->stream));
-    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    // accepted features' rows, in feature order (larvio.cpp:2185-2201 appends only the rows that pass the gate)
-    std::vector<StackRow> map; int rows = 0;
-    for (int f = 0; f < n_feats; ++f) {
-        if (h_gamma) h_gamma[f] = res[f].gamma;
-        if (h_accept) h_accept[f] = res[f].accept;
-        if (!res[f].accept) continue;
-        const int M = h_feats[f].n_obs, c = res[f].c;
-        for (int k = 0; k < res[f].rows; ++k) {
-            StackRow s; s.g_off = hj[f].stage_off; s.r_off = hj[f].stage_off + (long long)2 * M * c * 2; s.src_row = res[f].first_row + k; s.c = c; s.ccol_off = hj[f].ccol_off;
-            s.dst_row = rows + k; s.job = -1; s.pad = 0;
-            map.push_back(s);
-        }
-        rows += res[f].rows;
-    }
-    *rows_out = rows;
-    if (rows > rows_cap) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "%d stacked rows exceed rows_cap %d", rows, rows_cap);
-    if (rows == 0) return LVK_OK;
-    LVK_HIP(ctx, hipMemcpyAsync(d_in + o_map, map.data(), sizeof(StackRow) * map.size(), hipMemcpyHostToDevice, ctx->stream));
-    st = lvk_launch_stack_rows(ctx, d_fout, (const StackRow*)(d_in + o_map), rows, d_staging, d_ccols, (double*)(d_out + oH), ld, N, (double*)(d_out + o_r));
-    if (st != LVK_OK) return st;
-    LVK_HIP(ctx, hipMemcpy2DAsync(h_H, sizeof(double) * N, d_out + oH, sizeof(double) * ld, sizeof(double) * N, rows, hipMemcpyDeviceToHost, ctx->stream));
-    LVK_HIP(ctx, hipMemcpyAsync(h_r, d_out + o_r, sizeof(double) * rows, hipMemcpyDeviceToHost, ctx->stream));
-    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LVK_OK;
-}
-
-extern "C" lvk_status lvk_ekf_feature_rows(lvk_context* ctx, const lvk_clone* h_clones, int n_clones, const lvk_feature_job* h_jobs, int n_jobs,
-                                           const int* h_clone_rank, const double* h_obs, const double* h_obs_vel, const lvk_cam_pose* h_cams, int n_obs,
-                                           const double* h_P, int N, int ldp, int leg_dim, int if_fej, int estimate_td, double sigma2, int mode,
-                                           lvk_feature_result* h_res, double* h_blocks, int* h_ccols, double* h_H, int ldh, int h_rows, double* h_r,
-                                           int* rows_out)
+// lvk_ekf_feature_rows (include/lvk_c.h); h_blocks and h_ccols may be null here (lvk_ekf_gate_and_stack does not want them)
+static lvk_status feature_rows_stage(lvk_context* ctx, const lvk_clone* h_clones, int n_clones, const lvk_feature_job* h_jobs, int n_jobs,
+                                     const int* h_clone_rank, const double* h_obs, const double* h_obs_vel, const lvk_cam_pose* h_cams, int n_obs,
+                                     const double* h_P, int N, int ldp, int leg_dim, int if_fej, int estimate_td, double sigma2, int mode,
+                                     lvk_feature_result* h_res, double* h_blocks, int* h_ccols, double* h_H, int ldh, int h_rows, double* h_r,
+                                     int* rows_out)
 {
     static_assert(sizeof(lvk_feature_result) == sizeof(FeatResult), "lvk_feature_result is FeatResult");
     if (!ctx || !h_clones || n_clones <= 0 || !h_jobs || n_jobs <= 0 || !h_clone_rank || !h_obs || !h_obs_vel || n_obs <= 0 || !h_P || !h_res ||
-        !h_blocks || !h_ccols || !h_H || !h_r || !rows_out || N < 22 || ldp < N || ldh < N || h_rows < 0)
+        !h_H || !h_r || !rows_out || N < 22 || ldp < N || ldh < N || h_rows < 0)
         return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_feature_rows: bad argument");
     if (leg_dim != 22 && leg_dim != 46) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_feature_rows: leg_dim %d (22 or 46)", leg_dim);
     if (N < leg_dim + 6 * n_clones) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_feature_rows: N %d < leg_dim + 6 n_clones", N);
@@ -686,12 +603,10 @@ extern "C" lvk_status lvk_ekf_feature_rows(lvk_context* ctx, const lvk_clone* h_
             if (f.fcol < col0 || (f.gate && f.fcol >= N)) return lvk_set_error(ctx, LVK_ERR_ARG, "job %d: feature column %d outside the feature states", j, f.fcol);
             if (!(f.inv_depth != 0.)) return lvk_set_error(ctx, LVK_ERR_ARG, "job %d: zero inverse depth", j);
         }
-        const int c = (f.type == LVK_FJ_MSCKF) ? 7 + 6 * M : 7 + 6 + 6 * M + 1;
-        const int first = f.type == LVK_FJ_MSCKF ? 3 : f.type == LVK_FJ_EKF_NEW ? 1 : 0;
         m_max = std::max(m_max, M); max_rows = std::max(max_rows, 2 * M);
-        if (f.gate) gate_max = std::max(gate_max, 2 * M - first);
-        if (f.type != LVK_FJ_EKF_NEW) cand_rows += 2 * M - first;
-        stage += (size_t)4 * M * c + 2 * M; ccols += c; n_tri += f.tri_pending;
+        if (f.gate) gate_max = std::max(gate_max, fj_rows(f.type, M));
+        if (f.type != LVK_FJ_EKF_NEW) cand_rows += fj_rows(f.type, M);
+        stage += (size_t)fj_stage_doubles(f.type, M); ccols += (size_t)fj_cols(f.type, M); n_tri += f.tri_pending;
     }
     max_rows = lvk_feature_rows_route(max_rows, gate_max);
     if (mode & LVK_FR_GENERAL) max_rows = std::max(max_rows, FRS_ROWS + 2);
@@ -699,35 +614,26 @@ extern "C" lvk_status lvk_ekf_feature_rows(lvk_context* ctx, const lvk_clone* h_
     if (cand_rows > h_rows) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "%d candidate dense rows exceed h_rows %d", cand_rows, h_rows);
     const int stride = (mode & LVK_FR_STRIDE) ? m_max : 0;
     const int tot = stride ? stride * n_jobs : n_obs;
+    std::vector<StackRow> map; std::vector<double> hs;              // (declared ahead of the stage: it waits for the copies that name them)
     // one input blob (clones, jobs, observations, P, triangulation jobs + poses, the stacking map), staging, one output blob
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = (o + bytes + 63) & ~(size_t)63; return at; };
-    const size_t o_cl = take(sizeof(CloneDev) * n_clones), o_job = take(sizeof(FeatJob) * n_jobs), o_rk = take(sizeof(int) * tot), o_z = take(16 * (size_t)tot),
-                 o_zv = take(16 * (size_t)tot), o_P = take(sizeof(double) * (size_t)N * ldp), o_tj = take(sizeof(TriJob) * std::max(n_tri, 1)),
-                 o_cam = take(sizeof(CamPose) * tot), o_crk = take(sizeof(int) * tot), o_map = take(sizeof(StackRow) * (size_t)std::max(cand_rows, 1)), in_bytes = o;
-    o = 0;
-    const size_t o_H = take(sizeof(double) * (size_t)std::max(h_rows, 1) * ldh), o_r = take(sizeof(double) * std::max(h_rows, 1)), o_fo = take(sizeof(FeatResult) * n_jobs),
-                 o_tri = take(sizeof(TriResult) * n_jobs), o_tridev = take(sizeof(TriResult) * n_jobs), out_bytes = o;
-    const size_t o_cc = (sizeof(double) * stage + 63) & ~(size_t)63;
-    char* d_in = (char*)lvk_ctx_scratch(ctx, 9, in_bytes);
-    char* d_st = (char*)lvk_ctx_scratch(ctx, 10, o_cc + sizeof(int) * ccols);
-    char* d_out = (char*)lvk_ctx_scratch(ctx, 11, out_bytes);
-    if (!d_in || !d_st || !d_out) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
-    std::vector<char> h(in_bytes, 0);
-    CloneDev* hc = (CloneDev*)(h.data() + o_cl);
-    for (int i = 0; i < n_clones; ++i) {
-        memcpy(hc[i].q, h_clones[i].q, 32); memcpy(hc[i].p, h_clones[i].p, 24); memcpy(hc[i].p_fej, h_clones[i].p_fej, 24);
-        memcpy(hc[i].R_b2c, h_clones[i].R_b2c, 72); memcpy(hc[i].t_c_b, h_clones[i].t_c_b, 24);
-    }
-    FeatJob* hj = (FeatJob*)(h.data() + o_job);
-    int* hr = (int*)(h.data() + o_rk); double* hz = (double*)(h.data() + o_z); double* hv = (double*)(h.data() + o_zv);
-    TriJob* htj = (TriJob*)(h.data() + o_tj); CamPose* hcam = (CamPose*)(h.data() + o_cam);
-    std::vector<StackRow> map;
+    Stage sg(ctx);
+    const size_t o_cl = sg.take(Stage::IN, sizeof(CloneDev) * n_clones), o_job = sg.take(Stage::IN, sizeof(FeatJob) * n_jobs), o_rk = sg.take(Stage::IN, sizeof(int) * tot),
+                 o_z = sg.take(Stage::IN, 16 * (size_t)tot), o_zv = sg.take(Stage::IN, 16 * (size_t)tot), o_P = sg.take(Stage::IN, sizeof(double) * (size_t)N * ldp),
+                 o_tj = sg.take(Stage::IN, sizeof(TriJob) * n_tri), o_cam = sg.take(Stage::IN, sizeof(CamPose) * tot), o_crk = sg.take(Stage::IN, sizeof(int) * tot),
+                 o_map = sg.take(Stage::IN, sizeof(StackRow) * (size_t)cand_rows);
+    const size_t o_st = sg.take(Stage::MID, sizeof(double) * stage), o_cc = sg.take(Stage::MID, sizeof(int) * ccols);
+    const size_t nH = sizeof(double) * (size_t)h_rows * ldh, nr = sizeof(double) * h_rows;
+    const size_t o_H = sg.take(Stage::OUT, nH), o_r = sg.take(Stage::OUT, nr), o_fo = sg.take(Stage::OUT, sizeof(FeatResult) * n_jobs),
+                 o_tri = sg.take(Stage::OUT, sizeof(TriResult) * n_jobs), o_tridev = sg.take(Stage::OUT, sizeof(TriResult) * n_jobs);
+    LVK_TRY(sg.alloc());
+    for (int i = 0; i < n_clones; ++i) clone_dev_from(h_clones[i], sg.host<CloneDev>(o_cl) + i);
+    FeatJob* hj = sg.host<FeatJob>(o_job);
+    int* hr = sg.host<int>(o_rk); double* hz = sg.host<double>(o_z); double* hv = sg.host<double>(o_zv);
+    TriJob* htj = sg.host<TriJob>(o_tj); CamPose* hcam = sg.host<CamPose>(o_cam);
     size_t s_off = 0, c_off = 0; int d0 = 0, it = 0;
     for (int j = 0; j < n_jobs; ++j) {
         const lvk_feature_job& f = h_jobs[j];
-        const int M = f.n_obs, c = (f.type == LVK_FJ_MSCKF) ? 7 + 6 * M : 7 + 6 + 6 * M + 1;
-        const int first = f.type == LVK_FJ_MSCKF ? 3 : f.type == LVK_FJ_EKF_NEW ? 1 : 0;
+        const int M = f.n_obs;
         FeatJob& d = hj[j];
         d.type = f.type; d.n_obs = M; d.obs_off = stride ? j * stride : f.obs_off; d.anchor_rank = f.type == LVK_FJ_MSCKF ? 0 : f.anchor_rank;
         d.fcol = f.type == LVK_FJ_MSCKF ? 0 : f.fcol;
@@ -748,85 +654,111 @@ extern "C" lvk_status lvk_ekf_feature_rows(lvk_context* ctx, const lvk_clone* h_
             memcpy(t.position_in, f.p_w, 24);
         }
         if (f.type != LVK_FJ_EKF_NEW && slots) {
-            const int nout = 2 * M - first;
+            const int nout = fj_rows(f.type, M);
             if (mode & LVK_FR_DIRECT) d.dst_row1 = d0 + 1;
-            else
-                for (int k = 0; k < nout; ++k) {
-                    StackRow s; s.g_off = d.stage_off; s.r_off = d.stage_off + (long long)4 * M * c; s.src_row = first + k; s.c = c; s.ccol_off = d.ccol_off;
-                    s.dst_row = d0 + k; s.job = j; s.pad = 0;
-                    map.push_back(s);
-                }
+            else for (int k = 0; k < nout; ++k) map.push_back(fj_stack_row(d, fj_first_row(f.type) + k, d0 + k, j));
             d0 += nout;
         }
-        s_off += (size_t)4 * M * c + 2 * M; c_off += c;
+        s_off += (size_t)fj_stage_doubles(f.type, M); c_off += (size_t)fj_cols(f.type, M);
     }
     if (!stride) {
         memcpy(hr, h_clone_rank, sizeof(int) * n_obs);
         memcpy(hz, h_obs, 16 * (size_t)n_obs); memcpy(hv, h_obs_vel, 16 * (size_t)n_obs);
     }
-    memcpy(h.data() + o_P, h_P, sizeof(double) * (size_t)N * ldp);
+    memcpy(sg.host<double>(o_P), h_P, sizeof(double) * (size_t)N * ldp);
     if (n_tri) {
         if (!stride) memcpy(hcam, h_cams, sizeof(CamPose) * n_obs);
-        for (int i = 0; i < tot; ++i) ((int*)(h.data() + o_crk))[i] = i;
+        for (int i = 0; i < tot; ++i) sg.host<int>(o_crk)[i] = i;
     }
-    if (!map.empty()) memcpy(h.data() + o_map, map.data(), sizeof(StackRow) * map.size());
-    LVK_HIP(ctx, hipMemcpyAsync(d_in, h.data(), in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (h_rows > 0) {
-        LVK_HIP(ctx, hipMemcpyAsync(d_out + o_H, h_H, sizeof(double) * (size_t)h_rows * ldh, hipMemcpyHostToDevice, ctx->stream));
-        LVK_HIP(ctx, hipMemcpyAsync(d_out + o_r, h_r, sizeof(double) * h_rows, hipMemcpyHostToDevice, ctx->stream));
-    }
-    LVK_HIP(ctx, hipMemsetAsync(d_out + o_fo, 0, out_bytes - o_fo, ctx->stream));      // results and both triangulation result arrays
-    FilterFlags fl; fl.leg_dim = leg_dim; fl.if_fej = if_fej ? 1 : 0; fl.estimate_td = estimate_td ? 1 : 0; fl.pad = 0; fl.sigma2 = sigma2;
-    double* d_staging = (double*)d_st; int* d_ccols = (int*)(d_st + o_cc);
-    FeatResult* d_fout = (FeatResult*)(d_out + o_fo);
-    TriResult* d_tridev = (TriResult*)(d_out + o_tridev);
-    lvk_status st = LVK_OK;
-    if (n_tri) st = lvk_launch_triangulate(ctx, (const TriJob*)(d_in + o_tj), n_tri, (const CamPose*)(d_in + o_cam), (const int*)(d_in + o_crk), (const double*)(d_in + o_z),
-                                           (TriResult*)(d_out + o_tri), d_tridev);
-    if (st == LVK_OK)
-        st = lvk_launch_feature_rows(ctx, (const FeatJob*)(d_in + o_job), n_jobs, max_rows, (const CloneDev*)(d_in + o_cl), (const int*)(d_in + o_rk), (const double*)(d_in + o_z),
-                                     (const double*)(d_in + o_zv), (const double*)(d_in + o_P), ldp, fl, d_staging, d_ccols, d_fout, nullptr,
-                                     (mode & LVK_FR_DIRECT) ? (double*)(d_out + o_H) : nullptr, ldh, N, (mode & LVK_FR_DIRECT) ? (double*)(d_out + o_r) : nullptr,
-                                     stride, n_clones, n_tri ? d_tridev : nullptr);
-    if (st == LVK_OK && !map.empty())
-        st = lvk_launch_stack_rows(ctx, d_fout, (const StackRow*)(d_in + o_map), (int)map.size(), d_staging, d_ccols, (double*)(d_out + o_H), ldh, N, (double*)(d_out + o_r));
-    if (st != LVK_OK) return st;
-    LVK_HIP(ctx, hipMemcpyAsync(h_res, d_fout, sizeof(FeatResult) * n_jobs, hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<double> hs(stage);
-    LVK_HIP(ctx, hipMemcpyAsync(hs.data(), d_staging, sizeof(double) * stage, hipMemcpyDeviceToHost, ctx->stream));
-    LVK_HIP(ctx, hipMemcpyAsync(h_ccols, d_ccols, sizeof(int) * ccols, hipMemcpyDeviceToHost, ctx->stream));
+    if (!map.empty()) memcpy(sg.host<StackRow>(o_map), map.data(), sizeof(StackRow) * map.size());
+    LVK_TRY(sg.upload());
+    LVK_TRY(sg.put(Stage::OUT, o_H, h_H, nH));
+    LVK_TRY(sg.put(Stage::OUT, o_r, h_r, nr));
+    LVK_HIP(ctx, hipMemsetAsync(sg.at<char>(Stage::OUT, o_fo), 0, sg.bytes[Stage::OUT] - o_fo, ctx->stream));      // results and both triangulation result arrays
+    const FilterFlags fl = filter_flags(leg_dim, if_fej, estimate_td, sigma2);
+    double* d_staging = sg.at<double>(Stage::MID, o_st); int* d_ccols = sg.at<int>(Stage::MID, o_cc);
+    double* d_H = sg.at<double>(Stage::OUT, o_H); double* d_r = sg.at<double>(Stage::OUT, o_r);
+    FeatResult* d_fout = sg.at<FeatResult>(Stage::OUT, o_fo);
+    TriResult* d_tridev = sg.at<TriResult>(Stage::OUT, o_tridev);
+    const double* d_z = sg.at<double>(Stage::IN, o_z); const StackRow* d_map = sg.at<StackRow>(Stage::IN, o_map);
+    if (n_tri) LVK_TRY(lvk_launch_triangulate(ctx, sg.at<TriJob>(Stage::IN, o_tj), n_tri, sg.at<CamPose>(Stage::IN, o_cam), sg.at<int>(Stage::IN, o_crk), d_z,
+                                              sg.at<TriResult>(Stage::OUT, o_tri), d_tridev));
+    LVK_TRY(lvk_launch_feature_rows(ctx, sg.at<FeatJob>(Stage::IN, o_job), n_jobs, max_rows, sg.at<CloneDev>(Stage::IN, o_cl), sg.at<int>(Stage::IN, o_rk), d_z,
+                                    sg.at<double>(Stage::IN, o_zv), sg.at<double>(Stage::IN, o_P), ldp, fl, d_staging, d_ccols, d_fout, nullptr,
+                                    (mode & LVK_FR_DIRECT) ? d_H : nullptr, ldh, N, (mode & LVK_FR_DIRECT) ? d_r : nullptr, stride, n_clones, n_tri ? d_tridev : nullptr));
+    LVK_TRY(lvk_launch_stack_rows(ctx, d_fout, d_map, (int)map.size(), d_staging, d_ccols, d_H, ldh, N, d_r));
+    LVK_TRY(sg.get(h_res, Stage::OUT, o_fo, sizeof(FeatResult) * n_jobs));
+    if (h_blocks) { hs.resize(stage); LVK_TRY(sg.get(hs.data(), Stage::MID, o_st, sizeof(double) * stage)); }
+    if (h_ccols) LVK_TRY(sg.get(h_ccols, Stage::MID, o_cc, sizeof(int) * ccols));
     LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    // [G | r] of every job, from its staging slot G [rows x c] | T [rows x c] | r [rows]
+    // [G | r] of every job, from its staging slot
     size_t b_off = 0;
-    for (int j = 0; j < n_jobs; ++j) {
-        const int rows = 2 * h_jobs[j].n_obs, c = h_res[j].c;
-        const double* G = hs.data() + hj[j].stage_off; const double* r = G + (size_t)2 * rows * c;
+    for (int j = 0; h_blocks && j < n_jobs; ++j) {
+        const int rows = 2 * hj[j].n_obs, c = h_res[j].c;
+        const double* G = hs.data() + hj[j].stage_off; const double* r = G + fj_r_off(hj[j].type, hj[j].n_obs);
         for (int a = 0; a < rows; ++a) { memcpy(h_blocks + b_off + (size_t)a * (c + 1), G + (size_t)a * c, sizeof(double) * c); h_blocks[b_off + (size_t)a * (c + 1) + c] = r[a]; }
         b_off += (size_t)rows * (c + 1);
     }
     if (!slots) {
         // the host reads the gate back and stacks the accepted jobs' rows only (larvio.cpp:2185-2201)
         for (int j = 0; j < n_jobs; ++j) {
-            if (h_jobs[j].type == LVK_FJ_EKF_NEW || !h_res[j].accept) continue;
-            const int M = h_jobs[j].n_obs, c = h_res[j].c, first = h_jobs[j].type == LVK_FJ_MSCKF ? 3 : 0;
-            for (int k = 0; k < 2 * M - first; ++k) {
-                StackRow s; s.g_off = hj[j].stage_off; s.r_off = hj[j].stage_off + (long long)4 * M * c; s.src_row = first + k; s.c = c; s.ccol_off = hj[j].ccol_off;
-                s.dst_row = d0 + k; s.job = -1; s.pad = 0;
-                map.push_back(s);
-            }
-            d0 += 2 * M - first;
+            if (hj[j].type == JOB_EKF_NEW || !h_res[j].accept) continue;
+            const int nout = fj_rows(hj[j].type, hj[j].n_obs);
+            for (int k = 0; k < nout; ++k) map.push_back(fj_stack_row(hj[j], fj_first_row(hj[j].type) + k, d0 + k, -1));
+            d0 += nout;
         }
-        *rows_out = d0;                                                 // <= cand_rows <= h_rows, checked before the launches
-        if (d0 > 0) {
-            LVK_HIP(ctx, hipMemcpyAsync(d_in + o_map, map.data(), sizeof(StackRow) * map.size(), hipMemcpyHostToDevice, ctx->stream));
-            st = lvk_launch_stack_rows(ctx, d_fout, (const StackRow*)(d_in + o_map), (int)map.size(), d_staging, d_ccols, (double*)(d_out + o_H), ldh, N, (double*)(d_out + o_r));
-            if (st != LVK_OK) return st;
-        }
-    } else *rows_out = d0;
-    if (h_rows > 0) {
-        LVK_HIP(ctx, hipMemcpyAsync(h_H, d_out + o_H, sizeof(double) * (size_t)h_rows * ldh, hipMemcpyDeviceToHost, ctx->stream));
-        LVK_HIP(ctx, hipMemcpyAsync(h_r, d_out + o_r, sizeof(double) * h_rows, hipMemcpyDeviceToHost, ctx->stream));
+        LVK_TRY(sg.put(Stage::IN, o_map, map.data(), sizeof(StackRow) * map.size()));      // d0 <= cand_rows <= h_rows, checked before the launches
+        LVK_TRY(lvk_launch_stack_rows(ctx, d_fout, d_map, (int)map.size(), d_staging, d_ccols, d_H, ldh, N, d_r));
     }
-    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *rows_out = d0;
+    LVK_TRY(sg.get(h_H, Stage::OUT, o_H, nH));
+    LVK_TRY(sg.get(h_r, Stage::OUT, o_r, nr));
+    return sg.wait();
+}
+
+extern "C" lvk_status lvk_ekf_feature_rows(lvk_context* ctx, const lvk_clone* h_clones, int n_clones, const lvk_feature_job* h_jobs, int n_jobs,
+                                           const int* h_clone_rank, const double* h_obs, const double* h_obs_vel, const lvk_cam_pose* h_cams, int n_obs,
+                                           const double* h_P, int N, int ldp, int leg_dim, int if_fej, int estimate_td, double sigma2, int mode,
+                                           lvk_feature_result* h_res, double* h_blocks, int* h_ccols, double* h_H, int ldh, int h_rows, double* h_r,
+                                           int* rows_out)
+{
+    if (!h_blocks || !h_ccols) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_feature_rows: bad argument");
+    return feature_rows_stage(ctx, h_clones, n_clones, h_jobs, n_jobs, h_clone_rank, h_obs, h_obs_vel, h_cams, n_obs, h_P, N, ldp, leg_dim, if_fej, estimate_td, sigma2, mode,
+                              h_res, h_blocks, h_ccols, h_H, ldh, h_rows, h_r, rows_out);
+}
+
+// The MSCKF-only, leg_dim 22, host-stacking case of the entry above: the gate is read back and the accepted features' rows are stacked
+// in feature order (larvio.cpp:2185-2201 appends only the rows that pass the gate), here into a packed N-wide H of rows_cap rows
+extern "C" lvk_status lvk_ekf_gate_and_stack(lvk_context* ctx, const lvk_clone* h_clones, int n_clones, const lvk_msckf_feature* h_feats, int n_feats,
+                                             const int* h_clone_rank, const double* h_obs, const double* h_obs_vel, const double* h_P, int N,
+                                             int if_fej, int estimate_td, double sigma2, double* h_H, double* h_r, int rows_cap, int* rows_out,
+                                             double* h_gamma, int* h_accept)
+{
+    if (!ctx || !h_clones || n_clones <= 0 || !h_feats || n_feats <= 0 || !h_clone_rank || !h_obs || !h_obs_vel || !h_P || !h_H || !h_r || !rows_out ||
+        N < 22 + 6 * n_clones) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_gate_and_stack: bad argument");
+    std::vector<lvk_feature_job> jobs((size_t)n_feats);
+    int tot = 0, cand_rows = 0;
+    for (int f = 0; f < n_feats; ++f) {
+        const int M = h_feats[f].n_obs;
+        if (M < 2 || M > 64 || h_feats[f].obs_off < 0) return lvk_set_error(ctx, LVK_ERR_ARG, "feature %d: 2..64 observations required", f);
+        for (int k = 0; k < M; ++k) { const int cr = h_clone_rank[h_feats[f].obs_off + k]; if (cr < 0 || cr >= n_clones) return lvk_set_error(ctx, LVK_ERR_ARG, "clone rank out of range"); }
+        tot = std::max(tot, h_feats[f].obs_off + M);
+        lvk_feature_job& j = jobs[(size_t)f];
+        j.type = LVK_FJ_MSCKF; j.n_obs = M; j.obs_off = h_feats[f].obs_off; j.gate = fj_rows(JOB_MSCKF, M);      // the gate's degrees of freedom
+        memcpy(j.p_w, h_feats[f].p_w, 24); memcpy(j.p_fej, h_feats[f].p_w, 24);
+        cand_rows += fj_rows(JOB_MSCKF, M);
+    }
+    // every candidate row has a place in H and r here; the caller's hold rows_cap, of which only the accepted rows are written
+    std::vector<lvk_feature_result> res((size_t)n_feats); std::vector<double> H((size_t)cand_rows * N, 0.), r((size_t)cand_rows, 0.);
+    int rows = 0;
+    LVK_TRY(feature_rows_stage(ctx, h_clones, n_clones, jobs.data(), n_feats, h_clone_rank, h_obs, h_obs_vel, nullptr, tot, h_P, N, N, 22, if_fej, estimate_td, sigma2, 0,
+                               res.data(), nullptr, nullptr, H.data(), N, cand_rows, r.data(), &rows));
+    for (int f = 0; f < n_feats; ++f) {
+        if (h_gamma) h_gamma[f] = res[(size_t)f].gamma;
+        if (h_accept) h_accept[f] = res[(size_t)f].accept;
+    }
+    *rows_out = rows;
+    if (rows > rows_cap) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "%d stacked rows exceed rows_cap %d", rows, rows_cap);
+    memcpy(h_H, H.data(), sizeof(double) * (size_t)rows * N); memcpy(h_r, r.data(), sizeof(double) * (size_t)rows);
     return LVK_OK;
 }

@@ -4,6 +4,7 @@
 #pragma once
 #include "lvk_internal.h"
 #include "be_dev.h"
+#include <vector>
 
 // Workspace of one measurement update, passed by value.  B: m x (n+1), S: m x m.  info: the factorisation's report words, in DEVICE
 // memory (the final GEMM reads them: GemmRider::gate); info_host: their mirror in device-mapped host memory, written only when one
@@ -13,6 +14,44 @@ struct UpdateWs { double* B; int ldb; double* S; int lds; int* info; hipEvent_t 
 // sharded update: rank g's jobs [job_lo, job_lo + job_n) and its k compressed rows, stacked from row_off (host writes, k_shard_unpack reads)
 // LVK_SHARD_HDR, the bytes of the header every rank's block starts with, is part of the wire layout: include/lvk_c.h
 struct ShardMeta { int job_lo, job_n, k, row_off; };
+
+// Staging of a stage-level entry (host buffers in, launchers, host buffers out): up to three device blobs in the context's shared
+// stage slots - IN (what the host composes and uploads in one copy, through the mirror this owns), MID (device-only work space), OUT
+// (results; may be pre-filled from the caller's memory) - each laid out as regions aligned to 256 bytes.  Usage: take() every region,
+// alloc(), fill host(), upload(), launch on at(), get() the results, wait().  The destructor waits for the stream too, so that no exit,
+// failing or not, leaves an asynchronous copy behind that names the mirror or a caller's buffer.
+struct Stage {
+    enum { IN, MID, OUT };
+    lvk_context* ctx; size_t bytes[3] = {0, 0, 0}; char* dev[3] = {nullptr, nullptr, nullptr}; std::vector<char> mirror; bool waited = false;
+    explicit Stage(lvk_context* c) : ctx(c) {}
+    Stage(const Stage&) = delete;
+    ~Stage() { if (!waited) (void)hipStreamSynchronize(ctx->stream); }
+    size_t take(int blob, size_t n) { const size_t at = bytes[blob]; bytes[blob] = (at + (n ? n : 1) + 255) & ~(size_t)255; return at; }      // offset of a new region (never empty: its pointer stays valid)
+    lvk_status alloc()
+    {
+        const int slot[3] = {LVK_SCR_STAGE_IN, LVK_SCR_STAGE_MID, LVK_SCR_STAGE_OUT};
+        for (int b = 0; b < 3; ++b)
+            if (bytes[b] && !(dev[b] = (char*)lvk_ctx_scratch(ctx, slot[b], bytes[b]))) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
+        mirror.assign(bytes[IN], 0);
+        return LVK_OK;
+    }
+    template <class T> T* host(size_t off) { return (T*)(mirror.data() + off); }                    // a region of IN, in the mirror
+    template <class T> T* at(int blob, size_t off) const { return (T*)(dev[blob] + off); }          // a region, on the device
+    lvk_status upload() { return put(IN, 0, mirror.data(), bytes[IN]); }
+    lvk_status put(int blob, size_t off, const void* h, size_t n)                                   // host memory that outlives the call -> region
+    {
+        if (n) LVK_HIP(ctx, hipMemcpyAsync(dev[blob] + off, h, n, hipMemcpyHostToDevice, ctx->stream));
+        return LVK_OK;
+    }
+    lvk_status get(void* h, int blob, size_t off, size_t n)                                         // region -> host memory, queued
+    {
+        if (n) LVK_HIP(ctx, hipMemcpyAsync(h, dev[blob] + off, n, hipMemcpyDeviceToHost, ctx->stream));
+        return LVK_OK;
+    }
+    lvk_status wait() { waited = true; LVK_HIP(ctx, hipStreamSynchronize(ctx->stream)); return LVK_OK; }
+};
+// `call` returns lvk_status: pass a failure on
+#define LVK_TRY(call) do { const lvk_status st_ = (call); if (st_ != LVK_OK) return st_; } while (0)
 
 // be_linalg.hip
 lvk_status lvk_stage_copy2(lvk_context* ctx, void* d_dst0, const void* d_src0, size_t bytes0, void* d_dst1, const void* d_src1, size_t bytes1);

@@ -114,7 +114,7 @@ lvk_status lvk_launch_landmark_cov(lvk_context* ctx, const double* d_P, int ldp,
     return LVK_OK;
 }
 
-// (C ABI) jobs go to scratch slot 13, the results come back through slot 14; one wait per call
+// (C ABI) jobs go up in the stage's input blob, the results come back through its output blob; one wait per call
 extern "C" lvk_status lvk_ekf_landmark_cov(lvk_context* ctx, const double* d_P, int ldp, int n, const lvk_landmark_job* h_jobs, int n_jobs, double* h_cov9)
 {
     if (!ctx || !d_P || !h_jobs || !h_cov9 || n_jobs < 0 || ldp < n)
@@ -125,13 +125,11 @@ extern "C" lvk_status lvk_ekf_landmark_cov(lvk_context* ctx, const double* d_P, 
                                  k, h_jobs[k].anchor_col, h_jobs[k].anchor_col + 5, h_jobs[k].feat_col, h_jobs[k].inv_depth, n, n);
     if (n_jobs == 0) return LVK_OK;
     const size_t jbytes = sizeof(lvk_landmark_job) * (size_t)n_jobs, obytes = sizeof(double) * 9 * (size_t)n_jobs;
-    lvk_landmark_job* d_jobs = (lvk_landmark_job*)lvk_ctx_scratch(ctx, 13, jbytes);
-    double* d_out = (double*)lvk_ctx_scratch(ctx, 14, obytes);
-    if (!d_jobs || !d_out) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_ekf_landmark_cov: scratch allocation failed");
-    LVK_HIP(ctx, hipMemcpyAsync(d_jobs, h_jobs, jbytes, hipMemcpyHostToDevice, ctx->stream));
-    lvk_status st = lvk_launch_landmark_cov(ctx, d_P, ldp, d_jobs, n_jobs, d_out);
-    if (st != LVK_OK) return st;
-    LVK_HIP(ctx, hipMemcpyAsync(h_cov9, d_out, obytes, hipMemcpyDeviceToHost, ctx->stream));
-    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LVK_OK;
+    Stage sg(ctx);
+    const size_t o_jobs = sg.take(Stage::IN, jbytes), o_out = sg.take(Stage::OUT, obytes);
+    LVK_TRY(sg.alloc());
+    LVK_TRY(sg.put(Stage::IN, o_jobs, h_jobs, jbytes));
+    LVK_TRY(lvk_launch_landmark_cov(ctx, d_P, ldp, sg.at<lvk_landmark_job>(Stage::IN, o_jobs), n_jobs, sg.at<double>(Stage::OUT, o_out)));
+    LVK_TRY(sg.get(h_cov9, Stage::OUT, o_out, obytes));
+    return sg.wait();
 }

@@ -185,7 +185,7 @@ lvk_status lvk_ldlt_factor_solve(lvk_context* ctx, double* S, int ld, int m, con
 {
     const size_t shm = lvk_ldlt_lds_bytes(m);
     if (shm > 158 * 1024) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "pivoted LDLT: %d rows do not fit the factor kernel's LDS", m);
-    if (shm > 60 * 1024) LVK_LDS_OPTIN(ctx, 14, k_ldlt_factor, shm);
+    if (shm > 60 * 1024) LVK_LDS_OPTIN(ctx, k_ldlt_factor, shm);
     hipLaunchKernelGGL(k_ldlt_factor, dim3(1), dim3(256), shm, ctx->stream, S, ld, m, Dg, perm, cnt);
     hipLaunchKernelGGL(k_ldlt_solve, dim3((nbcols + 63) / 64), dim3(64), 0, ctx->stream, (const double*)S, ld, m, (const double*)Dg, (const int*)perm, B, ldb, nbcols, Bp, X);
     LVK_LAUNCH_CHECK(ctx);

@@ -786,8 +786,8 @@ static lvk_status launch_chol_solve(lvk_context* ctx, double* S, int lds_, int m
     hipStream_t s = ctx->stream;
     const int MB = CF_MAXB * CP_NB;
     const size_t ybytes = sizeof(double) * CF_MAXB * CP_NB * CP_NB;
-    const bool fresh = ctx->scratch_bytes[12] < ybytes + 64;
-    char* ws = (char*)lvk_ctx_scratch(ctx, 12, ybytes + 64);
+    const bool fresh = ctx->scratch_bytes[LVK_SCR_CHOL_WS] < ybytes + 64;
+    char* ws = (char*)lvk_ctx_scratch(ctx, LVK_SCR_CHOL_WS, ybytes + 64);
     if (!ws) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
     int* flag = (int*)(ws + ybytes);
     if (fresh || ctx->chol_epoch > (1 << 27)) { LVK_HIP(ctx, hipMemsetAsync(flag, 0, 64, s)); ctx->chol_epoch = 0; }
@@ -799,7 +799,7 @@ static lvk_status launch_chol_solve(lvk_context* ctx, double* S, int lds_, int m
     // never waits for anybody, so solvers that were dispatched ahead of it only spin until it gets a CU - no ordering assumption
     // is needed for progress, only for speed.
     static const int chv = [] { const char* e = getenv("LVK_CHOL_VARIANT"); return (e && atoi(e) == 2) ? 2 : 1; }();
-    if (chv == 2) LVK_LDS_OPTIN(ctx, 8, k_chol_fused<2>, shm); else LVK_LDS_OPTIN(ctx, 13, k_chol_fused<1>, shm);
+    if (chv == 2) LVK_LDS_OPTIN(ctx, k_chol_fused<2>, shm); else LVK_LDS_OPTIN(ctx, k_chol_fused<1>, shm);
     for (int off = 0; off < m; off += MB) {
         const int mb = (m - off) < MB ? (m - off) : MB, rest = m - off - mb;
         double* S11 = S + (size_t)off * lds_ + off; double* B1 = B + (size_t)off * ldb;
@@ -840,13 +840,13 @@ lvk_status lvk_update_core(lvk_context* ctx, double* P, int ldp, int n, const do
 // The same update through the pivoted LDL^T (be_ldlt.hip), for an S that need not be positive definite - what the reference computes:
 //     K^T = X = S.ldlt().solve(H P) ;  dx = K r ;  P <- (I - K H) P = P - X^T (H P) ;  P <- (P + P^T) / 2      (larvio.cpp:1456-1460, 1578-1594)
 // ws.B / ws.S as for lvk_update_core; the pivot-order copies of [HP | r] and of X, D, the permutation and the two counters
-// (negative / zero D entries) live in context scratch slot 15.  *d_cnt_out = where the counters are (device).
+// (negative / zero D entries) live in the context scratch slot LVK_SCR_LDLT_WS.  *d_cnt_out = where the counters are (device).
 lvk_status lvk_update_ldlt_core(lvk_context* ctx, double* P, int ldp, int n, const double* H, int ldh, int m, const double* r, double sigma2,
                                 double* dx, UpdateWs ws, int** d_cnt_out, int** d_perm_out)
 {
     hipStream_t s = ctx->stream;
     const size_t mat = sizeof(double) * (size_t)(m > 0 ? m : 1) * ws.ldb, vec = (sizeof(double) * (size_t)(m > 0 ? m : 1) + 63) & ~(size_t)63;
-    char* x = (char*)lvk_ctx_scratch(ctx, 15, 2 * mat + 2 * vec + 64);
+    char* x = (char*)lvk_ctx_scratch(ctx, LVK_SCR_LDLT_WS, 2 * mat + 2 * vec + 64);
     if (!x) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
     double* Bp = (double*)x; double* X = (double*)(x + mat); double* Dg = (double*)(x + 2 * mat); int* perm = (int*)(x + 2 * mat + vec); int* cnt = (int*)(x + 2 * mat + 2 * vec);
     *d_cnt_out = cnt; if (d_perm_out) *d_perm_out = perm;
@@ -882,10 +882,10 @@ lvk_status lvk_cov_propagate_augment(lvk_context* ctx, const double* Pin, int ld
         PhiQ22 pq;
         memcpy(pq.phi, h_phi, sizeof pq.phi);
         for (int i = 0; i < 15; ++i) memcpy(pq.q + 15 * i, h_q + (size_t)22 * i, sizeof(double) * 15);
-        if (shmem > 64 * 1024) LVK_LDS_OPTIN(ctx, 3, (k_cov_propagate_augment<22, true>), shmem);     // strips of > ~1400 clone / feature columns
+        if (shmem > 64 * 1024) LVK_LDS_OPTIN(ctx, (k_cov_propagate_augment<22, true>), shmem);     // strips of > ~1400 clone / feature columns
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_propagate_augment<22, true>), grid, dim3(256), shmem, ctx->stream, Pin, ldin, Pout, ldout, n_out, pose_rows, (const double*)nullptr, pq);
     } else if (L == 46) {
-        if (shmem > 64 * 1024) LVK_LDS_OPTIN(ctx, 9, (k_cov_propagate_augment<46, false>), shmem);
+        if (shmem > 64 * 1024) LVK_LDS_OPTIN(ctx, (k_cov_propagate_augment<46, false>), shmem);
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_propagate_augment<46, false>), grid, dim3(256), shmem, ctx->stream, Pin, ldin, Pout, ldout, n_out, pose_rows, d_phiq, PhiQ22());
     } else return lvk_set_error(ctx, LVK_ERR_UNSUPPORTED, "IMU block of %d states", L);
     LVK_LAUNCH_CHECK(ctx);
@@ -919,9 +919,9 @@ extern "C" lvk_status lvk_ekf_update(lvk_context* ctx, double* d_P, int ldp, int
         return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_update: bad argument");
     UpdateWs ws;
     ws.ldb = (n + 1 + 7) & ~7; ws.lds = (m + 7) & ~7;
-    ws.B = (double*)lvk_ctx_scratch(ctx, 4, sizeof(double) * (size_t)(m > 0 ? m : 1) * ws.ldb);
-    ws.S = (double*)lvk_ctx_scratch(ctx, 5, sizeof(double) * (size_t)(m > 0 ? m : 1) * (ws.lds > 0 ? ws.lds : 8));
-    ws.info = (int*)lvk_ctx_scratch(ctx, 6, 64);
+    ws.B = (double*)lvk_ctx_scratch(ctx, LVK_SCR_UPDATE_B, sizeof(double) * (size_t)(m > 0 ? m : 1) * ws.ldb);
+    ws.S = (double*)lvk_ctx_scratch(ctx, LVK_SCR_UPDATE_S, sizeof(double) * (size_t)(m > 0 ? m : 1) * (ws.lds > 0 ? ws.lds : 8));
+    ws.info = (int*)lvk_ctx_scratch(ctx, LVK_SCR_UPDATE_INFO, 64);
     if (!ws.B || !ws.S || !ws.info) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
     LVK_HIP(ctx, hipMemsetAsync(ws.info, 0, 64, ctx->stream));
     lvk_status st = lvk_update_core(ctx, d_P, ldp, n, d_H, ldh, m, d_r, sigma2, d_dx, ws);
@@ -944,8 +944,8 @@ static lvk_status ekf_update_ldlt_impl(lvk_context* ctx, double* d_P, int ldp, i
     if (lvk_ldlt_lds_bytes(m) > 158 * 1024) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_ekf_update_ldlt: %d rows do not fit the factor kernel's LDS", m);
     UpdateWs ws;
     ws.ldb = (n + 1 + 7) & ~7; ws.lds = (m + 7) & ~7;
-    ws.B = (double*)lvk_ctx_scratch(ctx, 4, sizeof(double) * (size_t)(m > 0 ? m : 1) * ws.ldb);
-    ws.S = (double*)lvk_ctx_scratch(ctx, 5, sizeof(double) * (size_t)(m > 0 ? m : 1) * (ws.lds > 0 ? ws.lds : 8));
+    ws.B = (double*)lvk_ctx_scratch(ctx, LVK_SCR_UPDATE_B, sizeof(double) * (size_t)(m > 0 ? m : 1) * ws.ldb);
+    ws.S = (double*)lvk_ctx_scratch(ctx, LVK_SCR_UPDATE_S, sizeof(double) * (size_t)(m > 0 ? m : 1) * (ws.lds > 0 ? ws.lds : 8));
     ws.info = nullptr;
     if (!ws.B || !ws.S) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
     int* d_cnt = nullptr; int* d_perm = nullptr;
@@ -1015,7 +1015,7 @@ extern "C" lvk_status lvk_chol_solve(lvk_context* ctx, double* d_S, int lds, int
 {
     if (!ctx || !h_info || m < 0 || nbcols < 0 || lds < m || ldb < nbcols || (m > 0 && (!d_S || (nbcols > 0 && !d_B))) || (lds & 3) || ((uintptr_t)d_S & 31))
         return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_chol_solve: bad argument");
-    int* d_info = (int*)lvk_ctx_scratch(ctx, 6, 64);
+    int* d_info = (int*)lvk_ctx_scratch(ctx, LVK_SCR_UPDATE_INFO, 64);
     if (!d_info) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
     LVK_HIP(ctx, hipMemsetAsync(d_info, 0, 64, ctx->stream));
     if (m > 0) { lvk_status st = launch_chol_solve(ctx, d_S, lds, m, d_B, ldb, nbcols, d_info); if (st != LVK_OK) return st; }
@@ -1026,19 +1026,7 @@ extern "C" lvk_status lvk_chol_solve(lvk_context* ctx, double* d_S, int lds, int
 
 // ------------------------------------------------------------------------- stage-level entries of the structural covariance operations
 // (C ABI, include/lvk_c.h): the launchers above on caller-owned device matrices, host-side checks of what each kernel assumes, one
-// wait per call.  Small host tables go to scratch slot 13, the append's nn x n intermediate to slot 14.
-static lvk_status cov_stage_wait(lvk_context* ctx, lvk_status st)
-{
-    if (st != LVK_OK) return st;
-    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LVK_OK;
-}
-static const void* cov_stage_upload(lvk_context* ctx, const void* h, size_t bytes)
-{
-    void* d = lvk_ctx_scratch(ctx, 13, bytes);
-    if (!d || hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return nullptr;
-    return d;
-}
+// wait per call.  Small host tables go to the stage's input blob, the append's nn x n intermediate to its middle one.
 
 extern "C" lvk_status lvk_ekf_cov_propagate_augment(lvk_context* ctx, const double* d_Pin, int ldin, double* d_Pout, int ldout, int n_out, int pose_rows,
                                                     int L, const double* h_phi, const double* h_q)
@@ -1054,13 +1042,14 @@ extern "C" lvk_status lvk_ekf_cov_propagate_augment(lvk_context* ctx, const doub
             for (int j = 0; j < 22; ++j)
                 if ((i >= 15 || j >= 15) && h_q[i * 22 + j] != 0.0)
                     return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_cov_propagate_augment: Q(%d, %d) = %g, Q must be zero outside its leading 15 x 15 for L = 22", i, j, h_q[i * 22 + j]);
-        return cov_stage_wait(ctx, lvk_cov_propagate_augment(ctx, d_Pin, ldin, d_Pout, ldout, n_out, pose_rows, L, h_phi, h_q, nullptr));
     }
-    double* d_phiq = (double*)lvk_ctx_scratch(ctx, 13, sizeof(double) * 2 * L * L);
-    if (!d_phiq) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
-    LVK_HIP(ctx, hipMemcpyAsync(d_phiq, h_phi, sizeof(double) * L * L, hipMemcpyHostToDevice, ctx->stream));
-    LVK_HIP(ctx, hipMemcpyAsync(d_phiq + L * L, h_q, sizeof(double) * L * L, hipMemcpyHostToDevice, ctx->stream));
-    return cov_stage_wait(ctx, lvk_cov_propagate_augment(ctx, d_Pin, ldin, d_Pout, ldout, n_out, pose_rows, L, h_phi, h_q, d_phiq));
+    Stage sg(ctx);
+    const size_t nb = sizeof(double) * L * L, o_phiq = sg.take(Stage::IN, 2 * nb);      // [Phi | Q], read only when L != 22
+    LVK_TRY(sg.alloc());
+    LVK_TRY(sg.put(Stage::IN, o_phiq, h_phi, nb));
+    LVK_TRY(sg.put(Stage::IN, o_phiq + nb, h_q, nb));
+    LVK_TRY(lvk_cov_propagate_augment(ctx, d_Pin, ldin, d_Pout, ldout, n_out, pose_rows, L, h_phi, h_q, sg.at<double>(Stage::IN, o_phiq)));
+    return sg.wait();
 }
 
 extern "C" lvk_status lvk_ekf_cov_gather(lvk_context* ctx, const double* d_Pin, int ldin, double* d_Pout, int ldout, const int* h_idx, int n)
@@ -1069,9 +1058,12 @@ extern "C" lvk_status lvk_ekf_cov_gather(lvk_context* ctx, const double* d_Pin, 
         return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_cov_gather: bad argument");
     for (int a = 0; a < n; ++a)
         if (h_idx[a] < 0 || h_idx[a] >= ldin) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_cov_gather: idx[%d] = %d outside [0, ldin)", a, h_idx[a]);
-    const int* d_idx = (const int*)cov_stage_upload(ctx, h_idx, sizeof(int) * (size_t)n);
-    if (!d_idx) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_ekf_cov_gather: index upload failed");
-    return cov_stage_wait(ctx, lvk_cov_gather(ctx, d_Pin, ldin, d_Pout, ldout, d_idx, n));
+    Stage sg(ctx);
+    const size_t o_idx = sg.take(Stage::IN, sizeof(int) * (size_t)n);
+    LVK_TRY(sg.alloc());
+    LVK_TRY(sg.put(Stage::IN, o_idx, h_idx, sizeof(int) * (size_t)n));
+    LVK_TRY(lvk_cov_gather(ctx, d_Pin, ldin, d_Pout, ldout, sg.at<int>(Stage::IN, o_idx), n));
+    return sg.wait();
 }
 
 extern "C" lvk_status lvk_ekf_cov_reanchor(lvk_context* ctx, double* d_P, int ld, int n, const double* h_J, int fc)
@@ -1081,9 +1073,12 @@ extern "C" lvk_status lvk_ekf_cov_reanchor(lvk_context* ctx, double* d_P, int ld
     int nnz = 0;
     for (int k = 0; k < n; ++k) nnz += h_J[k] != 0.0;
     if (nnz > 64) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_cov_reanchor: J has %d non-zeros, the kernel holds at most 64", nnz);
-    const double* d_J = (const double*)cov_stage_upload(ctx, h_J, sizeof(double) * (size_t)n);
-    if (!d_J) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_ekf_cov_reanchor: upload of J failed");
-    return cov_stage_wait(ctx, lvk_cov_reanchor(ctx, d_P, ld, n, d_J, fc));
+    Stage sg(ctx);
+    const size_t o_J = sg.take(Stage::IN, sizeof(double) * (size_t)n);
+    LVK_TRY(sg.alloc());
+    LVK_TRY(sg.put(Stage::IN, o_J, h_J, sizeof(double) * (size_t)n));
+    LVK_TRY(lvk_cov_reanchor(ctx, d_P, ld, n, sg.at<double>(Stage::IN, o_J), fc));
+    return sg.wait();
 }
 
 extern "C" lvk_status lvk_ekf_cov_append_features(lvk_context* ctx, double* d_P, int ld, int n, int nn, const double* d_H1, int ldh, const double* h_H2,
@@ -1092,8 +1087,10 @@ extern "C" lvk_status lvk_ekf_cov_append_features(lvk_context* ctx, double* d_P,
     if (!ctx || !d_P || n <= 0 || nn < 0 || ld < n + nn || (nn > 0 && (!d_H1 || !h_H2 || !d_r1 || !d_dx || !d_dx_new || ldh < n)))
         return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_cov_append_features: bad argument");
     if (nn == 0) return LVK_OK;
-    const double* d_H2 = (const double*)cov_stage_upload(ctx, h_H2, sizeof(double) * (size_t)nn);
-    double* tmp = (double*)lvk_ctx_scratch(ctx, 14, sizeof(double) * (size_t)nn * n);
-    if (!d_H2 || !tmp) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_ekf_cov_append_features: scratch allocation failed");
-    return cov_stage_wait(ctx, lvk_cov_append_features(ctx, d_P, ld, n, nn, d_H1, ldh, d_H2, d_r1, d_dx, sigma2, tmp, d_dx_new));
+    Stage sg(ctx);
+    const size_t o_H2 = sg.take(Stage::IN, sizeof(double) * (size_t)nn), o_tmp = sg.take(Stage::MID, sizeof(double) * (size_t)nn * n);
+    LVK_TRY(sg.alloc());
+    LVK_TRY(sg.put(Stage::IN, o_H2, h_H2, sizeof(double) * (size_t)nn));
+    LVK_TRY(lvk_cov_append_features(ctx, d_P, ld, n, nn, d_H1, ldh, sg.at<double>(Stage::IN, o_H2), d_r1, d_dx, sigma2, sg.at<double>(Stage::MID, o_tmp), d_dx_new));
+    return sg.wait();
 }

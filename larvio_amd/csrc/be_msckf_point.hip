@@ -1,14 +1,14 @@
 // be_msckf_point.hip — first-order position covariance of the MSCKF points the filter triangulates (lvk_ekf_msckf_point_cov,
 // include/lvk_c.h).  For a point with M observations from distinct clones, with Hx_t / He_t / Hf_t of d_msckf_obs_jacobian (be_dev.h):
 //   A = sum_t Hf_t^T Hf_t,  G_t = A^-1 Hf_t^T,  B = sum_t G_t Hc[2t:2t+2, :],  Sigma = sigma2 A^-1 + B P[cc, cc] B^T
-// where Hc (2M x c, c = 7 + 6M) is the compact block k_feature_rows builds before its Householder step and cc its column map.
+// where Hc (2M x c, c = fj_cols(JOB_MSCKF, M)) is the compact block k_feature_rows builds before its Householder step and cc its column map.
 #include "be_host.h"
 #include <math.h>
 #include <vector>
 
 #define MP_THREADS 256
 #define MP_MAX_OBS 64
-#define MP_MAX_C (7 + 6 * MP_MAX_OBS)
+#define MP_MAX_C fj_cols(JOB_MSCKF, MP_MAX_OBS)
 
 // One workgroup per point.  Hc is never formed: row block t of it is non-zero in columns 0..6 (He_t and, under estimate_td, the
 // observation's zv) and 7+6t..7+6t+5 (Hx_t), so thread t < M
@@ -32,7 +32,7 @@ __global__ __launch_bounds__(MP_THREADS) void k_msckf_point_cov(const double* __
     const int jb = blockIdx.x, t = threadIdx.x;
     if (jb >= n_jobs) return;                            // (uniform over the workgroup)
     const PointJob job = jobs[jb];
-    const int M = job.n_obs, c = 7 + 6 * M;
+    const int M = job.n_obs, c = fj_cols(JOB_MSCKF, M);
     double p_w[3] = {job.p_w[0], job.p_w[1], job.p_w[2]};
     int tri_ok = 1;
     if (tri && job.tri_slot1 > 0) {                      // the triangulation queued ahead of this launch, as k_feature_rows reads it
@@ -130,7 +130,7 @@ lvk_status lvk_launch_msckf_point_cov(lvk_context* ctx, const double* d_P, int l
     return LVK_OK;
 }
 
-// (C ABI) clone table, jobs and observations go up in one blob (scratch slot 9), the results come back through slot 11; one wait per call
+// (C ABI) clone table, jobs and observations go up in one blob, the results come back through the output blob; one wait per call
 extern "C" lvk_status lvk_ekf_msckf_point_cov(lvk_context* ctx, const double* d_P, int ldp, int n, const lvk_clone* h_clones, int n_clones,
                                               const lvk_msckf_point_job* h_jobs, int n_jobs, const int* h_clone_rank, const double* h_obs, const double* h_obs_vel,
                                               int leg_dim, int if_fej, int estimate_td, double sigma2, double* h_cov9, int* h_ok)
@@ -155,36 +155,21 @@ extern "C" lvk_status lvk_ekf_msckf_point_cov(lvk_context* ctx, const double* d_
         tot = std::max(tot, (size_t)f.obs_off + (size_t)M);
     }
     if (n_jobs == 0) return LVK_OK;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = (o + bytes + 63) & ~(size_t)63; return at; };
-    const size_t o_cl = take(sizeof(CloneDev) * (size_t)n_clones), o_job = take(sizeof(PointJob) * (size_t)n_jobs), o_rk = take(sizeof(int) * tot), o_z = take(16 * tot),
-                 o_zv = take(16 * tot), in_bytes = o;
-    const size_t o_ok = (sizeof(double) * 9 * (size_t)n_jobs + 63) & ~(size_t)63, out_bytes = o_ok + sizeof(int) * (size_t)n_jobs;
-    char* d_in = (char*)lvk_ctx_scratch(ctx, 9, in_bytes);
-    char* d_out = (char*)lvk_ctx_scratch(ctx, 11, out_bytes);
-    if (!d_in || !d_out) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_ekf_msckf_point_cov: scratch allocation failed");
-    std::vector<char> h(in_bytes, 0);
-    CloneDev* hc = (CloneDev*)(h.data() + o_cl);
-    for (int i = 0; i < n_clones; ++i) {
-        memcpy(hc[i].q, h_clones[i].q, 32); memcpy(hc[i].p, h_clones[i].p, 24); memcpy(hc[i].p_fej, h_clones[i].p_fej, 24);
-        memcpy(hc[i].R_b2c, h_clones[i].R_b2c, 72); memcpy(hc[i].t_c_b, h_clones[i].t_c_b, 24);
-    }
-    PointJob* hj = (PointJob*)(h.data() + o_job);
+    Stage sg(ctx);
+    const size_t o_cl = sg.take(Stage::IN, sizeof(CloneDev) * (size_t)n_clones), o_job = sg.take(Stage::IN, sizeof(PointJob) * (size_t)n_jobs), o_rk = sg.take(Stage::IN, sizeof(int) * tot),
+                 o_z = sg.take(Stage::IN, 16 * tot), o_zv = sg.take(Stage::IN, 16 * tot);
+    const size_t n_cov = sizeof(double) * 9 * (size_t)n_jobs, n_ok = sizeof(int) * (size_t)n_jobs, o_cov = sg.take(Stage::OUT, n_cov), o_ok = sg.take(Stage::OUT, n_ok);
+    LVK_TRY(sg.alloc());
+    for (int i = 0; i < n_clones; ++i) clone_dev_from(h_clones[i], sg.host<CloneDev>(o_cl) + i);
+    PointJob* hj = sg.host<PointJob>(o_job);
     for (int j = 0; j < n_jobs; ++j) { hj[j].n_obs = h_jobs[j].n_obs; hj[j].obs_off = h_jobs[j].obs_off; hj[j].tri_slot1 = 0; hj[j].pad = 0; memcpy(hj[j].p_w, h_jobs[j].p_w, 24); }
-    memcpy(h.data() + o_rk, h_clone_rank, sizeof(int) * tot);
-    memcpy(h.data() + o_z, h_obs, 16 * tot); memcpy(h.data() + o_zv, h_obs_vel, 16 * tot);
-    FilterFlags fl; fl.leg_dim = leg_dim; fl.if_fej = if_fej ? 1 : 0; fl.estimate_td = estimate_td ? 1 : 0; fl.pad = 0; fl.sigma2 = sigma2;
-    // h is pageable and dies with this call: whichever step fails, the stream is waited for before the call returns
-    const lvk_status st = [&]() -> lvk_status {
-        LVK_HIP(ctx, hipMemcpyAsync(d_in, h.data(), in_bytes, hipMemcpyHostToDevice, ctx->stream));
-        const lvk_status ls = lvk_launch_msckf_point_cov(ctx, d_P, ldp, (const PointJob*)(d_in + o_job), n_jobs, (const CloneDev*)(d_in + o_cl), (const int*)(d_in + o_rk),
-                                                         (const double*)(d_in + o_z), (const double*)(d_in + o_zv), fl, nullptr, (double*)d_out, (int*)(d_out + o_ok));
-        if (ls != LVK_OK) return ls;
-        LVK_HIP(ctx, hipMemcpyAsync(h_cov9, d_out, sizeof(double) * 9 * (size_t)n_jobs, hipMemcpyDeviceToHost, ctx->stream));
-        LVK_HIP(ctx, hipMemcpyAsync(h_ok, d_out + o_ok, sizeof(int) * (size_t)n_jobs, hipMemcpyDeviceToHost, ctx->stream));
-        LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return LVK_OK;
-    }();
-    if (st != LVK_OK) (void)hipStreamSynchronize(ctx->stream);
-    return st;
+    memcpy(sg.host<int>(o_rk), h_clone_rank, sizeof(int) * tot);
+    memcpy(sg.host<double>(o_z), h_obs, 16 * tot); memcpy(sg.host<double>(o_zv), h_obs_vel, 16 * tot);
+    LVK_TRY(sg.upload());
+    LVK_TRY(lvk_launch_msckf_point_cov(ctx, d_P, ldp, sg.at<PointJob>(Stage::IN, o_job), n_jobs, sg.at<CloneDev>(Stage::IN, o_cl), sg.at<int>(Stage::IN, o_rk),
+                                       sg.at<double>(Stage::IN, o_z), sg.at<double>(Stage::IN, o_zv), filter_flags(leg_dim, if_fej, estimate_td, sigma2), nullptr,
+                                       sg.at<double>(Stage::OUT, o_cov), sg.at<int>(Stage::OUT, o_ok)));
+    LVK_TRY(sg.get(h_cov9, Stage::OUT, o_cov, n_cov));
+    LVK_TRY(sg.get(h_ok, Stage::OUT, o_ok, n_ok));
+    return sg.wait();
 }

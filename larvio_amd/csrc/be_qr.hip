@@ -280,10 +280,10 @@ size_t lvk_qr_sparse_lds_bytes(int rows, int ncols, int N)
     return sizeof(double) * ((size_t)(ncols + 1) * Rp + (size_t)ncols + 2 + 2 * (Rp > 256 ? Rp : 256)) + sizeof(int) * (size_t)N + 16;    // (2 x 256: the register kernel's padded reflector buffers)
 }
 template <int RPL, int QUADS>
-static lvk_status launch_qr_reg(lvk_context* ctx, int slot, const double* d_Hin, int ldin, const double* d_rin, double* d_Hout, int ldout, double* d_rout,
+static lvk_status launch_qr_reg(lvk_context* ctx, const double* d_Hin, int ldin, const double* d_rin, double* d_Hout, int ldout, double* d_rout,
                                 const QrBlock* d_blocks, int n_blocks, const int* d_cols, int N, size_t max_lds)
 {
-    if (max_lds > 64 * 1024) LVK_LDS_OPTIN(ctx, slot, (k_qr_sparse_reg<RPL, QUADS>), max_lds);
+    if (max_lds > 64 * 1024) LVK_LDS_OPTIN(ctx, (k_qr_sparse_reg<RPL, QUADS>), max_lds);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_qr_sparse_reg<RPL, QUADS>), dim3(n_blocks), dim3(QS_THREADS), max_lds, ctx->stream, d_Hin, ldin, d_rin, d_Hout, ldout, d_rout, d_blocks, d_cols, N);
     LVK_LAUNCH_CHECK(ctx);
     return LVK_OK;
@@ -295,10 +295,10 @@ lvk_status lvk_qr_sparse_level(lvk_context* ctx, const double* d_Hin, int ldin, 
     if (max_lds > 160 * 1024) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "QR node needs %zu bytes of LDS", max_lds);
     // register-resident nodes where every node of the level fits one of the compiled shapes (rows <= 16 RPL, columns + 1 <= 64 QUADS)
     const int rpl = (max_rows + 15) / 16, quads = (max_cols + 1 + 63) / 64;
-#define QR_REG(R_, Q_, slot_) return launch_qr_reg<R_, Q_>(ctx, slot_, d_Hin, ldin, d_rin, d_Hout, ldout, d_rout, d_blocks, n_blocks, d_cols, N, max_lds)
-    if (max_rows > 0 && quads == 1) { if (rpl <= 8) QR_REG(8, 1, 12); if (rpl <= 16) QR_REG(16, 1, 13); }        // (every node the planner makes; anything else: the LDS kernel below)
+#define QR_REG(R_, Q_) return launch_qr_reg<R_, Q_>(ctx, d_Hin, ldin, d_rin, d_Hout, ldout, d_rout, d_blocks, n_blocks, d_cols, N, max_lds)
+    if (max_rows > 0 && quads == 1) { if (rpl <= 8) QR_REG(8, 1); if (rpl <= 16) QR_REG(16, 1); }        // (every node the planner makes; anything else: the LDS kernel below)
 #undef QR_REG
-    if (max_lds > 64 * 1024) LVK_LDS_OPTIN(ctx, 11, k_qr_sparse, max_lds);
+    if (max_lds > 64 * 1024) LVK_LDS_OPTIN(ctx, k_qr_sparse, max_lds);
     hipLaunchKernelGGL(k_qr_sparse, dim3(n_blocks), dim3(QS_THREADS), max_lds, ctx->stream, d_Hin, ldin, d_rin, d_Hout, ldout, d_rout, d_blocks, d_cols, N);
     LVK_LAUNCH_CHECK(ctx);
     return LVK_OK;
@@ -453,22 +453,23 @@ extern "C" lvk_status lvk_ekf_compress_qr_groups(lvk_context* ctx, double* d_H, 
     lvk_qr_sparse_plan(g, cols, levels, &m2);
     *rows_out = rows;
     if (levels.empty()) return LVK_OK;
-    double* Hb = (double*)lvk_ctx_scratch(ctx, 7, sizeof(double) * (size_t)rows * ld);
-    double* rb = (double*)lvk_ctx_scratch(ctx, 8, sizeof(double) * (size_t)rows);
+    double* Hb = (double*)lvk_ctx_scratch(ctx, LVK_SCR_QR_H, sizeof(double) * (size_t)rows * ld);
+    double* rb = (double*)lvk_ctx_scratch(ctx, LVK_SCR_QR_R, sizeof(double) * (size_t)rows);
+    if (!Hb || !rb) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
     size_t nb = 0, ncl = 0; for (auto& L : levels) { nb += L.blocks.size(); ncl += L.cols.size() + 1; }
-    char* meta = (char*)lvk_ctx_scratch(ctx, 9, sizeof(QrBlock) * nb + sizeof(int) * ncl);
-    if (!Hb || !rb || !meta) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
-    QrBlock* d_blocks = (QrBlock*)meta; int* d_cols = (int*)(meta + sizeof(QrBlock) * nb);
-    std::vector<QrBlock> hb; std::vector<int> hc;
-    for (auto& L : levels) { hb.insert(hb.end(), L.blocks.begin(), L.blocks.end()); hc.insert(hc.end(), L.cols.begin(), L.cols.end()); hc.push_back(0); }
-    LVK_HIP(ctx, hipMemcpyAsync(d_blocks, hb.data(), sizeof(QrBlock) * nb, hipMemcpyHostToDevice, ctx->stream));
-    LVK_HIP(ctx, hipMemcpyAsync(d_cols, hc.data(), sizeof(int) * ncl, hipMemcpyHostToDevice, ctx->stream));
-    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // hb / hc are stack-local
+    Stage sg(ctx);                                                      // the plan's blocks and column lists, level after level
+    const size_t o_blocks = sg.take(Stage::IN, sizeof(QrBlock) * nb), o_cols = sg.take(Stage::IN, sizeof(int) * ncl);
+    LVK_TRY(sg.alloc());
+    {
+        QrBlock* hb = sg.host<QrBlock>(o_blocks); int* hc = sg.host<int>(o_cols);
+        for (auto& L : levels) { hb = std::copy(L.blocks.begin(), L.blocks.end(), hb); hc = std::copy(L.cols.begin(), L.cols.end(), hc); *hc++ = 0; }
+    }
+    LVK_TRY(sg.upload());
+    const QrBlock* d_blocks = sg.at<QrBlock>(Stage::IN, o_blocks); const int* d_cols = sg.at<int>(Stage::IN, o_cols);
     double* H = d_H; double* r = d_r; size_t ob = 0, oc = 0;
     for (auto& L : levels) {
         double* Ho = (H == d_H) ? Hb : d_H; double* ro = (r == d_r) ? rb : d_r;
-        lvk_status st = lvk_qr_sparse_level(ctx, H, ld, r, Ho, ld, ro, d_blocks + ob, (int)L.blocks.size(), d_cols + oc, cols, L.lds, L.max_rows, L.max_cols);
-        if (st != LVK_OK) return st;
+        LVK_TRY(lvk_qr_sparse_level(ctx, H, ld, r, Ho, ld, ro, d_blocks + ob, (int)L.blocks.size(), d_cols + oc, cols, L.lds, L.max_rows, L.max_cols));
         ob += L.blocks.size(); oc += L.cols.size() + 1;
         H = Ho; r = ro;
     }
@@ -477,5 +478,5 @@ extern "C" lvk_status lvk_ekf_compress_qr_groups(lvk_context* ctx, double* d_H, 
         LVK_HIP(ctx, hipMemcpyAsync(d_r, r, sizeof(double) * m2, hipMemcpyDeviceToDevice, ctx->stream));
     }
     *rows_out = m2;
-    return LVK_OK;
+    return sg.wait();
 }

@@ -320,15 +320,15 @@ static lvk_status caqr_run(lvk_context* ctx, double* d_H, int ld, int m, int n, 
 {
     const int CH = 16384 / NB;
     const int nch_max = (m + CH - 1) / CH;
-    double* Vws = (double*)lvk_ctx_scratch(ctx, 7, sizeof(double) * ((size_t)nch_max * CH * NB + (size_t)CH * NB));
-    double* Tws = (double*)lvk_ctx_scratch(ctx, 8, sizeof(double) * ((size_t)(nch_max + 1) * NB * NB));
+    double* Vws = (double*)lvk_ctx_scratch(ctx, LVK_SCR_QR_H, sizeof(double) * ((size_t)nch_max * CH * NB + (size_t)CH * NB));
+    double* Tws = (double*)lvk_ctx_scratch(ctx, LVK_SCR_QR_R, sizeof(double) * ((size_t)(nch_max + 1) * NB * NB));
     if (!Vws || !Tws) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
     double* V2 = Vws + (size_t)nch_max * CH * NB; double* T2 = Tws + (size_t)nch_max * NB * NB;
     const size_t lds_f = sizeof(double) * ((size_t)CH * (NB + 1) + 2 * (size_t)CH + 2 * NB + 2 * NB * NB + 2);
     const size_t lds_a = sizeof(double) * ((size_t)CH * (NB + 1) + NB * NB + 4 * NB * 17 + 2) + sizeof(int) * (size_t)CH;
     if (lds_f > 160 * 1024 || lds_a > 160 * 1024) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "CAQR: LDS budget exceeded (%zu / %zu bytes)", lds_f, lds_a);
-    LVK_LDS_OPTIN(ctx, NB == 32 ? 5 : 6, k_caqr_factor<NB>, lds_f);
-    LVK_LDS_OPTIN(ctx, NB == 32 ? 7 : 4, k_caqr_apply<NB>, lds_a);
+    LVK_LDS_OPTIN(ctx, k_caqr_factor<NB>, lds_f);
+    LVK_LDS_OPTIN(ctx, k_caqr_apply<NB>, lds_a);
     hipStream_t s = ctx->stream;
     const int panels = (n + NB - 1) / NB;
     for (int p = 0; p < panels; ++p) {

@@ -167,7 +167,7 @@ void lvk_shard_comm_destroy(lvk_shard_comm* c)
 }
 
 // ------------------------------------------------------------------------- stage entries (parity tests): host buffers in, the
-// launchers above on scratch slots 9 (inputs) and 10 (outputs), one wait, host buffers out
+// launchers above on the stage's input and output blobs, one wait, host buffers out
 lvk_status lvk_shard_pack_stage(lvk_context* ctx, int rank, const double* h_X, int ld, const double* h_rX, int k, int ncols,
                                 const lvk_feature_result* h_res, int n_res, size_t res_bytes, int fill, void* h_send, size_t bytes_per_rank)
 {
@@ -180,22 +180,18 @@ lvk_status lvk_shard_pack_stage(lvk_context* ctx, int rank, const double* h_X, i
         return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_shard_pack_stage: res_bytes %zu (a multiple of 256, >= 32 n_res)", res_bytes);
     if (bytes_per_rank % 8 || bytes_per_rank < LVK_SHARD_HDR + res_bytes + sizeof(double) * (size_t)k * ((size_t)ncols + 1))
         return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_shard_pack_stage: bytes_per_rank %zu (a multiple of 8, >= header + res_bytes + 8 k (ncols + 1))", bytes_per_rank);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
+    Stage sg(ctx);
     const size_t nX = sizeof(double) * (size_t)k * ld, nr = sizeof(double) * (size_t)k, nres = sizeof(FeatResult) * (size_t)n_res;
-    const size_t o_X = take(nX), o_r = take(nr), o_res = take(nres), in_bytes = std::max(o, (size_t)256);
-    char* d_in = (char*)lvk_ctx_scratch(ctx, 9, in_bytes);
-    char* d_send = (char*)lvk_ctx_scratch(ctx, 10, bytes_per_rank);
-    if (!d_in || !d_send) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
-    if (nX) LVK_HIP(ctx, hipMemcpyAsync(d_in + o_X, h_X, nX, hipMemcpyHostToDevice, ctx->stream));
-    if (nr) LVK_HIP(ctx, hipMemcpyAsync(d_in + o_r, h_rX, nr, hipMemcpyHostToDevice, ctx->stream));
-    if (nres) LVK_HIP(ctx, hipMemcpyAsync(d_in + o_res, h_res, nres, hipMemcpyHostToDevice, ctx->stream));
+    const size_t o_X = sg.take(Stage::IN, nX), o_r = sg.take(Stage::IN, nr), o_res = sg.take(Stage::IN, nres), o_send = sg.take(Stage::OUT, bytes_per_rank);
+    LVK_TRY(sg.alloc());
+    LVK_TRY(sg.put(Stage::IN, o_X, h_X, nX));
+    LVK_TRY(sg.put(Stage::IN, o_r, h_rX, nr));
+    LVK_TRY(sg.put(Stage::IN, o_res, h_res, nres));
+    char* d_send = sg.at<char>(Stage::OUT, o_send);
     LVK_HIP(ctx, hipMemsetAsync(d_send, fill & 0xFF, bytes_per_rank, ctx->stream));
-    lvk_status st = lvk_shard_pack(ctx, (const FeatResult*)(d_in + o_res), n_res, (const double*)(d_in + o_X), ld, (const double*)(d_in + o_r), k, ncols, d_send, res_bytes, rank);
-    if (st != LVK_OK) return st;
-    LVK_HIP(ctx, hipMemcpyAsync(h_send, d_send, bytes_per_rank, hipMemcpyDeviceToHost, ctx->stream));
-    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LVK_OK;
+    LVK_TRY(lvk_shard_pack(ctx, sg.at<FeatResult>(Stage::IN, o_res), n_res, sg.at<double>(Stage::IN, o_X), ld, sg.at<double>(Stage::IN, o_r), k, ncols, d_send, res_bytes, rank));
+    LVK_TRY(sg.get(h_send, Stage::OUT, o_send, bytes_per_rank));
+    return sg.wait();
 }
 
 lvk_status lvk_shard_unpack_stage(lvk_context* ctx, const void* h_recv, size_t bytes_per_rank, const lvk_shard_meta* h_meta, int world, int ncols, int k_max,
@@ -216,34 +212,24 @@ lvk_status lvk_shard_unpack_stage(lvk_context* ctx, const void* h_recv, size_t b
         if (m.job_lo < 0 || m.job_n < 0 || (long long)m.job_lo + m.job_n > n_fout || sizeof(FeatResult) * (size_t)m.job_n > res_bytes)
             return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_shard_unpack_stage: rank %d's jobs [%d, %d + %d) leave the %d results or res_bytes", g, m.job_lo, m.job_lo, m.job_n, n_fout);
     }
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
+    Stage sg(ctx);
     const size_t n_recv = bytes_per_rank * (size_t)world, n_meta = sizeof(ShardMeta) * (size_t)world;
-    const size_t o_recv = take(n_recv), o_meta = take(n_meta), in_bytes = o;
-    o = 0;
+    const size_t o_recv = sg.take(Stage::IN, n_recv), o_meta = sg.take(Stage::IN, n_meta);
+    // the outputs start as the caller's buffers hold them: what the kernel leaves alone comes back unchanged (absent ones: no bytes)
     const size_t nH = sizeof(double) * (size_t)rows * ld, nr = sizeof(double) * (size_t)rows, nf = sizeof(FeatResult) * (size_t)n_fout;
-    const size_t o_H = take(nH), o_r = take(nr), o_f = take(nf), o_fh = take(nf), o_flag = take(sizeof(int)), out_bytes = o;
-    char* d_in = (char*)lvk_ctx_scratch(ctx, 9, in_bytes);
-    char* d_out = (char*)lvk_ctx_scratch(ctx, 10, out_bytes);
-    if (!d_in || !d_out) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
-    LVK_HIP(ctx, hipMemcpyAsync(d_in + o_recv, h_recv, n_recv, hipMemcpyHostToDevice, ctx->stream));
-    LVK_HIP(ctx, hipMemcpyAsync(d_in + o_meta, h_meta, n_meta, hipMemcpyHostToDevice, ctx->stream));
-    if (nH) LVK_HIP(ctx, hipMemcpyAsync(d_out + o_H, h_H, nH, hipMemcpyHostToDevice, ctx->stream));
-    if (nr) LVK_HIP(ctx, hipMemcpyAsync(d_out + o_r, h_r, nr, hipMemcpyHostToDevice, ctx->stream));
-    if (nf) LVK_HIP(ctx, hipMemcpyAsync(d_out + o_f, h_fout, nf, hipMemcpyHostToDevice, ctx->stream));
-    if (nf && h_fout_host) LVK_HIP(ctx, hipMemcpyAsync(d_out + o_fh, h_fout_host, nf, hipMemcpyHostToDevice, ctx->stream));
-    if (h_peer_fail) LVK_HIP(ctx, hipMemcpyAsync(d_out + o_flag, h_peer_fail, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    lvk_status st = lvk_shard_unpack(ctx, d_in + o_recv, bytes_per_rank, res_bytes, (const ShardMeta*)(d_in + o_meta), world, ncols, k_max, (FeatResult*)(d_out + o_f),
-                                     h_fout_host ? (FeatResult*)(d_out + o_fh) : nullptr, (double*)(d_out + o_H), ld, (double*)(d_out + o_r),
-                                     h_peer_fail ? (int*)(d_out + o_flag) : nullptr);
-    if (st != LVK_OK) return st;
-    if (nH) LVK_HIP(ctx, hipMemcpyAsync(h_H, d_out + o_H, nH, hipMemcpyDeviceToHost, ctx->stream));
-    if (nr) LVK_HIP(ctx, hipMemcpyAsync(h_r, d_out + o_r, nr, hipMemcpyDeviceToHost, ctx->stream));
-    if (nf) LVK_HIP(ctx, hipMemcpyAsync(h_fout, d_out + o_f, nf, hipMemcpyDeviceToHost, ctx->stream));
-    if (nf && h_fout_host) LVK_HIP(ctx, hipMemcpyAsync(h_fout_host, d_out + o_fh, nf, hipMemcpyDeviceToHost, ctx->stream));
-    if (h_peer_fail) LVK_HIP(ctx, hipMemcpyAsync(h_peer_fail, d_out + o_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LVK_OK;
+    const size_t nfh = h_fout_host ? nf : 0, nflag = h_peer_fail ? sizeof(int) : 0;
+    const size_t o_H = sg.take(Stage::OUT, nH), o_r = sg.take(Stage::OUT, nr), o_f = sg.take(Stage::OUT, nf), o_fh = sg.take(Stage::OUT, nfh), o_flag = sg.take(Stage::OUT, nflag);
+    void* const h_out[5] = {h_H, h_r, h_fout, h_fout_host, h_peer_fail};
+    const size_t o_out[5] = {o_H, o_r, o_f, o_fh, o_flag}, n_out[5] = {nH, nr, nf, nfh, nflag};
+    LVK_TRY(sg.alloc());
+    LVK_TRY(sg.put(Stage::IN, o_recv, h_recv, n_recv));
+    LVK_TRY(sg.put(Stage::IN, o_meta, h_meta, n_meta));
+    for (int i = 0; i < 5; ++i) LVK_TRY(sg.put(Stage::OUT, o_out[i], h_out[i], n_out[i]));
+    LVK_TRY(lvk_shard_unpack(ctx, sg.at<char>(Stage::IN, o_recv), bytes_per_rank, res_bytes, sg.at<ShardMeta>(Stage::IN, o_meta), world, ncols, k_max, sg.at<FeatResult>(Stage::OUT, o_f),
+                             h_fout_host ? sg.at<FeatResult>(Stage::OUT, o_fh) : nullptr, sg.at<double>(Stage::OUT, o_H), ld, sg.at<double>(Stage::OUT, o_r),
+                             h_peer_fail ? sg.at<int>(Stage::OUT, o_flag) : nullptr));
+    for (int i = 0; i < 5; ++i) LVK_TRY(sg.get(h_out[i], Stage::OUT, o_out[i], n_out[i]));
+    return sg.wait();
 }
 
 const char* lvk_shard_comm_error(const lvk_shard_comm* c) { return c ? c->err : "null communicator"; }

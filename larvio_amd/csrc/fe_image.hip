@@ -945,7 +945,7 @@ lvk_status lvk_clahe_u8(lvk_context* ctx, const uint8_t* d_src, int w, int h, in
     int clip = 0;
     if (clip_limit > 0.0) { clip = (int)(clip_limit * total / 256); if (clip < 1) clip = 1; }
     const size_t nt = (size_t)tiles_x * tiles_y;
-    uint8_t* lut = (uint8_t*)lvk_ctx_scratch(ctx, 0, nt * 256);
+    uint8_t* lut = (uint8_t*)lvk_ctx_scratch(ctx, LVK_SCR_CLAHE_LUT, nt * 256);
     if (!lut) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
     int vec4; clahe_launch_shape(d_src, w, h, sstride, tw, th, tiles_x, tiles_y, &vec4);
     hipLaunchKernelGGL(k_clahe_lut, dim3(tiles_x * tiles_y), dim3(256), 0, ctx->stream, d_src, w, h, sstride, tw, th, tiles_x, clip, lut_scale, lut, vec4);
@@ -1154,7 +1154,7 @@ lvk_status lvk_gftt_run(lvk_context* ctx, const float* d_eig, const uint8_t* d_m
     { int mb = (w * h / 4 + 2047) / 2048; mb = mb < 128 ? 128 : mb > 1024 ? 1024 : mb;      // ~8 four-pixel loads per lane
       hipLaunchKernelGGL(k_masked_max, dim3(mb), dim3(256), 0, ctx->stream, d_eig, d_mask, w * h, d_scratch); }
     hipLaunchKernelGGL(k_gftt_candidates, dim3((w - 2 + GC_COLS - 1) / GC_COLS, (h - 2 + GC_ROWS - 1) / GC_ROWS), dim3(GC_COLS), 0, ctx->stream, d_eig, d_mask, w, h, quality, d_scratch, d_cands, cand_cap);
-    LVK_LDS_OPTIN(ctx, 2, k_gftt_select, shm);   // the opt-in must leave room for the kernel's static LDS: ask for what is launched
+    LVK_LDS_OPTIN(ctx, k_gftt_select, shm);   // the opt-in must leave room for the kernel's static LDS: ask for what is launched
     hipLaunchKernelGGL(k_gftt_select, dim3(1), dim3(1024), shm, ctx->stream, (const unsigned long long*)d_cands, cand_cap, w, h, max_corners, cell,
                        (float)(min_distance * min_distance), surv_cap, acc_cap, d_scratch, d_out, cap, d_n_out, d_sub);
     LVK_LAUNCH_CHECK(ctx);
@@ -1195,8 +1195,8 @@ extern "C" lvk_status lvk_good_features_from_map(lvk_context* ctx, const float* 
         return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_good_features_from_map: bad argument");
     const int cand_cap = w * h;
     size_t cand_alloc = 1; while (cand_alloc < (size_t)cand_cap) cand_alloc <<= 1;     // bitonic sort pads to a power of two in place
-    unsigned* scratch = (unsigned*)lvk_ctx_scratch(ctx, 2, GF_SCRATCH_UINTS * sizeof(unsigned));
-    unsigned long long* cands = (unsigned long long*)lvk_ctx_scratch(ctx, 3, sizeof(unsigned long long) * cand_alloc);
+    unsigned* scratch = (unsigned*)lvk_ctx_scratch(ctx, LVK_SCR_GFTT_WORK, GF_SCRATCH_UINTS * sizeof(unsigned));
+    unsigned long long* cands = (unsigned long long*)lvk_ctx_scratch(ctx, LVK_SCR_GFTT_CANDS, sizeof(unsigned long long) * cand_alloc);
     if (!scratch || !cands) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
     return lvk_gftt_run(ctx, d_eig, d_mask, w, h, max_corners, quality, min_distance, scratch, cands, cand_cap, d_out, cap, d_n_out, nullptr, false, false);
 }
@@ -1206,7 +1206,7 @@ extern "C" lvk_status lvk_good_features(lvk_context* ctx, const lvk_pyramid* p, 
 {
     if (!ctx || !p || !d_out || !d_n_out) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_good_features: bad argument");
     const int w = p->w[0], h = p->h[0];
-    float* eig = (float*)lvk_ctx_scratch(ctx, 1, sizeof(float) * (size_t)w * h);
+    float* eig = (float*)lvk_ctx_scratch(ctx, LVK_SCR_GFTT_EIG, sizeof(float) * (size_t)w * h);
     if (!eig) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
     lvk_status st = lvk_min_eigen_map(ctx, p, eig);
     if (st == LVK_OK) st = lvk_good_features_from_map(ctx, eig, d_mask, w, h, max_corners, quality, min_distance, d_out, cap, d_n_out);

@@ -49,7 +49,25 @@ static inline void* lvk_bar_alloc(int device, size_t bytes)
 #define LVK_MAX_LEVELS 8
 #define LVK_ORB_BORDER 32
 
-#define LVK_SCRATCH_SLOTS 16
+// Scratch slots of a context (lvk_ctx_scratch): one name per user, or per group of users that share a buffer on purpose.
+// Sharing is safe under one rule: every user of a shared slot ends with a wait for the context's stream (or, where it returns with work
+// still queued, is followed on that stream by whatever reuses the buffer), and lvk_ctx_scratch waits for the stream before it frees a
+// buffer to grow it - so no two users ever have work in flight on one buffer.
+enum lvk_scratch_slot {
+    LVK_SCR_CLAHE_LUT,                  // front-end: CLAHE look-up tables
+    LVK_SCR_GFTT_EIG,                   // corner selection, stage entry: response map
+    LVK_SCR_GFTT_WORK,                  // corner selection: counters and bins
+    LVK_SCR_GFTT_CANDS,                 // corner selection: candidate keys
+    LVK_SCR_UPDATE_B,                   // measurement update: B = [H P | r]
+    LVK_SCR_UPDATE_S,                   // measurement update: S
+    LVK_SCR_UPDATE_INFO,                // measurement update: the factorisation's report words
+    LVK_SCR_QR_H, LVK_SCR_QR_R,         // shared by the grouped-QR stage entry (ping-pong copy of H, r) and CAQR (V, T): one runs after the other on the stream
+    LVK_SCR_STAGE_IN, LVK_SCR_STAGE_MID, LVK_SCR_STAGE_OUT,   // shared by every stage entry (input blob, staging, output blob): each ends with a stream wait
+    LVK_SCR_CHOL_WS,                    // fused Cholesky: diagonal-block inverses and the panel flag (lvk_context::chol_epoch)
+    LVK_SCR_LDLT_WS,                    // LDL^T update: pivot-ordered copies of [HP | r] and X, D, the permutation, the counters
+    LVK_SCRATCH_SLOTS
+};
+#define LVK_LDS_OPTIN_KERNELS 24        // kernels that ask for more dynamic LDS than the default (fewer than that today)
 struct lvk_context {
     int device;
     hipStream_t stream;
@@ -60,18 +78,29 @@ struct lvk_context {
     void* scratch[LVK_SCRATCH_SLOTS];
     size_t scratch_bytes[LVK_SCRATCH_SLOTS];
     // dynamic-LDS opt-ins (hipFuncAttributeMaxDynamicSharedMemorySize) already made through THIS context: function attributes are
-    // per device, so the cache lives here and not in a process-wide static (one slot per kernel instantiation, numbered at the call sites)
-    size_t lds_optin[24];
+    // per device, so the cache lives here and not in a process-wide static.  Keyed on the kernel's function pointer, filled in order
+    // of first use, searched linearly: two kernels cannot share an entry
+    struct { const void* fn; size_t bytes; } lds_optin[LVK_LDS_OPTIN_KERNELS];
     // fused Cholesky + solve (be_linalg.hip, k_chol_fused): the factor workgroup hands panels to the solver workgroups through a flag
-    // that only ever grows; chol_epoch numbers the launches, chol_ws (scratch slot 12) holds the diagonal-block inverses and the flag
+    // that only ever grows; chol_epoch numbers the launches, chol_ws (LVK_SCR_CHOL_WS) holds the diagonal-block inverses and the flag
     int chol_epoch;
 };
+// the bytes this context has already opted `fn` in to (a fresh entry: 0); nullptr when the table is full - the caller then opts in uncached
+static inline size_t* lvk_lds_optin_entry(lvk_context* ctx, const void* fn)
+{
+    for (int i = 0; i < LVK_LDS_OPTIN_KERNELS; ++i) {
+        if (ctx->lds_optin[i].fn == fn) return &ctx->lds_optin[i].bytes;
+        if (!ctx->lds_optin[i].fn) { ctx->lds_optin[i].fn = fn; return &ctx->lds_optin[i].bytes; }
+    }
+    return nullptr;
+}
 // opt in to `bytes` of dynamic LDS for `fn` if this context has not already asked for at least that much
-#define LVK_LDS_OPTIN(ctx, slot, fn, bytes)                                                                             \
+#define LVK_LDS_OPTIN(ctx, fn, bytes)                                                                                   \
     do {                                                                                                                \
-        if ((ctx)->lds_optin[slot] < (size_t)(bytes)) {                                                                 \
+        size_t* have_ = lvk_lds_optin_entry((ctx), (const void*)(fn));                                                  \
+        if (!have_ || *have_ < (size_t)(bytes)) {                                                                       \
             LVK_HIP(ctx, hipFuncSetAttribute((const void*)(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes))); \
-            (ctx)->lds_optin[slot] = (size_t)(bytes);                                                                   \
+            if (have_) *have_ = (size_t)(bytes);                                                                        \
         }                                                                                                               \
     } while (0)
 void* lvk_ctx_scratch(lvk_context* ctx, int slot, size_t bytes);
