@@ -47,6 +47,13 @@ class LarVio {
     bool setMsckfPoints(bool on);
     void takeMsckfPoints(std::vector<FeatureIDType>& ids, std::vector<Eigen::Vector3d>& positions, std::vector<double>& cov9, std::vector<int>& n_obs);
 
+    // not in the reference: the clones the pruning removes, each with its absolute 6 x 6 covariance and the covariance of its pose
+    // relative to the nearest newer surviving clone (lvk_ekf_set_keyframe_export / lvk_ekf_take_keyframes, lvk_c.h; drained on read),
+    // and the same for the clones still in the window (lvk_ekf_get_window_cov: 36 doubles per clone each, row-major)
+    bool setKeyframeExport(bool on);
+    void takeKeyframes(std::vector<lvk_keyframe>& keyframes);
+    bool getWindowCov(std::vector<long long>& ids, std::vector<double>& cov_abs36, std::vector<double>& cov_rel36);
+
     typedef boost::shared_ptr<LarVio> Ptr;
     typedef boost::shared_ptr<const LarVio> ConstPtr;
 

@@ -207,6 +207,37 @@ void LarVio::takeMsckfPoints(std::vector<FeatureIDType>& ids, std::vector<Eigen:
     }
 }
 
+bool LarVio::setKeyframeExport(bool on)
+{
+    finish();
+    return ekf && lvk_ekf_set_keyframe_export(ekf, on ? 1 : 0) == LVK_OK;
+}
+
+void LarVio::takeKeyframes(std::vector<lvk_keyframe>& keyframes)
+{
+    finish();
+    keyframes.clear();
+    std::vector<lvk_keyframe> buf(1024);
+    for (;;) {
+        const int n = lvk_ekf_take_keyframes(ekf, buf.data(), 1024);
+        keyframes.insert(keyframes.end(), buf.begin(), buf.begin() + n);
+        if (n < 1024) break;
+    }
+}
+
+bool LarVio::getWindowCov(std::vector<long long>& ids, std::vector<double>& cov_abs36, std::vector<double>& cov_rel36)
+{
+    finish();
+    std::vector<int64_t> id(256); cov_abs36.resize(36 * 256); cov_rel36.resize(36 * 256);
+    int n = 0;
+    const bool ok = ekf && lvk_ekf_get_window_cov(ekf, id.data(), cov_abs36.data(), cov_rel36.data(), 256, &n) == LVK_OK;
+    if (!ok) n = 0;
+    ids.clear();
+    for (int i = 0; i < n; ++i) ids.push_back((long long)id[(size_t)i]);
+    cov_abs36.resize((size_t)36 * n); cov_rel36.resize((size_t)36 * n);
+    return ok;
+}
+
 void LarVio::getActiveeMapPointPositions(std::map<larvio::FeatureIDType, Eigen::Vector3d>& mMapPoints)
 {
     finish();

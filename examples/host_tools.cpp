@@ -6,6 +6,8 @@
 //   host_tools images <data.csv>           one "stamp name" line per image
 //   host_tools euroc-args [options...]     the dataset driver's options as it parses them, one "name value" line each (exit 1 + the
 //                                          driver's message on an unknown option)
+//   host_tools euroc-args-all [options...] the same with every field (euroc-args keeps the six lines it has always printed)
+//   host_tools keyframe-line <id> <to_id> <88 doubles: time to_time q p rel_q rel_p cov_abs cov_rel>      the --keyframes-out line of that record
 //   host_tools msckf-line <id> <x y z> <9 covariance entries, row-major> <n_obs>      the --msckf-out line of that point
 #include "lvk_config.hpp"
 #include "lvk_dataset.hpp"
@@ -70,11 +72,23 @@ int main(int argc, char** argv)
                     o.max_frames, o.pipelined ? 1 : 0);
         return 0;
     }
+    if (argc >= 2 && !std::strcmp(argv[1], "euroc-args-all")) {
+        lvk::EurocArgs o; std::string bad;
+        if (!lvk::parse_euroc_args(argc, argv, 2, &o, &bad)) { std::fprintf(stderr, "unknown option %s\n", bad.c_str()); return 1; }
+        std::printf("tum %s\nmask %s\nmap_out %s\nmsckf_out %s\nkeyframes_out %s\nmax_frames %ld\npipelined %d\n", o.tum.c_str(), o.mask.c_str(), o.map_out.c_str(),
+                    o.msckf_out.c_str(), o.keyframes_out.c_str(), o.max_frames, o.pipelined ? 1 : 0);
+        return 0;
+    }
+    if (argc == 92 && !std::strcmp(argv[1], "keyframe-line")) {
+        double v[88]; for (int i = 0; i < 88; ++i) v[i] = std::strtod(argv[4 + i], nullptr);
+        lvk::write_keyframe(stdout, std::atoll(argv[2]), std::atoll(argv[3]), v);
+        return 0;
+    }
     if (argc == 16 && !std::strcmp(argv[1], "msckf-line")) {
         double v[12]; for (int i = 0; i < 12; ++i) v[i] = std::strtod(argv[3 + i], nullptr);
         lvk::write_msckf_point(stdout, std::atoll(argv[2]), v, v + 3, std::atoi(argv[15]));
         return 0;
     }
-    std::fprintf(stderr, "usage: host_tools config|png|imu|images|euroc-args|msckf-line ...\n");
+    std::fprintf(stderr, "usage: host_tools config|png|imu|images|euroc-args|euroc-args-all|msckf-line|keyframe-line ...\n");
     return 2;
 }

@@ -2,7 +2,7 @@
 // Pangolin): same command line, same loop, same log files (msckf_2_state.txt / msckf_2_takeoff.txt in the configuration's
 // output_dir, written by lvk::LarVio as larvio.cpp:388,446-453 does), running on liblvk_hip.so.
 //
-//   larvio_euroc path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE]
+//   larvio_euroc path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE] [--keyframes-out FILE]
 //
 // --mask restricts corner detection to the non-zero pixels of an 8-bit PNG of the configured resolution (ImageProcessor::setMask:
 // a fisheye vignette, the vehicle's own body); a mask of another size is an error.
@@ -11,6 +11,10 @@
 // --msckf-out turns the filter's MSCKF-point export on (LarVio::setMsckfPoints) and writes one line per point the lost-feature updates
 // triangulated, accepted and erased: "id x y z" + the nine entries of its 3 x 3 position covariance, row-major + its observation count.
 // The list is drained after every update; --pipelined drains it once, at the end (the filter keeps the newest 65536 points).
+// --keyframes-out turns the filter's keyframe export on (LarVio::setKeyframeExport) and writes one line per clone the pruning removed:
+// "id to_id time to_time q(4) p(3) rel_q(4) rel_p(3) cov_abs(36) cov_rel(36)" - its pose, the pose of clone to_id relative to it, its
+// absolute 6 x 6 covariance and the covariance of that relative pose (lvk_c.h, lvk_ekf_pose_rel_cov).  Drained after every update;
+// --pipelined drains once, at the end.
 // --tum writes "t x y z qx qy qz qw" (body in world, absolute stamps, 17 significant digits) for tools/traj_rmse.py.
 // --pipelined runs the same loop through lvk::VioPipeline: the filter update of a message overlaps the front-end of the next
 // frames on a second HIP stream; the trajectory is the same, written from the filter thread's odometry callback.
@@ -64,6 +68,21 @@ struct MsckfOut {
     void close() { if (f) { std::fclose(f); f = nullptr; } }
 };
 
+// --keyframes-out: the pruned clones collected so far (drained after every update)
+struct KeyframesOut {
+    FILE* f; long n;
+    void drain(lvk::LarVio& Estimator)
+    {
+        if (!f) return;
+        std::vector<lvk_keyframe> kf;
+        do {
+            Estimator.takeKeyframes(kf);
+            for (size_t i = 0; i < kf.size(); ++i, ++n) lvk::write_keyframe(f, (long long)kf[i].id, (long long)kf[i].to_id, &kf[i].time);
+        } while (!kf.empty());
+    }
+    void close() { if (f) { std::fclose(f); f = nullptr; } }
+};
+
 struct OdometrySink { FILE* tum; long n_odo; };
 static void on_odometry(void* user, double, const lvk::LarVio& Estimator)
 {
@@ -73,7 +92,7 @@ static void on_odometry(void* user, double, const lvk::LarVio& Estimator)
 }
 
 static int run_pipelined(const char* image_dir, const std::vector<lvk::ImuData>& allImuData, const std::vector<lvk::ImgInfo>& allImgInfo, long max_frames,
-                         lvk::ImageProcessor& ImgProcesser, lvk::LarVio& Estimator, FILE* tum, MapOut& map_out, MsckfOut& msckf_out)
+                         lvk::ImageProcessor& ImgProcesser, lvk::LarVio& Estimator, FILE* tum, MapOut& map_out, MsckfOut& msckf_out, KeyframesOut& kf_out)
 {
     typedef std::chrono::steady_clock Clock;
     lvk::VioPipeline pipe(ImgProcesser, Estimator);
@@ -103,6 +122,7 @@ static int run_pipelined(const char* image_dir, const std::vector<lvk::ImuData>&
     if (tum) std::fclose(tum);
     map_out.drain(Estimator); map_out.close();
     msckf_out.drain(Estimator); msckf_out.close();
+    kf_out.drain(Estimator); kf_out.close();
     std::printf("frames %zu  feature messages %ld  odometry updates %ld  state dim %d\n", n_frames, n_msgs, sink.n_odo, lvk_ekf_dim(Estimator.handle()));
     std::printf("pipelined: %.3f ms/frame in the driver thread   image read+decode %.3f ms/frame\n", n_frames ? 1e3 * t_proc / n_frames : 0.0, n_frames ? 1e3 * t_io / n_frames : 0.0);
     if (t_proc > 0) std::printf("processing rate %.1f frames/s (pipelined, host buffers)\n", n_frames / t_proc);
@@ -112,7 +132,7 @@ static int run_pipelined(const char* image_dir, const std::vector<lvk::ImuData>&
 int main(int argc, char** argv)
 {
     if (argc < 5) {
-        std::fprintf(stderr, "Usage: %s path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE]\n", argv[0]);
+        std::fprintf(stderr, "Usage: %s path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE] [--keyframes-out FILE]\n", argv[0]);
         return 1;
     }
     lvk::EurocArgs opt; std::string bad;
@@ -159,7 +179,12 @@ int main(int argc, char** argv)
         if (!(msckf_out.f = std::fopen(opt.msckf_out.c_str(), "w"))) { std::perror(opt.msckf_out.c_str()); return 1; }
         if (!Estimator.setMsckfPoints(true)) { std::fprintf(stderr, "larvio_euroc: %s\n", (pipelined ? ctx2 : ctx).error()); return 1; }
     }
-    if (pipelined) return run_pipelined(argv[3], allImuData, allImgInfo, max_frames, ImgProcesser, Estimator, tum, map_out, msckf_out);
+    KeyframesOut kf_out = {nullptr, 0};
+    if (!opt.keyframes_out.empty()) {
+        if (!(kf_out.f = std::fopen(opt.keyframes_out.c_str(), "w"))) { std::perror(opt.keyframes_out.c_str()); return 1; }
+        if (!Estimator.setKeyframeExport(true)) { std::fprintf(stderr, "larvio_euroc: %s\n", (pipelined ? ctx2 : ctx).error()); return 1; }
+    }
+    if (pipelined) return run_pipelined(argv[3], allImuData, allImgInfo, max_frames, ImgProcesser, Estimator, tum, map_out, msckf_out, kf_out);
 
     typedef std::chrono::steady_clock Clock;
     double t_fe = 0, t_be = 0, t_io = 0; long n_fe = 0, n_be = 0, n_odo = 0;
@@ -193,10 +218,12 @@ int main(int argc, char** argv)
             if (tum) write_tum(tum, Estimator);
         }
         msckf_out.drain(Estimator);
+        kf_out.drain(Estimator);
     }
     if (tum) std::fclose(tum);
     map_out.drain(Estimator); map_out.close();
     msckf_out.drain(Estimator); msckf_out.close();
+    kf_out.drain(Estimator); kf_out.close();
     std::printf("frames %ld  feature messages %ld  odometry updates %ld  state dim %d\n", n_fe, n_be, n_odo, lvk_ekf_dim(Estimator.handle()));
     std::printf("front-end %.3f ms/frame   back-end %.3f ms/message   image read+decode %.3f ms/frame\n", n_fe ? 1e3 * t_fe / n_fe : 0.0,
                 n_be ? 1e3 * t_be / n_be : 0.0, n_fe ? 1e3 * t_io / n_fe : 0.0);

@@ -1,5 +1,5 @@
 // lvk_euroc_args.hpp — the options of examples/larvio_euroc after its four positional arguments, and the line format of its
-// --msckf-out file; host-only, so that examples/host_tools can show both on a machine without a GPU.
+// --msckf-out and --keyframes-out files; host-only, so that examples/host_tools can show both on a machine without a GPU.
 #pragma once
 #include <cstdio>
 #include <cstdlib>
@@ -8,7 +8,7 @@
 
 namespace lvk {
 
-struct EurocArgs { std::string tum, mask, map_out, msckf_out; long max_frames; bool pipelined; EurocArgs() : max_frames(-1), pipelined(false) {} };
+struct EurocArgs { std::string tum, mask, map_out, msckf_out, keyframes_out; long max_frames; bool pipelined; EurocArgs() : max_frames(-1), pipelined(false) {} };
 
 // argv[first..]: false, with the offending word in *bad, on an unknown option or an option without its value
 inline bool parse_euroc_args(int argc, char** argv, int first, EurocArgs* o, std::string* bad)
@@ -20,6 +20,7 @@ inline bool parse_euroc_args(int argc, char** argv, int first, EurocArgs* o, std
         else if (!std::strcmp(argv[a], "--mask") && a + 1 < argc) o->mask = argv[++a];
         else if (!std::strcmp(argv[a], "--map-out") && a + 1 < argc) o->map_out = argv[++a];
         else if (!std::strcmp(argv[a], "--msckf-out") && a + 1 < argc) o->msckf_out = argv[++a];
+        else if (!std::strcmp(argv[a], "--keyframes-out") && a + 1 < argc) o->keyframes_out = argv[++a];
         else { if (bad) *bad = argv[a]; return false; }
     }
     return true;
@@ -30,6 +31,15 @@ inline void write_msckf_point(FILE* f, long long id, const double* p, const doub
 {
     std::fprintf(f, "%lld %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %d\n", id, p[0], p[1], p[2], c[0], c[1], c[2], c[3], c[4],
                  c[5], c[6], c[7], c[8], n_obs);
+}
+
+// one --keyframes-out line: "id to_id time to_time q(4) p(3) rel_q(4) rel_p(3) cov_abs(36) cov_rel(36)", the matrices row-major (17
+// significant digits: the doubles round-trip); v: the 88 doubles from time on, in that order
+inline void write_keyframe(FILE* f, long long id, long long to_id, const double* v)
+{
+    std::fprintf(f, "%lld %lld", id, to_id);
+    for (int i = 0; i < 88; ++i) std::fprintf(f, " %.17g", v[i]);
+    std::fprintf(f, "\n");
 }
 
 }   // namespace lvk

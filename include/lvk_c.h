@@ -337,6 +337,35 @@ typedef struct { int anchor_col, feat_col, pad0, pad1;      /* first of the anch
                  double obs_anchor[2], inv_depth; } lvk_landmark_job;
 lvk_status lvk_ekf_landmark_cov(lvk_context* ctx, const double* d_P, int ldp, int n, const lvk_landmark_job* h_jobs, int n_jobs, double* h_cov9);
 
+/* Covariance of one pose relative to another (and the absolute 6 x 6 block of one pose), one 6 x 6 matrix per job, read off a
+ * device-resident covariance (n x n, row-major, leading dimension ldp) without moving it.  The error state is the one the filter's
+ * state injection applies (larvio.cpp:1476-1575):
+ *   attitude   q <- small_angle_quat(d_theta) * q     (Hamilton, [x y z w]; R(q) maps body to world), i.e. R <- (I + [d_theta]x) R
+ *   position   p <- p + d_p
+ * A clone's columns are leg_dim + 6 c (d_theta) and leg_dim + 6 c + 3 (d_p); the IMU state's are 0..2 and 6..8 (velocity sits between
+ * them), which is why a job names the first d_theta column and the first d_p column of each pose separately.
+ * For two poses a, b:  R_ab = R_a^T R_b,  p_ab = R_a^T (p_b - p_a),  d = p_b - p_a.  The error of the relative pose is defined by
+ *   R_ab,true = (I + [d_phi]x) R_ab,   p_ab,true = p_ab + d_rho,
+ * and to first order, under the injection above,
+ *   d_phi = R_a^T (d_theta_b - d_theta_a),   d_rho = R_a^T [d]x d_theta_a + R_a^T (d_p_b - d_p_a).
+ * With the column order [d_theta_a d_p_a d_theta_b d_p_b] and the output order [d_phi; d_rho], Sigma_rel = J P[those, those] J^T with
+ *   J = [ -R_a^T       0      R_a^T  0
+ *          R_a^T [d]x  -R_a^T  0      R_a^T ].
+ * (The signs were confirmed against inject() by central differences of (log(R_ab' R_ab^T), p_ab' - p_ab) under that injection:
+ * tests/pose_rel_ref.py; they agree with the form above.)  A rigid motion of the world (d_theta_a = d_theta_b = theta,
+ * d_p_x = [theta]x p_x + t) gives d_phi = d_rho = 0: the four unobservable directions of a VIO, in which the absolute covariance
+ * grows without bound, cancel in Sigma_rel.
+ * An ABSOLUTE job (a_theta_col < 0; a_p_col, q_a, p_a, q_b, p_b unused) returns the 6 x 6 block of b in the order [d_theta_b d_p_b]: a
+ * pure gather, bit for bit the entries of P (so as symmetric as P is).
+ * Nothing outside the job's twelve (six) rows and columns of P is read; every sum runs in a fixed order (the same input gives the
+ * same bits); for a relative job the lower triangle is a copy of the upper one.  q_b is not used by the covariance (it is part of
+ * the job so that one record describes both poses).  h_cov36: 36 doubles per job, row-major.  The call waits for its launch.
+ * LVK_ERR_ARG, with nothing launched and the context still usable, when a pointer is null, n_jobs < 0, ldp < n, or a column triple
+ * a job names (c..c+2 for each of its four - absolute: two - columns) leaves [0, n).  n_jobs == 0 is LVK_OK. */
+typedef struct { int a_theta_col, a_p_col, b_theta_col, b_p_col;   /* first of three columns each; a_theta_col < 0: absolute job */
+                 double q_a[4], p_a[3], q_b[4], p_b[3]; } lvk_pose_rel_job;
+lvk_status lvk_ekf_pose_rel_cov(lvk_context* ctx, const double* d_P, int ldp, int n, const lvk_pose_rel_job* h_jobs, int n_jobs, double* h_cov36);
+
 typedef struct {
     /* names and meaning as LarVio::loadParameters reads them (larvio.cpp:58-311, config/euroc.yaml) */
     int if_fej, estimate_extrin, estimate_td, if_zupt_valid;
@@ -485,6 +514,41 @@ int        lvk_ekf_take_lost_features_cov(lvk_ekf* e, int64_t* h_ids, double* h_
  * is a transport while the switch is on. */
 lvk_status lvk_ekf_set_msckf_points(lvk_ekf* e, int on);
 int        lvk_ekf_take_msckf_points(lvk_ekf* e, int64_t* h_ids, double* h_pos_w, double* h_cov9, int* h_n_obs, int cap);
+/* The keyframe export: the pose side of the two exports above.  A clone that the pruning removes from the window is gone, and the only
+ * pose uncertainty a caller can otherwise get is the absolute one (lvk_ekf_get_cov_imu), which grows without bound along the four
+ * unobservable directions.  lvk_ekf_set_keyframe_export (off by default) keeps every pruned clone as a record with the covariances of
+ * lvk_ekf_pose_rel_cov (conventions there): while on, the pruning - the two-clone case and the zero-velocity one-clone case - queues one
+ * absolute and one relative job for each clone it removes, AFTER the pruning update's correction has been injected and BEFORE the
+ * clone's rows and columns leave the covariance: the last covariance in which the clone exists, with the poses that belong to it.
+ * b (to_id) is the nearest NEWER clone that survives this pruning; two adjacent removed clones share it.  Every record therefore points
+ * forward in time to a clone that is exported later or is still in the window (lvk_ekf_get_window_cov): the records form a connected
+ * chain.  The results go to the filter's pinned download buffer and are attached to the records by the time the update's call,
+ * lvk_ekf_wait or any getter returns; a pruning update that would otherwise return without any wait behind that launch makes one
+ * more stream wait - only while the switch is on.  With it off the filter launches exactly the kernels it launched before this entry
+ * point existed.  State, covariance and counters are the same bits with the switch on or off; blocking, deferred and pipelined
+ * (lvk_vio_pipe) runs give the same records.
+ *   id, time        the removed clone (a);  to_id, to_time: b
+ *   q, p            a's pose (body in world) as the filter last held it
+ *   rel_q, rel_p    R_ab = R_a^T R_b as a quaternion [x y z w], p_ab = R_a^T (p_b - p_a), from the poses of that instant
+ *   cov_abs         a's 6 x 6 block, order [d_theta d_p], row-major: bit for bit the entries of the covariance
+ *   cov_rel         Sigma_rel of (a, b), order [d_phi d_rho], row-major, exactly symmetric
+ * lvk_ekf_take_keyframes drains the list in pruning order (within one pruning: ascending id), up to cap records per call, and returns
+ * the count.  The list holds at most 65536 records: the oldest half goes when it is full.
+ * lvk_ekf_get_window_cov: for the clones of lvk_ekf_get_clones, in that order (up to cap; *n_out = how many), each clone's id, its
+ * absolute block (36 doubles) and, for clone i < n - 1, Sigma_rel to clone i + 1 (36 doubles); the last clone gets 36 NaNs.  One
+ * launch and one wait, on the context's stream behind whatever is queued.  h_ids, h_cov_abs36, h_cov_rel36 may each be null.  A failed
+ * handle answers as lvk_ekf_get_cov does.
+ * The edges are marginals of ONE joint distribution: consecutive relative poses share clones and are correlated.  Using them as
+ * independent factors of a pose graph is the usual approximation, not an identity.
+ * The sharded update does not export: with a transport set (lvk_ekf_set_shard) switching on is refused with LVK_ERR_UNSUPPORTED, and so
+ * is a transport while the switch is on. */
+typedef struct { int64_t id, to_id; double time, to_time;
+                 double q[4], p[3];            /* the clone's pose as the filter last held it */
+                 double rel_q[4], rel_p[3];    /* R_ab as a quaternion, p_ab; a = this clone, b = to_id */
+                 double cov_abs[36], cov_rel[36]; } lvk_keyframe;
+lvk_status lvk_ekf_set_keyframe_export(lvk_ekf* e, int on);
+int        lvk_ekf_take_keyframes(lvk_ekf* e, lvk_keyframe* h_out, int cap);
+lvk_status lvk_ekf_get_window_cov(lvk_ekf* e, int64_t* h_ids, double* h_cov_abs36, double* h_cov_rel36, int cap, int* n_out);
 /* What the moving-start initialiser (FlexibleInitializer.cpp:11-25 -> DynamicInitializer.cpp) handed to the filter, with the intermediate
  * results of the successful attempt - for parity tests against an independent restatement fed the same messages:
  *   valid        1 once the dynamic initialiser has succeeded on this handle (0: never ran, or the static one fired)

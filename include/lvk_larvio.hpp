@@ -200,6 +200,27 @@ public:
         const int n = ekf_ ? lvk_ekf_take_msckf_points(ekf_, ids.data(), xyz.data(), cov.data(), n_obs.data(), 4096) : 0;
         ids.resize((size_t)n); xyz.resize((size_t)3 * n); cov.resize((size_t)9 * n); n_obs.resize((size_t)n);
     }
+    // The keyframe export (lvk_ekf_set_keyframe_export / lvk_ekf_take_keyframes / lvk_ekf_get_window_cov; conventions in lvk_c.h):
+    // setKeyframeExport(true), after initialize(), makes the pruning keep every clone it removes as an lvk_keyframe - pose, absolute
+    // 6 x 6 covariance and the covariance of its pose relative to the nearest newer surviving clone; takeKeyframes hands out up to 1024
+    // of them per call.  getWindowCov: the clones still in the window - ids, 36 doubles of absolute block each and 36 of Sigma_rel to
+    // the next clone (NaN for the last).
+    bool setKeyframeExport(bool on) { return ekf_ && lvk_ekf_set_keyframe_export(ekf_, on ? 1 : 0) == LVK_OK; }
+    void takeKeyframes(std::vector<lvk_keyframe>& out)
+    {
+        out.resize(1024);
+        const int n = ekf_ ? lvk_ekf_take_keyframes(ekf_, out.data(), 1024) : 0;
+        out.resize((size_t)n);
+    }
+    bool getWindowCov(std::vector<int64_t>& ids, std::vector<double>& cov_abs, std::vector<double>& cov_rel) const
+    {
+        ids.resize(256); cov_abs.resize(36 * 256); cov_rel.resize(36 * 256);
+        int n = 0;
+        const bool ok = ekf_ && lvk_ekf_get_window_cov(ekf_, ids.data(), cov_abs.data(), cov_rel.data(), 256, &n) == LVK_OK;
+        if (!ok) n = 0;
+        ids.resize((size_t)n); cov_abs.resize((size_t)36 * n); cov_rel.resize((size_t)36 * n);
+        return ok;
+    }
     lvk_ekf* handle() const { return ekf_; }
 private:
     friend class VioPipeline;

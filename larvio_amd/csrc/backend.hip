@@ -203,6 +203,12 @@ struct lvk_ekf {
     struct MsckfPoint { long long id; double p[3]; double cov[9]; int n_obs; };
     std::vector<MsckfPoint> msckf_points;
     bool msckf_points_on = false; size_t down_mp = 0, down_mpok = 0, mp_lo = 0; int mp_cap = 0, mp_n = 0;
+    // lvk_ekf_set_keyframe_export: the clones the pruning removes, each with its absolute 6 x 6 block and the covariance of its pose
+    // relative to the nearest newer surviving clone (k_pose_rel_cov), computed before its columns leave P (drained on read).
+    // kf_pending: the last kf_pending entries of keyframes wait for their results - record i's absolute block in slot 2 i of the
+    // download buffer (down_kf), its relative one in slot 2 i + 1 - attached like the lost-feature covariance (kf_mark as lost_cov_mark)
+    std::vector<lvk_keyframe> keyframes;
+    bool keyframes_on = false; size_t down_kf = 0; int kf_pending = 0, kf_mark = 0;
     double sigma2, zupt_v2, zupt_p2, zupt_q2, imu_img_time_th, Qc[12];
     double x_min, y_min, grid_w, grid_h;
     std::vector<int> grid_count;
@@ -502,6 +508,62 @@ static lvk_status lost_cov_attach(lvk_ekf* e)
     const double* src = (const double*)(e->h_down + e->down_lm);
     for (size_t i = 0; i < k; ++i) if (e->lost_cov_slot[i] >= 0) memcpy(e->lost_slam[base + i].cov, src + 9 * (size_t)e->lost_cov_slot[i], 72);
     e->lost_cov_slot.clear();
+    return LVK_OK;
+}
+// lvk_ekf_set_keyframe_export: one record per clone in rm (those in the window, ascending rank), and k_pose_rel_cov queued for them on the
+// covariance as it is now (the pruning update applied, their columns still in place); b = the nearest newer clone not in rm
+static lvk_status keyframes_queue(lvk_ekf* e, const long long* rm, int nrm)
+{
+    int ra[2], n = 0;
+    for (int k = 0; k < nrm && k < 2; ++k) { const int r = clone_rank(e, rm[k]); if (r >= 0) ra[n++] = r; }
+    if (n == 2 && ra[0] > ra[1]) std::swap(ra[0], ra[1]);
+    if (n == 0) return LVK_OK;
+    lvk_pose_rel_job* hj = up_alloc<lvk_pose_rel_job>(e, (size_t)2 * n);
+    if (!hj) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "upload arena exhausted");
+    memset(hj, 0, sizeof(lvk_pose_rel_job) * 2 * (size_t)n);
+    if (e->keyframes.size() + (size_t)n > (size_t)1 << 16) e->keyframes.erase(e->keyframes.begin(), e->keyframes.begin() + (1 << 15));
+    for (int i = 0; i < n; ++i) {
+        const Clone& a = e->clones[(size_t)ra[i]];
+        int rb = ra[i] + 1;
+        while (rb < (int)e->clones.size() && (rb == ra[0] || rb == ra[n - 1])) ++rb;
+        lvk_keyframe kf; memset(&kf, 0, sizeof kf);
+        kf.id = a.id; kf.time = a.time; memcpy(kf.q, a.q, 32); memcpy(kf.p, a.p, 24);
+        for (int t = 0; t < 36; ++t) kf.cov_abs[t] = kf.cov_rel[t] = NAN;
+        lvk_pose_rel_job* ja = hj + 2 * i; lvk_pose_rel_job* jr = ja + 1;
+        ja->a_theta_col = ja->a_p_col = -1; ja->b_theta_col = LEG + 6 * ra[i]; ja->b_p_col = ja->b_theta_col + 3;
+        memcpy(ja->q_b, a.q, 32); memcpy(ja->p_b, a.p, 24);
+        *jr = *ja;                                      // no newer clone survives (the pruning never removes the newest): the absolute block twice, NaN kept below
+        kf.to_id = -1; kf.to_time = NAN;
+        for (int t = 0; t < 4; ++t) kf.rel_q[t] = NAN;
+        for (int t = 0; t < 3; ++t) kf.rel_p[t] = NAN;
+        if (rb < (int)e->clones.size()) {
+            const Clone& b = e->clones[(size_t)rb];
+            kf.to_id = b.id; kf.to_time = b.time;
+            const double qa_inv[4] = {-a.q[0], -a.q[1], -a.q[2], a.q[3]}, d[3] = {b.p[0] - a.p[0], b.p[1] - a.p[1], b.p[2] - a.p[2]};
+            double Ra[9];
+            quat_mul(qa_inv, b.q, kf.rel_q); quat_to_rot(a.q, Ra); m3t_v(Ra, d, kf.rel_p);
+            jr->a_theta_col = LEG + 6 * ra[i]; jr->a_p_col = jr->a_theta_col + 3; jr->b_theta_col = LEG + 6 * rb; jr->b_p_col = jr->b_theta_col + 3;
+            memcpy(jr->q_a, a.q, 32); memcpy(jr->p_a, a.p, 24); memcpy(jr->q_b, b.q, 32); memcpy(jr->p_b, b.p, 24);
+        }
+        if (!lvk_pose_rel_job_ok(ja, e->N) || !lvk_pose_rel_job_ok(jr, e->N)) return lvk_set_error(e->ctx, LVK_ERR_ARG, "internal: a keyframe job leaves the %d x %d covariance", e->N, e->N);
+        e->keyframes.push_back(kf);
+    }
+    e->kf_pending = n; e->kf_mark = e->n_sync;
+    const double* P = e->dP[e->cur]; const lvk_pose_rel_job* d_jobs = dev(e, hj); double* out = (double*)(e->dh_down + e->down_kf);
+    return run_or_defer(e, [=]() { return lvk_launch_pose_rel_cov(e->ctx, P, e->ld, d_jobs, 2 * n, out); });
+}
+static lvk_status keyframes_attach(lvk_ekf* e)
+{
+    if (e->kf_pending <= 0) return LVK_OK;
+    if (e->n_sync == e->kf_mark) { EKF_HIP(hipStreamSynchronize(e->ctx->stream)); e->n_sync++; }
+    const size_t k = (size_t)e->kf_pending, base = e->keyframes.size() - k;
+    const double* src = (const double*)(e->h_down + e->down_kf);
+    for (size_t i = 0; i < k; ++i) {
+        lvk_keyframe& kf = e->keyframes[base + i];
+        memcpy(kf.cov_abs, src + 72 * i, 288);
+        if (kf.to_id >= 0) memcpy(kf.cov_rel, src + 72 * i + 36, 288);
+    }
+    e->kf_pending = 0;
     return LVK_OK;
 }
 // P loses the rows / columns marked in drop (N flags)
@@ -2089,6 +2151,7 @@ static lvk_status prune_imu_state_buffer(lvk_ekf* e)
             any = true;
         }
         if (any) {
+            if (e->keyframes_on) { st = keyframes_queue(e, rm, nrm); if (st != LVK_OK) return st; }
             st = cov_drop(e, drop);
             if (st != LVK_OK) return st;
             for (int k = 0; k < nrm; ++k) { const int seq = clone_rank(e, rm[k]); if (seq >= 0) { e->clones.erase(e->clones.begin() + seq); e->ranks_dirty = true; e->rcam_valid = false; } }
@@ -2371,7 +2434,8 @@ lvk_status lvk_ekf_create(lvk_context* ctx, const lvk_ekf_config* cfg, lvk_ekf**
     e->down_mp = e->down_lm + ((sizeof(double) * 9 * (size_t)e->lm_cap + 255) & ~(size_t)255);     // lvk_ekf_set_msckf_points: 9 doubles + an ok word per MSCKF job of one update
     e->mp_cap = 2 * e->feat_cap;
     e->down_mpok = e->down_mp + ((sizeof(double) * 9 * (size_t)e->mp_cap + 255) & ~(size_t)255);
-    e->down_cap = e->down_mpok + ((sizeof(int) * (size_t)e->mp_cap + 255) & ~(size_t)255);
+    e->down_kf = e->down_mpok + ((sizeof(int) * (size_t)e->mp_cap + 255) & ~(size_t)255);         // lvk_ekf_set_keyframe_export: 2 x 36 doubles per removed clone, two clones per pruning
+    e->down_cap = e->down_kf + 4 * 36 * sizeof(double);
     ok = ok && hipHostMalloc((void**)&e->h_up, e->up_cap) == hipSuccess && hipHostMalloc((void**)&e->h_down, e->down_cap) == hipSuccess;
     if (ok) {
         // No copy commands on the filter's chain (each ~8 us of API + copy + barrier; ten of them were 385 -> 336 us per update):
@@ -2539,7 +2603,7 @@ static lvk_status ekf_process_impl(lvk_ekf* e, double ts, const lvk_feature_obs*
     e->up_half ^= 1; e->n_sync = 0;
     e->up_off = e->up_flushed = e->up_half ? e->up_cap / 2 : 0; e->up_lim = e->up_off + e->up_cap / 2;
     e->colcache.cols.reset();                           // column lists depend on the clones' ranks, which this call changes
-    e->lost_cov_slot.clear(); e->mp_n = 0;
+    e->lost_cov_slot.clear(); e->mp_n = 0; e->kf_pending = 0;
     if (!e->b_first_features) {
         if (n_imu > 0 && imu[0].t - ts - e->td <= 0.0) e->b_first_features = true;
         else return LVK_OK;
@@ -2588,6 +2652,8 @@ static lvk_status ekf_process_impl(lvk_ekf* e, double ts, const lvk_feature_obs*
     if (e->n_sync == 0) { EKF_HIP(hipStreamSynchronize(e->ctx->stream)); e->n_sync++; }
     st = lost_cov_attach(e);
     if (st != LVK_OK) return st;
+    st = keyframes_attach(e);
+    if (st != LVK_OK) return st;
     prof_harvest(e, false);
 #ifdef LVK_MSG_HASH_LOG   // debugging aid, compiled out of the product (make CXXFLAGS+=-DLVK_MSG_HASH_LOG); bounded: the first 65536 messages
     {   // LVK_MSG_HASH=<file>: one line per processed message (time stamp, size, FNV-1a of its bytes, IMU samples used + their hash, td
@@ -2623,6 +2689,7 @@ lvk_status lvk_ekf_set_shard(lvk_ekf* e, int rank, int world, lvk_exchange_fn fn
     ekf_quiesce(e);
     if (fn && e->indefinite_policy == LVK_INDEFINITE_LDLT) return lvk_set_error(e->ctx, LVK_ERR_UNSUPPORTED, "lvk_ekf_set_shard: the sharded update has no pivoted fallback (LVK_INDEFINITE_LDLT is set)");
     if (fn && e->msckf_points_on) return lvk_set_error(e->ctx, LVK_ERR_UNSUPPORTED, "lvk_ekf_set_shard: the sharded update does not export MSCKF points (lvk_ekf_set_msckf_points is on)");
+    if (fn && e->keyframes_on) return lvk_set_error(e->ctx, LVK_ERR_UNSUPPORTED, "lvk_ekf_set_shard: the sharded update does not export keyframes (lvk_ekf_set_keyframe_export is on)");
     EKF_HIP(hipStreamSynchronize(e->ctx->stream));
     if (S.d_send) hipFree(S.d_send); if (S.d_recv) hipFree(S.d_recv);
     S.d_send = S.d_recv = nullptr; S.cap = 0; S.xk_cap = 0;
@@ -2830,6 +2897,54 @@ int lvk_ekf_take_msckf_points(lvk_ekf* e, int64_t* ids, double* pos_w, double* c
     }
     e->msckf_points.erase(e->msckf_points.begin(), e->msckf_points.begin() + n);
     return n;
+}
+lvk_status lvk_ekf_set_keyframe_export(lvk_ekf* e, int on)
+{
+    if (!e) return LVK_ERR_ARG;
+    ekf_quiesce(e);
+    if (on && e->shard.fn) return lvk_set_error(e->ctx, LVK_ERR_UNSUPPORTED, "lvk_ekf_set_keyframe_export: the sharded update does not export keyframes");
+    e->keyframes_on = on != 0;
+    return LVK_OK;
+}
+int lvk_ekf_take_keyframes(lvk_ekf* e, lvk_keyframe* out, int cap)
+{
+    if (!e || !out || cap <= 0) return 0;
+    ekf_quiesce(e);
+    const int n = std::min((int)e->keyframes.size(), cap);
+    if (n) memcpy(out, e->keyframes.data(), sizeof(lvk_keyframe) * (size_t)n);
+    e->keyframes.erase(e->keyframes.begin(), e->keyframes.begin() + n);
+    return n;
+}
+lvk_status lvk_ekf_get_window_cov(lvk_ekf* e, int64_t* ids, double* cov_abs36, double* cov_rel36, int cap, int* n_out)
+{
+    if (!e || !n_out || cap < 0) return lvk_set_error(e ? e->ctx : nullptr, LVK_ERR_ARG, "lvk_ekf_get_window_cov: bad argument");
+    ekf_quiesce(e);
+    if (e->failed != LVK_OK) return e->failed;
+    const int n = std::min((int)e->clones.size(), cap);
+    *n_out = n;
+    if (ids) for (int i = 0; i < n; ++i) ids[i] = e->clones[(size_t)i].id;
+    if (n == 0 || (!cov_abs36 && !cov_rel36)) return LVK_OK;
+    // jobs 0..n-1: the absolute blocks; n..2n-2: clone i relative to clone i + 1 (against the whole window, also when cap cuts the list)
+    const int n_rel = std::min(n, (int)e->clones.size() - 1);
+    std::vector<lvk_pose_rel_job> jobs((size_t)(n + n_rel));
+    memset(jobs.data(), 0, sizeof(lvk_pose_rel_job) * jobs.size());
+    for (int i = 0; i < n + n_rel; ++i) {
+        lvk_pose_rel_job& j = jobs[(size_t)i];
+        const int ia = i < n ? -1 : i - n, ib = i < n ? i : i - n + 1;
+        const Clone& b = e->clones[(size_t)ib];
+        j.a_theta_col = j.a_p_col = -1; j.b_theta_col = LEG + 6 * ib; j.b_p_col = j.b_theta_col + 3;
+        memcpy(j.q_b, b.q, 32); memcpy(j.p_b, b.p, 24);
+        if (ia >= 0) { const Clone& a = e->clones[(size_t)ia]; j.a_theta_col = LEG + 6 * ia; j.a_p_col = j.a_theta_col + 3; memcpy(j.q_a, a.q, 32); memcpy(j.p_a, a.p, 24); }
+    }
+    std::vector<double> out(36 * jobs.size());
+    lvk_status st = lvk_ekf_pose_rel_cov(e->ctx, e->dP[e->cur], e->ld, e->N, jobs.data(), (int)jobs.size(), out.data());
+    if (st != LVK_OK) return st;
+    if (cov_abs36) memcpy(cov_abs36, out.data(), sizeof(double) * 36 * (size_t)n);
+    if (cov_rel36) {
+        for (int i = 36 * n_rel; i < 36 * n; ++i) cov_rel36[i] = NAN;
+        memcpy(cov_rel36, out.data() + 36 * (size_t)n, sizeof(double) * 36 * (size_t)n_rel);
+    }
+    return LVK_OK;
 }
 lvk_status lvk_ekf_get_feature_cov(lvk_ekf* e, int64_t* ids, int64_t* anchor_ids, double* pos_w, double* cov9, int cap, int* n_out)
 {

@@ -70,6 +70,9 @@ void lvk_cov_symmetrize(lvk_context* ctx, double* P, int ld, int n);
 // be_landmark.hip
 bool lvk_landmark_job_ok(const lvk_landmark_job* j, int n);
 lvk_status lvk_launch_landmark_cov(lvk_context* ctx, const double* d_P, int ldp, const lvk_landmark_job* d_jobs, int n_jobs, double* d_cov9);
+// be_pose_rel.hip
+bool lvk_pose_rel_job_ok(const lvk_pose_rel_job* j, int n);
+lvk_status lvk_launch_pose_rel_cov(lvk_context* ctx, const double* d_P, int ldp, const lvk_pose_rel_job* d_jobs, int n_jobs, double* d_cov36);
 // be_msckf_point.hip
 lvk_status lvk_launch_msckf_point_cov(lvk_context* ctx, const double* d_P, int ldp, const PointJob* d_jobs, int n_jobs, const CloneDev* d_clones, const int* d_rank,
                                       const double* d_z, const double* d_zv, FilterFlags fl, const TriResult* d_tri, double* d_cov9, int* d_ok);

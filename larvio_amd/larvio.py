@@ -14,6 +14,10 @@ CLONE = np.dtype([("id", np.int64), ("time", np.float64), ("dt", np.float64), ("
                   ("p_fej", np.float64, 3), ("R_b2c", np.float64, 9), ("t_c_b", np.float64, 3), ("q_cam", np.float64, 4),
                   ("p_cam", np.float64, 3)])
 
+# lvk_keyframe (include/lvk_c.h): one pruned clone
+KEYFRAME = np.dtype([("id", np.int64), ("to_id", np.int64), ("time", np.float64), ("to_time", np.float64), ("q", np.float64, 4), ("p", np.float64, 3),
+                     ("rel_q", np.float64, 4), ("rel_p", np.float64, 3), ("cov_abs", np.float64, (6, 6)), ("cov_rel", np.float64, (6, 6))])
+
 _CFG_INT = ["if_fej", "estimate_extrin", "estimate_td", "if_zupt_valid", "sw_size", "max_track_len", "least_observation_number",
             "max_features_in_one_grid", "aug_grid_rows", "aug_grid_cols", "width", "height"]
 _CFG_DBL = ["td", "pub_frequency", "imu_rate", "noise_gyro", "noise_acc", "noise_gyro_bias", "noise_acc_bias", "noise_feature",
@@ -70,6 +74,9 @@ def _L():
         L.lvk_ekf_take_lost_features_cov.argtypes = [vp, vp, vp, vp, i]; L.lvk_ekf_take_lost_features_cov.restype = i
         L.lvk_ekf_set_msckf_points.argtypes = [vp, i]; L.lvk_ekf_set_msckf_points.restype = i
         L.lvk_ekf_take_msckf_points.argtypes = [vp, vp, vp, vp, vp, i]; L.lvk_ekf_take_msckf_points.restype = i
+        L.lvk_ekf_set_keyframe_export.argtypes = [vp, i]; L.lvk_ekf_set_keyframe_export.restype = i
+        L.lvk_ekf_take_keyframes.argtypes = [vp, vp, i]; L.lvk_ekf_take_keyframes.restype = i
+        L.lvk_ekf_get_window_cov.argtypes = [vp, vp, vp, vp, i, pi]; L.lvk_ekf_get_window_cov.restype = i
         L.lvk_ekf_get_state.argtypes = [vp, vp]; L.lvk_ekf_get_state.restype = i
         L.lvk_ekf_get_cov.argtypes = [vp, vp]; L.lvk_ekf_get_cov.restype = i
         L.lvk_ekf_get_cov_imu.argtypes = [vp, i, vp]; L.lvk_ekf_get_cov_imu.restype = i
@@ -523,6 +530,32 @@ class LarVio:
             if n < 4096:
                 break
         return tuple(np.concatenate(o) for o in out)
+
+    def set_keyframe_export(self, on=True):
+        """lvk_ekf_set_keyframe_export: while on, every clone the pruning removes is kept as a KEYFRAME record with its absolute 6 x 6
+        covariance and the covariance of its pose relative to the nearest newer surviving clone (take_keyframes hands them out);
+        refused (LvkError) with a shard transport set"""
+        self.ctx.check(_L().lvk_ekf_set_keyframe_export(self._h, int(bool(on))))
+
+    def take_keyframes(self):
+        """lvk_ekf_take_keyframes: a structured array (dtype KEYFRAME) of the clones pruned since the last call, in pruning order"""
+        out = []
+        while True:
+            buf = np.zeros(1024, KEYFRAME)
+            n = _L().lvk_ekf_take_keyframes(self._h, _p(buf), 1024)
+            out.append(buf[:n].copy())
+            if n < 1024:
+                break
+        return np.concatenate(out)
+
+    def get_window_cov(self):
+        """lvk_ekf_get_window_cov: (ids, absolute blocks (n, 6, 6), Sigma_rel of clone i to clone i + 1 (n, 6, 6); NaN for the last clone)
+        for the clones of clones(), in that order"""
+        cap = 256
+        ids = np.zeros(cap, np.int64); ca = np.zeros((cap, 6, 6)); cr = np.zeros((cap, 6, 6)); n = C.c_int(0)
+        self.ctx.check(_L().lvk_ekf_get_window_cov(self._h, _p(ids), _p(ca), _p(cr), cap, C.byref(n)))
+        n = n.value
+        return ids[:n].copy(), ca[:n].copy(), cr[:n].copy()
 
     def set_shard(self, rank, world, fn, user, keepalive=None):
         """lvk_ekf_set_shard: this filter does the per-feature device work of rank `rank` of `world`; fn/user = the all-gather

@@ -204,6 +204,24 @@ def landmark_cov(ctx, P, jobs, n=None):
     return out
 
 
+POSE_REL_JOB = np.dtype([("a_theta_col", np.int32), ("a_p_col", np.int32), ("b_theta_col", np.int32), ("b_p_col", np.int32), ("q_a", np.float64, 4),
+                         ("p_a", np.float64, 3), ("q_b", np.float64, 4), ("p_b", np.float64, 3)])
+
+
+def pose_rel_cov(ctx, P, jobs, n=None):
+    """lvk_ekf_pose_rel_cov: the 6 x 6 covariance of every POSE_REL_JOB record - pose b relative to pose a, or b's own block when
+    a_theta_col < 0 - read off the covariance P.  P: a whole row-major buffer (its row length is the leading dimension, contents go to
+    the device as they are) whose leading n x n block (default: all rows) is the covariance.  -> (n_jobs, 6, 6)"""
+    P = np.ascontiguousarray(P, np.float64); jobs = np.ascontiguousarray(jobs, POSE_REL_JOB)
+    n = P.shape[0] if n is None else int(n)
+    out = np.full((len(jobs), 6, 6), np.nan)
+    L = lib()
+    L.lvk_ekf_pose_rel_cov.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]; L.lvk_ekf_pose_rel_cov.restype = C.c_int
+    dP = ctx.to_device(P)
+    ctx.check(L.lvk_ekf_pose_rel_cov(ctx.h, _p(dP), P.shape[1], n, _p(jobs), len(jobs), _p(out)))
+    return out
+
+
 MSCKF_POINT_JOB = np.dtype([("n_obs", np.int32), ("obs_off", np.int32), ("p_w", np.float64, 3)])
 
 
