@@ -10,307 +10,17 @@
 // per feature), Jacobians + null-space projection + chi-square gate (one workgroup per feature, compact columns),
 // row stacking, Householder compression, and the FP64-MFMA update.  feature_idp_dim = 1, use_schmidt = 0,
 // calib_imu = 0 or 1 (LEG_DIM 22 / 46) — config/euroc.yaml:8-10,105,108 and its calibration variant; anything else is refused.
-#include "lvk_internal.h"
-#include "be_dev.h"
-#include "be_host.h"
+// The filter object and the helpers its files share are in be_filter.h; the exports beside the state (drain lists, covariance
+// getters) are in be_export.hip, the pipelined driver in be_pipe.hip.
+#include "be_filter.h"
 #include "be_host_math.h"
-#include "be_qr.h"
 #include "be_init.h"
-#include <vector>
-#include <map>
-#include <stdexcept>
-#include <algorithm>
-#include <iterator>
 #include <new>
 #include <float.h>
 #include <sched.h>
 #include <pthread.h>
-#include <atomic>
-#include <functional>
-#include <thread>
-#include <mutex>
-#include <condition_variable>
-#include <deque>
 
-#define LEG (e->leg)           // LEG_DIM: 22, or 46 with online IMU-intrinsics calibration (larvio.cpp:158-161)
-#define LEG_MAX 46
 #define GRAV 9.81
-
-// ------------------------------------------------------------------------- host records
-struct Obs { long long sid; double z[2], zv[2]; };
-struct Feature {
-    long long id = 0;
-    std::vector<Obs> obs;                  // ascending state id (std::map in the reference)
-    double position[3] = {0, 0, 0}, position_fej[3] = {0, 0, 0};
-    bool is_initialized = false;
-    long long id_anchor = -1;
-    double inv_depth = 0, obs_anchor[3] = {0, 0, 0};
-    bool in_state = false, ekf_feature = false;
-    int total_obs = 0;
-    int find(long long sid) const
-    {   // obs is sorted by state id and almost every query asks for the newest one or two: look there first, then bisect
-        const int n = (int)obs.size();
-        if (n == 0) return -1;
-        if (obs[n - 1].sid == sid) return n - 1;
-        if (obs[n - 1].sid < sid) return -1;
-        if (n >= 2 && obs[n - 2].sid == sid) return n - 2;
-        int lo = 0, hi = n - 2;                                   // first index with sid >= wanted, in [0, n-2)
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if (obs[mid].sid < sid) lo = mid + 1; else hi = mid; }
-        return (lo < n && obs[lo].sid == sid) ? lo : -1;
-    }
-    void set(long long sid, double u, double v, double uv, double vv)
-    {
-        int i = find(sid);
-        if (i < 0) {
-            Obs o; o.sid = sid;
-            auto it = obs.end(); while (it != obs.begin() && (it - 1)->sid > sid) --it;     // appended at the end in the normal case
-            it = obs.insert(it, o); i = (int)(it - obs.begin());
-        }
-        obs[i].z[0] = u; obs[i].z[1] = v; obs[i].zv[0] = uv; obs[i].zv[1] = vv;
-    }
-    void erase(long long sid) { int i = find(sid); if (i >= 0) obs.erase(obs.begin() + i); }
-    void reset(long long new_id)
-    {   // the state of Feature() with this id; the observation list keeps its capacity (recycled objects: no allocation per new track)
-        id = new_id; obs.clear();
-        for (int k = 0; k < 3; ++k) { position[k] = 0; position_fej[k] = 0; obs_anchor[k] = 0; }
-        is_initialized = false; id_anchor = -1; inv_depth = 0; in_state = false; ekf_feature = false; total_obs = 0;
-    }
-};
-
-// map_server (std::map<FeatureIDType, Feature> in the reference, include/larvio/larvio.h:150): an id-ordered container with the slice
-// of the std::map interface the filter uses.  Ids are handed out in increasing order and features die in bulk, so the order lives
-// in ONE sorted array of (id, pointer) slots: lookups are a bisection over 16-byte entries that stay in cache, new tracks are appended,
-// a walk in id order is a linear scan (the next features' records are prefetched on the way), and erase only marks the slot -
-// the marks are swept once per message (purge()), after the message had its chance to re-create a feature that was used and erased
-// while its track lived on (every track is, every max_track_len frames; larvio.cpp:2240-2246).  Feature objects come from a free
-// list and keep their address while they are in the map (the update's row jobs hold pointers to them).
-// At configs[4] (2000 tracks) the std::map's pointer chasing was ~130 us per message in add_observations alone and as much again in the
-// scans of the update.
-class FeatureMap {
-  public:
-    struct Slot { long long id; Feature* f; bool live; };
-    struct Ref { const long long first; Feature& second; Ref* operator->() { return this; } };
-    class iterator {
-      public:
-        typedef std::forward_iterator_tag iterator_category; typedef Ref value_type; typedef long difference_type; typedef Ref* pointer; typedef Ref reference;
-        iterator() : m(nullptr), i(0) {}
-        iterator(const FeatureMap* m_, size_t i_) : m(m_), i(i_) { skip(); }
-        Ref operator*() const { const Slot& s = m->slots[i]; return Ref{s.id, *s.f}; }
-        Ref operator->() const { return **this; }
-        iterator& operator++() { ++i; skip(); return *this; }
-        iterator operator++(int) { iterator t = *this; ++*this; return t; }
-        bool operator==(const iterator& o) const { return i == o.i; }
-        bool operator!=(const iterator& o) const { return i != o.i; }
-        size_t index() const { return i; }
-      private:
-        void skip()
-        {
-            const size_t n = m->slots.size();
-            while (i < n && !m->slots[i].live) ++i;
-            if (i + 8 < n) {                                      // records a few features ahead: the object, then (one step later) its observations
-                __builtin_prefetch(m->slots[i + 8].f);
-                const Feature* g = m->slots[i + 4].f;
-                __builtin_prefetch((const char*)g + 64); __builtin_prefetch(g->obs.data());
-            }
-        }
-        const FeatureMap* m; size_t i;
-        friend class FeatureMap;
-    };
-    FeatureMap() {}
-    FeatureMap(const FeatureMap&) = delete;
-    FeatureMap& operator=(const FeatureMap&) = delete;
-    ~FeatureMap() { for (Slot& s : slots) delete s.f; for (Feature* f : spare) delete f; }
-    size_t size() const { return n_live; }
-    bool empty() const { return n_live == 0; }
-    iterator begin() const { return iterator(this, 0); }
-    iterator end() const { iterator it; it.m = this; it.i = slots.size(); return it; }
-    iterator find(long long id) const { const size_t k = lower(id); return (k < slots.size() && slots[k].id == id && slots[k].live) ? at_index(k) : end(); }
-    Feature& at(long long id) const { const size_t k = lower(id); if (!(k < slots.size() && slots[k].id == id && slots[k].live)) throw std::out_of_range("FeatureMap::at"); return *slots[k].f; }
-    Feature& operator[](long long id) { return *slots[obtain(id)].f; }
-    // both emplace forms: the feature value is always a fresh one in the callers (Feature()), so only the id is used
-    std::pair<iterator, bool> emplace(long long id, const Feature&) { const size_t before = n_live; const size_t k = obtain(id); return std::make_pair(at_index(k), n_live != before); }
-    iterator emplace_hint(const iterator&, long long id, const Feature&) { return at_index(obtain(id)); }
-    size_t erase(long long id) { const size_t k = lower(id); if (!(k < slots.size() && slots[k].id == id && slots[k].live)) return 0; slots[k].live = false; --n_live; ++n_dead; return 1; }
-    iterator erase(const iterator& it) { Slot& s = slots[it.i]; if (s.live) { s.live = false; --n_live; ++n_dead; } return iterator(this, it.i + 1); }
-    // sweep the erased slots (their objects go back to the free list); invalidates iterators, keeps the addresses of live features
-    void purge()
-    {
-        if (!n_dead) return;
-        size_t w = 0;
-        for (size_t r = 0; r < slots.size(); ++r) { if (slots[r].live) slots[w++] = slots[r]; else spare.push_back(slots[r].f); }
-        slots.resize(w); n_dead = 0;
-    }
-  private:
-    size_t lower(long long id) const
-    {   // first slot with id >= wanted; the newest ids are asked for most
-        const size_t n = slots.size();
-        if (n == 0 || slots[n - 1].id < id) return n;
-        size_t lo = 0, hi = n - 1;
-        while (lo < hi) { const size_t mid = (lo + hi) >> 1; if (slots[mid].id < id) lo = mid + 1; else hi = mid; }
-        return lo;
-    }
-    iterator at_index(size_t k) const { iterator it; it.m = this; it.i = k; return it; }
-    Feature* fresh(long long id) { Feature* f; if (!spare.empty()) { f = spare.back(); spare.pop_back(); } else f = new Feature(); f->reset(id); return f; }
-    size_t obtain(long long id)
-    {   // index of the live slot of `id`, creating it (as a default feature) if there is none
-        const size_t k = lower(id);
-        if (k < slots.size() && slots[k].id == id) {
-            if (!slots[k].live) { slots[k].f->reset(id); slots[k].live = true; ++n_live; --n_dead; }      // erased earlier in this message cycle: a new feature under the old id
-            return k;
-        }
-        Slot s; s.id = id; s.f = fresh(id); s.live = true;
-        slots.insert(slots.begin() + (long)k, s);               // k == size() for a new track (ids grow): an append
-        ++n_live;
-        return k;
-    }
-    std::vector<Slot> slots; std::vector<Feature*> spare; size_t n_live = 0, n_dead = 0;
-};
-struct Clone {
-    long long id; double time, dt; double q[4], p[3], p_fej[3], R_b2c[9], t_c_b[3], q_cam[4], p_cam[3];
-};
-struct ImuS { double t; double q[4], p[3], v[3], bg[3], ba[3]; };
-
-struct lvk_ekf {
-    lvk_context* ctx;
-    lvk_ekf_config cfg;
-    // state_server
-    long long imu_id = 0; double imu_dt = 0;
-    ImuS s, s_old, s_fej_now, s_fej_old;
-    double R_b2c[9], t_c_b[3], td = 0;
-    std::vector<Clone> clones;
-    mutable std::vector<short> rank_tab; mutable long long rank_base = 0; mutable bool ranks_dirty = true;   // see clone_rank()
-    mutable std::vector<double> rcam; mutable bool rcam_valid = false;      // camera-to-world rotation of every clone (clone_Rcam), rebuilt after poses change
-    std::vector<long long> feature_states;
-    FeatureMap map;                                    // map_server (ascending id)
-    int leg = 22;
-    int N = 22;
-    double imx[24];                                     // T1 T2 T3 A1 A2 A3 M1 M2 (larvio.cpp:129-154)
-    double Tg[9], As[9], Ma[9];                         // updateImuMx (:3803-3846)
-    long long next_state_id = 0;
-    bool is_gravity_set = false, b_first_features = false, if_fej = false, if_zupt = false;
-    double m_gyro_old[3], m_acc_old[3];
-    double take_off_stamp = 0, last_update_time = 0, last_zupt_time = 0, tracking_rate = 0;
-    struct LostPoint { long long id; double p[3]; double cov[9]; };
-    std::vector<LostPoint> lost_slam;                   // in-state features that were lost, with their last world position (drained on read)
-    // lvk_ekf_set_lost_feature_cov: the position covariance of every lost point, computed (k_landmark_cov) before its column leaves P.
-    // lost_cov_slot: for the last lost_cov_slot.size() entries of lost_slam, where in the download buffer (down_lm) the kernel puts
-    // their Sigma (-1: no job, the anchor is outside the window); attached at the end of the call, behind a stream sync
-    // (lost_cov_mark = n_sync when the launch was queued: one more sync only if none has followed)
-    bool lost_cov_on = false; std::vector<int> lost_cov_slot; int lost_cov_mark = 0; size_t down_lm = 0; int lm_cap = 0;
-    // lvk_ekf_set_msckf_points: the MSCKF features a lost-feature update used and erased, with the position covariance k_msckf_point_cov
-    // computed for them ahead of that update (drained on read).  The kernel covers jobs [mp_lo, mp_lo + mp_n) of the update's batch and
-    // writes job k's Sigma / ok word to slot k - mp_lo of the download buffer (down_mp / down_mpok)
-    struct MsckfPoint { long long id; double p[3]; double cov[9]; int n_obs; };
-    std::vector<MsckfPoint> msckf_points;
-    bool msckf_points_on = false; size_t down_mp = 0, down_mpok = 0, mp_lo = 0; int mp_cap = 0, mp_n = 0;
-    // lvk_ekf_set_keyframe_export: the clones the pruning removes, each with its absolute 6 x 6 block and the covariance of its pose
-    // relative to the nearest newer surviving clone (k_pose_rel_cov), computed before its columns leave P (drained on read).
-    // kf_pending: the last kf_pending entries of keyframes wait for their results - record i's absolute block in slot 2 i of the
-    // download buffer (down_kf), its relative one in slot 2 i + 1 - attached like the lost-feature covariance (kf_mark as lost_cov_mark)
-    std::vector<lvk_keyframe> keyframes;
-    bool keyframes_on = false; size_t down_kf = 0; int kf_pending = 0, kf_mark = 0;
-    double sigma2, zupt_v2, zupt_p2, zupt_q2, imu_img_time_th, Qc[12];
-    double x_min, y_min, grid_w, grid_h;
-    std::vector<int> grid_count;
-    // The reference's grid_map is a std::map<int, vector> (larvio.h:383): a feature whose code falls outside the rows x cols cells (undistorted
-    // coordinates beyond the image bounds) gets a cell of its own, which updateGridMap never clears (larvio.cpp:3356-3366) - it only fills up
-    // and, once it holds max_features_in_one_grid ids, diverts every later feature with that code to the MSCKF branch (:1969-1975).
-    // reference_grid (the default) keeps that bookkeeping; lvk_ekf_config.legacy_grid = 1 or LVK_GRID_REFERENCE=0 selects what this
-    // library did before round 6 (such codes not counted at all) - an opt-out for comparing old records, not the reference's filter.
-    std::map<int, int> grid_phantom;
-    bool reference_grid = true;
-    std::vector<double> coarse_dis;
-    int static_counter = 0, static_num = 0; double lower_time_bound = 0;
-    lvk_status dyn_status = LVK_OK;
-    lvk_init::DynInit* dyn = nullptr;                    // the moving-start initialiser (be_init.h); lives until the filter has a state
-    char* d_dyn = nullptr; size_t dyn_cap = 0;           // device scratch of its RANSAC stage (dyn_ransac): grow-only
-    lvk_init_report init_report = {};                    // what it handed over (lvk_ekf_init_report); valid = 0 until it has
-    int init_calls = 0, init_ransac_calls = 0;
-    std::map<long long, std::pair<double, double>> init_features;
-    long counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    lvk_status failed = LVK_OK; char failed_msg[256] = {0};   // sticky: set by the first lvk_ekf_process that returned an error
-    // per-frame composed transition (processModel): Phi_tot, Q_tot
-    double Phi_tot[LEG_MAX * LEG_MAX], Q_tot[LEG_MAX * LEG_MAX]; bool have_prop = false;
-    // device
-    int ld = 0, nmax = 0, rows_cap = 0, hrows = 0, feat_cap = 0, obs_cap = 0;
-    double* dP[2] = {nullptr, nullptr}; int cur = 0;
-    int* d_idx = nullptr; double *d_phiq = nullptr, *d_J = nullptr, *d_dx = nullptr, *d_tmp = nullptr;
-    TriJob* d_tri = nullptr; TriResult* d_triout = nullptr; FeatJob* d_fj = nullptr; FeatResult* d_fout = nullptr;
-    TriResult* d_tridev = nullptr;                      // device copy of the triangulation results, indexed by the row job that consumes them (FJ_TRI_PENDING)
-    int* d_rank = nullptr; double *d_z = nullptr, *d_zv = nullptr; CamPose* d_cams = nullptr; CloneDev* d_clones = nullptr;
-    double* d_staging = nullptr; size_t staging_cap = 0; int* d_ccols = nullptr; size_t ccols_cap = 0; StackRow* d_map = nullptr;
-    double *d_H = nullptr, *d_r = nullptr, *d_H1 = nullptr, *d_H2 = nullptr, *d_r1 = nullptr;
-    double *d_Hb = nullptr, *d_rb = nullptr;            // ping-pong partner of d_H / d_r for the levels of the structure-aware compression
-    int sparse_qr_min_rows = 480;
-    std::vector<int> tri_ranks; std::vector<double> tri_z;       // view pools of the triangulation requests of the current batch
-    struct ColCache { int type = -1, ncols = 0, anchor = 0, fcol = 0; std::vector<long long> sids; ColList cols; };
-    mutable ColCache colcache;                          // job_dense_cols: the column list of the previous job, reused when the next one has the same observation set
-    long qr_stats[4] = {0, 0, 0, 0};                    // [0] updates compressed [1] levels run [2] rows in [3] rows out
-    // sharded measurement update: this rank builds the feature rows of its contiguous slice, one all-gather of the
-    // compressed blocks (+ every feature's gate result), replicated update.  fn == nullptr = off; with a transport the sharded path
-    // runs at any world size, world 1 included (a loop-back that exercises pack -> all-gather -> unpack -> second stage on one GPU).
-    // The exchange buffers are allocated once, in lvk_ekf_set_shard, for xk_cap block rows per rank: nothing that can fail on one
-    // rank only sits between the ranks and their collective.
-    struct Shard { int rank = 0, world = 1; lvk_exchange_fn fn = nullptr; void* user = nullptr; char *d_send = nullptr, *d_recv = nullptr; size_t cap = 0; int xk_cap = 0;
-                   long stats[4] = {0, 0, 0, 0}; } shard;     // stats: [0] exchanges [1] bytes sent per rank (sum) [2] sharded updates [3] rows this rank stacked
-    size_t down_flag = 0;                               // offset in h_down of the word k_shard_unpack raises when a peer's block arrives poisoned
-    size_t down_info = 0;                               // offset in h_down of the factorisation's report words (update_health)
-    size_t down_p00 = 0; bool p00_valid = false;        // offset in h_down of the mirror of P[0:16, 0:16] (q v p bg ba[0]) the last update's final GEMM wrote; valid: nothing has touched that block since
-    UpdateWs ws;
-    // what to do when the Cholesky meets a non-positive pivot (lvk_ekf_set_indefinite_policy).  The update's last launch leaves P
-    // and dx alone then (GemmRider::gate), so under LVK_INDEFINITE_LDLT update_health() runs that one update again through the
-    // pivoted LDL^T: `last` is the stacked system the failed update read (still in place: nothing writes d_H / d_r before the sync
-    // that looks at the report), `redo` what the caller had queued behind the update and has to be queued again behind the new one.
-    int indefinite_policy = LVK_INDEFINITE_FAIL; long indefinite_fallbacks = 0;
-    struct LastUpdate { const double* H = nullptr; const double* r = nullptr; int m = 0, n = 0; } last;
-    std::function<lvk_status()> redo;
-    bool fell_back = false;                             // set by update_health when it re-ran the update: d_dx has changed since the caller's copy was queued
-    // pinned host arenas
-    char* h_up = nullptr; size_t up_cap = 0, up_off = 0, up_flushed = 0;
-    size_t up_lim = 0; int up_half = 0;                 // the arena is used in halves, alternating per call: kernels queued behind a call's last sync may still read its half while the next call stages into the other
-    int n_sync = 0;                                     // stream syncs of the current call (a call without any ends with one: see ekf_process_impl)
-    char* d_up = nullptr;                               // device mirror of the upload arena: ONE H2D copy per sync point
-    bool zero_copy = false;                             // d_up aliases the pinned arena (device-mapped host memory): no H2D copies at all
-    bool bar_push = false;                              // d_up is DEVICE memory that this thread writes through the PCIe BAR (flush_uploads): see lvk_ekf_create
-    int defer = 0; std::vector<std::function<lvk_status()>> deferred;   // launches waiting for a shared flush (begin_defer/end_defer)
-    CamPose* dv_cams = nullptr; CloneDev* dv_clones = nullptr;
-    // results come back WITHOUT copies: the kernels that produce them (triangulation, per-feature rows, the dx column of W^T[W|w])
-    // also write them into this device-mapped pinned buffer; the host reads it after the stream sync it needs anyway
-    char* h_down = nullptr; size_t down_cap = 0; char* dh_down = nullptr; size_t down_feat = 0, down_dx = 0;
-    // fired as soon as the number of IMU samples this call erases is final (before any GPU work): lets a pipelined driver
-    // hand the next frame's front-end the right buffer view while this update is still running
-    void (*on_consumed)(void*, int) = nullptr; void* on_consumed_user = nullptr;
-    // optional HIP-event bracket around the H P GEMM of every update (bench: MFMA utilisation of the P H^T contraction)
-    bool prof_on = false; double prof_ms = 0, prof_flops = 0; long prof_n = 0;
-    double prof_qr_ms = 0, prof_qr_flops = 0, prof_qr_rows = 0; long prof_qr_n = 0;     // the same bracket around every k_qr_sparse level (kind 1)
-    struct ProfEv { hipEvent_t a, b; double flops; int kind = 0; double rows = 0; };
-    struct Async;                                       // lvk_ekf_process_async: the worker that runs a queued update (created on first use)
-    Async* async = nullptr;
-    std::vector<ProfEv> prof_pending; std::vector<hipEvent_t> prof_free;
-};
-
-// ------------------------------------------------------------------------- deferred updates
-// lvk_ekf_process_async hands an update to this worker and returns; the next call that looks at the filter (any getter, the next
-// update, destroy) waits for it.  A blocking driver (app/larvioMain.cpp:104-116: processImage, processFeatures, getters) then gets
-// the front-end of the next frame running while the update of this one is still in flight, as far as its own getter calls allow.
-struct lvk_ekf::Async {
-    std::thread th; std::mutex mu; std::condition_variable cv;
-    std::atomic<int> state{0};                          // 0 idle, 1 an update is queued or running
-    std::atomic<bool> stop{false};
-    double ts = 0; std::vector<lvk_feature_obs> feats; std::vector<lvk_imu> imu; int expect_used = 0;
-    lvk_status st = LVK_OK; int updated = 0; long n_deferred = 0;
-    bool unwaited = false;                              // an update was queued and no call has waited for it yet (caller's thread only)
-};
-// every entry point that reads or changes the filter first waits for the queued update
-static void ekf_quiesce(const lvk_ekf* e)
-{
-    lvk_ekf::Async* a = e->async;
-    if (a) a->unwaited = false;
-    if (!a || a->state.load(std::memory_order_acquire) == 0) return;
-    for (int spin = 0; spin < 40000; ++spin) { if (a->state.load(std::memory_order_acquire) == 0) return; LVK_CPU_RELAX(); }
-    std::unique_lock<std::mutex> lk(a->mu);
-    a->cv.wait(lk, [&] { return a->state.load(std::memory_order_acquire) == 0; });
-}
 
 // ------------------------------------------------------------------------- host-side phase tracer (LVK_EKF_TRACE=1)
 #include <chrono>
@@ -345,22 +55,6 @@ static const char* const TRS_NAMES[8] = {"update w/o new feature: jobs staged (l
     "  compression planned / launched", "  update core launched (4 kernels)", "batch_imu: (unused)", "(unused)", "(unused)"};
 
 // ------------------------------------------------------------------------- small helpers
-// rank of a clone in the window by state id: direct-address table over [first id, last id] (ids only grow; the window spans a few
-// dozen of them), rebuilt lazily after the clone list changes - the linear search ran thousands of times per update
-static int clone_rank(const lvk_ekf* e, long long id)
-{
-    if (e->ranks_dirty) {
-        e->rank_tab.clear();
-        e->rank_base = e->clones.empty() ? 0 : e->clones.front().id;
-        if (!e->clones.empty()) {
-            e->rank_tab.assign((size_t)(e->clones.back().id - e->rank_base + 1), (short)-1);
-            for (size_t i = 0; i < e->clones.size(); ++i) e->rank_tab[(size_t)(e->clones[i].id - e->rank_base)] = (short)i;
-        }
-        e->ranks_dirty = false;
-    }
-    const long long k = id - e->rank_base;
-    return (k < 0 || k >= (long long)e->rank_tab.size()) ? -1 : e->rank_tab[(size_t)k];
-}
 // R(q_cam) of clone `rank`: checkMotion (feature.hpp:334-381) asks for it twice per feature, thousands of times per update at
 // configs[4]; the clones' poses only change at state injection and when the window changes
 static const double* clone_Rcam(const lvk_ekf* e, int rank)
@@ -372,7 +66,6 @@ static const double* clone_Rcam(const lvk_ekf* e, int rank)
     }
     return &e->rcam[9 * (size_t)rank];
 }
-static int fs_rank(const lvk_ekf* e, long long id) { for (size_t i = 0; i < e->feature_states.size(); ++i) if (e->feature_states[i] == id) return (int)i; return -1; }
 static void clone_refresh_cam(const lvk_ekf* e, Clone* c)
 {   // larvio.cpp:1529-1541
     double R_c2b[9], R_b2w[9], R_c2w[9], t[3];
@@ -380,35 +73,6 @@ static void clone_refresh_cam(const lvk_ekf* e, Clone* c)
     rot_to_quat(R_c2w, c->q_cam);
     m3_v(R_b2w, e->t_c_b, t);
     for (int i = 0; i < 3; ++i) c->p_cam[i] = c->p[i] + t[i];
-}
-template <typename T> static T* up_alloc(lvk_ekf* e, size_t n)
-{   // bump allocation in the pinned upload arena (reset once per frame; copies are stream-ordered)
-    size_t bytes = (sizeof(T) * n + 63) & ~(size_t)63;
-    if (e->up_off + bytes > e->up_lim) return nullptr;
-    T* p = (T*)(e->h_up + e->up_off); e->up_off += bytes; return p;
-}
-#define EKF_HIP(call) LVK_HIP(e->ctx, call)
-template <typename T> static T* dev(lvk_ekf* e, T* host) { return (T*)(e->d_up + ((char*)host - e->h_up)); }
-static lvk_status flush_uploads(lvk_ekf* e)
-{   // everything staged in the pinned arena since the last flush goes up in one stream-ordered copy
-    if (e->bar_push) {                                                   // the host pushes what it staged into the device-resident arena
-        if (e->up_off > e->up_flushed) { memcpy(e->d_up + e->up_flushed, e->h_up + e->up_flushed, e->up_off - e->up_flushed); LVK_STORE_FENCE(); e->up_flushed = e->up_off; }
-        return LVK_OK;
-    }
-    if (e->zero_copy) { e->up_flushed = e->up_off; return LVK_OK; }     // kernels read the pinned arena directly
-    if (e->up_off > e->up_flushed) {
-        EKF_HIP(hipMemcpyAsync(e->d_up + e->up_flushed, e->h_up + e->up_flushed, e->up_off - e->up_flushed, hipMemcpyHostToDevice, e->ctx->stream));
-        e->up_flushed = e->up_off;
-    }
-    return LVK_OK;
-}
-// A launch that reads staged data.  Normally: flush what is staged, launch.  Between begin_defer and end_defer the launches are held
-// back so that several of them share ONE host-to-device copy (each copy is ~4 us on the filter's dependent chain plus its barrier).
-static lvk_status run_or_defer(lvk_ekf* e, std::function<lvk_status()> fn)
-{
-    if (e->defer > 0) { e->deferred.push_back(std::move(fn)); return LVK_OK; }
-    lvk_status st = flush_uploads(e);
-    return st == LVK_OK ? fn() : st;
 }
 static void begin_defer(lvk_ekf* e) { e->defer += 1; }
 static lvk_status end_defer(lvk_ekf* e)
@@ -471,99 +135,6 @@ static lvk_status cov_gather(lvk_ekf* e, const std::vector<int>& idx)
     lvk_status st = run_or_defer(e, [=]() { return lvk_cov_gather(e->ctx, src, e->ld, dst, e->ld, d_idx, n); });
     if (st != LVK_OK) return st;
     e->cur ^= 1; e->N = n;
-    return LVK_OK;
-}
-// the landmark-covariance job of in-state feature f (state column LEG + 6 clones + fs_index) from the host state, as inject() reads it;
-// false when the injection would skip the feature (anchor not in the window) or the depth is degenerate
-static bool landmark_job(const lvk_ekf* e, const Feature& f, int fs_index, lvk_landmark_job* j)
-{
-    const int ar = clone_rank(e, f.id_anchor);
-    if (ar < 0) return false;
-    memset(j, 0, sizeof *j);
-    j->anchor_col = LEG + 6 * ar; j->feat_col = LEG + 6 * (int)e->clones.size() + fs_index;
-    memcpy(j->q_anchor, e->clones[(size_t)ar].q, 32); memcpy(j->R_b2c, e->R_b2c, 72); memcpy(j->t_c_b, e->t_c_b, 24);
-    j->obs_anchor[0] = f.obs_anchor[0]; j->obs_anchor[1] = f.obs_anchor[1]; j->inv_depth = f.inv_depth;
-    return lvk_landmark_job_ok(j, e->N);
-}
-// lvk_ekf_set_lost_feature_cov: queue k_landmark_cov for the lost in-state features on the covariance as it is now (their columns
-// still in place); the results go to the pinned download buffer and are attached by lost_cov_attach()
-static lvk_status lost_cov_queue(lvk_ekf* e, const std::vector<long long>& ekf_lost)
-{
-    e->lost_cov_slot.assign(ekf_lost.size(), -1);
-    lvk_landmark_job* hj = up_alloc<lvk_landmark_job>(e, ekf_lost.size());
-    if (!hj) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "upload arena exhausted");
-    int n = 0;
-    for (size_t k = 0; k < ekf_lost.size(); ++k)
-        if (n < e->lm_cap && landmark_job(e, e->map.at(ekf_lost[k]), fs_rank(e, ekf_lost[k]), hj + n)) e->lost_cov_slot[k] = n++;
-    e->lost_cov_mark = e->n_sync;
-    if (n == 0) return LVK_OK;
-    const double* P = e->dP[e->cur]; const lvk_landmark_job* d_jobs = dev(e, hj); double* out = (double*)(e->dh_down + e->down_lm);
-    return run_or_defer(e, [=]() { return lvk_launch_landmark_cov(e->ctx, P, e->ld, d_jobs, n, out); });
-}
-static lvk_status lost_cov_attach(lvk_ekf* e)
-{
-    if (e->lost_cov_slot.empty()) return LVK_OK;
-    if (e->n_sync == e->lost_cov_mark) { EKF_HIP(hipStreamSynchronize(e->ctx->stream)); e->n_sync++; }
-    const size_t k = e->lost_cov_slot.size(), base = e->lost_slam.size() - k;
-    const double* src = (const double*)(e->h_down + e->down_lm);
-    for (size_t i = 0; i < k; ++i) if (e->lost_cov_slot[i] >= 0) memcpy(e->lost_slam[base + i].cov, src + 9 * (size_t)e->lost_cov_slot[i], 72);
-    e->lost_cov_slot.clear();
-    return LVK_OK;
-}
-// lvk_ekf_set_keyframe_export: one record per clone in rm (those in the window, ascending rank), and k_pose_rel_cov queued for them on the
-// covariance as it is now (the pruning update applied, their columns still in place); b = the nearest newer clone not in rm
-static lvk_status keyframes_queue(lvk_ekf* e, const long long* rm, int nrm)
-{
-    int ra[2], n = 0;
-    for (int k = 0; k < nrm && k < 2; ++k) { const int r = clone_rank(e, rm[k]); if (r >= 0) ra[n++] = r; }
-    if (n == 2 && ra[0] > ra[1]) std::swap(ra[0], ra[1]);
-    if (n == 0) return LVK_OK;
-    lvk_pose_rel_job* hj = up_alloc<lvk_pose_rel_job>(e, (size_t)2 * n);
-    if (!hj) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "upload arena exhausted");
-    memset(hj, 0, sizeof(lvk_pose_rel_job) * 2 * (size_t)n);
-    if (e->keyframes.size() + (size_t)n > (size_t)1 << 16) e->keyframes.erase(e->keyframes.begin(), e->keyframes.begin() + (1 << 15));
-    for (int i = 0; i < n; ++i) {
-        const Clone& a = e->clones[(size_t)ra[i]];
-        int rb = ra[i] + 1;
-        while (rb < (int)e->clones.size() && (rb == ra[0] || rb == ra[n - 1])) ++rb;
-        lvk_keyframe kf; memset(&kf, 0, sizeof kf);
-        kf.id = a.id; kf.time = a.time; memcpy(kf.q, a.q, 32); memcpy(kf.p, a.p, 24);
-        for (int t = 0; t < 36; ++t) kf.cov_abs[t] = kf.cov_rel[t] = NAN;
-        lvk_pose_rel_job* ja = hj + 2 * i; lvk_pose_rel_job* jr = ja + 1;
-        ja->a_theta_col = ja->a_p_col = -1; ja->b_theta_col = LEG + 6 * ra[i]; ja->b_p_col = ja->b_theta_col + 3;
-        memcpy(ja->q_b, a.q, 32); memcpy(ja->p_b, a.p, 24);
-        *jr = *ja;                                      // no newer clone survives (the pruning never removes the newest): the absolute block twice, NaN kept below
-        kf.to_id = -1; kf.to_time = NAN;
-        for (int t = 0; t < 4; ++t) kf.rel_q[t] = NAN;
-        for (int t = 0; t < 3; ++t) kf.rel_p[t] = NAN;
-        if (rb < (int)e->clones.size()) {
-            const Clone& b = e->clones[(size_t)rb];
-            kf.to_id = b.id; kf.to_time = b.time;
-            const double qa_inv[4] = {-a.q[0], -a.q[1], -a.q[2], a.q[3]}, d[3] = {b.p[0] - a.p[0], b.p[1] - a.p[1], b.p[2] - a.p[2]};
-            double Ra[9];
-            quat_mul(qa_inv, b.q, kf.rel_q); quat_to_rot(a.q, Ra); m3t_v(Ra, d, kf.rel_p);
-            jr->a_theta_col = LEG + 6 * ra[i]; jr->a_p_col = jr->a_theta_col + 3; jr->b_theta_col = LEG + 6 * rb; jr->b_p_col = jr->b_theta_col + 3;
-            memcpy(jr->q_a, a.q, 32); memcpy(jr->p_a, a.p, 24); memcpy(jr->q_b, b.q, 32); memcpy(jr->p_b, b.p, 24);
-        }
-        if (!lvk_pose_rel_job_ok(ja, e->N) || !lvk_pose_rel_job_ok(jr, e->N)) return lvk_set_error(e->ctx, LVK_ERR_ARG, "internal: a keyframe job leaves the %d x %d covariance", e->N, e->N);
-        e->keyframes.push_back(kf);
-    }
-    e->kf_pending = n; e->kf_mark = e->n_sync;
-    const double* P = e->dP[e->cur]; const lvk_pose_rel_job* d_jobs = dev(e, hj); double* out = (double*)(e->dh_down + e->down_kf);
-    return run_or_defer(e, [=]() { return lvk_launch_pose_rel_cov(e->ctx, P, e->ld, d_jobs, 2 * n, out); });
-}
-static lvk_status keyframes_attach(lvk_ekf* e)
-{
-    if (e->kf_pending <= 0) return LVK_OK;
-    if (e->n_sync == e->kf_mark) { EKF_HIP(hipStreamSynchronize(e->ctx->stream)); e->n_sync++; }
-    const size_t k = (size_t)e->kf_pending, base = e->keyframes.size() - k;
-    const double* src = (const double*)(e->h_down + e->down_kf);
-    for (size_t i = 0; i < k; ++i) {
-        lvk_keyframe& kf = e->keyframes[base + i];
-        memcpy(kf.cov_abs, src + 72 * i, 288);
-        if (kf.to_id >= 0) memcpy(kf.cov_rel, src + 72 * i + 36, 288);
-    }
-    e->kf_pending = 0;
     return LVK_OK;
 }
 // P loses the rows / columns marked in drop (N flags)
@@ -906,24 +477,6 @@ static int batch_imu(lvk_ekf* e, double time_bound, const lvk_imu* imu, int n_im
     return used;
 }
 
-// how many samples batch_imu will erase, without touching the state: time stamps only - the state time t0, the bound (image time +
-// td) and the threshold.  t_after = the state time batch_imu leaves behind.
-static int imu_erase_count(double t0, double time_bound, double th, const lvk_imu* imu, int n_imu, double* t_after)
-{
-    int used = 0; double t = t0;
-    for (int i = 0; i < n_imu; ++i) {
-        if (imu[i].t <= t) { ++used; continue; }
-        if (imu[i].t - time_bound > th) break;
-        t = imu[i].t; ++used;
-    }
-    if (t_after) *t_after = t;
-    return used;
-}
-static int batch_imu_count(const lvk_ekf* e, double time_bound, const lvk_imu* imu, int n_imu, double* t_after = nullptr)
-{
-    return imu_erase_count(e->s.t, time_bound, e->imu_img_time_th, imu, n_imu, t_after);
-}
-
 static lvk_status state_augmentation(lvk_ekf* e)
 {   // larvio.cpp:720-801; the covariance part is an index gather (rows/cols {0,1,2,6,7,8} duplicated before the feature block)
     Clone c; memset(&c, 0, sizeof c);
@@ -1150,10 +703,33 @@ static bool feat_check_motion(const lvk_ekf* e, const Feature& f, bool if_tracke
 }
 
 // One feature-rows job (rows on the device) ------------------------------------------------------------
-struct RowJob { Feature* f; int type; std::vector<long long> sids; bool want_gate; int dof; FeatJob dev; FeatResult res; FeatJob* hdev = nullptr; bool tri_pending = false; };   // hdev: the job's record in the upload arena (patched until the launch is flushed)
+// the job of an MSCKF feature over the given observations, or over all it has
+static RowJob msckf_job(Feature* f, std::vector<long long> sids, int tri = -1)
+{
+    RowJob r; r.f = f; r.type = JOB_MSCKF; r.want_gate = true; r.dof = 2 * (int)sids.size() - 3; r.tri = tri; r.sids = std::move(sids);
+    return r;
+}
+static RowJob msckf_job(Feature* f, int tri = -1)
+{
+    std::vector<long long> sids; sids.reserve(f->obs.size()); for (const Obs& o : f->obs) sids.push_back(o.sid);
+    return msckf_job(f, std::move(sids), tri);
+}
+// the two rows of a tracked in-state feature's newest observation
+static RowJob tracked_job(const lvk_ekf* e, Feature* f)
+{
+    RowJob r; r.f = f; r.type = JOB_EKF_TRACKED; r.sids = {e->imu_id}; r.want_gate = true; r.dof = 2;
+    return r;
+}
+// a feature about to enter the state: its MSCKF-form gate job, then its rows over every observation but the anchor's
+static void new_feature_jobs(Feature* f, std::vector<RowJob>& jobs)
+{
+    jobs.push_back(msckf_job(f));
+    RowJob r; r.f = f; r.type = JOB_EKF_NEW; r.want_gate = false; r.dof = 0;
+    for (const Obs& o : f->obs) if (o.sid != f->id_anchor) r.sids.push_back(o.sid);
+    jobs.push_back(r);
+}
 
 typedef std::vector<std::pair<size_t, size_t>> JobRanges;
-struct RowObs { const int* rank = nullptr; const double *z = nullptr, *zv = nullptr; };      // where a batch's observations lie on the device (FeatJob::obs_off indexes them)
 static lvk_status launch_feature_rows(lvk_ekf* e, std::vector<RowJob>& jobs, const JobRanges* ranges = nullptr, RowObs* obs_out = nullptr)
 {   // stages the jobs and queues k_feature_rows (for the given index ranges only, in the sharded update); nothing is read back
     // (fetch_feature_results does that)
@@ -1174,8 +750,8 @@ static lvk_status launch_feature_rows(lvk_ekf* e, std::vector<RowJob>& jobs, con
         const int M = (int)j.sids.size();
         FeatJob& d = j.dev; memset(&d, 0, sizeof d);
         if (obs_stride) off = i * (size_t)obs_stride;
-        d.type = j.type; d.n_obs = M; d.obs_off = (int)off; d.want_gate = (j.want_gate ? FJ_GATE : 0) | (j.tri_pending ? FJ_TRI_PENDING : 0);
-        any_pending = any_pending || j.tri_pending;
+        d.type = j.type; d.n_obs = M; d.obs_off = (int)off; d.want_gate = (j.want_gate ? FJ_GATE : 0) | (j.tri >= 0 ? FJ_TRI_PENDING : 0);
+        any_pending = any_pending || j.tri >= 0;
         d.anchor_rank = (j.type == JOB_MSCKF) ? 0 : clone_rank(e, f->id_anchor);
         d.fcol = (j.type == JOB_MSCKF) ? 0 : LEG + 6 * (int)e->clones.size() + fs_rank(e, f->id);
         d.stage_off = (long long)stage; d.ccol_off = (int)ccols;
@@ -1214,42 +790,6 @@ static lvk_status launch_feature_rows(lvk_ekf* e, std::vector<RowJob>& jobs, con
     }
     return LVK_OK;
 }
-// lvk_ekf_set_msckf_points: queue k_msckf_point_cov for the MSCKF jobs [lo, hi) of the batch launch_feature_rows has just staged, on the
-// covariance as it is now (the one the update starts from), on the observations that launch staged (obs); the results go to the pinned
-// download buffer, msckf_point_record() reads them behind the wait the update makes for its gate results
-static lvk_status msckf_points_queue(lvk_ekf* e, const std::vector<RowJob>& jobs, size_t lo, size_t hi, const RowObs& obs)
-{
-    e->mp_n = 0;
-    if (!e->msckf_points_on || hi <= lo) return LVK_OK;
-    if (!obs.rank || !obs.z || !obs.zv) return lvk_set_error(e->ctx, LVK_ERR_ARG, "internal: MSCKF points queued without a staged batch");
-    if (hi - lo > (size_t)e->mp_cap) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "internal: %zu MSCKF jobs exceed the %d result slots of the point export", hi - lo, e->mp_cap);
-    const int n = (int)(hi - lo);
-    PointJob* hj = up_alloc<PointJob>(e, (size_t)n);
-    if (!hj) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "upload arena exhausted");
-    for (int k = 0; k < n; ++k) {
-        const RowJob& j = jobs[lo + (size_t)k];
-        hj[k].n_obs = j.dev.n_obs; hj[k].obs_off = j.dev.obs_off; hj[k].tri_slot1 = j.tri_pending ? (int)(lo + (size_t)k) + 1 : 0; hj[k].pad = 0;
-        memcpy(hj[k].p_w, j.dev.p_w, 24);
-    }
-    e->mp_lo = lo; e->mp_n = n;
-    const FilterFlags fl = filter_flags(LEG, e->if_fej, e->cfg.estimate_td, e->sigma2);
-    const double* P = e->dP[e->cur]; const PointJob* d_jobs = dev(e, hj); const CloneDev* d_cl = e->dv_clones;
-    const int* d_r = obs.rank; const double* d_z = obs.z; const double* d_v = obs.zv; const TriResult* d_tri = e->d_tridev;
-    double* out = (double*)(e->dh_down + e->down_mp); int* ok = (int*)(e->dh_down + e->down_mpok);
-    return run_or_defer(e, [=]() { return lvk_launch_msckf_point_cov(e->ctx, P, e->ld, d_jobs, n, d_cl, d_r, d_z, d_v, fl, d_tri, out, ok); });
-}
-// job k of the batch was an MSCKF feature that triangulated and passed its gate, and is about to be erased: keep it (after the stream
-// wait that covers the launch above)
-static void msckf_point_record(lvk_ekf* e, const RowJob& j, size_t k)
-{
-    if (e->mp_n <= 0 || k < e->mp_lo || k >= e->mp_lo + (size_t)e->mp_n) return;
-    const size_t slot = k - e->mp_lo;
-    if (!((const int*)(e->h_down + e->down_mpok))[slot]) return;
-    if (e->msckf_points.size() >= (size_t)1 << 16) e->msckf_points.erase(e->msckf_points.begin(), e->msckf_points.begin() + (1 << 15));
-    lvk_ekf::MsckfPoint mp; mp.id = j.f->id; memcpy(mp.p, j.f->position, 24); mp.n_obs = (int)j.sids.size();
-    memcpy(mp.cov, (const double*)(e->h_down + e->down_mp) + 9 * slot, 72);
-    e->msckf_points.push_back(mp);
-}
 static lvk_status shard_peer_check(lvk_ekf* e);
 // results of the queued jobs (+ optionally n_dx doubles of d_dx in the same sync)
 static lvk_status fetch_feature_results(lvk_ekf* e, std::vector<RowJob>& jobs, double* dx = nullptr, size_t n_dx = 0)
@@ -1261,13 +801,6 @@ static lvk_status fetch_feature_results(lvk_ekf* e, std::vector<RowJob>& jobs, d
     for (size_t i = 0; i < jobs.size(); ++i) jobs[i].res = ho[i];
     if (n_dx) memcpy(dx, e->h_down + e->down_dx, sizeof(double) * n_dx);      // written by the W^T[W|w] launch of the update
     return LVK_OK;
-}
-static lvk_status run_feature_rows(lvk_ekf* e, std::vector<RowJob>& jobs)
-{
-    if (jobs.empty()) return LVK_OK;
-    lvk_status st = launch_feature_rows(e, jobs);
-    if (st == LVK_OK) st = fetch_feature_results(e, jobs);
-    return st;
 }
 // row layout of a job, known before it runs: MSCKF blocks lose the 3 rows of the null-space projection, a new in-state
 // feature's block keeps its range row first, a tracked in-state feature contributes its 2 rows as they are
@@ -1595,7 +1128,7 @@ static lvk_status gated_update(lvk_ekf* e, std::vector<RowJob>& jobs, const size
     begin_defer(e);                                     // the jobs (and their row slots) go up in one copy
     RowObs obs;
     lvk_status st = launch_feature_rows(e, jobs, sharded ? &own : nullptr, &obs);
-    if (st == LVK_OK && !sharded) st = msckf_points_queue(e, jobs, mp_lo, mp_hi, obs);      // [mp_lo, mp_hi): the MSCKF jobs of a lost-feature update (lvk_ekf_set_msckf_points)
+    if (st == LVK_OK && !sharded) st = lvk_ekf_msckf_points_queue(e, jobs, mp_lo, mp_hi, obs);      // [mp_lo, mp_hi): the MSCKF jobs of a lost-feature update (lvk_ekf_set_msckf_points)
     if (tr[0] >= 0) TR(tr[0]);
     TRS(0);
     if (st != LVK_OK && !sharded) { end_defer(e); return st; }      // sharded: a local failure still goes through the exchange (shard_stage1, pre_fail)
@@ -1631,99 +1164,77 @@ static void gated_update_apply(lvk_ekf* e, const std::vector<double>& dx, int ac
     e->counters[counter]++;
     e->counters[2] = accepted;
 }
-// removeLostFeatures when no feature can enter the state in this update (the usual message: the augmentation grid is full, or no
-// track has reached max_track_len in a free cell) and the update is not sharded: NOTHING on the host depends on a device result
-// before the update is launched.  The triangulations of the features that need one are queued and consumed ON THE DEVICE by the row
-// kernel (FJ_TRI_PENDING: a failed triangulation = a rejected job = zero rows, which leave the update unchanged), every candidate
-// row has its slot, and triangulation results, gate results and dx come back in ONE sync.  Same decisions, same rows, same update
-// as the general path below (larvio.cpp:1897-2005): only the order in which the host learns them differs.
-static lvk_status remove_lost_fast(lvk_ekf* e, const std::vector<long long>& ekf_ids, bool* fall_back)
+// What a gated update leaves to the host, after its sync.  The MSCKF jobs [order[0]) in ascending order: a job whose triangulation
+// was consumed on the device (RowJob::tri) has its answer read and applied in `mode`, and one whose triangulation failed is not used
+// (its rows were zeroed on the device); the others pass through gate_ok and are recorded as MSCKF points.  retire(job, tri_ok) is
+// the caller's bookkeeping for each of them.  Then the tracked in-state jobs [order[1]), two rows each.  Returns the accepted rows.
+template <class Retire>
+static int settle_update(lvk_ekf* e, const std::vector<RowJob>& jobs, const size_t (&order)[2][2], const std::vector<TriReq>& reqs, int mode, Retire retire)
 {
-    *fall_back = false;
+    int accepted = 0;
+    for (size_t k = order[0][0]; k < order[0][1]; ++k) {
+        const RowJob& j = jobs[k];
+        bool tri_ok = true;
+        if (j.tri >= 0) { const TriAns a = tri_answer(e, reqs[(size_t)j.tri], k); apply_tri(j.f, mode, a); tri_ok = a.ok; }
+        if (tri_ok && gate_ok(e, j)) { accepted += job_rows(j); lvk_ekf_msckf_point_record(e, j, k); }
+        retire(j, tri_ok);
+    }
+    for (size_t k = order[1][0]; k < order[1][1]; ++k) if (gate_ok(e, jobs[k])) accepted += 2;
+    return accepted;
+}
+// The triage of removeLostFeatures (larvio.cpp:1897-2005) over the features outside the state, in map order: which are invalid, which
+// wait (not listed), which are candidates for this update, and which triangulations those ask for (reqs).  admission: may the EKF
+// branch (:1945-1960) be taken in this message?  If not, only the MSCKF branch's request is made - initializePosition (mode 0) for a
+// feature that is not initialised and has moved enough - and a tracked feature that has not moved waits.  If it may, a long tracked
+// feature asks for both branches (mode 2, always from the two-view guess, and mode 0: the EKF branch resets is_initialized first) and
+// stays listed whatever its motion, because the replay decides its branch.
+struct Cand { Feature* f; bool tracked, invalid, motion; int idx_pos, idx_inv; };
+static void lost_triage(lvk_ekf* e, bool admission, std::vector<Cand>& cands, std::vector<TriReq>& reqs)
+{
     const lvk_ekf_config& c = e->cfg;
-    struct Pick { Feature* f; bool lost; int tri; };
-    std::vector<Pick> picks; std::vector<long long> invalid; std::vector<TriReq> reqs;
-    e->tri_ranks.clear(); e->tri_z.clear();
-    const int n_ekf = (int)ekf_ids.size();
+    cands.clear(); reqs.clear(); e->tri_ranks.clear(); e->tri_z.clear();
     for (auto kv : e->map) {
         Feature& f = kv.second;
         if (f.in_state) continue;
-        const bool tracked = f.find(e->imu_id) >= 0;
-        if (!tracked) { if ((int)f.obs.size() < c.least_observation_number) { invalid.push_back(f.id); continue; } }
-        else if (!((int)f.obs.size() >= c.max_track_len)) continue;
-        int tri = -1;
-        if (!f.is_initialized) {
-            if (!feat_check_motion(e, f, tracked)) { if (!tracked) invalid.push_back(f.id); continue; }
-            reqs.emplace_back(); make_tri_req(e, &f, 0, &reqs.back()); tri = (int)reqs.size() - 1;
-            reqs.back().slot = n_ekf + (int)picks.size();
+        Cand cd = {&f, f.find(e->imu_id) >= 0, false, false, -1, -1};
+        if (cd.tracked && (int)f.obs.size() < c.max_track_len) continue;
+        const bool both = cd.tracked && admission;
+        if (!cd.tracked && (int)f.obs.size() < c.least_observation_number) cd.invalid = true;
+        else if (!f.is_initialized || both) {
+            cd.motion = feat_check_motion(e, f, cd.tracked);
+            if (!cd.motion && !both) { if (cd.tracked) continue; cd.invalid = true; }     // a lost feature that has not moved is invalid (:1911-1916); a tracked one waits for more views
         }
-        picks.push_back({&f, !tracked, tri});
-    }
-    for (long long id : invalid) e->map.erase(id);
-    if (picks.empty() && ekf_ids.empty()) return LVK_OK;
-    {   // Every candidate keeps its row slots here, also the ones whose (pending) triangulation will fail - the general path drops those
-        // before it stacks.  If the slots could exceed the stacked-row capacity while the rows that survive might still fit, take the
-        // general path (two waits) instead of failing the handle with LVK_ERR_CAPACITY.
-        long bound = 2L * n_ekf; bool pending = false;
-        for (const Pick& pk : picks) { bound += 2L * (long)pk.f->obs.size() - 3; pending |= pk.tri >= 0; }
-        if (bound > (long)e->hrows && pending) { *fall_back = true; return LVK_OK; }
-    }
-    std::vector<RowJob> jobs; jobs.reserve(ekf_ids.size() + picks.size());
-    for (long long id : ekf_ids) { Feature& f = e->map[id]; RowJob r; r.f = &f; r.type = JOB_EKF_TRACKED; r.sids = {e->imu_id}; r.want_gate = true; r.dof = 2; jobs.push_back(r); }
-    for (const Pick& pk : picks) {
-        RowJob r; r.f = pk.f; r.type = JOB_MSCKF; r.want_gate = true; r.dof = 2 * (int)pk.f->obs.size() - 3; r.tri_pending = pk.tri >= 0;
-        r.sids.reserve(pk.f->obs.size()); for (auto& o : pk.f->obs) r.sids.push_back(o.sid);
-        jobs.push_back(r);
-    }
-    TR(TR_RLF_PRE);
-    lvk_status st = launch_triangulation(e, reqs);
-    if (st != LVK_OK) return st;
-    TR(TR_RLF_TRI);
-    TR(TR_RLF_TRIAGE);
-    std::vector<double> dx;
-    st = gated_update(e, jobs, {{(size_t)n_ekf, jobs.size()}, {0, (size_t)n_ekf}}, {-1, TR_RLF_UPD, TR_RLF_DX}, dx, nullptr, 0, (size_t)n_ekf, jobs.size());
-    if (st != LVK_OK) return st;
-    int accepted = 0;
-    for (size_t k = (size_t)n_ekf; k < jobs.size(); ++k) {
-        const Pick& pk = picks[k - (size_t)n_ekf];
-        if (pk.tri >= 0) {
-            const TriAns a = tri_answer(e, reqs[(size_t)pk.tri], k);
-            apply_tri(pk.f, 0, a);
-            if (!a.ok) { if (pk.lost) e->map.erase(pk.f->id); continue; }      // a lost feature that cannot be triangulated is invalid (:1921-1925); a tracked one waits for more views
+        if (cd.motion) {
+            if (both && !f.ekf_feature) { reqs.emplace_back(); make_tri_req(e, &f, 2, &reqs.back()); reqs.back().use_pos = false; cd.idx_inv = (int)reqs.size() - 1; }
+            if (!f.is_initialized || (both && !f.ekf_feature)) { reqs.emplace_back(); make_tri_req(e, &f, 0, &reqs.back()); cd.idx_pos = (int)reqs.size() - 1; }
         }
-        if (gate_ok(e, jobs[k])) { accepted += job_rows(jobs[k]); msckf_point_record(e, jobs[k], k); }
-        e->map.erase(pk.f->id);                          // used (:2240-2246)
+        cands.push_back(cd);
     }
-    for (size_t k = 0; k < (size_t)n_ekf; ++k) if (gate_ok(e, jobs[k])) accepted += 2;
-    gated_update_apply(e, dx, accepted, 0);
-    TR(TR_RLF_INJ);
-    return LVK_OK;
 }
 static lvk_status remove_lost_features(lvk_ekf* e)
 {
     const lvk_ekf_config& c = e->cfg;
     const int cells = c.aug_grid_rows * c.aug_grid_cols;
-    std::vector<long long> ekf_ids, ekf_lost;
+    std::vector<Feature*> ekf_tracked; std::vector<long long> ekf_lost;
     std::vector<const Feature*> long_tracked;                    // tracked, not in the state, max_track_len observations: what may ask for admission
     for (auto kv : e->map) {
         Feature& f = kv.second;
         const bool tracked = f.find(e->imu_id) >= 0;
-        if (f.in_state) { if (tracked) ekf_ids.push_back(f.id); else ekf_lost.push_back(f.id); }
+        if (f.in_state) { if (tracked) ekf_tracked.push_back(&f); else ekf_lost.push_back(f.id); }
         else if (tracked && (int)f.obs.size() >= c.max_track_len) long_tracked.push_back(&f);
     }
     lvk_status st;
     if (!ekf_lost.empty()) {                                     // rmLostFeaturesCov (:3296-3348): all lost columns in one gather
         std::vector<char> drop(e->N, 0);
         for (long long id : ekf_lost) drop[LEG + 6 * (int)e->clones.size() + fs_rank(e, id)] = 1;
-        if (e->lost_cov_on) { st = lost_cov_queue(e, ekf_lost); if (st != LVK_OK) return st; }
+        if (e->lost_cov_on) { st = lvk_ekf_lost_cov_queue(e, ekf_lost); if (st != LVK_OK) return st; }
         st = cov_drop(e, drop);
         if (st != LVK_OK) return st;
         for (long long id : ekf_lost) {
             const Feature& f = e->map.at(id);                    // lost_slam_features (:3342): kept for getStableMapPointPositions
-            if (e->lost_slam.size() >= (size_t)1 << 16) e->lost_slam.erase(e->lost_slam.begin(), e->lost_slam.begin() + (1 << 15));
             lvk_ekf::LostPoint lp = {id, {f.position[0], f.position[1], f.position[2]}, {}};
             for (double& v : lp.cov) v = NAN;
-            e->lost_slam.push_back(lp);
+            drain_append(e->lost_slam, lp);
             e->feature_states.erase(e->feature_states.begin() + fs_rank(e, id)); e->map.erase(id);
         }
     }
@@ -1739,8 +1250,16 @@ static lvk_status remove_lost_features(lvk_ekf* e)
     }
     st = upload_clones(e);
     if (st != LVK_OK) return st;
+    // Two routes consume one triage.  DEVICE-CONSUMED, when no feature can enter the state in this update (the usual message: the
+    // augmentation grid is full, or no track has reached max_track_len in a free cell) and the update is not sharded: NOTHING on the
+    // host depends on a device result before the update is launched.  The triangulations are queued and consumed on the device by the
+    // row kernel (FJ_TRI_PENDING: a failed triangulation = a rejected job = zero rows, which leave the update unchanged), every
+    // candidate is a job and has its row slots, and triangulation results, gate results and dx come back in ONE sync.
+    // HOST-REPLAYED otherwise: the triangulations are waited for and the candidates replayed in map order, the grid filling while the
+    // replay runs.  Same decisions, same rows, same update (larvio.cpp:1897-2005): only the order in which the host learns them differs.
+    bool on_device = false;
     if (!e->if_zupt && !e->shard.fn) {
-        // can the triage below take its EKF branch for anybody (:1945-1960)?  The grid only fills up while it runs, so "nobody now" is final.
+        // can the replay take its EKF branch for anybody (:1945-1960)?  The grid only fills up while it runs, so "nobody now" is final.
         bool admission = false;
         if (e->s.t - e->last_zupt_time > 5 && (int)e->feature_states.size() < c.max_features_in_one_grid * cells)
             for (const Feature* f : long_tracked) {
@@ -1748,202 +1267,185 @@ static lvk_status remove_lost_features(lvk_ekf* e)
                 const int gcount = grid_occupancy(e, code, cells);
                 if (gcount < c.max_features_in_one_grid) { admission = true; break; }
             }
-        if (!admission) { bool fall_back = false; const lvk_status fs = remove_lost_fast(e, ekf_ids, &fall_back); if (!fall_back) return fs; }
+        on_device = !admission;
     }
-    // ---- pass 1: every triangulation the triage may ask for, batched on the device, then replayed in map order.
-    //      (a) lost, not initialised: initializePosition.  (b) tracked long, not in state: the EKF branch wants
-    //      initializeInvParamPosition (always from the two-view guess), the MSCKF branch initializePosition.
-    std::vector<TriReq> reqs; std::vector<TriAns> ans;
-    e->tri_ranks.clear(); e->tri_z.clear();
-    struct Cand { Feature* f; int idx_pos = -1, idx_inv = -1; bool motion; };
-    std::vector<Cand> cands;
-    for (auto kv : e->map) {
-        Feature& f = kv.second;
-        if (f.in_state) continue;
-        const bool tracked = f.find(e->imu_id) >= 0;
-        Cand cd; cd.f = &f; cd.motion = false;
-        if (!tracked) {
-            if ((int)f.obs.size() < c.least_observation_number) continue;
-            if (!f.is_initialized) { cd.motion = feat_check_motion(e, f, tracked); if (cd.motion) { reqs.emplace_back(); make_tri_req(e, &f, 0, &reqs.back()); cd.idx_pos = (int)reqs.size() - 1; } }
-        } else {
-            if (!((int)f.obs.size() >= c.max_track_len)) continue;
-            cd.motion = feat_check_motion(e, f, tracked);
-            if (cd.motion) {
-                if (!f.ekf_feature) { reqs.emplace_back(); make_tri_req(e, &f, 2, &reqs.back()); reqs.back().use_pos = false; cd.idx_inv = (int)reqs.size() - 1; }
-                if (!f.is_initialized || !f.ekf_feature) {
-                    // the MSCKF branch runs initializePosition only when !is_initialized; the EKF branch resets is_initialized first.
-                    reqs.emplace_back(); make_tri_req(e, &f, 0, &reqs.back()); cd.idx_pos = (int)reqs.size() - 1;
-                }
-            }
+    std::vector<Cand> cands; std::vector<TriReq> reqs; std::vector<RowJob> jobs;
+    lost_triage(e, !on_device, cands, reqs);
+    if (on_device) {
+        // Every candidate keeps its row slots on this route, also the ones whose (pending) triangulation will fail - the replay drops
+        // those before it stacks.  If the slots could exceed the stacked-row capacity while the rows that survive might still fit,
+        // replay on the host (two waits) instead of failing the handle with LVK_ERR_CAPACITY.
+        long bound = 2L * (long)ekf_tracked.size(); size_t n_jobs = ekf_tracked.size();
+        for (const Cand& cd : cands) if (!cd.invalid) { bound += 2L * (long)cd.f->obs.size() - 3; ++n_jobs; }
+        jobs.reserve(n_jobs);
+        if (bound > (long)e->hrows && !reqs.empty()) { on_device = false; lost_triage(e, true, cands, reqs); }
+    }
+    for (const Cand& cd : cands) if (cd.invalid) e->map.erase(cd.f->id);
+    // ---- device batch: [new: msckf-form gate | new: ekf rows] [tracked ekf] [msckf]
+    std::vector<Feature*> msckf, ekf_new;
+    size_t j_ekf = 0, j_msckf = ekf_tracked.size();
+    if (on_device) {
+        for (Feature* f : ekf_tracked) jobs.push_back(tracked_job(e, f));
+        for (const Cand& cd : cands) {
+            if (cd.invalid) continue;
+            if (cd.idx_pos >= 0) reqs[(size_t)cd.idx_pos].slot = (int)jobs.size();
+            jobs.push_back(msckf_job(cd.f, cd.idx_pos));
         }
-        cands.push_back(cd);
-    }
-    TR(TR_RLF_PRE);
-    st = run_triangulation(e, reqs, ans);
-    if (st != LVK_OK) return st;
-    TR(TR_RLF_TRI);
-    // ---- pass 2: sequential triage (map order) with the precomputed results
-    std::vector<long long> invalid, msckf, ekf_new;
-    size_t ci = 0;
-    for (auto kv : e->map) {
-        Feature& f = kv.second;
-        if (f.in_state) continue;
-        const bool tracked = f.find(e->imu_id) >= 0;
-        if (!tracked) {
-            if ((int)f.obs.size() < c.least_observation_number) { invalid.push_back(f.id); continue; }
-            Cand& cd = cands[ci++];
-            if (!f.is_initialized) {
-                if (!cd.motion) { invalid.push_back(f.id); continue; }
-                apply_tri(&f, 0, ans[cd.idx_pos]);
-                if (!ans[cd.idx_pos].ok) { invalid.push_back(f.id); continue; }
+        if (jobs.empty()) return LVK_OK;
+        TR(TR_RLF_PRE);
+        st = launch_triangulation(e, reqs);
+        if (st != LVK_OK) return st;
+        TR(TR_RLF_TRI);
+    } else {
+        std::vector<TriAns> ans;
+        TR(TR_RLF_PRE);
+        st = run_triangulation(e, reqs, ans);
+        if (st != LVK_OK) return st;
+        TR(TR_RLF_TRI);
+        for (const Cand& cd : cands) {
+            if (cd.invalid) continue;
+            Feature& f = *cd.f;
+            if (!cd.tracked) {
+                if (!f.is_initialized) {
+                    apply_tri(&f, 0, ans[(size_t)cd.idx_pos]);
+                    if (!ans[(size_t)cd.idx_pos].ok) { e->map.erase(f.id); continue; }      // a lost feature that cannot be triangulated is invalid (:1921-1925)
+                }
+                msckf.push_back(&f);
+                continue;
             }
-            msckf.push_back(f.id);
-        } else {
-            if (!((int)f.obs.size() >= c.max_track_len)) continue;
-            Cand& cd = cands[ci++];
-            const int oi = f.find(e->imu_id);
-            const int code = grid_code(e, f.obs[oi].z);
+            const int code = grid_code(e, f.obs[(size_t)f.find(e->imu_id)].z);
             const int gcount = grid_occupancy(e, code, cells);
             if (gcount < c.max_features_in_one_grid && e->s.t - e->last_zupt_time > 5 &&
                 (int)(e->feature_states.size() + ekf_new.size()) < c.max_features_in_one_grid * cells) {
                 if (!f.ekf_feature) {
                     f.is_initialized = false;
-                    if (cd.motion) apply_tri(&f, 2, ans[cd.idx_inv]);
+                    if (cd.motion) apply_tri(&f, 2, ans[(size_t)cd.idx_inv]);
                 }
                 if (!f.is_initialized) continue;
-                ekf_new.push_back(f.id);
+                ekf_new.push_back(&f);
                 grid_add(e, code, cells);
             } else {
-                if (!f.is_initialized) { if (cd.motion && cd.idx_pos >= 0) apply_tri(&f, 0, ans[cd.idx_pos]); }
+                if (!f.is_initialized && cd.idx_pos >= 0) apply_tri(&f, 0, ans[(size_t)cd.idx_pos]);
                 if (!f.is_initialized) continue;
-                msckf.push_back(f.id);
+                msckf.push_back(&f);
             }
         }
-    }
-    for (long long id : invalid) e->map.erase(id);
-    if (msckf.empty() && ekf_new.empty() && ekf_ids.empty()) return LVK_OK;
-    if (!e->if_zupt) {
-        const int N = e->N;
-        const size_t n_fs_old = e->feature_states.size();
-        for (long long id : ekf_new) { e->map[id].in_state = true; e->feature_states.push_back(id); }
-        // ---- device batch: [new: msckf-form gate | new: ekf rows] [tracked ekf] [msckf]
-        std::vector<RowJob> jobs;
-        auto all_sids = [](Feature& f) { std::vector<long long> v; for (auto& o : f.obs) v.push_back(o.sid); return v; };
-        for (long long id : ekf_new) {
-            Feature& f = e->map[id];
-            RowJob g; g.f = &f; g.type = JOB_MSCKF; g.sids = all_sids(f); g.want_gate = true; g.dof = 2 * (int)f.obs.size() - 3; jobs.push_back(g);
-            RowJob r; r.f = &f; r.type = JOB_EKF_NEW; r.want_gate = false; r.dof = 0;
-            for (auto& o : f.obs) if (o.sid != f.id_anchor) r.sids.push_back(o.sid);
-            jobs.push_back(r);
-        }
-        const size_t j_ekf = jobs.size();
-        for (long long id : ekf_ids) { Feature& f = e->map[id]; RowJob r; r.f = &f; r.type = JOB_EKF_TRACKED; r.sids = {e->imu_id}; r.want_gate = true; r.dof = 2; jobs.push_back(r); }
-        const size_t j_msckf = jobs.size();
-        for (long long id : msckf) { Feature& f = e->map[id]; RowJob r; r.f = &f; r.type = JOB_MSCKF; r.sids = all_sids(f); r.want_gate = true; r.dof = 2 * (int)f.obs.size() - 3; jobs.push_back(r); }
-        // NOTE: the feature column index of a new feature must be its FINAL one (after rejected candidates are dropped);
-        // it is not used by JOB_EKF_NEW rows (the feature column never reaches H_o), so any value works here.
-        TR(TR_RLF_TRIAGE);
-        if (ekf_new.empty()) {
-            std::vector<double> dx;                     // no feature enters the state: gate results and dx in one sync (j_ekf == 0)
-            st = gated_update(e, jobs, {{j_msckf, jobs.size()}, {j_ekf, j_msckf}}, {-1, TR_RLF_UPD, TR_RLF_DX}, dx, nullptr, 0, j_msckf, jobs.size());
-            if (st != LVK_OK) return st;
-            int accepted = 0;
-            for (size_t k = j_msckf; k < jobs.size(); ++k) if (gate_ok(e, jobs[k])) { accepted += job_rows(jobs[k]); msckf_point_record(e, jobs[k], k); }
-            for (size_t k = j_ekf; k < j_msckf; ++k) if (gate_ok(e, jobs[k])) accepted += 2;
-            gated_update_apply(e, dx, accepted, 0);
-            for (long long id : msckf) e->map.erase(id);
+        if (msckf.empty() && ekf_new.empty() && ekf_tracked.empty()) return LVK_OK;
+        if (e->if_zupt) {
+            for (Feature* f : msckf) { f->is_initialized = false; e->map.erase(f->id); }
             TR(TR_RLF_INJ);
             return LVK_OK;
         }
-        // A feature is about to enter the state: its gate has to be read before the rows are laid out.  Sharded: the (few) new
-        // features' jobs run on every rank (their first rows initialise the new covariance columns everywhere, and every rank reads
-        // their gate from its own results), the rest is split.  The other jobs' rows all get their slot and the device zeroes the
-        // rows of rejected features - exactly as in the branch above - so their gate results travel WITH the compressed blocks:
-        // one exchange per update, and the host reads them after the update together with dx.
-        const bool sharded = e->shard.fn != nullptr;
-        std::vector<size_t> jb; JobRanges rgs;
-        if (sharded) {
-            shard_bounds(jobs, j_ekf, jobs.size(), e->shard.world, jb);
-            rgs.push_back({0, j_ekf}); rgs.push_back({jb[(size_t)e->shard.rank], jb[(size_t)e->shard.rank + 1]});
-            st = launch_feature_rows(e, jobs, &rgs);
-            if (st == LVK_OK) st = fetch_feature_results(e, jobs);          // local sync: only jobs [0, j_ekf) are looked at before the exchange
-            if (st != LVK_OK) shard_abort(e);                               // the exchange's size depends on those results: cannot post a poisoned block
-        } else {
-            RowObs obs;
-            st = launch_feature_rows(e, jobs, nullptr, &obs);
-            if (st == LVK_OK) st = msckf_points_queue(e, jobs, j_msckf, jobs.size(), obs);
-            if (st == LVK_OK) st = fetch_feature_results(e, jobs);
-        }
-        if (st != LVK_OK) return st;
-        auto own_of = [&](size_t k) { return sharded ? shard_owner(jb, k) : 0; };
-        TR(TR_RLF_ROWS);
-        // ---- accepted sets and row layout: H_o = [H_msckf ; H_ekf ; top rows of the new block] (:1612-1626)
-        std::vector<StackRow> map_o, map_1; std::vector<RowGroup> grp;
-        int rows_m = 0, rows_e = 0, top = 0;
-        if (sharded) {
-            for (size_t k = j_msckf; k < jobs.size(); ++k) { const int r = job_rows(jobs[k]); push_rows(map_o, jobs[k], job_first_row(jobs[k]), r, rows_m, (int)k, &grp, e, N, own_of(k)); rows_m += r; }
-            for (size_t k = j_ekf; k < j_msckf; ++k) { push_rows(map_o, jobs[k], 0, 2, rows_m + rows_e, (int)k, &grp, e, N, own_of(k)); rows_e += 2; }
-        } else {
-            for (size_t k = j_msckf; k < jobs.size(); ++k) if (gate_ok(e, jobs[k])) { push_rows(map_o, jobs[k], jobs[k].res.first_row, jobs[k].res.rows, rows_m, -1, &grp, e, N, own_of(k)); rows_m += jobs[k].res.rows; msckf_point_record(e, jobs[k], k); }
-            for (size_t k = j_ekf; k < j_msckf; ++k) if (gate_ok(e, jobs[k])) { push_rows(map_o, jobs[k], 0, 2, rows_m + rows_e, -1, &grp, e, N, own_of(k)); rows_e += 2; }
-        }
-        std::vector<long long> acc_ids; std::vector<double> h2;
-        std::vector<size_t> acc_jobs;
-        for (size_t k = 0; k < j_ekf; k += 2) {
-            Feature* f = jobs[k].f;
-            if (gate_ok(e, jobs[k])) { acc_ids.push_back(f->id); acc_jobs.push_back(k + 1); h2.push_back(jobs[k + 1].res.h2); }
-            else f->in_state = false;
-        }
-        for (size_t a = 0; a < acc_jobs.size(); ++a) {
-            const RowJob& j = jobs[acc_jobs[a]];
-            push_rows(map_o, j, 1, j.res.rows, rows_m + rows_e + top, -1, &grp, e, N); top += j.res.rows;
-            push_rows(map_1, j, 0, 1, (int)a);
-        }
-        e->feature_states.resize(n_fs_old);
-        for (long long id : acc_ids) e->feature_states.push_back(id);
-        int m = rows_m + rows_e + top; const int n_acc = (int)acc_ids.size();
-        if (m + n_acc > 0) {
-            if (m > e->hrows) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "too many measurement rows (%d)", m);
-            if (sharded) { st = shard_stage1(e, map_o, grp, N, &jb, &m); e->shard.stats[2]++; }         // the new features' top rows belong to rank 0 (owner 0)
-            else st = stack_rows(e, map_o, e->d_H, N, e->d_r);
-            if (st == LVK_OK && n_acc) st = stack_rows(e, map_1, e->d_H1, N, e->d_r1);
-            if (st != LVK_OK) return st;
-            std::vector<double> dx;
-            st = dense_update(e, m, dx, n_acc, &grp);
-            if (st != LVK_OK) return st;
-            if (n_acc) {
-                double* hh = up_alloc<double>(e, n_acc);
-                if (!hh) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "upload arena exhausted");
-                memcpy(hh, h2.data(), sizeof(double) * n_acc);
-                st = flush_uploads(e);
-                if (N + n_acc > e->nmax) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "state dimension exceeds capacity");
-                const double* d_hh = dev(e, hh);
-                e->redo = [e, N, n_acc, d_hh]() { return lvk_cov_append_features(e->ctx, e->dP[e->cur], e->ld, N, n_acc, e->d_H1, e->ld, d_hh, e->d_r1, e->d_dx, e->sigma2, e->d_tmp, e->d_dx + N); };
-                if (st == LVK_OK) st = e->redo();
-                if (st != LVK_OK) return st;
-            }
-            TR(TR_RLF_UPD);
-            st = d2h_sync(e, dx.data(), e->d_dx, sizeof(double) * (size_t)(N + n_acc));
-            if (st != LVK_OK) return st;
-            TR(TR_RLF_DX);
-            bool effective = true;
-            if (sharded) {                              // every rank's gate results arrived with the blocks (k_shard_unpack wrote the host mirror)
-                const FeatResult* ho = (const FeatResult*)(e->h_down + e->down_feat);
-                int accepted = top;
-                for (size_t k = j_ekf; k < jobs.size(); ++k) { jobs[k].res = ho[k]; if (gate_ok(e, jobs[k])) accepted += k >= j_msckf ? job_rows(jobs[k]) : 2; }
-                effective = accepted + n_acc > 0;       // everything gated out: all stacked rows were zero, the update changed nothing (as the unsharded filter, which skips it)
-            }
-            if (effective) {
-                inject(e, dx.data());
-                e->N = N + n_acc;
-                e->last_update_time = e->s.t;
-                e->counters[0]++;
-            }
-        }
-    } else {
-        for (long long id : msckf) { auto it = e->map.find(id); if (it != e->map.end()) it->second.is_initialized = false; }
+        for (Feature* f : ekf_new) new_feature_jobs(f, jobs);
+        j_ekf = jobs.size();
+        for (Feature* f : ekf_tracked) jobs.push_back(tracked_job(e, f));
+        j_msckf = jobs.size();
+        for (Feature* f : msckf) jobs.push_back(msckf_job(f));
     }
-    for (long long id : msckf) e->map.erase(id);
+    TR(TR_RLF_TRIAGE);
+    const int N = e->N;
+    const size_t order[2][2] = {{j_msckf, jobs.size()}, {j_ekf, j_msckf}};      // H_o = [H_msckf ; H_ekf], the reference's order (:1612-1626)
+    if (ekf_new.empty()) {
+        std::vector<double> dx;                         // no feature enters the state: gate results and dx in one sync
+        st = gated_update(e, jobs, order, {-1, TR_RLF_UPD, TR_RLF_DX}, dx, nullptr, 0, j_msckf, jobs.size());
+        if (st != LVK_OK) return st;
+        // used features leave the map (:2240-2246); so does a lost one that cannot be triangulated, while a tracked one waits for more views
+        const int accepted = settle_update(e, jobs, order, reqs, 0, [e](const RowJob& j, bool tri_ok) { if (tri_ok || j.f->find(e->imu_id) < 0) e->map.erase(j.f->id); });
+        gated_update_apply(e, dx, accepted, 0);
+        TR(TR_RLF_INJ);
+        return LVK_OK;
+    }
+    // A feature is about to enter the state: its gate has to be read before the rows are laid out.  Sharded: the (few) new
+    // features' jobs run on every rank (their first rows initialise the new covariance columns everywhere, and every rank reads
+    // their gate from its own results), the rest is split.  The other jobs' rows all get their slot and the device zeroes the
+    // rows of rejected features - exactly as in the branch above - so their gate results travel WITH the compressed blocks:
+    // one exchange per update, and the host reads them after the update together with dx.
+    // NOTE: the feature column index of a new feature must be its FINAL one (after rejected candidates are dropped);
+    // it is not used by JOB_EKF_NEW rows (the feature column never reaches H_o), so any value works here.
+    const size_t n_fs_old = e->feature_states.size();
+    for (Feature* f : ekf_new) { f->in_state = true; e->feature_states.push_back(f->id); }
+    const bool sharded = e->shard.fn != nullptr;
+    std::vector<size_t> jb; JobRanges rgs;
+    if (sharded) {
+        shard_bounds(jobs, j_ekf, jobs.size(), e->shard.world, jb);
+        rgs.push_back({0, j_ekf}); rgs.push_back({jb[(size_t)e->shard.rank], jb[(size_t)e->shard.rank + 1]});
+        st = launch_feature_rows(e, jobs, &rgs);
+        if (st == LVK_OK) st = fetch_feature_results(e, jobs);          // local sync: only jobs [0, j_ekf) are looked at before the exchange
+        if (st != LVK_OK) shard_abort(e);                               // the exchange's size depends on those results: cannot post a poisoned block
+    } else {
+        RowObs obs;
+        st = launch_feature_rows(e, jobs, nullptr, &obs);
+        if (st == LVK_OK) st = lvk_ekf_msckf_points_queue(e, jobs, j_msckf, jobs.size(), obs);
+        if (st == LVK_OK) st = fetch_feature_results(e, jobs);
+    }
+    if (st != LVK_OK) return st;
+    TR(TR_RLF_ROWS);
+    // ---- accepted sets and row layout: H_o = [H_msckf ; H_ekf ; top rows of the new block] (:1612-1626).  Sharded, every job keeps
+    //      its slot (the device zeroes the rows of a rejected one); unsharded, only the accepted jobs are laid out, as they came back
+    std::vector<StackRow> map_o, map_1; std::vector<RowGroup> grp;
+    int m = 0;
+    for (const auto& rg : order)
+        for (size_t k = rg[0]; k < rg[1]; ++k) {
+            const RowJob& j = jobs[k];
+            if (sharded) { push_rows(map_o, j, job_first_row(j), job_rows(j), m, (int)k, &grp, e, N, shard_owner(jb, k)); m += job_rows(j); continue; }
+            if (!gate_ok(e, j)) continue;
+            const bool tracked = j.type == JOB_EKF_TRACKED;
+            const int first = tracked ? 0 : j.res.first_row, rows = tracked ? 2 : j.res.rows;
+            push_rows(map_o, j, first, rows, m, -1, &grp, e, N); m += rows;
+            if (!tracked) lvk_ekf_msckf_point_record(e, j, k);
+        }
+    std::vector<long long> acc_ids; std::vector<double> h2;
+    int top = 0;
+    for (size_t k = 0; k < j_ekf; k += 2) {
+        Feature* f = jobs[k].f;
+        if (!gate_ok(e, jobs[k])) { f->in_state = false; continue; }
+        const RowJob& j = jobs[k + 1];
+        push_rows(map_1, j, 0, 1, (int)acc_ids.size());
+        push_rows(map_o, j, 1, j.res.rows, m, -1, &grp, e, N); m += j.res.rows; top += j.res.rows;
+        acc_ids.push_back(f->id); h2.push_back(j.res.h2);
+    }
+    e->feature_states.resize(n_fs_old);
+    for (long long id : acc_ids) e->feature_states.push_back(id);
+    const int n_acc = (int)acc_ids.size();
+    if (m + n_acc > 0) {
+        if (m > e->hrows) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "too many measurement rows (%d)", m);
+        if (sharded) { st = shard_stage1(e, map_o, grp, N, &jb, &m); e->shard.stats[2]++; }         // the new features' top rows belong to rank 0 (owner 0)
+        else st = stack_rows(e, map_o, e->d_H, N, e->d_r);
+        if (st == LVK_OK && n_acc) st = stack_rows(e, map_1, e->d_H1, N, e->d_r1);
+        if (st != LVK_OK) return st;
+        std::vector<double> dx;
+        st = dense_update(e, m, dx, n_acc, &grp);
+        if (st != LVK_OK) return st;
+        if (n_acc) {
+            double* hh = up_alloc<double>(e, n_acc);
+            if (!hh) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "upload arena exhausted");
+            memcpy(hh, h2.data(), sizeof(double) * n_acc);
+            st = flush_uploads(e);
+            if (N + n_acc > e->nmax) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "state dimension exceeds capacity");
+            const double* d_hh = dev(e, hh);
+            e->redo = [e, N, n_acc, d_hh]() { return lvk_cov_append_features(e->ctx, e->dP[e->cur], e->ld, N, n_acc, e->d_H1, e->ld, d_hh, e->d_r1, e->d_dx, e->sigma2, e->d_tmp, e->d_dx + N); };
+            if (st == LVK_OK) st = e->redo();
+            if (st != LVK_OK) return st;
+        }
+        TR(TR_RLF_UPD);
+        st = d2h_sync(e, dx.data(), e->d_dx, sizeof(double) * (size_t)(N + n_acc));
+        if (st != LVK_OK) return st;
+        TR(TR_RLF_DX);
+        bool effective = true;
+        if (sharded) {                              // every rank's gate results arrived with the blocks (k_shard_unpack wrote the host mirror)
+            const FeatResult* ho = (const FeatResult*)(e->h_down + e->down_feat);
+            int accepted = top;
+            for (size_t k = j_ekf; k < jobs.size(); ++k) { jobs[k].res = ho[k]; if (gate_ok(e, jobs[k])) accepted += k >= j_msckf ? job_rows(jobs[k]) : 2; }
+            effective = accepted + n_acc > 0;       // everything gated out: all stacked rows were zero, the update changed nothing (as the unsharded filter, which skips it)
+        }
+        if (effective) {
+            inject(e, dx.data());
+            e->N = N + n_acc;
+            e->last_update_time = e->s.t;
+            e->counters[0]++;
+        }
+    }
+    for (Feature* f : msckf) e->map.erase(f->id);
     TR(TR_RLF_INJ);
     return LVK_OK;
 }
@@ -2049,11 +1551,13 @@ static lvk_status prune_imu_state_buffer(lvk_ekf* e)
         find_redundant(e, rm); nrm = 2;
     } else { rm[0] = e->imu_id - 1; nrm = 1; }
     lvk_status st;
-    // pass A: re-anchoring (host + rank-1 covariance op) and collection of the features that need a triangulation
-    struct Use { Feature* f; std::vector<long long> inv; int tri = -1; bool motion = true; };
+    // pass A: re-anchoring (host + rank-1 covariance op) and collection of the features the update uses, with the triangulations they need.
+    // Unsharded, those are consumed on the device by the row kernel (FJ_TRI_PENDING, see remove_lost_features): each names the job slot
+    // of its feature, and the host reads it together with the gate results and dx, after the update.  Sharded, they are waited for.
+    struct Use { Feature* f; std::vector<long long> inv; int tri = -1; };
     std::vector<Use> uses; std::vector<TriReq> reqs; std::vector<TriAns> ans;
+    const bool tri_on_device = !e->shard.fn;
     e->tri_ranks.clear(); e->tri_z.clear();
-    bool clones_uploaded = false;
     for (auto kv : e->map) {
         Feature& f = kv.second;
         struct { long long v[2]; int n = 0; void push_back(long long x) { v[n++] = x; } bool empty() const { return n == 0; } size_t size() const { return (size_t)n; }
@@ -2081,65 +1585,34 @@ static lvk_status prune_imu_state_buffer(lvk_ekf* e)
             if (!e->if_zupt && !f.ekf_feature && inv.size() > 1) {
                 Use u; u.f = &f; u.inv.assign(inv.begin(), inv.end());
                 if (!f.is_initialized) {
-                    const bool tracked = f.find(e->imu_id) >= 0;
-                    u.motion = feat_check_motion(e, f, tracked);
-                    if (u.motion) { reqs.emplace_back(); make_tri_req(e, &f, 1, &reqs.back()); u.tri = (int)reqs.size() - 1; }
+                    if (!feat_check_motion(e, f, f.find(e->imu_id) >= 0)) continue;      // has not moved enough: not used
+                    reqs.emplace_back(); make_tri_req(e, &f, 1, &reqs.back()); u.tri = (int)reqs.size() - 1;
+                    if (tri_on_device) reqs.back().slot = (int)uses.size();
                 }
                 uses.push_back(u);
             }
         }
     }
-    std::vector<Use*> used;
     TR(TR_PR_PRE);
-    // unsharded: the triangulations are consumed on the device by the row kernel (FJ_TRI_PENDING, see remove_lost_fast) - the host
-    // reads them together with the gate results and dx, after the update
-    const bool tri_on_device = !e->shard.fn;
-    if (!e->if_zupt && !uses.empty()) {
-        if (tri_on_device) {
-            for (auto& u : uses) {
-                if (!u.f->is_initialized) { if (!u.motion) continue; reqs[(size_t)u.tri].slot = (int)used.size(); }
-                used.push_back(&u);
-            }
-            if (!reqs.empty()) {
-                st = upload_clones(e); clones_uploaded = true;
-                if (st == LVK_OK) st = launch_triangulation(e, reqs);
-                if (st != LVK_OK) return st;
-            }
-        } else {
-            if (!reqs.empty()) {
-                st = upload_clones(e); clones_uploaded = true;
-                if (st == LVK_OK) st = run_triangulation(e, reqs, ans);
-                if (st != LVK_OK) return st;
-            }
-            for (auto& u : uses) {
-                if (!u.f->is_initialized) {
-                    if (!u.motion) continue;
-                    apply_tri(u.f, 1, ans[u.tri]);
-                    if (!ans[u.tri].ok) continue;
-                }
-                used.push_back(&u);
-            }
-        }
+    std::vector<RowJob> jobs;
+    if (!uses.empty()) {
+        st = upload_clones(e);
+        if (st == LVK_OK && !reqs.empty()) st = tri_on_device ? launch_triangulation(e, reqs) : run_triangulation(e, reqs, ans);
+        if (st != LVK_OK) return st;
+    }
+    for (const Use& u : uses) {
+        if (u.tri >= 0 && !tri_on_device) { apply_tri(u.f, 1, ans[(size_t)u.tri]); if (!ans[(size_t)u.tri].ok) continue; }
+        jobs.push_back(msckf_job(u.f, u.inv, tri_on_device ? u.tri : -1));
     }
     TR(TR_PR_TRI);
-    if (!e->if_zupt && !used.empty()) {
-        if (!clones_uploaded) { st = upload_clones(e); if (st != LVK_OK) return st; }
-        std::vector<RowJob> jobs;
-        for (Use* u : used) { RowJob r; r.f = u->f; r.type = JOB_MSCKF; r.sids = u->inv; r.want_gate = true; r.dof = 2 * (int)u->inv.size() - 3; r.tri_pending = tri_on_device && u->tri >= 0 && !u->f->is_initialized; jobs.push_back(r); }
-        // measurementUpdate_msckf (:1420-1602), gate decided on the device (gated_update): one sync for gate + dx
+    if (!jobs.empty()) {
+        // measurementUpdate_msckf (:1420-1602), gate decided on the device (gated_update): one sync for gate + dx, and for
+        // initializePosition_AssignAnchor's pending results (:2420-2440)
         std::vector<double> dx;
-        st = gated_update(e, jobs, {{0, jobs.size()}, {0, 0}}, {TR_PR_ROWS, TR_PR_UPD, TR_PR_DX}, dx, rm, nrm);
+        const size_t order[2][2] = {{0, jobs.size()}, {0, 0}};
+        st = gated_update(e, jobs, order, {TR_PR_ROWS, TR_PR_UPD, TR_PR_DX}, dx, rm, nrm);
         if (st != LVK_OK) return st;
-        int accepted = 0;
-        for (size_t k = 0; k < jobs.size(); ++k) {
-            if (jobs[k].tri_pending) {                   // initializePosition_AssignAnchor's result (:2420-2440), read now
-                const TriAns a = tri_answer(e, reqs[(size_t)used[k]->tri], k);
-                apply_tri(used[k]->f, 1, a);
-                if (!a.ok) continue;                      // not used in this update (its rows were zeroed on the device)
-            }
-            if (gate_ok(e, jobs[k])) accepted += job_rows(jobs[k]);
-        }
-        gated_update_apply(e, dx, accepted, 1);
+        gated_update_apply(e, dx, settle_update(e, jobs, order, reqs, 1, [](const RowJob&, bool) {}), 1);
     } else drop_observations(e, rm, nrm);
     {   // both clones' rows/columns leave P in ONE gather (the reference deletes them one after the other, :2563-2638)
         std::vector<char> drop(e->N, 0);
@@ -2151,7 +1624,7 @@ static lvk_status prune_imu_state_buffer(lvk_ekf* e)
             any = true;
         }
         if (any) {
-            if (e->keyframes_on) { st = keyframes_queue(e, rm, nrm); if (st != LVK_OK) return st; }
+            if (e->keyframes_on) { st = lvk_ekf_keyframes_queue(e, rm, nrm); if (st != LVK_OK) return st; }
             st = cov_drop(e, drop);
             if (st != LVK_OK) return st;
             for (int k = 0; k < nrm; ++k) { const int seq = clone_rank(e, rm[k]); if (seq >= 0) { e->clones.erase(e->clones.begin() + seq); e->ranks_dirty = true; e->rcam_valid = false; } }
@@ -2363,6 +1836,8 @@ void lvk_ekf_destroy(lvk_ekf* e)
     delete e;
 }
 
+static lvk_status ekf_process_guarded(lvk_ekf* e, double ts, const lvk_feature_obs* feats, int n_feats, const lvk_imu* imu, int n_imu, int* n_consumed, int* updated,
+                                      lvk_feats_fn fetch, void* fetch_user);
 lvk_status lvk_ekf_create(lvk_context* ctx, const lvk_ekf_config* cfg, lvk_ekf** out)
 {
     if (!ctx || !cfg || !out) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_ekf_create: bad argument");
@@ -2372,7 +1847,7 @@ lvk_status lvk_ekf_create(lvk_context* ctx, const lvk_ekf_config* cfg, lvk_ekf**
     g_tr.on = getenv("LVK_EKF_TRACE") != nullptr;
     lvk_ekf* e = new (std::nothrow) lvk_ekf();
     if (!e) return LVK_ERR_DEVICE;
-    e->ctx = ctx; e->cfg = *cfg;
+    e->ctx = ctx; e->cfg = *cfg; e->process = ekf_process_guarded;
     const lvk_ekf_config& c = e->cfg;
     e->leg = c.calib_imu_instrinsic ? 46 : 22;
     memset(e->imx, 0, sizeof e->imx);
@@ -2489,7 +1964,6 @@ lvk_status lvk_ekf_set_state(lvk_ekf* e, double t, const double q[4], const doub
 // feats == nullptr && fetch != nullptr: the message is collected through fetch() as late as the algorithm allows - after the IMU
 // samples have been integrated and the propagation / augmentation kernels are queued - so that a pipelined driver overlaps that
 // work with the front-end that is still producing the message (the static initializer needs the message first and asks at once).
-typedef lvk_status (*lvk_feats_fn)(void* user, const lvk_feature_obs** feats, int* n_feats);
 // event brackets of the profiled launches (lvk_ekf_profile): harvested when both events have fired (all = after a stream sync)
 static void prof_harvest(lvk_ekf* e, bool all)
 {
@@ -2508,8 +1982,6 @@ static void prof_harvest(lvk_ekf* e, bool all)
 }
 static lvk_status ekf_process_impl(lvk_ekf* e, double ts, const lvk_feature_obs* feats, int n_feats, const lvk_imu* imu, int n_imu, int* n_consumed, int* updated,
                                    lvk_feats_fn fetch, void* fetch_user);
-static lvk_status ekf_process_guarded(lvk_ekf* e, double ts, const lvk_feature_obs* feats, int n_feats, const lvk_imu* imu, int n_imu, int* n_consumed, int* updated,
-                                      lvk_feats_fn fetch, void* fetch_user);
 
 lvk_status lvk_ekf_process(lvk_ekf* e, double ts, const lvk_feature_obs* feats, int n_feats, const lvk_imu* imu, int n_imu, int* n_consumed, int* updated)
 {
@@ -2650,9 +2122,7 @@ static lvk_status ekf_process_impl(lvk_ekf* e, double ts, const lvk_feature_obs*
     // it reads the half of the upload arena the NEXT call leaves alone: the call returns without waiting for it.  The call after
     // that reuses this half - behind at least one stream sync of the call in between, which is why a call that had none ends with one.
     if (e->n_sync == 0) { EKF_HIP(hipStreamSynchronize(e->ctx->stream)); e->n_sync++; }
-    st = lost_cov_attach(e);
-    if (st != LVK_OK) return st;
-    st = keyframes_attach(e);
+    st = lvk_ekf_exports_attach(e);
     if (st != LVK_OK) return st;
     prof_harvest(e, false);
 #ifdef LVK_MSG_HASH_LOG   // debugging aid, compiled out of the product (make CXXFLAGS+=-DLVK_MSG_HASH_LOG); bounded: the first 65536 messages
@@ -2752,8 +2222,7 @@ lvk_status lvk_ekf_get_state(const lvk_ekf* e, double* o)
     if (!e || !o) return LVK_ERR_ARG;
     ekf_quiesce(e);
     if (e->failed != LVK_OK) return e->failed;           // a half-applied update: state, clone list and covariance layout are out of step
-    o[0] = e->s.t; memcpy(o + 1, e->s.q, 32); memcpy(o + 5, e->s.v, 24); memcpy(o + 8, e->s.p, 24); memcpy(o + 11, e->s.bg, 24); memcpy(o + 14, e->s.ba, 24);
-    memcpy(o + 17, e->R_b2c, 72); memcpy(o + 26, e->t_c_b, 24); o[29] = e->td;
+    ekf_state30(e, o);
     return LVK_OK;
 }
 lvk_status lvk_ekf_get_cov(lvk_ekf* e, double* h_P)
@@ -2845,137 +2314,12 @@ int lvk_ekf_get_features(const lvk_ekf* e, int64_t* ids, double* inv_depth, doub
     }
     return n;
 }
-int lvk_ekf_take_lost_features(lvk_ekf* e, int64_t* ids, double* pos_w, int cap)
-{
-    if (!e || !ids || !pos_w || cap <= 0) return 0;
-    ekf_quiesce(e);
-    const int n = std::min((int)e->lost_slam.size(), cap);
-    for (int i = 0; i < n; ++i) { ids[i] = e->lost_slam[i].id; memcpy(pos_w + 3 * i, e->lost_slam[i].p, 24); }
-    e->lost_slam.erase(e->lost_slam.begin(), e->lost_slam.begin() + n);
-    return n;
-}
-int lvk_ekf_take_lost_features_cov(lvk_ekf* e, int64_t* ids, double* pos_w, double* cov9, int cap)
-{
-    if (!e || cap <= 0) return 0;
-    ekf_quiesce(e);
-    const int n = std::min((int)e->lost_slam.size(), cap);
-    for (int i = 0; i < n; ++i) {
-        const lvk_ekf::LostPoint& lp = e->lost_slam[i];
-        if (ids) ids[i] = lp.id;
-        if (pos_w) memcpy(pos_w + 3 * i, lp.p, 24);
-        if (cov9) memcpy(cov9 + 9 * i, lp.cov, 72);
-    }
-    e->lost_slam.erase(e->lost_slam.begin(), e->lost_slam.begin() + n);
-    return n;
-}
-lvk_status lvk_ekf_set_lost_feature_cov(lvk_ekf* e, int on)
-{
-    if (!e) return LVK_ERR_ARG;
-    ekf_quiesce(e);
-    e->lost_cov_on = on != 0;
-    return LVK_OK;
-}
-lvk_status lvk_ekf_set_msckf_points(lvk_ekf* e, int on)
-{
-    if (!e) return LVK_ERR_ARG;
-    ekf_quiesce(e);
-    if (on && e->shard.fn) return lvk_set_error(e->ctx, LVK_ERR_UNSUPPORTED, "lvk_ekf_set_msckf_points: the sharded update does not export MSCKF points");
-    e->msckf_points_on = on != 0;
-    return LVK_OK;
-}
-int lvk_ekf_take_msckf_points(lvk_ekf* e, int64_t* ids, double* pos_w, double* cov9, int* n_obs, int cap)
-{
-    if (!e || cap <= 0) return 0;
-    ekf_quiesce(e);
-    const int n = std::min((int)e->msckf_points.size(), cap);
-    for (int i = 0; i < n; ++i) {
-        const lvk_ekf::MsckfPoint& mp = e->msckf_points[i];
-        if (ids) ids[i] = mp.id;
-        if (pos_w) memcpy(pos_w + 3 * i, mp.p, 24);
-        if (cov9) memcpy(cov9 + 9 * i, mp.cov, 72);
-        if (n_obs) n_obs[i] = mp.n_obs;
-    }
-    e->msckf_points.erase(e->msckf_points.begin(), e->msckf_points.begin() + n);
-    return n;
-}
-lvk_status lvk_ekf_set_keyframe_export(lvk_ekf* e, int on)
-{
-    if (!e) return LVK_ERR_ARG;
-    ekf_quiesce(e);
-    if (on && e->shard.fn) return lvk_set_error(e->ctx, LVK_ERR_UNSUPPORTED, "lvk_ekf_set_keyframe_export: the sharded update does not export keyframes");
-    e->keyframes_on = on != 0;
-    return LVK_OK;
-}
-int lvk_ekf_take_keyframes(lvk_ekf* e, lvk_keyframe* out, int cap)
-{
-    if (!e || !out || cap <= 0) return 0;
-    ekf_quiesce(e);
-    const int n = std::min((int)e->keyframes.size(), cap);
-    if (n) memcpy(out, e->keyframes.data(), sizeof(lvk_keyframe) * (size_t)n);
-    e->keyframes.erase(e->keyframes.begin(), e->keyframes.begin() + n);
-    return n;
-}
-lvk_status lvk_ekf_get_window_cov(lvk_ekf* e, int64_t* ids, double* cov_abs36, double* cov_rel36, int cap, int* n_out)
-{
-    if (!e || !n_out || cap < 0) return lvk_set_error(e ? e->ctx : nullptr, LVK_ERR_ARG, "lvk_ekf_get_window_cov: bad argument");
-    ekf_quiesce(e);
-    if (e->failed != LVK_OK) return e->failed;
-    const int n = std::min((int)e->clones.size(), cap);
-    *n_out = n;
-    if (ids) for (int i = 0; i < n; ++i) ids[i] = e->clones[(size_t)i].id;
-    if (n == 0 || (!cov_abs36 && !cov_rel36)) return LVK_OK;
-    // jobs 0..n-1: the absolute blocks; n..2n-2: clone i relative to clone i + 1 (against the whole window, also when cap cuts the list)
-    const int n_rel = std::min(n, (int)e->clones.size() - 1);
-    std::vector<lvk_pose_rel_job> jobs((size_t)(n + n_rel));
-    memset(jobs.data(), 0, sizeof(lvk_pose_rel_job) * jobs.size());
-    for (int i = 0; i < n + n_rel; ++i) {
-        lvk_pose_rel_job& j = jobs[(size_t)i];
-        const int ia = i < n ? -1 : i - n, ib = i < n ? i : i - n + 1;
-        const Clone& b = e->clones[(size_t)ib];
-        j.a_theta_col = j.a_p_col = -1; j.b_theta_col = LEG + 6 * ib; j.b_p_col = j.b_theta_col + 3;
-        memcpy(j.q_b, b.q, 32); memcpy(j.p_b, b.p, 24);
-        if (ia >= 0) { const Clone& a = e->clones[(size_t)ia]; j.a_theta_col = LEG + 6 * ia; j.a_p_col = j.a_theta_col + 3; memcpy(j.q_a, a.q, 32); memcpy(j.p_a, a.p, 24); }
-    }
-    std::vector<double> out(36 * jobs.size());
-    lvk_status st = lvk_ekf_pose_rel_cov(e->ctx, e->dP[e->cur], e->ld, e->N, jobs.data(), (int)jobs.size(), out.data());
-    if (st != LVK_OK) return st;
-    if (cov_abs36) memcpy(cov_abs36, out.data(), sizeof(double) * 36 * (size_t)n);
-    if (cov_rel36) {
-        for (int i = 36 * n_rel; i < 36 * n; ++i) cov_rel36[i] = NAN;
-        memcpy(cov_rel36, out.data() + 36 * (size_t)n, sizeof(double) * 36 * (size_t)n_rel);
-    }
-    return LVK_OK;
-}
-lvk_status lvk_ekf_get_feature_cov(lvk_ekf* e, int64_t* ids, int64_t* anchor_ids, double* pos_w, double* cov9, int cap, int* n_out)
-{
-    if (!e || !n_out || cap < 0) return lvk_set_error(e ? e->ctx : nullptr, LVK_ERR_ARG, "lvk_ekf_get_feature_cov: bad argument");
-    ekf_quiesce(e);
-    if (e->failed != LVK_OK) return e->failed;
-    const int n = std::min((int)e->feature_states.size(), cap);
-    std::vector<lvk_landmark_job> jobs; std::vector<int> slot((size_t)n, -1);
-    jobs.reserve((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        const Feature& f = e->map.at(e->feature_states[i]);
-        if (ids) ids[i] = f.id;
-        if (anchor_ids) anchor_ids[i] = f.id_anchor;
-        if (pos_w) memcpy(pos_w + 3 * i, f.position, 24);
-        lvk_landmark_job j;
-        if (cov9 && landmark_job(e, f, i, &j)) { slot[(size_t)i] = (int)jobs.size(); jobs.push_back(j); }
-    }
-    *n_out = n;
-    if (!cov9) return LVK_OK;
-    for (int i = 0; i < 9 * n; ++i) cov9[i] = NAN;
-    if (jobs.empty()) return LVK_OK;
-    std::vector<double> out(9 * jobs.size());
-    lvk_status st = lvk_ekf_landmark_cov(e->ctx, e->dP[e->cur], e->ld, e->N, jobs.data(), (int)jobs.size(), out.data());
-    if (st != LVK_OK) return st;
-    for (int i = 0; i < n; ++i) if (slot[(size_t)i] >= 0) memcpy(cov9 + 9 * i, &out[9 * (size_t)slot[(size_t)i]], 72);
-    return LVK_OK;
-}
 void lvk_ekf_counters(const lvk_ekf* e, long* out8) { if (e && out8) { ekf_quiesce(e); memcpy(out8, e->counters, sizeof e->counters); } }
 
-lvk_status lvk_vio_process(lvk_frontend* fe, lvk_ekf* ekf, const lvk_image* img, double ts,
-                           const lvk_imu* h_imu, int n_imu, int* n_consumed, int* has_msg, int* updated)
+// one frame through both halves: the front-end waits for its feature message, `process` (lvk_ekf_process, or lvk_ekf_process_async: what
+// the adapter classes do under the reference's blocking drivers, processImage returning the message to the caller) takes it
+static lvk_status vio_step(lvk_frontend* fe, lvk_ekf* ekf, const lvk_image* img, double ts, const lvk_imu* h_imu, int n_imu, int* n_consumed, int* has_msg, int* updated,
+                           lvk_status (*process)(lvk_ekf*, double, const lvk_feature_obs*, int, const lvk_imu*, int, int*, int*))
 {
     if (!fe || !ekf || !n_consumed || !has_msg || !updated) return LVK_ERR_ARG;
     *n_consumed = 0; *updated = 0; *has_msg = 0;
@@ -2984,355 +2328,15 @@ lvk_status lvk_vio_process(lvk_frontend* fe, lvk_ekf* ekf, const lvk_image* img,
     int n_out = 0;
     lvk_status st = lvk_frontend_process(fe, img, ts, h_imu, n_imu, msg.data(), (int)msg.size(), &n_out, has_msg);
     if (st != LVK_OK || !*has_msg) return st;
-    return lvk_ekf_process(ekf, ts, msg.data(), n_out, h_imu, n_imu, n_consumed, updated);
+    return process(ekf, ts, msg.data(), n_out, h_imu, n_imu, n_consumed, updated);
 }
-
-// The same two calls with the update deferred (lvk_ekf_process_async): what the adapter classes do under the reference's blocking
-// drivers.  The front-end half still waits for its feature message (processImage returns it to the caller).
-lvk_status lvk_vio_process_deferred(lvk_frontend* fe, lvk_ekf* ekf, const lvk_image* img, double ts,
-                                    const lvk_imu* h_imu, int n_imu, int* n_consumed, int* has_msg, int* will_update)
+lvk_status lvk_vio_process(lvk_frontend* fe, lvk_ekf* ekf, const lvk_image* img, double ts, const lvk_imu* h_imu, int n_imu, int* n_consumed, int* has_msg, int* updated)
 {
-    if (!fe || !ekf || !n_consumed || !has_msg || !will_update) return LVK_ERR_ARG;
-    *n_consumed = 0; *will_update = 0; *has_msg = 0;
-    static thread_local std::vector<lvk_feature_obs> msg;
-    if (msg.size() < 8192) msg.resize(8192);
-    int n_out = 0;
-    lvk_status st = lvk_frontend_process(fe, img, ts, h_imu, n_imu, msg.data(), (int)msg.size(), &n_out, has_msg);
-    if (st != LVK_OK || !*has_msg) return st;
-    return lvk_ekf_process_async(ekf, ts, msg.data(), n_out, h_imu, n_imu, n_consumed, will_update);
+    return vio_step(fe, ekf, img, ts, h_imu, n_imu, n_consumed, has_msg, updated, lvk_ekf_process);
 }
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------- pipelined driver
-// The reference's driver thread alternates processImage and processFeatures (app/larvioMain.cpp:87-117).  The two halves only
-// meet at the feature message and at the shared IMU vector, so here the back-end of frame k runs on its own context (stream)
-// in a worker thread while the front-end of frame k+1 runs on the caller's thread.  The one coupling that needs care is the
-// IMU vector: processFeatures erases what it consumed and the NEXT processImage integrates gyro samples from whatever is
-// left — submit() therefore waits until the erase count of every queued update is known (it is final before any GPU work).
-// The count depends on time stamps, on the state time the previous update's IMU batch leaves behind (time stamps again) and on the
-// camera-IMU time offset td, which every update moves a little (micro-seconds).  So when the count is the same for td - margin and
-// td + margin (LVK_PIPE_TD_MARGIN, 0.5 ms: the bound "image time + td + half an IMU period" is then at least that far from any IMU
-// sample) submit() takes it at once from the last published td and the caller's thread runs on while up to two updates are in
-// flight; the filter's thread checks the count against the real td when the job starts (never different in any run here; counted in
-// lvk_vio_pipe_early_counts if it ever is, and the IMU window is put right for the frames that follow).  Otherwise - an IMU sample
-// sample within the margin of the bound - it waits as before.
-// Two guards keep a wrong early count from ever reaching the filter (round-3 advice): (1) the IMU view of an update is NOT a copy made at
-// submit time but is cut by the filter's thread, when the job starts, from the driver's buffer at the filter's own head (the sum of the TRUE
-// counts of the updates before it) - so the filter integrates exactly the samples the sequential loop would, whatever submit() guessed;
-// a wrong guess can only have shown a few front-end frames a gyro window that starts one sample off (counted in n_early_wrong, and the
-// caller's head is put right at once); (2) submit() only guesses while td is quiet: the largest |td step| of the last eight updates,
-// times the updates that can be in flight, must stay well inside the margin - while td is still converging from a bad initial value
-// every frame waits for its count.
-static double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-struct lvk_vio_pipe {
-    lvk_frontend* fe; lvk_ekf* ekf;
-    std::vector<lvk_imu> imu; size_t head = 0;          // the driver's imu_msg_buffer = imu[head..) as the CALLER's thread sees it (early counts applied)
-    size_t base = 0, fhead = 0;                         // absolute index of imu[0]; absolute index the FILTER has consumed up to (true counts only)
-    struct Job { double ts; int slot = -1; std::vector<lvk_imu> view; size_t end_abs = 0; bool precounted = false; double t_submit = 0;      // slot: the front-end's message ring entry; view: cut by the worker from [fhead, end_abs)
-                 bool early = false; int n_pre = 0; double t0_pre = 0; };                                                // early: counted by submit() from the published td (to be checked)
-    std::vector<float> lat_us;                          // image-in -> state-out of every message-carrying frame (submit entry to update done)
-    bool cur_precounted = false;                        // the running job's erase count was already applied by submit()
-    std::deque<Job> q;
-    std::thread worker; std::mutex mu; std::condition_variable cv_job, cv_state;
-    std::atomic<unsigned> gen{0};                       // bumped on every state change: waiters poll it WITHOUT the mutex
-    int unknown_consume = 0;                            // queued or running updates whose erase count is not final yet
-    // what submit() needs for an early count, all under mu: the filter is initialised, td after the last finished update, the state
-    // time after the IMU batch of the last COUNTED job (the filter's own s.t belongs to its thread while a job runs)
-    bool steady = false; double td_pub = 0, state_t = 0, td_margin = 5e-4;
-    static constexpr int TD_HIST = 32;
-    double td_steps[TD_HIST] = {}; long n_td = 0;                       // |td change| of the last TD_HIST finished updates
-    double td_factor = 4.0;                             // see td_quiet(); LVK_PIPE_TD_FACTOR (read when the pipeline is created)
-    int depth = 2;                                      // updates the caller may have in flight when a frame starts (LVK_PIPE_DEPTH; 1: never more than one update ahead - lower latency, the filter's thread waits for messages)
-    long n_early = 0, n_early_wrong = 0;
-    int in_flight = 0;                                  // queued + running
-    long n_updates = 0, n_msgs = 0;
-    lvk_status st = LVK_OK;
-    bool stop = false;
-    std::vector<lvk_feature_obs> wmsg;                  // the worker's copy of the message it is processing
-    lvk_odometry_fn on_update = nullptr; void* on_update_user = nullptr;
-    double t_busy = 0, t_idle = 0, t_submit_wait = 0, t_fe = 0;
-    struct Ev { double t; int what; };                    // LVK_PIPE_LOG=<file>: event log (0 submit begin, 1 wait done, 2 front-end done,
-    std::vector<Ev> log; bool logging = false;            //  3 job queued [4 precounted], 5 job start, 6 job end)
-    void ev(int what) { if (logging) log.push_back({now_us(), what}); }   // LVK_EKF_TRACE: where the two threads spend their time (us)
-    bool td_quiet() const
-    {   // may submit() trust the published td for a count?  (depth + 1) updates can move td before the counted one starts
-        // The largest |td step| of the last TD_HIST updates, times td_factor, times the updates in flight, must stay inside the margin.
-        // Pipeline fuzz (tools/gpu/fuzz_pipeline.py), 2 of 280 random configurations: a td that is poorly observable (fisheye at 20 Hz
-        // publishing; an initial td of milliseconds) sits still for dozens of updates and then steps by 1 ms - 25 times its largest step
-        // before - and two counts taken from the stale td were one sample off (the filter's own view never is; two front-end frames
-        // integrated their gyro prediction over another window than the sequential loop's).  No history of steps predicts that; what
-        // the factor buys is fewer guesses: at 8 (LVK_PIPE_TD_FACTOR=8) those configurations run bit for bit like the sequential loop
-        // and bench.py's 20-step line loses 10-15 % of its early counts' benefit (6,700-7,800 against 8,900-9,250 frames/s, same box);
-        // at the default 4 the benchmark is where it was and an unconfirmed count is counted and reported (lvk_vio_pipe_early_counts).
-        if (n_td < 3) return false;
-        double mx = 0; for (int i = 0; i < TD_HIST && i < n_td; ++i) mx = std::max(mx, td_steps[i]);
-        return td_factor * (depth + 1) * mx < td_margin;
-    }
-};
-
-static void pipe_on_consumed(void* user, int n)
-{   // fired by the filter once per call, when the number of samples it erases is final (before any GPU work)
-    lvk_vio_pipe* p = (lvk_vio_pipe*)user;
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        p->fhead += (size_t)n;                          // the filter's own head: true counts only
-        if (p->cur_precounted) return;
-        p->head += (size_t)n; p->unknown_consume -= 1;
-        p->gen.fetch_add(1, std::memory_order_release);
-    }
-    p->cv_state.notify_all();
-}
-// Both threads hand over within tens of microseconds: poll briefly before sleeping on the condition variable.
-// The poll reads only the generation counter, never the mutex: a waiter that re-locks in a tight loop makes the other thread's
-// (short) critical sections queue behind it - that alone added ~30 us to every filter update.
-template <typename Pred> static void pipe_wait(lvk_vio_pipe* p, std::unique_lock<std::mutex>& lk, std::condition_variable& cv, Pred pred)
+lvk_status lvk_vio_process_deferred(lvk_frontend* fe, lvk_ekf* ekf, const lvk_image* img, double ts, const lvk_imu* h_imu, int n_imu, int* n_consumed, int* has_msg, int* will_update)
 {
-    for (int round = 0; round < 64; ++round) {
-        if (pred()) return;
-        const unsigned seen = p->gen.load(std::memory_order_acquire);
-        lk.unlock();
-        for (int spin = 0; spin < 4000 && p->gen.load(std::memory_order_acquire) == seen; ++spin) LVK_CPU_RELAX();
-        lk.lock();
-    }
-    cv.wait(lk, pred);
-}
-
-static void pipe_worker(lvk_vio_pipe* p)
-{
-    hipSetDevice(p->ekf->ctx->device);
-    if (const char* pin = getenv("LVK_PIN_WORKER")) {       // optional: keep the filter thread on one core (less jitter on big hosts)
-        cpu_set_t allowed, one; CPU_ZERO(&allowed); CPU_ZERO(&one);
-        if (sched_getaffinity(0, sizeof allowed, &allowed) == 0) {
-            int want = atoi(pin), pick = -1, seen = 0;
-            for (int c = 0; c < CPU_SETSIZE; ++c) if (CPU_ISSET(c, &allowed)) { if (seen == want) pick = c; ++seen; }
-            if (pick < 0) for (int c = CPU_SETSIZE - 1; c >= 0; --c) if (CPU_ISSET(c, &allowed)) { pick = c; break; }
-            if (pick >= 0) { CPU_SET(pick, &one); pthread_setaffinity_np(pthread_self(), sizeof one, &one); }
-        }
-    }
-    for (;;) {
-        lvk_vio_pipe::Job job;
-        const double t0 = now_us();
-        {
-            std::unique_lock<std::mutex> lk(p->mu);
-            pipe_wait(p, lk, p->cv_job, [&] { return p->stop || !p->q.empty(); });
-            if (p->q.empty()) return;
-            job = std::move(p->q.front()); p->q.pop_front();
-            p->cur_precounted = job.precounted;
-        }
-        const double t1 = now_us();
-        {   // this update's IMU view: from the filter's own head to what the driver had pushed when the frame was submitted
-            std::lock_guard<std::mutex> lk(p->mu); p->ev(5);
-            const size_t lo = std::min(p->fhead - p->base, p->imu.size()), hi = std::min(std::max(job.end_abs - p->base, lo), p->imu.size());
-            job.view.assign(p->imu.begin() + (long)lo, p->imu.begin() + (long)hi);
-        }
-        // The erase count of this update depends on time stamps, the state time and td only - all final now that the previous update
-        // is done - so it is published BEFORE this thread blocks on the message: the caller's next frame needs nothing else from here.
-        if (!job.precounted && p->ekf->b_first_features && p->ekf->is_gravity_set) {
-            double t_after = 0;
-            const int n = batch_imu_count(p->ekf, job.ts + p->ekf->td, job.view.data(), (int)job.view.size(), &t_after);
-            {
-                std::lock_guard<std::mutex> lk(p->mu);
-                p->head += (size_t)n; p->unknown_consume -= 1; p->cur_precounted = true; p->state_t = t_after;
-                p->gen.fetch_add(1, std::memory_order_release);
-            }
-            p->cv_state.notify_all();
-        } else if (job.early) {
-            // counted by submit() from an older td: the same count with the td this update starts from?  (The filter is not affected
-            // either way - its view starts at its own head; a wrong guess only moved the window the front-end of the frames submitted
-            // since integrated its gyro prediction over.)
-            double t_after = 0;
-            const int n = batch_imu_count(p->ekf, job.ts + p->ekf->td, job.view.data(), (int)job.view.size(), &t_after);
-            if (n != job.n_pre || p->ekf->s.t != job.t0_pre) {
-                static const bool verbose = getenv("LVK_VERBOSE") != nullptr;
-                if (verbose) fprintf(stderr, "[lvk pipe] early erase count not confirmed at t = %.4f: %d samples counted from td %.6f and state time %.4f, %d with td %.6f and state time %.4f (|td steps| of the last updates up to %.2e)\n",
-                                     job.ts, job.n_pre, p->td_pub, job.t0_pre, n, p->ekf->td, p->ekf->s.t, *std::max_element(p->td_steps, p->td_steps + lvk_vio_pipe::TD_HIST));
-                std::lock_guard<std::mutex> lk(p->mu);
-                const long nh = (long)p->head + (n - job.n_pre);
-                p->head = (size_t)std::max(nh, (long)(p->fhead - p->base)); p->head = std::min(p->head, p->imu.size()); p->n_early_wrong += 1;
-                if (p->q.empty()) p->state_t = t_after;                 // later jobs were counted from the wrong state time: they are checked in turn
-                for (int i = 0; i < lvk_vio_pipe::TD_HIST; ++i) p->td_steps[i] = p->td_margin;   // and nobody guesses again until TD_HIST quiet updates have gone by
-                p->gen.fetch_add(1, std::memory_order_release);
-            }
-        }
-        int used = 0, upd = 0;
-        // the message itself is collected on THIS thread (the caller's thread queued the frame and went on), and only when the update
-        // needs it: IMU integration, covariance propagation and clone augmentation run while the front-end is still tracking
-        struct Fetch { lvk_vio_pipe* p; int slot; bool done; } fx{p, job.slot, false};
-        auto fetch = [](void* u, const lvk_feature_obs** f, int* n) -> lvk_status {
-            Fetch* x = (Fetch*)u;
-            lvk_status fs = lvk_frontend_fetch_msg(x->p->fe, x->slot, x->p->wmsg.data(), (int)x->p->wmsg.size(), n);
-            *f = x->p->wmsg.data(); x->done = true;
-            return fs;
-        };
-        lvk_status st = ekf_process_guarded(p->ekf, job.ts, nullptr, 0, job.view.data(), (int)job.view.size(), &used, &upd, fetch, &fx);
-        if (!fx.done) { const lvk_feature_obs* f = nullptr; int n = 0; fetch(&fx, &f, &n); }     // a call that returned early still frees its ring entry
-        if (st == LVK_OK && upd && p->on_update) { double s30[30]; lvk_ekf_get_state(p->ekf, s30); p->on_update(p->on_update_user, job.ts, s30); }
-        {
-            std::lock_guard<std::mutex> lk(p->mu);
-            const double t2 = now_us();
-            p->t_idle += t1 - t0; p->t_busy += t2 - t1; p->ev(6);
-            if (p->lat_us.size() < (size_t)1 << 20) p->lat_us.push_back((float)(t2 - job.t_submit));
-            if (st != LVK_OK && p->st == LVK_OK) p->st = st;
-            p->n_updates += upd; p->in_flight -= 1;
-            const bool was_steady = p->steady;
-            p->steady = p->ekf->b_first_features && p->ekf->is_gravity_set;
-            if (was_steady && p->steady && upd) { p->td_steps[p->n_td % lvk_vio_pipe::TD_HIST] = fabs(p->ekf->td - p->td_pub); p->n_td += 1; }
-            p->td_pub = p->ekf->td;
-            p->gen.fetch_add(1, std::memory_order_release);
-        }
-        p->cv_state.notify_all();
-    }
-}
-
-extern "C" {
-
-lvk_status lvk_vio_pipe_create(lvk_frontend* fe, lvk_ekf* ekf, lvk_vio_pipe** out)
-{
-    if (!fe || !ekf || !out) return LVK_ERR_ARG;
-    if (lvk_frontend_context(fe) == ekf->ctx)
-        return lvk_set_error(ekf->ctx, LVK_ERR_ARG, "lvk_vio_pipe_create: the front-end and the filter must live on different contexts (streams)");
-    lvk_vio_pipe* p = new lvk_vio_pipe();
-    p->fe = fe; p->ekf = ekf; p->wmsg.resize(8192);
-    p->logging = getenv("LVK_PIPE_LOG") != nullptr; if (p->logging) p->log.reserve(1 << 16);
-    if (const char* v = getenv("LVK_PIPE_DEPTH")) { const int d = atoi(v); if (d >= 1 && d <= 3) p->depth = d; }
-    if (const char* v = getenv("LVK_PIPE_TD_FACTOR")) { const double f = atof(v); if (f >= 1. && f <= 1e6) p->td_factor = f; }      // 3 = the message ring minus the entry being written
-    ekf->on_consumed = pipe_on_consumed; ekf->on_consumed_user = p;
-    p->worker = std::thread(pipe_worker, p);
-    *out = p;
-    return LVK_OK;
-}
-
-void lvk_vio_pipe_destroy(lvk_vio_pipe* p)
-{
-    if (!p) return;
-    { std::lock_guard<std::mutex> lk(p->mu); p->stop = true; p->gen.fetch_add(1, std::memory_order_release); }
-    p->cv_job.notify_all();
-    if (p->worker.joinable()) p->worker.join();
-    if (p->logging) { if (FILE* f = fopen(getenv("LVK_PIPE_LOG"), "w")) { for (auto& e : p->log) fprintf(f, "%.1f,%d\n", e.t, e.what); fclose(f); } }
-    p->ekf->on_consumed = nullptr; p->ekf->on_consumed_user = nullptr;
-    delete p;
-}
-
-lvk_status lvk_vio_pipe_push_imu(lvk_vio_pipe* p, const lvk_imu* h_imu, int n)
-{
-    if (!p || (n > 0 && !h_imu)) return LVK_ERR_ARG;
-    std::lock_guard<std::mutex> lk(p->mu);
-    // compaction: nothing in front of the filter's own head is needed by anybody (queued jobs cut their views from there on, the
-    // caller's head is never behind it)
-    const size_t done = p->fhead - p->base;
-    if (done > 4096 && p->unknown_consume == 0 && done <= p->head) { p->imu.erase(p->imu.begin(), p->imu.begin() + (long)done); p->head -= done; p->base = p->fhead; }
-    p->imu.insert(p->imu.end(), h_imu, h_imu + n);
-    return LVK_OK;
-}
-
-lvk_status lvk_vio_pipe_submit(lvk_vio_pipe* p, const lvk_image* img, double ts, int* has_msg)
-{
-    if (!p || !has_msg) return LVK_ERR_ARG;
-    *has_msg = 0;
-    size_t head, end;
-    // the image stage (upload, pyramid, ORB planes) does not look at the IMU buffer: queue it before waiting for the erase count
-    const double tb = now_us();
-    lvk_status st0 = lvk_frontend_begin(p->fe, img, ts);
-    if (st0 != LVK_OK) return st0;
-    const double t0 = now_us();
-    p->t_fe += t0 - tb;
-    {
-        std::unique_lock<std::mutex> lk(p->mu);
-        p->ev(0);
-        pipe_wait(p, lk, p->cv_state, [&] { return p->st != LVK_OK || (p->unknown_consume == 0 && p->in_flight <= p->depth); });     // a failed filter never keeps the caller waiting
-        if (p->st != LVK_OK) return p->st;
-        head = p->head; end = p->imu.size();
-        p->ev(1);
-    }
-    const double t1 = now_us();
-    p->t_submit_wait += t1 - t0;
-    // only this thread appends to imu, and no update can move `head` until a new job is queued below
-    int slot = -1;
-    lvk_status st = lvk_frontend_process_async(p->fe, img, ts, p->imu.data() + head, (int)(end - head), has_msg, &slot);
-    p->t_fe += now_us() - t1;
-    if (p->logging) { std::lock_guard<std::mutex> lk(p->mu); p->ev(2); }
-    if (st != LVK_OK || !*has_msg) return st;
-    lvk_vio_pipe::Job job;
-    job.t_submit = tb;
-    job.ts = ts; job.slot = slot;
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        job.end_abs = p->base + end;
-        const lvk_imu* view = p->imu.data() + head; const int n_view = (int)(end - head);
-        // With the worker idle the filter is quiescent: the erase count (timestamps, state time and td only) can be taken here
-        // and the next frame need not wait for the worker to wake up.
-        lvk_ekf* e = p->ekf;
-        bool counted = false;
-        if (p->in_flight == 0 && e->b_first_features && e->is_gravity_set) {
-            double t_after = 0;
-            p->head += (size_t)batch_imu_count(e, ts + e->td, view, n_view, &t_after);
-            p->state_t = t_after; p->td_pub = e->td; p->steady = true;
-            job.precounted = true; counted = true; p->ev(4);
-        } else if (p->in_flight > 0 && p->steady && p->td_quiet()) {
-            // every queued job is counted (the wait above), so state_t is the state time this job will start from
-            double ta = 0, tb2 = 0;
-            const int n_lo = imu_erase_count(p->state_t, ts + p->td_pub - p->td_margin, e->imu_img_time_th, view, n_view, &ta);
-            const int n_hi = imu_erase_count(p->state_t, ts + p->td_pub + p->td_margin, e->imu_img_time_th, view, n_view, &tb2);
-            if (n_lo == n_hi) {
-                job.precounted = true; job.early = true; job.n_pre = n_lo; job.t0_pre = p->state_t;
-                p->head += (size_t)n_lo; p->state_t = ta; p->n_early += 1; counted = true; p->ev(7);
-            }
-        }
-        if (!counted) { p->unknown_consume += 1; p->ev(3); }
-        p->q.push_back(std::move(job)); p->in_flight += 1; p->n_msgs += 1;
-        p->gen.fetch_add(1, std::memory_order_release);
-    }
-    p->cv_job.notify_one();
-    return LVK_OK;
-}
-
-lvk_status lvk_vio_pipe_stats(lvk_vio_pipe* p, double* out4, int reset)
-{
-    if (!p || !out4) return LVK_ERR_ARG;
-    std::lock_guard<std::mutex> lk(p->mu);
-    out4[0] = p->t_fe; out4[1] = p->t_submit_wait; out4[2] = p->t_busy; out4[3] = p->t_idle;
-    if (reset) p->t_busy = p->t_idle = p->t_fe = p->t_submit_wait = 0;
-    return LVK_OK;
-}
-
-lvk_status lvk_vio_pipe_early_counts(lvk_vio_pipe* p, long* n_early, long* n_wrong)
-{
-    if (!p) return LVK_ERR_ARG;
-    std::lock_guard<std::mutex> lk(p->mu);
-    if (n_early) *n_early = p->n_early;
-    if (n_wrong) *n_wrong = p->n_early_wrong;
-    return LVK_OK;
-}
-
-lvk_status lvk_vio_pipe_latency(lvk_vio_pipe* p, float* h_out_us, int cap, int* n_out, int reset)
-{
-    if (!p || !n_out || (cap > 0 && !h_out_us)) return LVK_ERR_ARG;
-    std::lock_guard<std::mutex> lk(p->mu);
-    const int n = std::min((int)p->lat_us.size(), cap);
-    for (int i = 0; i < n; ++i) h_out_us[i] = p->lat_us[i];
-    *n_out = n;
-    if (reset) p->lat_us.clear();
-    return LVK_OK;
-}
-
-lvk_status lvk_vio_pipe_on_update(lvk_vio_pipe* p, lvk_odometry_fn fn, void* user)
-{
-    if (!p) return LVK_ERR_ARG;
-    std::unique_lock<std::mutex> lk(p->mu);
-    pipe_wait(p, lk, p->cv_state, [&] { return p->in_flight == 0; });      // the worker reads the pair without the lock
-    p->on_update = fn; p->on_update_user = user;
-    return LVK_OK;
-}
-
-lvk_status lvk_vio_pipe_drain(lvk_vio_pipe* p, long* n_updates, long* n_msgs)
-{
-    if (!p) return LVK_ERR_ARG;
-    std::unique_lock<std::mutex> lk(p->mu);
-    pipe_wait(p, lk, p->cv_state, [&] { return p->in_flight == 0; });
-    if (n_updates) *n_updates = p->n_updates;
-    if (n_msgs) *n_msgs = p->n_msgs;
-    return p->st;
+    return vio_step(fe, ekf, img, ts, h_imu, n_imu, n_consumed, has_msg, will_update, lvk_ekf_process_async);
 }
 
 }  // extern "C"

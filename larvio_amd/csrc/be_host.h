@@ -1,6 +1,8 @@
 // be_host.h — what the back-end's translation units call in one another (host side): the records they pass by value and the
 // prototype of every lvk_* function that one be_*.hip / backend.hip defines and another calls.  Definers include it as well, so
-// the compiler checks each definition against the prototype its callers see.  (The structure-aware compression has be_qr.h.)
+// the compiler checks each definition against the prototype its callers see.  (The structure-aware compression has be_qr.h; the
+// filter object itself, which backend.hip shares with the exports of be_export.hip and the pipelined driver of be_pipe.hip, has
+// be_filter.h; no other object calls into backend.o - the pipelined driver reaches the update through lvk_ekf::process.)
 #pragma once
 #include "lvk_internal.h"
 #include "be_dev.h"
@@ -90,3 +92,10 @@ lvk_status lvk_qr_compress_dev(lvk_context* ctx, double* d_H, int ldh, int rows,
 lvk_status lvk_shard_pack(lvk_context* ctx, const FeatResult* d_res, int n_res, const double* d_X, int ld, const double* d_rX, int k, int ncols, char* d_send, size_t res_bytes, int rank);
 lvk_status lvk_shard_unpack(lvk_context* ctx, const char* d_recv, size_t bytes_per_rank, size_t res_bytes, const ShardMeta* d_meta, int world, int ncols, int k_max,
                             FeatResult* d_fout, FeatResult* d_fout_host, double* d_H, int ld, double* d_r, int* d_peer_fail);
+// be_export.hip: the drain lists' launches (queued before the columns they read leave P) and their read-back (be_filter.h has the records)
+struct RowJob; struct RowObs;
+lvk_status lvk_ekf_lost_cov_queue(lvk_ekf* e, const std::vector<long long>& ekf_lost);
+lvk_status lvk_ekf_keyframes_queue(lvk_ekf* e, const long long* rm, int nrm);
+lvk_status lvk_ekf_exports_attach(lvk_ekf* e);
+lvk_status lvk_ekf_msckf_points_queue(lvk_ekf* e, const std::vector<RowJob>& jobs, size_t lo, size_t hi, const RowObs& obs);
+void lvk_ekf_msckf_point_record(lvk_ekf* e, const RowJob& j, size_t k);

@@ -1,4 +1,4 @@
-// Host-only check of the pipelined driver's EARLY erase count (backend.hip: lvk_vio_pipe_submit) against the sequential rule it
+// Host-only check of the pipelined driver's EARLY erase count (be_pipe.hip: lvk_vio_pipe_submit) against the sequential rule it
 // stands in for (batch_imu, larvio.cpp:464-517: the count taken when the update starts, with the td of that moment).
 // Model: IMU stamps on a jittered grid with a random phase against the image grid, td a random walk, up to three updates between
 // the td a count is taken from and the td the update starts with.  Checked: (1) whenever the count is the same for td_pub - margin

@@ -2,7 +2,7 @@
 export is a pure observer (state, covariance and counters keep their bits), blocking and deferred runs give the same list, every record
 is a usable covariance, and the points sit on the simulation's true landmarks as their covariance says.
 
-Two configurations.  `sim` keeps max_track_len 6: features enter the state, both remove_lost_fast and the general path run, and a track
+Two configurations.  `sim` keeps max_track_len 6: features enter the state, both routes of remove_lost_features run, and a track
 longer than 6 messages is consumed in pieces - each piece is a record under the track's id.  `sim_long` sets max_track_len above the
 window, so a feature is consumed once, when it is lost: there the ids are distinct."""
 import numpy as np
