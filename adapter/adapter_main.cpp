@@ -6,6 +6,9 @@
 // a frame of this library) and the LAST N frames of the loop - processImage, processFeatures, every getter of larvioMain.cpp:117-170 -
 // are timed with the steady clock; one line "bench frames N seconds S frames_per_s F" is printed (bench.py: adapter_cpp).  --no-vis
 // leaves out getVisualImg (the viewer's picture: a device-to-host copy and a drawing pass per odometry message).
+// --input-format NAME[:SHIFT] (bgr8 rgb8 bgra8 rgba8 mono16 yuyv uyvy): ImageProcessor::setInputFormat, and every decoded grey frame is
+// handed over as a cv::Mat of that format whose grey IS the frame - (g, g, g[, 7]), g << SHIFT, (g, 128) / (128, g) - so that the run
+// must print what the default run prints.
 // The library's runtime settings (lvk_runtime_env: hardware queues, kernel arguments) need no call here: lvk_context_create applies
 // them, and the adapter's initialize() is this process's first HIP call - larvioMain.cpp itself links unchanged.
 #include <larvio/image_processor.h>
@@ -22,14 +25,43 @@
 
 using namespace larvio;
 
+// a grey frame as a cv::Mat of pixel format `format` (LVK_PIX_*) whose conversion gives the frame back
+static cv::Mat grey_as(const lvk::GreyImage& g, int format, int shift)
+{
+    if (format == LVK_PIX_MONO8) return cv::Mat(g.height, g.width, CV_8UC1, const_cast<unsigned char*>(g.data.data())).clone();
+    const int type = format == LVK_PIX_BGR8 || format == LVK_PIX_RGB8 ? CV_8UC3 : format == LVK_PIX_BGRA8 || format == LVK_PIX_RGBA8 ? CV_8UC4 : format == LVK_PIX_MONO16 ? CV_16UC1 : CV_8UC2;
+    cv::Mat m(g.height, g.width, type);
+    for (int y = 0; y < g.height; ++y) {
+        const unsigned char* s = g.data.data() + (size_t)y * g.width; unsigned char* d = m.ptr(y);
+        for (int x = 0; x < g.width; ++x) {
+            switch (format) {
+            case LVK_PIX_BGR8: case LVK_PIX_RGB8: d[3 * x] = d[3 * x + 1] = d[3 * x + 2] = s[x]; break;
+            case LVK_PIX_BGRA8: case LVK_PIX_RGBA8: d[4 * x] = d[4 * x + 1] = d[4 * x + 2] = s[x]; d[4 * x + 3] = 7; break;
+            case LVK_PIX_MONO16: { const unsigned short v = (unsigned short)(s[x] << shift); std::memcpy(d + 2 * x, &v, 2); break; }
+            case LVK_PIX_YUYV: d[2 * x] = s[x]; d[2 * x + 1] = 128; break;
+            default: d[2 * x] = 128; d[2 * x + 1] = s[x]; break;
+            }
+        }
+    }
+    return m;
+}
+
 int main(int argc, char** argv)
 {
     if (argc < 5) { std::fprintf(stderr, "Usage: %s path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt]\n", argv[0]); return 1; }
-    std::string tum_path; long bench_n = 0; bool vis_on = true;
+    std::string tum_path; long bench_n = 0; bool vis_on = true; int pix_format = LVK_PIX_MONO8, pix_shift = 0;
     for (int a = 5; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--tum") && a + 1 < argc) tum_path = argv[++a];
         else if (!std::strcmp(argv[a], "--bench") && a + 1 < argc) bench_n = std::atol(argv[++a]);
         else if (!std::strcmp(argv[a], "--no-vis")) vis_on = false;
+        else if (!std::strcmp(argv[a], "--input-format") && a + 1 < argc) {
+            static const char* const names[] = {"mono8", "bgr8", "rgb8", "bgra8", "rgba8", "mono16", "yuyv", "uyvy"};
+            std::string v = argv[++a]; const size_t colon = v.find(':');
+            if (colon != std::string::npos) { pix_shift = std::atoi(v.c_str() + colon + 1); v.resize(colon); }
+            pix_format = -1;
+            for (int f = 0; f < 8; ++f) if (v == names[f]) pix_format = f;
+            if (pix_format < 0) { std::fprintf(stderr, "--input-format: unknown format %s\n", v.c_str()); return 1; }
+        }
     }
     std::vector<lvk::ImuData> imu_rows; std::vector<lvk::ImgInfo> allImgInfo;
     if (!lvk::loadImuFile(argv[1], imu_rows) || !lvk::loadImageList(argv[2], allImgInfo)) { std::fprintf(stderr, "cannot read the sensor files\n"); return 1; }
@@ -41,6 +73,7 @@ int main(int argc, char** argv)
     ImageProcessorPtr ImgProcesser;                                   // larvioMain.cpp:42-48
     ImgProcesser.reset(new ImageProcessor(config_file));
     if (!ImgProcesser->initialize()) { std::fprintf(stderr, "Image Processer initialization failed!\n"); return 1; }
+    if (pix_format != LVK_PIX_MONO8 && !ImgProcesser->setInputFormat(pix_format, pix_shift)) { std::fprintf(stderr, "the input format was refused\n"); return 1; }
     LarVioPtr Estimator;                                              // :50-55
     Estimator.reset(new LarVio(config_file));
     if (!Estimator->initialize()) { std::fprintf(stderr, "Estimator initialization failed!\n"); return 1; }
@@ -62,7 +95,7 @@ int main(int argc, char** argv)
         lvk::GreyImage& image = bench_n > 0 ? preloaded[j] : image_file;
         ImageDataPtr imgPtr(new ImgData);                             // :88-95
         imgPtr->timeStampToSec = allImgInfo[j].timeStampToSec;
-        imgPtr->image = cv::Mat(image.height, image.width, CV_8UC1, image.data.data()).clone();
+        imgPtr->image = grey_as(image, pix_format, pix_shift);
         while (k < allImuData.size() && allImuData[k].timeStampToSec - imgPtr->timeStampToSec < 0.05) imu_msg_buffer.push_back(allImuData[k++]);   // :98-103
         MonoCameraMeasurementPtr features = new MonoCameraMeasurement;                                                  // :105
         const bool bProcess = ImgProcesser->processImage(imgPtr, imu_msg_buffer, features);                             // :107

@@ -32,6 +32,11 @@ public:
   // image_processor.cpp:130-219; true if `features` holds this frame's message
   bool processImage(const ImageDataPtr& msg, const std::vector<ImuData>& imu_msg_buffer, MonoCameraMeasurementPtr features);
 
+  // Not in the reference: the pixel format of msg->image from now on (LVK_PIX_* of lvk_c.h; lvk_frontend_set_input_format), for a
+  // caller that hands over the camera's own bgr8 / rgb8 / bgra8 / mono16 / yuv422 cv::Mat instead of cv_bridge's MONO8 conversion
+  // (ros_wrapper System.cpp:129).  After initialize(); shift: MONO16 only.  false = refused, the previous format stays in force.
+  bool setInputFormat(int format, int shift = 0);
+
   // Get publish image (image_processor.h:63-65): the last published frame as RGB with the tracked features marked
   cv::Mat getVisualImg() { vis_wanted = true; if (vis_pending) publishVisual(); return visual_img; }
 
@@ -50,6 +55,7 @@ private:
   bool vis_wanted = false, vis_shared = false;   // getVisualImg has been called at least once; vis_src still shares the caller's pixels
   bool vis_pending = false;      // a frame was published since visual_img was built
   long frames_seen = 0, vis_frame = 0;
+  int pix_format = LVK_PIX_MONO8, pix_shift = 0;   // what setInputFormat left in force
 };
 
 typedef ImageProcessor::Ptr ImageProcessorPtr;

@@ -29,6 +29,37 @@ bool ImageProcessor::initialize()
     return true;
 }
 
+// bytes per pixel of a LVK_PIX_* format (lvk_c.h)
+static int pix_bytes(int format)
+{
+    switch (format) {
+    case LVK_PIX_BGR8: case LVK_PIX_RGB8: return 3;
+    case LVK_PIX_BGRA8: case LVK_PIX_RGBA8: return 4;
+    case LVK_PIX_MONO16: case LVK_PIX_YUYV: case LVK_PIX_UYVY: return 2;
+    default: return 1;
+    }
+}
+// grey of one pixel as lvk_c.h defines it (lvk_image_to_gray): the picture of getVisualImg is drawn on the host
+static unsigned char pix_gray(const unsigned char* p, int format, int shift)
+{
+    switch (format) {
+    case LVK_PIX_BGR8: case LVK_PIX_BGRA8: return (unsigned char)((1868u * p[0] + 9617u * p[1] + 4899u * p[2] + 8192u) >> 14);
+    case LVK_PIX_RGB8: case LVK_PIX_RGBA8: return (unsigned char)((1868u * p[2] + 9617u * p[1] + 4899u * p[0] + 8192u) >> 14);
+    case LVK_PIX_MONO16: { unsigned short v; std::memcpy(&v, p, 2); const unsigned s = (unsigned)v >> shift; return (unsigned char)(s > 255u ? 255u : s); }
+    case LVK_PIX_UYVY: return p[1];
+    default: return p[0];
+    }
+}
+
+bool ImageProcessor::setInputFormat(int format, int shift)
+{
+    if (!fe) return false;
+    if (lvk_frontend_set_input_format(fe, format, shift) != LVK_OK) { std::printf("ImageProcessor::setInputFormat: %s\n", lvk_last_error(ctx)); return false; }
+    pix_format = format; pix_shift = shift;
+    vis_src = cv::Mat(); vis_shared = false; vis_pending = false;      // a picture of the previous format is not redrawn under the new one
+    return true;
+}
+
 bool ImageProcessor::processImage(const ImageDataPtr& msg, const std::vector<ImuData>& imu_msg_buffer, MonoCameraMeasurementPtr features)
 {
     if (!fe || !msg || !features) return false;
@@ -48,7 +79,12 @@ bool ImageProcessor::processImage(const ImageDataPtr& msg, const std::vector<Imu
         }
     }
     const cv::Mat& im = msg->image;
-    if (im.empty() || im.channels() != 1) { std::printf("ImageProcessor::processImage: an 8-bit single-channel image is expected\n"); return false; }
+    if (pix_format == LVK_PIX_MONO8) {
+        if (im.empty() || im.channels() != 1) { std::printf("ImageProcessor::processImage: an 8-bit single-channel image is expected\n"); return false; }
+    } else if (im.empty() || (int)im.elemSize() != pix_bytes(pix_format)) {
+        std::printf("ImageProcessor::processImage: the input format set needs %d bytes per pixel, this image has %d\n", pix_bytes(pix_format), im.empty() ? 0 : (int)im.elemSize());
+        return false;
+    }
     const lvk_image li = {im.data, im.cols, im.rows, (int)im.step, /*is_device=*/0};
     int n = 0, has = 0;
     ++frames_seen;
@@ -69,7 +105,7 @@ bool ImageProcessor::processImage(const ImageDataPtr& msg, const std::vector<Imu
     // caller's own cv::Mat, and only if no later frame has been processed since (publishVisual).
     if (vis_wanted) {
         if (!vis_shared && vis_src.rows == im.rows && vis_src.cols == im.cols && vis_src.type() == im.type() && vis_src.data != im.data && !vis_src.empty()) {
-            for (int y = 0; y < im.rows; ++y) std::memcpy(vis_src.ptr(y), im.ptr(y), (size_t)im.cols);
+            for (int y = 0; y < im.rows; ++y) std::memcpy(vis_src.ptr(y), im.ptr(y), (size_t)im.cols * im.elemSize());
         } else vis_src = im.clone();
         vis_shared = false;
     } else { vis_src = im; vis_shared = true; }
@@ -88,7 +124,8 @@ void ImageProcessor::publishVisual()
     cv::Mat rgb(gray.rows, gray.cols, CV_8UC3);
     for (int y = 0; y < gray.rows; ++y) {
         const unsigned char* s = gray.ptr(y); unsigned char* d = rgb.ptr(y);
-        for (int x = 0; x < gray.cols; ++x) { d[3 * x] = d[3 * x + 1] = d[3 * x + 2] = s[x]; }
+        if (pix_format == LVK_PIX_MONO8) for (int x = 0; x < gray.cols; ++x) { d[3 * x] = d[3 * x + 1] = d[3 * x + 2] = s[x]; }
+        else for (int x = 0, bp = pix_bytes(pix_format); x < gray.cols; ++x) { d[3 * x] = d[3 * x + 1] = d[3 * x + 2] = pix_gray(s + (size_t)x * bp, pix_format, pix_shift); }
     }
     const int cap = cfg.max_features_num;
     std::vector<lvk_pt2f> pts((size_t)cap); std::vector<int> life((size_t)cap); int n = 0;

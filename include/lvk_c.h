@@ -42,7 +42,8 @@ typedef struct lvk_frontend lvk_frontend;
 typedef struct { float x, y; } lvk_pt2f;
 /* One 8-bit grey image as the reference's ImageData carries it (include/sensors/ImageData.hpp: a cv::Mat knows its own size and
  * step).  stride = bytes between rows (cv::Mat::step); is_device: 0 = data is a host pointer (copied in through the front-end's
- * pinned staging, the caller may reuse the buffer as soon as the call returns), 1 = data is a device pointer. */
+ * pinned staging, the caller may reuse the buffer as soon as the call returns), 1 = data is a device pointer.  A front-end switched
+ * to another pixel format (lvk_frontend_set_input_format) takes the same struct: data = that format's bytes, stride still in bytes. */
 typedef struct { const uint8_t* data; int width, height, stride; int is_device; } lvk_image;
 /* include/sensors/ImuData.hpp:17-43 */
 typedef struct { double t; double gyro[3]; double acc[3]; } lvk_imu;
@@ -104,6 +105,33 @@ lvk_status lvk_pyramid_level(const lvk_pyramid* p, int level, int* w, int* h, in
                              int* istride, int* dstride, const uint8_t** d_img, const int16_t** d_der);
 /* ORB level-0 mosaic (border 32) and its 7x7 sigma-2 blurred copy; both (h+64) x (w+64), stride w+64 */
 lvk_status lvk_orb_prepare(lvk_context* ctx, const lvk_pyramid* p, uint8_t* d_ext, uint8_t* d_blur);
+
+/* Stage entry: a camera's pixel format to the 8-bit grey plane everything above reads - what the reference's ROS caller gets from
+ * cv_bridge::toCvShare(msg, MONO8) (ros_wrapper/src/larvio/src/System.cpp:129) before it calls processImage.  No counterpart in the
+ * reference's library itself.  The formulas ARE the contract, in integers:
+ *   MONO8          grey = the byte (a strided copy)
+ *   BGR8 / RGB8    grey = (1868*B + 9617*G + 4899*R + 8192) >> 14      (the weights sum to 2^14: no saturation is needed)
+ *   BGRA8 / RGBA8  the same on B, G, R; the fourth byte is ignored
+ *   MONO16         grey = min(255, v >> shift), v a uint16 in host byte order, shift in 0..8
+ *   YUYV / UYVY    grey = Y: byte 0 / byte 1 of each 2-byte pixel (Y0 U Y1 V / U Y0 V Y1)
+ * The colour line is the scalar 8-bit form OpenCV's 3.4 series documents for cvtColor; later releases use 15-bit constants that differ
+ * on rare pixels, and agreement with any OpenCV build is not claimed (PARITY.md).
+ * Reads, of source row y (at d_src + y * src_stride_bytes), the bytes [0, w * bytes_per_pixel) and nothing else; writes
+ * d_dst[y * dst_stride + x] for x < w and nothing else: padding keeps its bits.  d_src and d_dst may have any byte alignment and any
+ * stride that holds a row, except that MONO16 needs an even d_src and src_stride_bytes.  One launch on the context's stream, not waited for.
+ * LVK_ERR_ARG, with nothing launched and the context still usable: a null pointer, w or h <= 0, an unknown format, src_stride_bytes
+ * < w * bytes_per_pixel, dst_stride < w, shift outside 0..8 or non-zero for a format other than MONO16, an odd w for YUYV / UYVY, an
+ * odd d_src or src_stride_bytes for MONO16. */
+#define LVK_PIX_MONO8  0   /* the front-end's default input */
+#define LVK_PIX_BGR8   1
+#define LVK_PIX_RGB8   2
+#define LVK_PIX_BGRA8  3
+#define LVK_PIX_RGBA8  4
+#define LVK_PIX_MONO16 5
+#define LVK_PIX_YUYV   6
+#define LVK_PIX_UYVY   7
+lvk_status lvk_image_to_gray(lvk_context* ctx, const void* d_src, int src_stride_bytes, int w, int h,
+                             int format, int shift, uint8_t* d_dst, int dst_stride);
 
 /* replaces cv::goodFeaturesToTrack(img, maxCorners, quality, minDistance, mask, 3)
  * (image_processor.cpp:343, 1035-1036).  d_mask may be NULL; d_n_out = device int. */
@@ -200,6 +228,18 @@ int        lvk_frontend_state(const lvk_frontend* fe);   /* 1 FIRST_IMAGE 2 SECO
  * lvk_vio_pipe_drain - never between a submit and the drain that follows. */
 lvk_status lvk_frontend_set_mask(lvk_frontend* fe, const lvk_image* mask);
 int        lvk_frontend_has_mask(const lvk_frontend* fe);
+/* Input pixel format (LVK_PIX_*, shift as lvk_image_to_gray).  No reference counterpart: the reference's library takes MONO8 and its
+ * ROS caller converts on the host.  After the call every lvk_image given to this front-end - lvk_frontend_process, lvk_vio_process,
+ * lvk_vio_process_deferred, lvk_vio_pipe_submit - is in that format: data points at the format's bytes, width / height stay the
+ * configured resolution in pixels, stride is in bytes and must be >= width * bytes_per_pixel (LVK_ERR_ARG otherwise, the handle stays
+ * usable); a MONO16 device image also needs an even pointer and stride.  The raw bytes take the usual upload route and
+ * lvk_image_to_gray turns them into a grey plane the front-end owns, on the image stream in front of the pyramid; everything after that
+ * is the MONO8 path.  The call waits for the front-end's own streams, then resizes the upload buffers to the format's row bytes;
+ * LVK_ERR_ARG for an unknown format, a bad shift, or YUYV / UYVY on an odd configured width, LVK_ERR_DEVICE when a buffer cannot be
+ * had - either way the format in force stays.  LVK_PIX_MONO8 (the default) restores today's buffers and launches: no grey plane, no
+ * conversion kernel.  With a lvk_vio_pipe attached, call it before the first lvk_vio_pipe_submit or after lvk_vio_pipe_drain. */
+lvk_status lvk_frontend_set_input_format(lvk_frontend* fe, int format, int shift);
+int        lvk_frontend_input_format(const lvk_frontend* fe);
 /* cumulative LK work: point-levels processed and iterations executed (SURVEY §8d byte model) */
 lvk_status lvk_frontend_lk_stats(lvk_frontend* fe, uint64_t* point_levels, uint64_t* iterations);
 /* feature messages published so far (getFeatureMsg, image_processor.cpp:1076-1128) and the features they carried in total:

@@ -87,6 +87,16 @@ public:
         return true;
     }
     bool clearMask() { return fe_ && lvk_frontend_set_mask(fe_, nullptr) == LVK_OK; }
+    // pixel format of every ImageData from now on (lvk_frontend_set_input_format; the reference's ROS caller converts on the host
+    // instead): LVK_PIX_*; msg.data then points at that format's bytes and msg.step is in bytes.  shift: MONO16 only, grey =
+    // min(255, v >> shift).  After initialize(); with a VioPipeline before the first processImage or after drain().  false = refused,
+    // the previous format stays in force.
+    bool setInputFormat(int format, int shift = 0)
+    {
+        if (!fe_) return false;
+        if (lvk_frontend_set_input_format(fe_, format, shift) != LVK_OK) { std::fprintf(stderr, "ImageProcessor::setInputFormat: %s\n", lvk_last_error(ctx_)); return false; }
+        return true;
+    }
     lvk_frontend* handle() const { return fe_; }
 private:
     ImageProcessor(const ImageProcessor&); ImageProcessor& operator=(const ImageProcessor&);

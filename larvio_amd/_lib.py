@@ -19,11 +19,11 @@ ABI_SYMBOLS = [
     "lvk_runtime_env", "lvk_context_create", "lvk_context_destroy", "lvk_context_set_stream", "lvk_context_get_stream", "lvk_sync", "lvk_last_error", "lvk_version",
     "lvk_malloc", "lvk_free", "lvk_memcpy_h2d", "lvk_memcpy_d2h", "lvk_memset",
     "lvk_clahe_u8", "lvk_pyramid_create", "lvk_pyramid_destroy", "lvk_pyramid_build", "lvk_pyramid_build_clahe",
-    "lvk_pyramid_levels", "lvk_pyramid_level", "lvk_orb_prepare", "lvk_min_eigen_map", "lvk_good_features", "lvk_good_features_from_map",
+    "lvk_pyramid_levels", "lvk_pyramid_level", "lvk_orb_prepare", "lvk_image_to_gray", "lvk_min_eigen_map", "lvk_good_features", "lvk_good_features_from_map",
     "lvk_lk_track", "lvk_orb_describe", "lvk_hamming256_rows", "lvk_undistort_points", "lvk_find_fundamental_mask", "lvk_find_fundamental",
     "lvk_ransac_fundamental", "lvk_predict_homography",
     "lvk_frontend_create", "lvk_frontend_destroy", "lvk_frontend_process", "lvk_frontend_tracks", "lvk_frontend_new_pts",
-    "lvk_frontend_set_mask", "lvk_frontend_has_mask",
+    "lvk_frontend_set_mask", "lvk_frontend_has_mask", "lvk_frontend_set_input_format", "lvk_frontend_input_format",
     "lvk_frontend_state", "lvk_frontend_lk_stats", "lvk_frontend_msg_stats", "lvk_frontend_profile_enable", "lvk_frontend_profile_read",
     "lvk_frontend_stage_name",
     "lvk_ekf_compress_qr", "lvk_ekf_compress_qr_groups", "lvk_ekf_qr_plan", "lvk_ekf_update", "lvk_ekf_update_ldlt", "lvk_ekf_update_ldlt_perm", "lvk_dgemm", "lvk_dgemm_ex", "lvk_chol_solve", "lvk_ekf_cov_propagate_augment", "lvk_ekf_cov_gather", "lvk_ekf_cov_reanchor", "lvk_ekf_cov_append_features", "lvk_ekf_landmark_cov", "lvk_ekf_pose_rel_cov", "lvk_ekf_msckf_point_cov", "lvk_ekf_create", "lvk_ekf_destroy", "lvk_ekf_process", "lvk_ekf_process_async", "lvk_ekf_wait", "lvk_ekf_set_state",
@@ -42,12 +42,40 @@ class Image(C.Structure):
     _fields_ = [("data", C.c_void_p), ("width", C.c_int), ("height", C.c_int), ("stride", C.c_int), ("is_device", C.c_int)]
 
 
-def make_image(img=None, device_ptr=None, stride=None, shape=None):
+# LVK_PIX_* of include/lvk_c.h by name, and what a host array of each format looks like: (dtype, trailing dimension or None, bytes per pixel)
+PIX_FORMATS = {"mono8": 0, "bgr8": 1, "rgb8": 2, "bgra8": 3, "rgba8": 4, "mono16": 5, "yuyv": 6, "uyvy": 7}
+_PIX_ARRAY = {"mono8": (np.uint8, None, 1), "bgr8": (np.uint8, 3, 3), "rgb8": (np.uint8, 3, 3), "bgra8": (np.uint8, 4, 4), "rgba8": (np.uint8, 4, 4),
+              "mono16": (np.uint16, None, 2), "yuyv": (np.uint8, 2, 2), "uyvy": (np.uint8, 2, 2)}
+
+
+def pixfmt_bytes_per_pixel(fmt):
+    return _PIX_ARRAY[fmt][2]
+
+
+def pixfmt_host_array(img, fmt):
+    """The array an image of pixel format `fmt` must be: (H, W, 3|4) uint8 for the colour formats, (H, W) uint16 for mono16, (H, W, 2)
+    uint8 for the two YUV 4:2:2 layouts.  Returns it with contiguous pixels (rows may be strided); anything else is a ValueError that
+    names both the array and the format."""
+    dtype, last, _ = _PIX_ARRAY[fmt]
+    img = np.asarray(img)
+    want = f"(H, W{'' if last is None else ', %d' % last}) {np.dtype(dtype).name}"
+    if img.dtype != dtype or img.ndim != (2 if last is None else 3) or (last is not None and img.shape[2] != last):
+        raise ValueError(f"a {img.dtype.name} array of shape {img.shape} is not a {fmt} image: {want} is expected")
+    ok = img.strides[1] == img.itemsize * (last or 1) and (last is None or img.strides[2] == 1) and img.strides[0] >= img.shape[1] * img.strides[1]
+    return img if ok else np.ascontiguousarray(img)
+
+
+def make_image(img=None, device_ptr=None, stride=None, shape=None, fmt="mono8"):
     """lvk_image for a host array (H, W) uint8 — or for a device pointer with an explicit (H, W) shape and row stride.
+    fmt: the pixel format the front-end was switched to (ImageProcessor.set_input_format); the host array is then what
+    pixfmt_host_array describes and a device pointer's default stride is the format's row bytes.
     Returns (Image, keepalive): hold the second value until the call that consumes the image has returned."""
     if device_ptr is not None:
         h, w = shape
-        return Image(int(device_ptr), int(w), int(h), int(stride if stride is not None else w), 1), None
+        return Image(int(device_ptr), int(w), int(h), int(stride if stride is not None else w * _PIX_ARRAY[fmt][2]), 1), None
+    if fmt != "mono8":
+        img = pixfmt_host_array(img, fmt)
+        return Image(img.ctypes.data, img.shape[1], img.shape[0], img.strides[0], 0), img
     img = np.asarray(img)
     if img.dtype != np.uint8 or img.ndim != 2 or img.strides[1] != 1:
         img = np.ascontiguousarray(img, np.uint8)
@@ -102,6 +130,8 @@ def lib():
             "lvk_frontend_tracks": ([vp, vp, vp, vp, vp, vp, i, pi], i),
             "lvk_frontend_new_pts": ([vp, vp, i, pi], i), "lvk_frontend_state": ([vp], i),
             "lvk_frontend_set_mask": ([vp, C.POINTER(Image)], i), "lvk_frontend_has_mask": ([vp], i),
+            "lvk_image_to_gray": ([vp, vp, i, i, i, i, i, vp, i], i),
+            "lvk_frontend_set_input_format": ([vp, i, i], i), "lvk_frontend_input_format": ([vp], i),
             "lvk_frontend_lk_stats": ([vp, vp, vp], i),
             "lvk_frontend_msg_stats": ([vp, vp, vp], i),
             "lvk_frontend_profile_enable": ([vp, C.c_uint], i), "lvk_frontend_profile_read": ([vp, vp, vp, i], i),

@@ -10,6 +10,7 @@
 // (image_processor.h:215-230); the one order-preserving compaction happens inside the RANSAC
 // workgroup, which needs the compacted order anyway (OpenCV's RNG draws indices into it).
 #include "lvk_internal.h"
+#include "fe_pixfmt_dev.h"
 #include <atomic>
 #include <sched.h>
 #include "fe_track_dev.h"
@@ -794,6 +795,12 @@ struct lvk_frontend {
     // caller's region mask (lvk_frontend_set_mask; no reference counterpart): packed w x h, 0 / 255, allocated on first use and read-only to
     // every kernel; has_user_mask chooses k_mask_max<true> over k_mask_max<false> and hands the bootstrap detection a mask
     uint8_t* user_mask = nullptr; bool has_user_mask = false;
+    // caller's pixel format (lvk_frontend_set_input_format; no reference counterpart).  MONO8: d_gray stays null and nothing below differs
+    // from a front-end without the call.  Otherwise h_stage / d_ring / d_img hold RAW rows of width * bytes_per_pixel bytes and
+    // lvk_image_to_gray writes the packed grey plane d_gray on the image stream.  ONE plane is enough although three frames can be in
+    // flight: its only readers are the first kernels of the same frame's image stage, queued on that same stream right behind the
+    // conversion, and the next frame's conversion is queued behind them - the stream's order is the lock (as for d_img itself).
+    int pix_format = LVK_PIX_MONO8, pix_shift = 0; uint8_t* d_gray = nullptr;
     // The message buffer: pinned host memory (h_msg) and its device-mapped view (d_msg), and its length, same arrangement - a ring
     // of LVK_MSG_SLOTS messages so that a pipelined driver can let the GPU run ahead: processImage returns as soon as the frame is
     // queued and the filter's thread picks the message up when ev_msg[slot] has fired (lvk_frontend_fetch_msg).
@@ -1016,7 +1023,7 @@ void lvk_frontend_destroy(lvk_frontend* fe)
         if (i < 2) set_free(fe->set[i]);
     }
     void* ptrs[] = {fe->d_img, fe->w_curr, fe->wn_curr, fe->w_und, fe->wn_und, fe->new_pts, fe->w_status, fe->wn_status, fe->wn_desc, fe->eig, fe->mask,
-                    fe->gf_scratch, fe->gf_cands, fe->dev, fe->user_mask};
+                    fe->gf_scratch, fe->gf_cands, fe->dev, fe->user_mask, fe->d_gray};
     for (void* p : ptrs) if (p) hipFree(p);
     for (int i = 0; i < 3; ++i) { if (fe->h_stage[i]) hipHostFree(fe->h_stage[i]); if (fe->d_ring[i]) hipFree(fe->d_ring[i]); if (fe->ev_img[i]) hipEventDestroy(fe->ev_img[i]); }
     for (int i = 0; i < LVK_MSG_SLOTS; ++i) if (fe->ev_msg[i]) hipEventDestroy(fe->ev_msg[i]);
@@ -1200,7 +1207,15 @@ static lvk_status fe_check_image(lvk_frontend* fe, const lvk_image* img)
     if (!img || !img->data) return lvk_set_error(fe->ctx, LVK_ERR_ARG, "image: null pointer");
     if (img->width != c.width || img->height != c.height)
         return lvk_set_error(fe->ctx, LVK_ERR_ARG, "image is %dx%d, the front-end is configured for %dx%d", img->width, img->height, c.width, c.height);
-    if (img->stride < c.width) return lvk_set_error(fe->ctx, LVK_ERR_ARG, "image stride %d is smaller than the width %d", img->stride, c.width);
+    if (fe->pix_format == LVK_PIX_MONO8) {
+        if (img->stride < c.width) return lvk_set_error(fe->ctx, LVK_ERR_ARG, "image stride %d is smaller than the width %d", img->stride, c.width);
+        return LVK_OK;
+    }
+    const int row = c.width * lvk_pixfmt_bpp(fe->pix_format);
+    if (img->stride < row)
+        return lvk_set_error(fe->ctx, LVK_ERR_ARG, "image stride %d is smaller than a %s row of %d pixels (%d bytes)", img->stride, lvk_pixfmt_name(fe->pix_format), c.width, row);
+    if (fe->pix_format == LVK_PIX_MONO16 && img->is_device && ((((uintptr_t)img->data) | (unsigned)img->stride) & 1u))
+        return lvk_set_error(fe->ctx, LVK_ERR_ARG, "a mono16 device image needs an even address and stride");
     return LVK_OK;
 }
 
@@ -1211,6 +1226,7 @@ static lvk_status fe_image_stage(lvk_frontend* fe, const lvk_image* image, bool 
     lvk_status stc = fe_check_image(fe, image);
     if (stc != LVK_OK) return stc;
     const uint8_t* d_img = image->data; int d_stride = image->stride;
+    const size_t row = (size_t)c.width * lvk_pixfmt_bpp(fe->pix_format);     // bytes of one raw row (= width for MONO8)
     int slot = -1;
     g_ft.start();
     if (!image->is_device && fe->bar_push && !early) {
@@ -1219,11 +1235,11 @@ static lvk_status fe_image_stage(lvk_frontend* fe, const lvk_image* image, bool 
         if (fe->n_img >= 3) LVK_HIP(ctx, hipEventSynchronize(fe->ev_end[fe->n_img & 1]));   // (the same bound on frames in flight as the pinned-slot path)
         FT(FT_SLOT_WAIT);
         uint8_t* dd = fe->d_ring[slot];
-        if (image->stride == c.width) memcpy(dd, image->data, (size_t)c.width * c.height);
-        else for (int y = 0; y < c.height; ++y) memcpy(dd + (size_t)y * c.width, image->data + (size_t)y * image->stride, (size_t)c.width);
+        if ((size_t)image->stride == row) memcpy(dd, image->data, row * c.height);
+        else for (int y = 0; y < c.height; ++y) memcpy(dd + (size_t)y * row, image->data + (size_t)y * image->stride, row);
         LVK_STORE_FENCE();
         FT(FT_STAGE_COPY);
-        d_img = dd; d_stride = c.width;
+        d_img = dd; d_stride = (int)row;
         FT(FT_UPLOAD);
     } else if (!image->is_device) {
         slot = fe->stage_next; fe->stage_next = (slot + 1) % 3;
@@ -1232,11 +1248,11 @@ static lvk_status fe_image_stage(lvk_frontend* fe, const lvk_image* image, bool 
         if (fe->n_img >= 3) LVK_HIP(ctx, hipEventSynchronize(fe->ev_end[fe->n_img & 1]));
         FT(FT_SLOT_WAIT);
         uint8_t* hs = fe->h_stage[slot];
-        if (image->stride == c.width) memcpy(hs, image->data, (size_t)c.width * c.height);
-        else for (int y = 0; y < c.height; ++y) memcpy(hs + (size_t)y * c.width, image->data + (size_t)y * image->stride, (size_t)c.width);
+        if ((size_t)image->stride == row) memcpy(hs, image->data, row * c.height);
+        else for (int y = 0; y < c.height; ++y) memcpy(hs + (size_t)y * row, image->data + (size_t)y * image->stride, row);
         FT(FT_STAGE_COPY);
-        LVK_HIP(ctx, hipMemcpyAsync(fe->d_img, hs, (size_t)c.width * c.height, hipMemcpyHostToDevice, fe->side[1]->stream)); d_img = fe->d_img;
-        d_stride = c.width;
+        LVK_HIP(ctx, hipMemcpyAsync(fe->d_img, hs, row * c.height, hipMemcpyHostToDevice, fe->side[1]->stream)); d_img = fe->d_img;
+        d_stride = (int)row;
         FT(FT_UPLOAD);
     }
     lvk_status st;
@@ -1252,7 +1268,12 @@ static lvk_status fe_image_stage(lvk_frontend* fe, const lvk_image* image, bool 
     int mosaic_done = 0;
     {
         ProfScope ps(fe, 0, S0);
-        st = lvk_pyramid_build_with_orb(icx, fe->pyr[1], d_img, d_stride, c.flag_equalize, 3.0, 8, 8, fe->ext[1], &mosaic_done);
+        st = LVK_OK;
+        if (fe->pix_format != LVK_PIX_MONO8) {               // raw bytes of any of the three routes -> the packed grey plane
+            st = lvk_image_to_gray(icx, d_img, d_stride, c.width, c.height, fe->pix_format, fe->pix_shift, fe->d_gray, c.width);
+            d_img = fe->d_gray; d_stride = c.width;
+        }
+        if (st == LVK_OK) st = lvk_pyramid_build_with_orb(icx, fe->pyr[1], d_img, d_stride, c.flag_equalize, 3.0, 8, 8, fe->ext[1], &mosaic_done);
     }
     if (st != LVK_OK) return lvk_set_error(ctx, st, "%s", icx->err);
     // (the slot's readers - the two kernels above - are covered by the end-of-frame event of frame f-2 the caller waits for anyway, as in
@@ -1531,6 +1552,53 @@ lvk_status lvk_frontend_set_mask(lvk_frontend* fe, const lvk_image* mask)
     return LVK_OK;
 }
 int lvk_frontend_has_mask(const lvk_frontend* fe) { return fe && fe->has_user_mask ? 1 : 0; }
+
+// The caller's pixel format (no reference counterpart: its ROS caller converts on the host).  Everything queued so far is waited for
+// first, as in lvk_frontend_set_mask: a frame in flight keeps the buffers it was queued with.  The new upload buffers are all allocated
+// before an old one is freed, so that a failure leaves the front-end exactly as it was.
+lvk_status lvk_frontend_set_input_format(lvk_frontend* fe, int format, int shift)
+{
+    if (!fe) return LVK_ERR_ARG;
+    lvk_context* ctx = fe->ctx;
+    { lvk_status fs = fe_check_failed(fe); if (fs != LVK_OK) return fs; }
+    const int w = fe->cfg.width, h = fe->cfg.height, bpp = lvk_pixfmt_bpp(format);
+    if (!bpp) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_set_input_format: unknown format %d", format);
+    if (shift < 0 || shift > 8 || (shift != 0 && format != LVK_PIX_MONO16))
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_set_input_format: shift %d (0..8, and only with mono16; the format is %s)", shift, lvk_pixfmt_name(format));
+    if ((format == LVK_PIX_YUYV || format == LVK_PIX_UYVY) && (w & 1))
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_set_input_format: %s needs an even width, the front-end is configured for %dx%d", lvk_pixfmt_name(format), w, h);
+    if (fe->image_done)
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_set_input_format: the image stage of t = %.6f is still waiting for its lvk_frontend_process", fe->image_done_ts);
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < 2; ++i) LVK_HIP(ctx, hipStreamSynchronize(fe->side[i]->stream));
+    const size_t old_bytes = (size_t)w * h * lvk_pixfmt_bpp(fe->pix_format), bytes = (size_t)w * h * bpp;
+    uint8_t *n_stage[3] = {nullptr, nullptr, nullptr}, *n_ring[3] = {nullptr, nullptr, nullptr}, *n_img = nullptr, *n_gray = nullptr;
+    bool ok = true;
+    if (bytes != old_bytes) {
+        for (int i = 0; i < 3 && ok; ++i) ok = hipHostMalloc((void**)&n_stage[i], bytes) == hipSuccess;
+        for (int i = 0; i < 3 && ok && fe->bar_push; ++i) ok = (n_ring[i] = (uint8_t*)lvk_bar_alloc(ctx->device, bytes)) != nullptr;
+        ok = ok && dalloc(&n_img, bytes);
+    }
+    if (format != LVK_PIX_MONO8 && !fe->d_gray) ok = ok && dalloc(&n_gray, (size_t)w * h);
+    if (!ok) {
+        (void)hipGetLastError();
+        for (int i = 0; i < 3; ++i) { if (n_stage[i]) hipHostFree(n_stage[i]); if (n_ring[i]) hipFree(n_ring[i]); }
+        if (n_img) hipFree(n_img); if (n_gray) hipFree(n_gray);
+        return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_frontend_set_input_format: allocation failed (%s stays in force)", lvk_pixfmt_name(fe->pix_format));
+    }
+    if (bytes != old_bytes) {
+        for (int i = 0; i < 3; ++i) {
+            hipHostFree(fe->h_stage[i]); fe->h_stage[i] = n_stage[i];
+            if (fe->bar_push) { hipFree(fe->d_ring[i]); fe->d_ring[i] = n_ring[i]; fe->ev_img_set[i] = false; }
+        }
+        hipFree(fe->d_img); fe->d_img = n_img;
+    }
+    if (n_gray) fe->d_gray = n_gray;
+    if (format == LVK_PIX_MONO8 && fe->d_gray) { hipFree(fe->d_gray); fe->d_gray = nullptr; }
+    fe->pix_format = format; fe->pix_shift = shift;
+    return LVK_OK;
+}
+int lvk_frontend_input_format(const lvk_frontend* fe) { return fe ? fe->pix_format : -1; }
 
 lvk_status lvk_frontend_profile_enable(lvk_frontend* fe, unsigned stage_mask)
 {

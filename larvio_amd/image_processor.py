@@ -8,7 +8,7 @@ the reference's ``haveFeatures`` and the feature list is the ``MonoCameraMeasure
 import ctypes as C
 import os
 import numpy as np
-from ._lib import lib, _p, Context, FeConfig, LvkError, IMU, OBS, make_image
+from ._lib import lib, _p, Context, FeConfig, LvkError, IMU, OBS, make_image, PIX_FORMATS
 
 
 class MonoCameraMeasurement:
@@ -43,6 +43,7 @@ class ImageProcessor:
         self.config = dict(config)
         self.ctx = ctx
         self._h = None
+        self._pixfmt = "mono8"
 
     def initialize(self):
         if self.ctx is None:
@@ -60,14 +61,15 @@ class ImageProcessor:
         return True
 
     def processImage(self, img, imu_msg_buffer, ts=None, device_ptr=None, stride=None, shape=None):
-        """img: (H,W) uint8 array (host; its shape is checked against the configured resolution, as a cv::Mat's would be) — or pass
+        """img: (H,W) uint8 array (host; its shape is checked against the configured resolution, as a cv::Mat's would be; after
+        set_input_format: the array that format demands) — or pass
         device_ptr/stride (and shape=(H,W) if it is not the configured one) for an image already in HBM.
         imu_msg_buffer: structured array (t, gyro[3], acc[3]).  Returns (haveFeatures, MonoCameraMeasurement|None)."""
         if self._h is None:
             raise LvkError("ImageProcessor.initialize() has not succeeded")
         imu = np.ascontiguousarray(imu_msg_buffer, IMU)
         n_out, has = C.c_int(0), C.c_int(0)
-        im, keep = make_image(img, device_ptr, stride, shape if shape is not None else (self.config["height"], self.config["width"]))
+        im, keep = make_image(img, device_ptr, stride, shape if shape is not None else (self.config["height"], self.config["width"]), fmt=self._pixfmt)
         st = lib().lvk_frontend_process(self._h, C.byref(im), float(ts), _p(imu), len(imu), _p(self._out), self._cap,
                                         C.byref(n_out), C.byref(has))
         self.ctx.check(st)
@@ -109,6 +111,25 @@ class ImageProcessor:
     @property
     def has_mask(self):
         return bool(lib().lvk_frontend_has_mask(self._h))
+
+    def set_input_format(self, fmt, shift=0):
+        """Pixel format of every image from now on (lvk_frontend_set_input_format; the reference's ROS caller converts on the host
+        instead): "mono8" (the default), "bgr8", "rgb8", "bgra8", "rgba8" - (H, W, 3|4) uint8 -, "mono16" - (H, W) uint16, grey =
+        min(255, v >> shift), shift 0..8 -, "yuyv", "uyvy" - (H, W, 2) uint8, grey = Y.  The bytes are uploaded as they are and converted
+        on the GPU (include/lvk_c.h states the formulas); a device pointer's stride is in bytes.  With a VioPipeline call it before the
+        first step or after drain().  A refusal (LvkError) leaves the previous format in force."""
+        if self._h is None:
+            raise LvkError("ImageProcessor.initialize() has not succeeded")
+        if fmt not in PIX_FORMATS:
+            raise ValueError(f"unknown pixel format {fmt!r}: one of {', '.join(PIX_FORMATS)}")
+        self.ctx.check(lib().lvk_frontend_set_input_format(self._h, PIX_FORMATS[fmt], int(shift)))
+        self._pixfmt = fmt
+
+    @property
+    def input_format(self):
+        """name of the pixel format in force (lvk_frontend_input_format)"""
+        v = lib().lvk_frontend_input_format(self._h)
+        return next(k for k, n in PIX_FORMATS.items() if n == v)
 
     @property
     def state(self):

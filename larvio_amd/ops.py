@@ -5,7 +5,7 @@ These mirror, call for call, the OpenCV / ORBdescriptor functions the reference'
 """
 import ctypes as C
 import numpy as np
-from ._lib import lib, _p, Context, LvkError, IMU  # noqa: F401
+from ._lib import lib, _p, Context, LvkError, IMU, PIX_FORMATS, pixfmt_host_array  # noqa: F401
 
 
 def _u8(img):
@@ -22,6 +22,15 @@ def clahe(ctx, img, clip=3.0, tiles=(8, 8)):
     img = _u8(img); h, w = img.shape
     d_src = ctx.to_device(img); d_dst = ctx.alloc(img.nbytes)
     ctx.check(lib().lvk_clahe_u8(ctx.h, _p(d_src), w, h, w, _p(d_dst), w, clip, tiles[0], tiles[1]))
+    return ctx.to_host(d_dst, np.uint8, (h, w))
+
+
+def image_to_gray(ctx, img, fmt, shift=0):
+    """lvk_image_to_gray: an image in pixel format `fmt` (the array ImageProcessor.set_input_format describes) -> (H, W) uint8 grey"""
+    img = np.ascontiguousarray(pixfmt_host_array(img, fmt))
+    h, w = img.shape[:2]
+    d_src = ctx.to_device(img); d_dst = ctx.alloc(w * h)
+    ctx.check(lib().lvk_image_to_gray(ctx.h, _p(d_src), img.strides[0], w, h, PIX_FORMATS[fmt], int(shift), _p(d_dst), w))
     return ctx.to_host(d_dst, np.uint8, (h, w))
 
 

@@ -50,7 +50,7 @@ class VioDriver:
     def step(self, ts, hi, img=None, device_ptr=None, stride=None, shape=None):
         """hi = visible_end(ts) (precomputable).  Returns (has_msg, updated)."""
         used, has, upd = self._c
-        im, keep = make_image(img, device_ptr, stride, shape if shape is not None else self._shape)
+        im, keep = make_image(img, device_ptr, stride, shape if shape is not None else self._shape, fmt=self.fe._pixfmt)
         st = _L().lvk_vio_process(self.fe._h, self.be._h, C.byref(im), float(ts), C.c_void_p(self._base + self.lo * self._isz), hi - self.lo,
                                   C.byref(used), C.byref(has), C.byref(upd))
         self.fe.ctx.check(st)
@@ -65,7 +65,7 @@ class VioDeferred(VioDriver):
 
     def step(self, ts, hi, img=None, device_ptr=None, stride=None, shape=None):
         used, has, upd = self._c
-        im, keep = make_image(img, device_ptr, stride, shape if shape is not None else self._shape)
+        im, keep = make_image(img, device_ptr, stride, shape if shape is not None else self._shape, fmt=self.fe._pixfmt)
         st = _L().lvk_vio_process_deferred(self.fe._h, self.be._h, C.byref(im), float(ts), C.c_void_p(self._base + self.lo * self._isz), hi - self.lo,
                                            C.byref(used), C.byref(has), C.byref(upd))
         self.fe.ctx.check(st)
@@ -103,7 +103,7 @@ class VioPipeline:
         if hi > self.pushed:
             L.lvk_vio_pipe_push_imu(self._h, C.c_void_p(self._base + self.pushed * self._isz), hi - self.pushed)
             self.pushed = hi
-        im, keep = make_image(img, device_ptr, stride, shape if shape is not None else self._shape)
+        im, keep = make_image(img, device_ptr, stride, shape if shape is not None else self._shape, fmt=self.fe._pixfmt)
         st = L.lvk_vio_pipe_submit(self._h, C.byref(im), float(ts), C.byref(self._has))
         if st != 0:
             self.fe.ctx.check(st); self.be.ctx.check(st)
