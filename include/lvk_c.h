@@ -58,7 +58,9 @@ typedef struct {
  * launcher script: GPU_MAX_HW_QUEUES=8 (one hardware queue per stream of the library and of the application; HIP's default of 4 makes
  * streams share queues: -17 % frames/s), HIP_FORCE_DEV_KERNARG=1 (kernel arguments in device memory), and - opt-in - the calling
  * thread and every thread started after it bound to the physical cores of one L3 group of its socket (local_rank picks the group).
- * Variables already set by the user are respected.  Call it FIRST in main(), before any HIP call of the process; returns the flags
+ * Variables already set by the user are respected, with one exception: an explicit call with LVK_RT_HW_QUEUES raises a preset
+ * GPU_MAX_HW_QUEUES below 8 to 8 and reports the flag (8 or more is left alone; nothing above 8 is ever written) - the implicit call
+ * of lvk_context_create never overrides a variable.  Call it FIRST in main(), before any HIP call of the process; returns the flags
  * that took effect (a variable the user had set, or a call after this library has already initialised the runtime, reports nothing
  * for that flag; the environment is process-wide state: call it before other threads exist).  lvk_context_create applies LVK_RT_DEFAULT by itself (unless LVK_RUNTIME_ENV=0), which suffices when the library
  * is what makes the process's first HIP call.  No reference counterpart: the reference has no device. */

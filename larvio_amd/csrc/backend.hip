@@ -1065,7 +1065,7 @@ static lvk_status dense_update(lvk_ekf* e, int m, std::vector<double>& dx, int e
     e->last.H = H; e->last.r = r; e->last.m = m; e->last.n = e->N; e->redo = nullptr;
     if (e->prof_on && m > 0) {
         ws.ev_a = prof_take_event(e); ws.ev_b = prof_take_event(e);
-        e->prof_pending.push_back({ws.ev_a, ws.ev_b, 2.0 * m * (double)e->N * (double)e->N, 0, 0.0});
+        e->prof_pending.push_back({ws.ev_a, ws.ev_b, lvk_update_first_launch_flops(m, e->N), 0, 0.0});
     }
 #ifdef LVK_NPD_DEBUG   // debug builds only: the stacked system of every small update, as the update kernels are about to read it
     if (m > 0 && m <= 40) {
@@ -2195,7 +2195,7 @@ lvk_status lvk_ekf_init_report(const lvk_ekf* e, lvk_init_report* out)
     return LVK_OK;
 }
 lvk_status lvk_ekf_profile(lvk_ekf* e, int enable, double* out3)
-{   // out3 (optional): [ms inside the H P GEMM, its flops 2 m N^2, launches] since the last call, then reset
+{   // out3 (optional): [ms inside the update's first launch, its flops (lvk_update_first_launch_flops: H P, plus S's tiles where fused), launches] since the last call, then reset
     if (!e) return LVK_ERR_ARG;
     ekf_quiesce(e);
     hipStreamSynchronize(e->ctx->stream); prof_harvest(e, true);

@@ -10,7 +10,7 @@
 
 // Workspace of one measurement update, passed by value.  B: m x (n+1), S: m x m.  info: the factorisation's report words, in DEVICE
 // memory (the final GEMM reads them: GemmRider::gate); info_host: their mirror in device-mapped host memory, written only when one
-// is set; ev_*: optional bracket around the H P GEMM; dx_host: host-mapped mirror of dx; p00_host: of the updated P's leading
+// is set; ev_*: optional bracket around the update's first launch (H P, with S's partial planes where lvk_update_fused_s); dx_host: host-mapped mirror of dx; p00_host: of the updated P's leading
 // 16 x 16 block
 struct UpdateWs { double* B; int ldb; double* S; int lds; int* info; hipEvent_t ev_a = nullptr, ev_b = nullptr; double* dx_host = nullptr; double* p00_host = nullptr; int* info_host = nullptr; };
 // sharded update: rank g's jobs [job_lo, job_lo + job_n) and its k compressed rows, stacked from row_off (host writes, k_shard_unpack reads)
@@ -58,6 +58,8 @@ struct Stage {
 // be_linalg.hip
 lvk_status lvk_stage_copy2(lvk_context* ctx, void* d_dst0, const void* d_src0, size_t bytes0, void* d_dst1, const void* d_src1, size_t bytes1);
 lvk_status lvk_update_core(lvk_context* ctx, double* P, int ldp, int n, const double* H, int ldh, int m, const double* r, double sigma2, double* dx, UpdateWs ws);
+bool lvk_update_fused_s(int m);                           // lvk_update_core forms S inside the H P launch for this m
+double lvk_update_first_launch_flops(int m, int n);       // flops of what lvk_update_core brackets with UpdateWs::ev_a / ev_b
 lvk_status lvk_update_ldlt_core(lvk_context* ctx, double* P, int ldp, int n, const double* H, int ldh, int m, const double* r, double sigma2, double* dx, UpdateWs ws, int** d_cnt_out, int** d_perm_out);
 lvk_status lvk_cov_gather(lvk_context* ctx, const double* Pin, int ldin, double* Pout, int ldout, const int* d_idx, int n);
 lvk_status lvk_cov_propagate_augment(lvk_context* ctx, const double* Pin, int ldin, double* Pout, int ldout, int n_out, int pose_rows, int L,

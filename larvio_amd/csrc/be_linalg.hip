@@ -98,6 +98,122 @@ static void launch_dgemm(hipStream_t s, int M, int N, int K, const double* A, in
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dgemm_sk<TA, TB>), dim3((N + 15) / 16, (M + 15) / 16), dim3(256), 0, s, M, N, K, kc, A, lda, B, ldb, C, ldc, alpha, beta, diag_add, rd);
 }
 
+// ------------------------------------------------------------------------- [HP | r] and S = HP H^T as ordered partial planes, one launch
+// The update's first two products in ONE launch (m <= 160 rows: the one-fused-launch case of the Cholesky below), so that the
+// dependent chain loses a kernel boundary: S's only reader is the factor workgroup of k_chol_fused, which adds the planes up while
+// it loads them.  Workgroup (q, i) owns rows 16 i .. 16 i + 15 of H and column block q of the state (T tiles of 16 columns; at most
+// HS_NP blocks, so T = ceil(ceil(n / 16) / HS_NP)):
+//   phase 1  its tiles of HP exactly as k_dgemm_sk forms them (split-K over the four wavefronts, every fourth chunk of kc each, the
+//            partial tiles added in LDS in the order chunk 0, 1, 2, 3), written to B and kept in LDS;
+//   phase 2  Sp[q][tile i, tile j] = HP[rows i, block q] . H[rows j, block q]^T for every j <= (i | 1) - the lower triangle in 16 x 16
+//            tiles, plus the tile right of an even diagonal tile so that every 32 x 32 diagonal block the loader reads is complete -
+//            tile j on wavefront j & 3 (at most three each).
+// Phase 2's operand (H again) does not depend on phase 1, so it is requested up front: all global loads of a pass are in flight
+// before its first MFMA, one round trip per wavefront as in k_dgemm_sk.  A column block wider than HS_TG tiles (n > 240) takes
+// further passes, S accumulating in registers.  Every plane entry has exactly one writer and its value depends on indices alone: no
+// atomics, no grid-wide wait, reproducible run to run.  Planes: HS_PLD doubles per row, HS_PLD * 160 per plane; entries right of
+// the tiles written are never defined and never read as values (the loader masks columns >= m).
+#define HS_NP 3
+#define HS_TG 5
+#define HS_PLD 168
+#define HS_ROWS 160
+__global__ void __launch_bounds__(256) k_hp_splanes(int m, int n, int T, int kc, const double* __restrict__ H, int ldh, const double* __restrict__ P, int ldp,
+                                                   double* __restrict__ B, int ldb, const double* __restrict__ rin, double* __restrict__ Sp)
+{
+    __shared__ double red[4][HS_TG][4][64];
+    __shared__ double hp[16][16 * HS_TG + 1];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i16 = lane & 15, kk = lane >> 4;
+    const int q = blockIdx.x, rb = blockIdx.y, row0 = 16 * rb;
+    const int ntile = (n + 15) / 16, mt = (m + 15) / 16;
+    const int t_lo = q * T, t_hi = min(ntile, t_lo + T);
+    const int jmax = min(rb | 1, mt - 1);
+    if (q == 0 && wave == 0 && lane < 16 && row0 + lane < m) B[(size_t)(row0 + lane) * ldb + n] = rin[row0 + lane];
+    const int ar = row0 + i16;
+    const bool a_ok = ar < m;
+    d4 sacc[3];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) sacc[s] = d4{0., 0., 0., 0.};
+    for (int tg = t_lo; tg < t_hi; tg += HS_TG) {
+        const int nt = min(HS_TG, t_hi - tg), cg0 = 16 * tg;
+        // phase 2's operand: lane (i16, kk) holds H[16 j + i16][cg0 + 16 u + 4 kk + qq], the same permutation of k as hp is read with
+        double hb[3][HS_TG][4];
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            const int j = wave + 4 * s, jr = 16 * j + i16;
+            const bool j_ok = j <= jmax && jr < m;
+#pragma unroll
+            for (int u = 0; u < HS_TG; ++u)
+#pragma unroll
+                for (int qq = 0; qq < 4; ++qq) {
+                    const int c = cg0 + 16 * u + 4 * kk + qq;
+                    hb[s][u][qq] = (j_ok && u < nt && c < n) ? H[(size_t)jr * ldh + c] : 0.;
+                }
+        }
+        d4 acc[HS_TG];
+#pragma unroll
+        for (int t = 0; t < HS_TG; ++t) acc[t] = d4{0., 0., 0., 0.};
+        for (int k0 = wave * kc; k0 < n; k0 += 4 * kc) {
+            double a[16], b[HS_TG][16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+                const int k = k0 + 16 * (u >> 2) + 4 * kk + (u & 3);
+                const bool k_ok = 16 * (u >> 2) < kc && k < n;
+                a[u] = (a_ok && k_ok) ? H[(size_t)ar * ldh + k] : 0.;
+#pragma unroll
+                for (int t = 0; t < HS_TG; ++t) {
+                    const int bc = cg0 + 16 * t + i16;
+                    b[t][u] = (t < nt && bc < n && k_ok) ? P[(size_t)k * ldp + bc] : 0.;
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < HS_TG; ++t)
+#pragma unroll
+                for (int u = 0; u < 16; ++u)
+                    if (t < nt && 16 * (u >> 2) < kc && k0 + 16 * (u >> 2) < n) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[t][u], acc[t], 0, 0, 0);
+        }
+#pragma unroll
+        for (int t = 0; t < HS_TG; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) red[wave][t][r][lane] = acc[t][r];
+        __syncthreads();
+        for (int t = wave; t < nt; t += 4) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double sum = ((red[0][t][r][lane] + red[1][t][r][lane]) + red[2][t][r][lane]) + red[3][t][r][lane];
+                const int row = row0 + kk + 4 * r, col = cg0 + 16 * t + i16;
+                hp[kk + 4 * r][16 * t + i16] = sum;          // zero beyond row m / column n: its operands were
+                if (row < m && col < n) B[(size_t)row * ldb + col] = sum;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            if (wave + 4 * s > jmax) continue;
+#pragma unroll
+            for (int u = 0; u < HS_TG; ++u) {
+                if (u >= nt) continue;
+#pragma unroll
+                for (int qq = 0; qq < 4; ++qq) sacc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(hp[i16][16 * u + 4 * kk + qq], hb[s][u][qq], sacc[s], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+    double* plane = Sp + (size_t)q * HS_PLD * HS_ROWS;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        const int j = wave + 4 * s;
+        if (j > jmax) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = row0 + kk + 4 * r;
+            if (row < m) plane[(size_t)row * HS_PLD + 16 * j + i16] = sacc[s][r];
+        }
+    }
+}
+// column tiles per workgroup and planes for a state of n columns
+static inline int hs_tiles(int n) { const int nt = (n + 15) / 16; return (nt + HS_NP - 1) / HS_NP; }
+static inline int hs_planes(int n) { const int nt = (n + 15) / 16, T = hs_tiles(n); return (nt + T - 1) / T; }
+
 
 // ------------------------------------------------------------------------- structural covariance operations
 // Pout[a][b] = Pin[idx[a]][idx[b]]   (clone augmentation larvio.cpp:752-798, row/col deletion :2563-2638, :3311-3327)
@@ -623,10 +739,16 @@ __device__ __forceinline__ void cf_deferred(cf_blk* Sb, cf_blk& Yp, int p, int n
 // passes the block of S to the RIGHT of the diagonal block being factored (rows 0..m-1, the columns of the rows still to come), so
 // that the launch also produces L21^T = L11^-1 A21^T for a matrix taller than 160 rows (launch_chol_solve).  row0 = the first row
 // of this diagonal block in the whole matrix (error reporting).
-template <int CHV>      // 1: one pivot per step (chol32_inv_mfma, the default), 2: two (chol32_inv_mfma2; LVK_CHOL_VARIANT=2)
+// What the factor workgroup loads is np planes (Sp, pld doubles per row, pstride doubles apart) whose sum in plane order, plus sigma2 on
+// the diagonal, is the lower triangle of the matrix to factor: the partial planes of k_hp_splanes for the update's fused pair, or
+// S itself (Sp = S, pld = lds_, np = 1, sigma2 = 0) everywhere else.  L is written to S either way.
+// NPL: the most planes the loader can add (its loads are all in flight at once, 120 registers per plane): 1 wherever S itself is loaded -
+// that instantiation is the kernel as it was before there were planes - and HS_NP behind k_hp_splanes.
+template <int CHV, int NPL = 1>      // CHV 1: one pivot per step (chol32_inv_mfma, the default), 2: two (chol32_inv_mfma2; LVK_CHOL_VARIANT=2)
 __global__ void __launch_bounds__(256) k_chol_fused(double* __restrict__ S, int lds_, int m, double* __restrict__ B, int ldb, int nbcols,
                                                    double* __restrict__ B2, int ldb2, int nbcols2, int row0,
-                                                   double* __restrict__ Yg, int* __restrict__ flag, int base, int* __restrict__ info)
+                                                   double* __restrict__ Yg, int* __restrict__ flag, int base, int* __restrict__ info,
+                                                   const double* __restrict__ Sp, int pld, size_t pstride, int np, double sigma2)
 {
     extern __shared__ __attribute__((aligned(32))) double cf_smem[];
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63, i16 = lane & 15, kk = lane >> 4;
@@ -637,26 +759,32 @@ __global__ void __launch_bounds__(256) k_chol_fused(double* __restrict__ S, int 
         // ===================================================================== factor role
         cf_blk* Sb = (cf_blk*)cf_smem;                                   // lower blocks, cf_idx(bi, bj)
         cf_blk* Yb = (cf_blk*)(cf_smem + (size_t)(CF_MAXB * (CF_MAXB + 1) / 2) * CP_NB * CF_LD);    // two: panel p's inverse is published while p+1's is being built
-        {   // whole lower triangle: one 32-byte load per thread and block, all in flight
+        {   // whole lower triangle of every plane: one 32-byte load per thread, block and plane, all in flight before the first add
             const int row = t >> 3, c4 = (t & 7) * 4;
-            d4 v[CF_MAXB * (CF_MAXB + 1) / 2];
+            d4 v[NPL][CF_MAXB * (CF_MAXB + 1) / 2];
 #pragma unroll
-            for (int bi = 0; bi < CF_MAXB; ++bi)
+            for (int q = 0; q < NPL; ++q)
 #pragma unroll
-                for (int bj = 0; bj <= bi; ++bj) {
-                    const int gr = 32 * bi + row, gc = 32 * bj + c4;
-                    v[cf_idx(bi, bj)] = (bi < nblk && gr < m && row0 + gc + 3 < lds_) ? *(const d4*)(S + (size_t)gr * lds_ + gc) : zero4;   // S starts at column row0 of its buffer's rows
-                }
+                for (int bi = 0; bi < CF_MAXB; ++bi)
+#pragma unroll
+                    for (int bj = 0; bj <= bi; ++bj) {
+                        const int gr = 32 * bi + row, gc = 32 * bj + c4;
+                        v[q][cf_idx(bi, bj)] = ((NPL == 1 || q < np) && bi < nblk && gr < m && row0 + gc + 3 < pld) ? *(const d4*)(Sp + q * pstride + (size_t)gr * pld + gc) : zero4;   // S starts at column row0 of its buffer's rows
+                    }
 #pragma unroll
             for (int bi = 0; bi < CF_MAXB; ++bi)
 #pragma unroll
                 for (int bj = 0; bj <= bi; ++bj) {
                     if (bi >= nblk) continue;
                     const int gr = 32 * bi + row;
+                    d4 sum = v[0][cf_idx(bi, bj)];
+#pragma unroll
+                    for (int q = 1; q < NPL; ++q) if (q < np) sum += v[q][cf_idx(bi, bj)];     // plane order 0, 1, 2
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const int gc = 32 * bj + c4 + q;
-                        Sb[cf_idx(bi, bj)][row][c4 + q] = (gr < m && gc < m) ? v[cf_idx(bi, bj)][q] : (gr == gc ? 1.0 : 0.0);   // identity padding
+                        const double sv = (gr == gc && sigma2 != 0.) ? sum[q] + sigma2 : sum[q];
+                        Sb[cf_idx(bi, bj)][row][c4 + q] = (gr < m && gc < m) ? sv : (gr == gc ? 1.0 : 0.0);   // identity padding
                     }
                 }
         }
@@ -781,7 +909,9 @@ __global__ void __launch_bounds__(256) k_chol_fused(double* __restrict__ S, int 
 //   [S11 . ; S21 S22]:  the fused launch factors S11 = L11 L11^T, solves W1 = L11^-1 B1 and - through the second right-hand side, the
 //   block S12 = S21^T that k_dgemm left to the right of S11 (S is computed in full) - L21^T = L11^-1 S21^T, in place;
 //   then S22 -= L21 L21^T and B2 -= L21 W1 on the FP64 matrix cores, and the recursion continues on (S22, B2).
-static lvk_status launch_chol_solve(lvk_context* ctx, double* S, int lds_, int m, double* B, int ldb, int nbcols, int* info)
+// planes != nullptr (m <= 160 only): the matrix to factor is the sum of np planes of k_hp_splanes plus sigma2 I, and S only receives L.
+static lvk_status launch_chol_solve(lvk_context* ctx, double* S, int lds_, int m, double* B, int ldb, int nbcols, int* info,
+                                    const double* planes = nullptr, int np = 1, double sigma2 = 0.0)
 {
     hipStream_t s = ctx->stream;
     const int MB = CF_MAXB * CP_NB;
@@ -799,16 +929,20 @@ static lvk_status launch_chol_solve(lvk_context* ctx, double* S, int lds_, int m
     // never waits for anybody, so solvers that were dispatched ahead of it only spin until it gets a CU - no ordering assumption
     // is needed for progress, only for speed.
     static const int chv = [] { const char* e = getenv("LVK_CHOL_VARIANT"); return (e && atoi(e) == 2) ? 2 : 1; }();
-    if (chv == 2) LVK_LDS_OPTIN(ctx, k_chol_fused<2>, shm); else LVK_LDS_OPTIN(ctx, k_chol_fused<1>, shm);
+    if (planes) { if (chv == 2) LVK_LDS_OPTIN(ctx, (k_chol_fused<2, HS_NP>), shm); else LVK_LDS_OPTIN(ctx, (k_chol_fused<1, HS_NP>), shm); }
+    else if (chv == 2) LVK_LDS_OPTIN(ctx, k_chol_fused<2>, shm); else LVK_LDS_OPTIN(ctx, k_chol_fused<1>, shm);
     for (int off = 0; off < m; off += MB) {
         const int mb = (m - off) < MB ? (m - off) : MB, rest = m - off - mb;
         double* S11 = S + (size_t)off * lds_ + off; double* B1 = B + (size_t)off * ldb;
         double* S12 = S11 + mb;                       // rows off..off+mb-1, columns off+mb..m-1: A21^T
         const int base = 8 * ctx->chol_epoch++;
-        if (chv == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chol_fused<2>), dim3(1 + (nbcols + 63) / 64 + (rest + 63) / 64), dim3(256), shm, s, S11, lds_, mb, B1, ldb, nbcols,
-                                         S12, lds_, rest, off, (double*)ws, flag, base, info);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chol_fused<1>), dim3(1 + (nbcols + 63) / 64 + (rest + 63) / 64), dim3(256), shm, s, S11, lds_, mb, B1, ldb, nbcols,
-                                S12, lds_, rest, off, (double*)ws, flag, base, info);
+        const double* Sp = planes ? planes : S11; const int pld = planes ? HS_PLD : lds_; const size_t pstride = planes ? (size_t)HS_PLD * HS_ROWS : 0;
+        const int npl = planes ? np : 1; const double sg = planes ? sigma2 : 0.0;
+        const dim3 grid(1 + (nbcols + 63) / 64 + (rest + 63) / 64);
+#define CF_LAUNCH(...) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chol_fused<__VA_ARGS__>), grid, dim3(256), shm, s, S11, lds_, mb, B1, ldb, nbcols, S12, lds_, rest, off, (double*)ws, flag, base, info, Sp, pld, pstride, npl, sg)
+        if (planes) { if (chv == 2) CF_LAUNCH(2, HS_NP); else CF_LAUNCH(1, HS_NP); }
+        else if (chv == 2) CF_LAUNCH(2, 1); else CF_LAUNCH(1, 1);
+#undef CF_LAUNCH
         LVK_LAUNCH_CHECK(ctx);
         if (rest > 0) {
             double* S22 = S + (size_t)(off + mb) * lds_ + off + mb; double* B2 = B + (size_t)(off + mb) * ldb;
@@ -820,17 +954,46 @@ static lvk_status launch_chol_solve(lvk_context* ctx, double* S, int lds_, int m
 }
 
 // ------------------------------------------------------------------------- host drivers (internal + C ABI)
+// Whether an update of m rows takes the fused pair (k_hp_splanes + the plane-adding loader) - a function of m alone: the Cholesky's
+// one-launch case.  Taller updates need S in full (the recursion reads the block right of the diagonal block).  Built, measured, NOT
+// the default (the one launch takes longer than the two it replaces): LVK_UPDATE_FUSED_S=1 (read once) selects it,
+// anything else - LVK_UPDATE_FUSED_S=0 included - is the four-launch path for every m.
+bool lvk_update_fused_s(int m)
+{
+    static const bool on = [] { const char* e = getenv("LVK_UPDATE_FUSED_S"); return e && !strcmp(e, "1"); }();
+    return on && m > 0 && m <= CF_MAXB * CP_NB;
+}
+// flops of the launch between the update's two profiling events: 2 m n^2 for H P, plus - in the fused pair - 2 n per entry of the
+// 16 x 16 tiles of S it forms (tile row i: tiles 0 .. min(i | 1, tiles - 1))
+double lvk_update_first_launch_flops(int m, int n)
+{
+    double f = 2.0 * m * (double)n * (double)n;
+    if (lvk_update_fused_s(m)) { const int mt = (m + 15) / 16; for (int i = 0; i < mt; ++i) f += 2.0 * n * 256.0 * (((i | 1) < mt - 1 ? (i | 1) : mt - 1) + 1); }
+    return f;
+}
 // dx (device, n) and P updated in place.  B: m x (n+1) workspace, S: m x m workspace.
 lvk_status lvk_update_core(lvk_context* ctx, double* P, int ldp, int n, const double* H, int ldh, int m, const double* r, double sigma2,
                            double* dx, UpdateWs ws)
 {
     if (m <= 0) { LVK_HIP(ctx, hipMemsetAsync(dx, 0, sizeof(double) * (size_t)n, ctx->stream)); return LVK_OK; }
     hipStream_t s = ctx->stream;
-    if (ws.ev_a) hipEventRecord(ws.ev_a, s);
-    launch_dgemm<false, false>(s, m, n, n, H, ldh, P, ldp, ws.B, ws.ldb, 1.0, 0.0, 0.0, GemmRider{r, n, nullptr, 0, nullptr});   // [HP | r]
-    if (ws.ev_b) hipEventRecord(ws.ev_b, s);
-    launch_dgemm<false, true>(s, m, m, n, ws.B, ws.ldb, H, ldh, ws.S, ws.lds, 1.0, 0.0, sigma2);           // S = HP H^T + sigma2 I
-    { lvk_status cs = launch_chol_solve(ctx, ws.S, ws.lds, m, ws.B, ws.ldb, n + 1, ws.info); if (cs != LVK_OK) return cs; }                                    // S = L L^T ; W = L^-1 [HP | r]
+    if (lvk_update_fused_s(m)) {
+        // three dependent launches: [HP | r] with S as partial planes, the Cholesky whose loader adds them up, P -= W^T W
+        double* planes = (double*)lvk_ctx_scratch(ctx, LVK_SCR_UPDATE_SP, sizeof(double) * (size_t)HS_NP * HS_PLD * HS_ROWS);
+        if (!planes) return lvk_set_error(ctx, LVK_ERR_DEVICE, "scratch allocation failed");
+        const int np = hs_planes(n), kc = n >= 193 ? 64 : 16 * ((n + 63) / 64);
+        if (ws.ev_a) hipEventRecord(ws.ev_a, s);
+        hipLaunchKernelGGL(k_hp_splanes, dim3(np, (m + 15) / 16), dim3(256), 0, s, m, n, hs_tiles(n), kc, H, ldh, P, ldp, ws.B, ws.ldb, r, planes);
+        if (ws.ev_b) hipEventRecord(ws.ev_b, s);
+        LVK_LAUNCH_CHECK(ctx);
+        { lvk_status cs = launch_chol_solve(ctx, ws.S, ws.lds, m, ws.B, ws.ldb, n + 1, ws.info, planes, np, sigma2); if (cs != LVK_OK) return cs; }
+    } else {
+        if (ws.ev_a) hipEventRecord(ws.ev_a, s);
+        launch_dgemm<false, false>(s, m, n, n, H, ldh, P, ldp, ws.B, ws.ldb, 1.0, 0.0, 0.0, GemmRider{r, n, nullptr, 0, nullptr});   // [HP | r]
+        if (ws.ev_b) hipEventRecord(ws.ev_b, s);
+        launch_dgemm<false, true>(s, m, m, n, ws.B, ws.ldb, H, ldh, ws.S, ws.lds, 1.0, 0.0, sigma2);           // S = HP H^T + sigma2 I
+        { lvk_status cs = launch_chol_solve(ctx, ws.S, ws.lds, m, ws.B, ws.ldb, n + 1, ws.info); if (cs != LVK_OK) return cs; }                                    // S = L L^T ; W = L^-1 [HP | r]
+    }
     // W^T [W | w]: columns 0..n-1 update P (P -= W^T W), column n is dx = W^T w
     launch_dgemm<true, false>(s, n, n + 1, m, ws.B, ws.ldb, ws.B, ws.ldb, P, ldp, -1.0, 1.0, 0.0, GemmRider{nullptr, 0, dx, n, ws.dx_host, ws.p00_host, ws.info, ws.info_host});
     LVK_LAUNCH_CHECK(ctx);

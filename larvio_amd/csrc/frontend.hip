@@ -82,12 +82,15 @@ bool lvk_bar_usable(int device)
 
 // lvk_runtime_env (include/lvk_c.h): what a deployment should set before the HIP runtime initialises, done by the library.
 //  * GPU_MAX_HW_QUEUES=8: the front-end's three streams + the filter's (+ the application's own) each get a hardware queue; with HIP's
-//    default of 4, streams share queues and serialise (measured: 5800 -> 4800 frames/s).
+//    default of 4, streams share queues and serialise (measured: 5800 -> 4800 frames/s; round 6's pipeline: 10,100 -> 7,300).  An application that asks for it by name
+//    (an explicit lvk_runtime_env call with LVK_RT_HW_QUEUES) also gets a preset number below 8 raised to 8 - a launcher's or a
+//    machine's blanket default of 4 would otherwise turn the request into nothing without a word; 8 or more is left alone, and
+//    nothing above 8 is ever written.
 //  * HIP_FORCE_DEV_KERNARG=1: kernel arguments in device memory (~1 % on these chains of small kernels).
 //  * LVK_RT_BIND_L3 (opt-in: a library should not move its caller's threads unasked): the calling thread - and every thread it
 //    starts afterwards: the HIP runtime's, the filter's worker - onto the physical cores of ONE L3 group of the socket it runs on
 //    (rank r takes the r-th group): the caller's and the filter's thread hand each other messages every ~100 us.
-// Variables the user has set are left alone.  Effective only if called before the process's first HIP call; lvk_context_create
+// Otherwise variables the user has set are left alone: the implicit call below never overrides one.  Effective only if called before the process's first HIP call; lvk_context_create
 // calls it with LVK_RT_DEFAULT itself (LVK_RUNTIME_ENV=0 turns that off), which is early enough when the library makes that first call.
 static bool cpulist_parse(const char* path, cpu_set_t* out)
 {
@@ -148,18 +151,25 @@ static bool bind_l3_group(int local_rank)
 extern "C" {
 
 static std::atomic<bool> g_hip_touched{false};          // this library has made a HIP call in this process: the runtime has read its environment
-unsigned lvk_runtime_env(unsigned flags, int local_rank)
+// asked: the application called lvk_runtime_env itself (it may raise a preset GPU_MAX_HW_QUEUES below 8); the implicit call of lvk_context_create may not
+static unsigned runtime_env_apply(unsigned flags, int local_rank, bool asked)
 {
     unsigned done = 0;
     // a flag is reported only if it can still take effect: the variable was not set by the user and the runtime has not been
     // initialised through this library (a host application that initialised HIP itself is beyond what can be seen from here:
     // lvk_c.h says "call it first in main()")
     const bool early = !g_hip_touched.load();
-    if ((flags & LVK_RT_HW_QUEUES) && early && !getenv("GPU_MAX_HW_QUEUES")) { if (setenv("GPU_MAX_HW_QUEUES", "8", 0) == 0) done |= LVK_RT_HW_QUEUES; }
+    if ((flags & LVK_RT_HW_QUEUES) && early) {
+        const char* cur = getenv("GPU_MAX_HW_QUEUES");
+        bool set8 = !cur;
+        if (cur && asked) { char* end = nullptr; const long v = strtol(cur, &end, 10); set8 = end != cur && *end == 0 && v < 8; }    // a number below 8; anything else stays
+        if (set8 && setenv("GPU_MAX_HW_QUEUES", "8", 1) == 0) done |= LVK_RT_HW_QUEUES;
+    }
     if ((flags & LVK_RT_DEV_KERNARG) && early && !getenv("HIP_FORCE_DEV_KERNARG")) { if (setenv("HIP_FORCE_DEV_KERNARG", "1", 0) == 0) done |= LVK_RT_DEV_KERNARG; }
     if (flags & LVK_RT_BIND_L3) { if (bind_l3_group(local_rank)) done |= LVK_RT_BIND_L3; }
     return done;
 }
+unsigned lvk_runtime_env(unsigned flags, int local_rank) { return runtime_env_apply(flags, local_rank, true); }
 
 const char* lvk_version(void) { return "lvk-hip 0.1 (gfx950)"; }
 
@@ -212,7 +222,7 @@ lvk_status lvk_context_create(int device, lvk_context** out)
         if (!once.exchange(true)) { const char* sw = getenv("LVK_RUNTIME_ENV"); if (!(sw && !strcmp(sw, "0"))) {
             const char* bd = getenv("LVK_RUNTIME_BIND");               // "l3" or "l3:<local rank>": the opt-in core binding for a driver that cannot call lvk_runtime_env (the reference's own main())
             const bool l3 = bd && !strncmp(bd, "l3", 2);
-            lvk_runtime_env(LVK_RT_DEFAULT | (l3 ? LVK_RT_BIND_L3 : 0u), l3 && bd[2] == ':' ? atoi(bd + 3) : 0);
+            runtime_env_apply(LVK_RT_DEFAULT | (l3 ? LVK_RT_BIND_L3 : 0u), l3 && bd[2] == ':' ? atoi(bd + 3) : 0, false);
         } }
     }
     int count = 0;

@@ -60,6 +60,7 @@ enum lvk_scratch_slot {
     LVK_SCR_GFTT_CANDS,                 // corner selection: candidate keys
     LVK_SCR_UPDATE_B,                   // measurement update: B = [H P | r]
     LVK_SCR_UPDATE_S,                   // measurement update: S
+    LVK_SCR_UPDATE_SP,                  // measurement update: S as partial planes, one per block of state columns (k_hp_splanes)
     LVK_SCR_UPDATE_INFO,                // measurement update: the factorisation's report words
     LVK_SCR_QR_H, LVK_SCR_QR_R,         // shared by the grouped-QR stage entry (ping-pong copy of H, r) and CAQR (V, T): one runs after the other on the stream
     LVK_SCR_STAGE_IN, LVK_SCR_STAGE_MID, LVK_SCR_STAGE_OUT,   // shared by every stage entry (input blob, staging, output blob): each ends with a stream wait
