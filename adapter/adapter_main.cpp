@@ -1,7 +1,9 @@
 // adapter/adapter_main.cpp — the loop of the reference's app/larvioMain.cpp:84-117 written against the ADAPTER classes
 // (larvio::ImageProcessor / larvio::LarVio with the reference's own signatures), i.e. what larvioMain.cpp does once it is linked
 // against lvk_adapter instead of the image_processor / estimator libraries, minus the Pangolin viewer (:57-82,118-202).
-// Usage: adapter_main path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--bench N [--no-vis]]
+// Usage: adapter_main path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--bench N [--no-vis]] [--depth-out FILE]
+// --depth-out FILE: after every odometry message, LarVio::getFeaturesInCamera and one line per active map point in the format of
+// examples/larvio_euroc --depth-out (examples/lvk_euroc_args.hpp), stamped with the image's time.
 // --bench N: the image files are decoded before the loop starts (the reference's player reads them inside it; a PNG decode is ten times
 // a frame of this library) and the LAST N frames of the loop - processImage, processFeatures, every getter of larvioMain.cpp:117-170 -
 // are timed with the steady clock; one line "bench frames N seconds S frames_per_s F" is printed (bench.py: adapter_cpp).  --no-vis
@@ -15,6 +17,7 @@
 #include <larvio/larvio.h>
 
 #include "../examples/lvk_dataset.hpp"
+#include "../examples/lvk_euroc_args.hpp"
 #include "../examples/lvk_png.hpp"
 
 #include <chrono>
@@ -49,9 +52,10 @@ static cv::Mat grey_as(const lvk::GreyImage& g, int format, int shift)
 int main(int argc, char** argv)
 {
     if (argc < 5) { std::fprintf(stderr, "Usage: %s path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt]\n", argv[0]); return 1; }
-    std::string tum_path; long bench_n = 0; bool vis_on = true; int pix_format = LVK_PIX_MONO8, pix_shift = 0;
+    std::string tum_path, depth_path; long bench_n = 0; bool vis_on = true; int pix_format = LVK_PIX_MONO8, pix_shift = 0;
     for (int a = 5; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--tum") && a + 1 < argc) tum_path = argv[++a];
+        else if (!std::strcmp(argv[a], "--depth-out") && a + 1 < argc) depth_path = argv[++a];
         else if (!std::strcmp(argv[a], "--bench") && a + 1 < argc) bench_n = std::atol(argv[++a]);
         else if (!std::strcmp(argv[a], "--no-vis")) vis_on = false;
         else if (!std::strcmp(argv[a], "--input-format") && a + 1 < argc) {
@@ -79,6 +83,8 @@ int main(int argc, char** argv)
     if (!Estimator->initialize()) { std::fprintf(stderr, "Estimator initialization failed!\n"); return 1; }
 
     FILE* tum = tum_path.empty() ? nullptr : std::fopen(tum_path.c_str(), "w");
+    FILE* depth = depth_path.empty() ? nullptr : std::fopen(depth_path.c_str(), "w");
+    if (!depth_path.empty() && !depth) { std::perror(depth_path.c_str()); return 1; }
     size_t k = 0; long n_msgs = 0, n_odo = 0, n_stable = 0, n_active = 0;
     std::vector<ImuData> imu_msg_buffer;
     std::vector<lvk::GreyImage> preloaded;
@@ -115,6 +121,14 @@ int main(int argc, char** argv)
             const cv::Mat vis = vis_on ? ImgProcesser->getVisualImg() : cv::Mat();
             if (tum) std::fprintf(tum, "%.9f %.17g %.17g %.17g  %.17g %.17g %.17g  %.6e %.6e  %zu %d\n", imgPtr->timeStampToSec, T_b_w.translation()(0), T_b_w.translation()(1),
                                   T_b_w.translation()(2), vel(0), vel(1), vel(2), P_pose(0, 0), P_vel(0, 0), swPoses.size(), vis.cols * vis.rows * vis.channels());
+            if (depth) {
+                std::vector<FeatureIDType> ids; std::vector<Eigen::Vector3d> pos_c; std::vector<double> cov9;
+                if (!Estimator->getFeaturesInCamera(ids, pos_c, cov9)) { std::fprintf(stderr, "getFeaturesInCamera failed\n"); return 1; }
+                for (size_t i = 0; i < ids.size(); ++i) {
+                    const double p[3] = {pos_c[i](0), pos_c[i](1), pos_c[i](2)};
+                    lvk::write_depth_point(depth, imgPtr->timeStampToSec, (long long)ids[i], p, &cov9[9 * i]);
+                }
+            }
         }
     }
     if (bench_n > 0) {
@@ -123,6 +137,7 @@ int main(int argc, char** argv)
         std::printf("bench frames %ld seconds %.6f frames_per_s %.1f\n", bench_n, sec, (double)bench_n / sec);
     }
     if (tum) std::fclose(tum);
+    if (depth) std::fclose(depth);
     std::printf("frames %zu  feature messages %ld  odometry updates %ld  stable map points handed out %ld  active at the end %ld\n", allImgInfo.size(), n_msgs, n_odo, n_stable, n_active);
     return 0;
 }

@@ -54,6 +54,11 @@ class LarVio {
     void takeKeyframes(std::vector<lvk_keyframe>& keyframes);
     bool getWindowCov(std::vector<long long>& ids, std::vector<double>& cov_abs36, std::vector<double>& cov_rel36);
 
+    // not in the reference: the active map points in the camera frame of the current IMU state (to_clone_id -1) or of a clone of the
+    // window, each with its 3 x 3 covariance there, in which the unobservable global position and yaw cancel (lvk_ekf_get_feature_rel,
+    // lvk_c.h); cov9: 9 doubles per point, row-major, NaN where the anchor clone has left the window
+    bool getFeaturesInCamera(std::vector<FeatureIDType>& ids, std::vector<Eigen::Vector3d>& positions_c, std::vector<double>& cov9, long long to_clone_id = -1);
+
     typedef boost::shared_ptr<LarVio> Ptr;
     typedef boost::shared_ptr<const LarVio> ConstPtr;
 

@@ -238,6 +238,21 @@ bool LarVio::getWindowCov(std::vector<long long>& ids, std::vector<double>& cov_
     return ok;
 }
 
+bool LarVio::getFeaturesInCamera(std::vector<FeatureIDType>& ids, std::vector<Eigen::Vector3d>& positions_c, std::vector<double>& cov9, long long to_clone_id)
+{
+    finish();
+    std::vector<int64_t> id(4096); std::vector<double> pos(3 * 4096); cov9.resize(9 * 4096);
+    int n = 0;
+    const bool ok = ekf && lvk_ekf_get_feature_rel(ekf, (int64_t)to_clone_id, id.data(), nullptr, pos.data(), cov9.data(), 4096, &n) == LVK_OK;
+    if (!ok) n = 0;
+    ids.clear(); positions_c.clear();
+    for (int i = 0; i < n; ++i) {
+        ids.push_back((FeatureIDType)id[(size_t)i]); positions_c.push_back(Eigen::Vector3d(pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2]));
+    }
+    cov9.resize((size_t)9 * n);
+    return ok;
+}
+
 void LarVio::getActiveeMapPointPositions(std::map<larvio::FeatureIDType, Eigen::Vector3d>& mMapPoints)
 {
     finish();

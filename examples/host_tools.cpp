@@ -7,6 +7,9 @@
 //   host_tools euroc-args [options...]     the dataset driver's options as it parses them, one "name value" line each (exit 1 + the
 //                                          driver's message on an unknown option)
 //   host_tools euroc-args-all [options...] the same with every field (euroc-args keeps the six lines it has always printed)
+//   host_tools euroc-args-fields <f1,f2,...> [options...]   the fields named (tum mask map_out msckf_out keyframes_out depth_out max_frames
+//                                          pipelined), in that order: a new option needs no listing of its own (the two above keep their lines)
+//   host_tools depth-line <stamp> <id> <x y z> <9 covariance entries, row-major>      the --depth-out line of that point
 //   host_tools keyframe-line <id> <to_id> <88 doubles: time to_time q p rel_q rel_p cov_abs cov_rel>      the --keyframes-out line of that record
 //   host_tools msckf-line <id> <x y z> <9 covariance entries, row-major> <n_obs>      the --msckf-out line of that point
 #include "lvk_config.hpp"
@@ -15,6 +18,7 @@
 #include "lvk_png.hpp"
 #include <cstdio>
 #include <cstring>
+#include <string>
 
 static void show(const char* name, double v) { std::printf("%s %.17g\n", name, v); }
 static void show(const char* name, const double* v, int n) { std::printf("%s", name); for (int i = 0; i < n; ++i) std::printf(" %.17g", v[i]); std::printf("\n"); }
@@ -79,6 +83,26 @@ int main(int argc, char** argv)
                     o.msckf_out.c_str(), o.keyframes_out.c_str(), o.max_frames, o.pipelined ? 1 : 0);
         return 0;
     }
+    if (argc >= 3 && !std::strcmp(argv[1], "euroc-args-fields")) {
+        lvk::EurocArgs o; std::string bad;
+        if (!lvk::parse_euroc_args(argc, argv, 3, &o, &bad)) { std::fprintf(stderr, "unknown option %s\n", bad.c_str()); return 1; }
+        const struct { const char* name; std::string value; } all[] = {{"tum", o.tum}, {"mask", o.mask}, {"map_out", o.map_out}, {"msckf_out", o.msckf_out},
+            {"keyframes_out", o.keyframes_out}, {"depth_out", o.depth_out}, {"max_frames", std::to_string(o.max_frames)}, {"pipelined", o.pipelined ? "1" : "0"}};
+        const std::string want = argv[2];
+        for (size_t lo = 0; lo <= want.size();) {
+            size_t hi = want.find(',', lo); if (hi == std::string::npos) hi = want.size();
+            const std::string name = want.substr(lo, hi - lo); bool found = false;
+            for (const auto& f : all) if (name == f.name) { std::printf("%s %s\n", f.name, f.value.c_str()); found = true; }
+            if (!found) { std::fprintf(stderr, "unknown field %s\n", name.c_str()); return 2; }
+            lo = hi + 1;
+        }
+        return 0;
+    }
+    if (argc == 16 && !std::strcmp(argv[1], "depth-line")) {
+        double v[12]; for (int i = 0; i < 12; ++i) v[i] = std::strtod(argv[4 + i], nullptr);
+        lvk::write_depth_point(stdout, std::strtod(argv[2], nullptr), std::atoll(argv[3]), v, v + 3);
+        return 0;
+    }
     if (argc == 92 && !std::strcmp(argv[1], "keyframe-line")) {
         double v[88]; for (int i = 0; i < 88; ++i) v[i] = std::strtod(argv[4 + i], nullptr);
         lvk::write_keyframe(stdout, std::atoll(argv[2]), std::atoll(argv[3]), v);
@@ -89,6 +113,6 @@ int main(int argc, char** argv)
         lvk::write_msckf_point(stdout, std::atoll(argv[2]), v, v + 3, std::atoi(argv[15]));
         return 0;
     }
-    std::fprintf(stderr, "usage: host_tools config|png|imu|images|euroc-args|euroc-args-all|msckf-line|keyframe-line ...\n");
+    std::fprintf(stderr, "usage: host_tools config|png|imu|images|euroc-args|euroc-args-all|euroc-args-fields|msckf-line|keyframe-line|depth-line ...\n");
     return 2;
 }

@@ -2,7 +2,7 @@
 // Pangolin): same command line, same loop, same log files (msckf_2_state.txt / msckf_2_takeoff.txt in the configuration's
 // output_dir, written by lvk::LarVio as larvio.cpp:388,446-453 does), running on liblvk_hip.so.
 //
-//   larvio_euroc path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE] [--keyframes-out FILE]
+//   larvio_euroc path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE] [--keyframes-out FILE] [--depth-out FILE]
 //
 // --mask restricts corner detection to the non-zero pixels of an 8-bit PNG of the configured resolution (ImageProcessor::setMask:
 // a fisheye vignette, the vehicle's own body); a mask of another size is an error.
@@ -15,6 +15,9 @@
 // "id to_id time to_time q(4) p(3) rel_q(4) rel_p(3) cov_abs(36) cov_rel(36)" - its pose, the pose of clone to_id relative to it, its
 // absolute 6 x 6 covariance and the covariance of that relative pose (lvk_c.h, lvk_ekf_pose_rel_cov).  Drained after every update;
 // --pipelined drains once, at the end.
+// --depth-out writes, after every pose, one line per in-state feature: "timestamp id x y z s00 s01 s02 s11 s12 s22" - the point in the
+// camera frame of that pose and the upper triangle of its 3 x 3 covariance there (LarVio::getFeaturesInCamera; lvk_c.h,
+// lvk_ekf_landmark_rel_cov): s22 is the depth variance.  A getter only: the filter's outputs do not notice it.
 // --tum writes "t x y z qx qy qz qw" (body in world, absolute stamps, 17 significant digits) for tools/traj_rmse.py.
 // --pipelined runs the same loop through lvk::VioPipeline: the filter update of a message overlaps the front-end of the next
 // frames on a second HIP stream; the trajectory is the same, written from the filter thread's odometry callback.
@@ -83,21 +86,37 @@ struct KeyframesOut {
     void close() { if (f) { std::fclose(f); f = nullptr; } }
 };
 
-struct OdometrySink { FILE* tum; long n_odo; };
+// --depth-out: the in-state features in the camera frame of the pose just published
+struct DepthOut {
+    FILE* f; long n;
+    void write(const lvk::LarVio& Estimator)
+    {
+        if (!f) return;
+        std::vector<int64_t> ids, anchors; std::vector<double> xyz, cov;
+        double s[30];
+        if (lvk_ekf_get_state(Estimator.handle(), s) != LVK_OK || !Estimator.getFeaturesInCamera(ids, anchors, xyz, cov)) return;
+        for (size_t i = 0; i < ids.size(); ++i, ++n) lvk::write_depth_point(f, s[0], (long long)ids[i], &xyz[3 * i], &cov[9 * i]);
+    }
+    void close() { if (f) { std::fclose(f); f = nullptr; } }
+};
+
+struct OdometrySink { FILE* tum; long n_odo; DepthOut* depth; };
 static void on_odometry(void* user, double, const lvk::LarVio& Estimator)
 {
     OdometrySink* o = static_cast<OdometrySink*>(user);
     ++o->n_odo;
     if (o->tum) write_tum(o->tum, Estimator);
+    o->depth->write(Estimator);
 }
 
 static int run_pipelined(const char* image_dir, const std::vector<lvk::ImuData>& allImuData, const std::vector<lvk::ImgInfo>& allImgInfo, long max_frames,
-                         lvk::ImageProcessor& ImgProcesser, lvk::LarVio& Estimator, FILE* tum, MapOut& map_out, MsckfOut& msckf_out, KeyframesOut& kf_out)
+                         lvk::ImageProcessor& ImgProcesser, lvk::LarVio& Estimator, FILE* tum, MapOut& map_out, MsckfOut& msckf_out, KeyframesOut& kf_out,
+                         DepthOut& depth_out)
 {
     typedef std::chrono::steady_clock Clock;
     lvk::VioPipeline pipe(ImgProcesser, Estimator);
     if (!pipe.ok()) { std::fprintf(stderr, "cannot create the pipeline\n"); return 1; }
-    OdometrySink sink = {tum, 0};
+    OdometrySink sink = {tum, 0, &depth_out};
     pipe.onOdometry(on_odometry, &sink);
     const size_t n_frames = max_frames >= 0 && (size_t)max_frames < allImgInfo.size() ? (size_t)max_frames : allImgInfo.size();
     size_t k = 0; double t_proc = 0, t_io = 0; long n_msgs = 0, n_upd = 0;
@@ -123,6 +142,7 @@ static int run_pipelined(const char* image_dir, const std::vector<lvk::ImuData>&
     map_out.drain(Estimator); map_out.close();
     msckf_out.drain(Estimator); msckf_out.close();
     kf_out.drain(Estimator); kf_out.close();
+    depth_out.close();
     std::printf("frames %zu  feature messages %ld  odometry updates %ld  state dim %d\n", n_frames, n_msgs, sink.n_odo, lvk_ekf_dim(Estimator.handle()));
     std::printf("pipelined: %.3f ms/frame in the driver thread   image read+decode %.3f ms/frame\n", n_frames ? 1e3 * t_proc / n_frames : 0.0, n_frames ? 1e3 * t_io / n_frames : 0.0);
     if (t_proc > 0) std::printf("processing rate %.1f frames/s (pipelined, host buffers)\n", n_frames / t_proc);
@@ -132,7 +152,7 @@ static int run_pipelined(const char* image_dir, const std::vector<lvk::ImuData>&
 int main(int argc, char** argv)
 {
     if (argc < 5) {
-        std::fprintf(stderr, "Usage: %s path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE] [--keyframes-out FILE]\n", argv[0]);
+        std::fprintf(stderr, "Usage: %s path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE] [--keyframes-out FILE] [--depth-out FILE]\n", argv[0]);
         return 1;
     }
     lvk::EurocArgs opt; std::string bad;
@@ -184,7 +204,9 @@ int main(int argc, char** argv)
         if (!(kf_out.f = std::fopen(opt.keyframes_out.c_str(), "w"))) { std::perror(opt.keyframes_out.c_str()); return 1; }
         if (!Estimator.setKeyframeExport(true)) { std::fprintf(stderr, "larvio_euroc: %s\n", (pipelined ? ctx2 : ctx).error()); return 1; }
     }
-    if (pipelined) return run_pipelined(argv[3], allImuData, allImgInfo, max_frames, ImgProcesser, Estimator, tum, map_out, msckf_out, kf_out);
+    DepthOut depth_out = {nullptr, 0};
+    if (!opt.depth_out.empty() && !(depth_out.f = std::fopen(opt.depth_out.c_str(), "w"))) { std::perror(opt.depth_out.c_str()); return 1; }
+    if (pipelined) return run_pipelined(argv[3], allImuData, allImgInfo, max_frames, ImgProcesser, Estimator, tum, map_out, msckf_out, kf_out, depth_out);
 
     typedef std::chrono::steady_clock Clock;
     double t_fe = 0, t_be = 0, t_io = 0; long n_fe = 0, n_be = 0, n_odo = 0;
@@ -216,6 +238,7 @@ int main(int argc, char** argv)
         if (bPubOdo) {
             ++n_odo;
             if (tum) write_tum(tum, Estimator);
+            depth_out.write(Estimator);
         }
         msckf_out.drain(Estimator);
         kf_out.drain(Estimator);
@@ -224,6 +247,7 @@ int main(int argc, char** argv)
     map_out.drain(Estimator); map_out.close();
     msckf_out.drain(Estimator); msckf_out.close();
     kf_out.drain(Estimator); kf_out.close();
+    depth_out.close();
     std::printf("frames %ld  feature messages %ld  odometry updates %ld  state dim %d\n", n_fe, n_be, n_odo, lvk_ekf_dim(Estimator.handle()));
     std::printf("front-end %.3f ms/frame   back-end %.3f ms/message   image read+decode %.3f ms/frame\n", n_fe ? 1e3 * t_fe / n_fe : 0.0,
                 n_be ? 1e3 * t_be / n_be : 0.0, n_fe ? 1e3 * t_io / n_fe : 0.0);

@@ -1,5 +1,5 @@
 // lvk_euroc_args.hpp — the options of examples/larvio_euroc after its four positional arguments, and the line format of its
-// --msckf-out and --keyframes-out files; host-only, so that examples/host_tools can show both on a machine without a GPU.
+// --msckf-out, --keyframes-out and --depth-out files; host-only, so that examples/host_tools can show both on a machine without a GPU.
 #pragma once
 #include <cstdio>
 #include <cstdlib>
@@ -8,7 +8,7 @@
 
 namespace lvk {
 
-struct EurocArgs { std::string tum, mask, map_out, msckf_out, keyframes_out; long max_frames; bool pipelined; EurocArgs() : max_frames(-1), pipelined(false) {} };
+struct EurocArgs { std::string tum, mask, map_out, msckf_out, keyframes_out, depth_out; long max_frames; bool pipelined; EurocArgs() : max_frames(-1), pipelined(false) {} };
 
 // argv[first..]: false, with the offending word in *bad, on an unknown option or an option without its value
 inline bool parse_euroc_args(int argc, char** argv, int first, EurocArgs* o, std::string* bad)
@@ -21,6 +21,7 @@ inline bool parse_euroc_args(int argc, char** argv, int first, EurocArgs* o, std
         else if (!std::strcmp(argv[a], "--map-out") && a + 1 < argc) o->map_out = argv[++a];
         else if (!std::strcmp(argv[a], "--msckf-out") && a + 1 < argc) o->msckf_out = argv[++a];
         else if (!std::strcmp(argv[a], "--keyframes-out") && a + 1 < argc) o->keyframes_out = argv[++a];
+        else if (!std::strcmp(argv[a], "--depth-out") && a + 1 < argc) o->depth_out = argv[++a];
         else { if (bad) *bad = argv[a]; return false; }
     }
     return true;
@@ -40,6 +41,14 @@ inline void write_keyframe(FILE* f, long long id, long long to_id, const double*
     std::fprintf(f, "%lld %lld", id, to_id);
     for (int i = 0; i < 88; ++i) std::fprintf(f, " %.17g", v[i]);
     std::fprintf(f, "\n");
+}
+
+// one --depth-out line: "timestamp id x y z s00 s01 s02 s11 s12 s22" - the state time (9 decimals, as --tum writes it), the feature, its
+// position in the camera frame of that state and the upper triangle of its 3 x 3 covariance there (17 significant digits: the doubles
+// round-trip; s22 is the depth variance)
+inline void write_depth_point(FILE* f, double t, long long id, const double* p, const double* c)
+{
+    std::fprintf(f, "%.9f %lld %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", t, id, p[0], p[1], p[2], c[0], c[1], c[2], c[4], c[5], c[8]);
 }
 
 }   // namespace lvk

@@ -408,6 +408,41 @@ typedef struct { int a_theta_col, a_p_col, b_theta_col, b_p_col;   /* first of t
                  double q_a[4], p_a[3], q_b[4], p_b[3]; } lvk_pose_rel_job;
 lvk_status lvk_ekf_pose_rel_cov(lvk_context* ctx, const double* d_P, int ldp, int n, const lvk_pose_rel_job* h_jobs, int n_jobs, double* h_cov36);
 
+/* Anchored inverse-depth landmarks in the CAMERA frame of a target pose, with their 3 x 3 covariance there, one per job, read off a
+ * device-resident covariance (n x n, row-major, leading dimension ldp) without moving it.  The world-frame Sigma of
+ * lvk_ekf_landmark_cov contains the four directions a VIO cannot observe (global position and yaw), which grow without bound; the
+ * point relative to a camera of the window does not: here they cancel, as they do in lvk_ekf_pose_rel_cov.
+ * The point's world position p_w is exactly that of lvk_ekf_landmark_cov (the same anchored inverse-depth form, the same
+ * R(q_anchor) R_b2c^T taken through a quaternion and back), with p_cam = p_anchor + R(q_anchor) t_c_b.  For a target pose b
+ * (attitude q_b, position p_b, body to world) the point in b's camera frame is
+ *   p_c = R_b2c ( R_b^T (p_w - p_b) - t_c_b ).
+ * The error state is the one the filter's state injection applies (the conventions are stated at lvk_ekf_landmark_cov and
+ * lvk_ekf_pose_rel_cov): clone and IMU attitude R <- (I + [d_theta]x) R, position p <- p + d_p, extrinsic rotation
+ * R_b2c <- R_b2c R(small_angle_quat(d_theta_e))^T, extrinsic translation t_c_b <- t_c_b + d_t, inverse depth rho <- rho + d_rho.
+ * Nineteen columns of P matter, in this order:
+ *   [ d_theta_e d_t (15..20) | d_theta_a d_p_a (anchor_col..+5) | d_theta_b (b_theta_col..+2) | d_p_b (b_p_col..+2) | d_rho (feat_col) ].
+ * The target's d_theta and d_p columns are named separately, as in lvk_pose_rel_job: the target may be the IMU state (0 and 6) or any
+ * clone (leg_dim + 6 c and + 3).  Sigma = J P[those, those] J^T with, for R_a = R(q_anchor), M = R_b2c R_b^T, f_A = [u v 1] / rho,
+ * x = R_b2c^T f_A, r_c = p_w - p_cam,anchor (= R_a x), r = p_w - p_anchor, g = p_w - p_b and y = R_b^T g - t_c_b,
+ *   J = [ R_b2c [y]x - M R_a [x]x | M R_a - R_b2c | -M [r]x | M | M [g]x | -M | -M r_c / rho ].
+ * (Confirmed against inject() by central differences of p_c under that injection: tests/landmark_rel_ref.py; they agree with the
+ * form above.)  A rigid motion of the world (d_theta_a = d_theta_b = theta, d_p_x = [theta]x p_x + t) gives d p_c = 0.  With the target
+ * equal to the anchor clone (the same columns named twice - legal) every block but the last cancels: Sigma = sigma_rho^2 f_A f_A^T / rho^2.
+ * g is formed as r + (p_anchor - p_b): the two positions are subtracted first, so that the size of the world coordinates does not
+ * enter the rounding of p_c.
+ * Nothing outside those 19 rows and columns of P is read; every sum runs in a fixed order (the same input gives the same bits) and
+ * the lower triangle is a copy of the upper one.  h_out12: 12 doubles per job - p_c (3), then Sigma (9, row-major).  The call waits
+ * for its launch.
+ * LVK_ERR_ARG, with nothing launched and the context still usable, when a pointer is null, n_jobs < 0, ldp < n, a job's column range
+ * (15..20, anchor_col..anchor_col+5, b_theta_col..+2, b_p_col..+2, feat_col) leaves [0, n), or its inv_depth is 0.  n_jobs == 0 is
+ * LVK_OK. */
+typedef struct { int anchor_col, feat_col, pad0, pad1;      /* as lvk_landmark_job, field for field ... */
+                 double q_anchor[4], R_b2c[9], t_c_b[3];
+                 double obs_anchor[2], inv_depth;
+                 int b_theta_col, b_p_col;                  /* ... then the target: first of its three d_theta columns, first of its three d_p columns */
+                 double q_b[4], p_b[3], p_anchor[3]; } lvk_landmark_rel_job;   /* the target's pose; the anchor clone's position as lvk_clone.p */
+lvk_status lvk_ekf_landmark_rel_cov(lvk_context* ctx, const double* d_P, int ldp, int n, const lvk_landmark_rel_job* h_jobs, int n_jobs, double* h_out12);
+
 typedef struct {
     /* names and meaning as LarVio::loadParameters reads them (larvio.cpp:58-311, config/euroc.yaml) */
     int if_fej, estimate_extrin, estimate_td, if_zupt_valid;
@@ -530,6 +565,17 @@ int        lvk_ekf_take_lost_features(lvk_ekf* e, int64_t* h_ids, double* h_pos_
 lvk_status lvk_ekf_get_feature_cov(lvk_ekf* e, int64_t* h_ids, int64_t* h_anchor_ids, double* h_pos_w, double* h_cov9, int cap, int* n_out);
 lvk_status lvk_ekf_set_lost_feature_cov(lvk_ekf* e, int on);
 int        lvk_ekf_take_lost_features_cov(lvk_ekf* e, int64_t* h_ids, double* h_pos_w, double* h_cov9, int cap);
+/* The same map points where a consumer that steers or renders needs them: in the camera frame of a pose of the window, with the
+ * covariance of lvk_ekf_landmark_rel_cov (conventions there), in which the unobservable global position and yaw cancel - the depth
+ * sigma is sqrt(Sigma[2][2]).  The in-state features in the order of lvk_ekf_get_features - id, anchor clone id, p_c (3 doubles) and
+ * Sigma (9 doubles, row-major, exactly symmetric) - up to cap of them; *n_out = how many.  to_clone_id == -1: the current IMU state
+ * is the target (state columns 0.. and 6..); otherwise the id of a clone of lvk_ekf_get_clones - an id that is not in the window is
+ * LVK_ERR_ARG and the handle stays usable.  The jobs are built from the host state exactly as lvk_ekf_get_feature_cov builds them,
+ * plus the target's pose and the anchor clone's position; one launch on the context's stream behind whatever the last update left
+ * queued, and the call waits for it.  Any output pointer except n_out may be null.  A feature whose anchor clone is not in the window
+ * gets NaNs in position and Sigma.  A failed handle answers as lvk_ekf_get_cov does.  Under the sharded update (lvk_ekf_set_shard)
+ * the call runs on the rank's own replica of the covariance.  A getter only: no switch, no state, nothing added to lvk_ekf_process*. */
+lvk_status lvk_ekf_get_feature_rel(lvk_ekf* e, int64_t to_clone_id, int64_t* h_ids, int64_t* h_anchor_ids, double* h_pos_c, double* h_cov9, int cap, int* n_out);
 /* The MSCKF points: every lost-feature update triangulates the features that never enter the state (hundreds to thousands per message),
  * uses them once and forgets them.  lvk_ekf_set_msckf_points (off by default) keeps them, each with the covariance of
  * lvk_ekf_msckf_point_cov (conventions there): while on, the lost-feature update queues that kernel for its MSCKF jobs ahead of its

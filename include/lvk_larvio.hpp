@@ -193,6 +193,18 @@ public:
         ids.resize((size_t)n); anchor_ids.resize((size_t)n); xyz.resize((size_t)3 * n); cov.resize((size_t)9 * n);
         return ok;
     }
+    // The same map points in the camera frame of a pose of the window (lvk_ekf_get_feature_rel; conventions in lvk_c.h): xyz_c holds
+    // 3 doubles per point, cov 9 (row-major; cov[9 k + 8] is the depth variance), NaN where the anchor clone has left the window.
+    // to_clone_id -1: the current IMU state; otherwise a clone id of getSwPoses' window - false when it is not there.
+    bool getFeaturesInCamera(std::vector<int64_t>& ids, std::vector<int64_t>& anchor_ids, std::vector<double>& xyz_c, std::vector<double>& cov, int64_t to_clone_id = -1) const
+    {
+        ids.resize(4096); anchor_ids.resize(4096); xyz_c.resize(3 * 4096); cov.resize(9 * 4096);
+        int n = 0;
+        const bool ok = ekf_ && lvk_ekf_get_feature_rel(ekf_, to_clone_id, ids.data(), anchor_ids.data(), xyz_c.data(), cov.data(), 4096, &n) == LVK_OK;
+        if (!ok) n = 0;
+        ids.resize((size_t)n); anchor_ids.resize((size_t)n); xyz_c.resize((size_t)3 * n); cov.resize((size_t)9 * n);
+        return ok;
+    }
     bool setLostFeatureCov(bool on) { return ekf_ && lvk_ekf_set_lost_feature_cov(ekf_, on ? 1 : 0) == LVK_OK; }
     void takeLostFeaturesCov(std::vector<int64_t>& ids, std::vector<double>& xyz, std::vector<double>& cov)
     {

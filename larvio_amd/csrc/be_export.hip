@@ -1,6 +1,6 @@
 // be_export.hip — what the filter hands out beside its state (host code only, no kernel): the drain lists of lost in-state features,
 // used MSCKF points and pruned clones (lvk_ekf_set_lost_feature_cov / _msckf_points / _keyframe_export), each queued on the covariance
-// before the columns it needs leave it and attached behind a stream sync, and the two covariance getters that build the same jobs.
+// before the columns it needs leave it and attached behind a stream sync, and the covariance getters that build the same jobs.
 #include "be_filter.h"
 #include "be_host_math.h"
 
@@ -262,6 +262,52 @@ lvk_status lvk_ekf_get_feature_cov(lvk_ekf* e, int64_t* ids, int64_t* anchor_ids
     lvk_status st = lvk_ekf_landmark_cov(e->ctx, e->dP[e->cur], e->ld, e->N, jobs.data(), (int)jobs.size(), out.data());
     if (st != LVK_OK) return st;
     for (int i = 0; i < n; ++i) if (slot[(size_t)i] >= 0) memcpy(cov9 + 9 * i, &out[9 * (size_t)slot[(size_t)i]], 72);
+    return LVK_OK;
+}
+lvk_status lvk_ekf_get_feature_rel(lvk_ekf* e, int64_t to_clone_id, int64_t* ids, int64_t* anchor_ids, double* pos_c, double* cov9, int cap, int* n_out)
+{
+    if (!e || !n_out || cap < 0) return lvk_set_error(e ? e->ctx : nullptr, LVK_ERR_ARG, "lvk_ekf_get_feature_rel: bad argument");
+    ekf_quiesce(e);
+    if (e->failed != LVK_OK) return e->failed;
+    // the target: the IMU state (columns 0.. and 6..) or a clone of the window
+    int bt = 0, bp = 6; const double* q_b = e->s.q; const double* p_b = e->s.p;
+    if (to_clone_id != -1) {
+        const int br = clone_rank(e, to_clone_id);
+        if (br < 0) return lvk_set_error(e->ctx, LVK_ERR_ARG, "lvk_ekf_get_feature_rel: clone %lld is not in the window", (long long)to_clone_id);
+        bt = LEG + 6 * br; bp = bt + 3; q_b = e->clones[(size_t)br].q; p_b = e->clones[(size_t)br].p;
+    }
+    const int n = std::min((int)e->feature_states.size(), cap);
+    std::vector<lvk_landmark_rel_job> jobs; std::vector<int> slot((size_t)n, -1);
+    jobs.reserve((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const Feature& f = e->map.at(e->feature_states[i]);
+        if (ids) ids[i] = f.id;
+        if (anchor_ids) anchor_ids[i] = f.id_anchor;
+        lvk_landmark_job lj;
+        if ((!pos_c && !cov9) || !landmark_job(e, f, i, &lj)) continue;
+        lvk_landmark_rel_job j; memset(&j, 0, sizeof j);
+        static_assert(offsetof(lvk_landmark_rel_job, b_theta_col) == sizeof(lvk_landmark_job) && offsetof(lvk_landmark_rel_job, inv_depth) == offsetof(lvk_landmark_job, inv_depth),
+                      "lvk_landmark_rel_job starts with the fields of lvk_landmark_job");
+        memcpy(&j, &lj, sizeof lj);
+        j.b_theta_col = bt; j.b_p_col = bp; memcpy(j.q_b, q_b, 32); memcpy(j.p_b, p_b, 24);
+        memcpy(j.p_anchor, e->clones[(size_t)clone_rank(e, f.id_anchor)].p, 24);
+        if (!lvk_landmark_rel_job_ok(&j, e->N)) continue;
+        slot[(size_t)i] = (int)jobs.size(); jobs.push_back(j);
+    }
+    *n_out = n;
+    if (!pos_c && !cov9) return LVK_OK;
+    if (pos_c) for (int i = 0; i < 3 * n; ++i) pos_c[i] = NAN;
+    if (cov9) for (int i = 0; i < 9 * n; ++i) cov9[i] = NAN;
+    if (jobs.empty()) return LVK_OK;
+    std::vector<double> out(12 * jobs.size());
+    lvk_status st = lvk_ekf_landmark_rel_cov(e->ctx, e->dP[e->cur], e->ld, e->N, jobs.data(), (int)jobs.size(), out.data());
+    if (st != LVK_OK) return st;
+    for (int i = 0; i < n; ++i) {
+        if (slot[(size_t)i] < 0) continue;
+        const double* o = &out[12 * (size_t)slot[(size_t)i]];
+        if (pos_c) memcpy(pos_c + 3 * i, o, 24);
+        if (cov9) memcpy(cov9 + 9 * i, o + 3, 72);
+    }
     return LVK_OK;
 }
 

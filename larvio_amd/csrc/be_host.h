@@ -74,6 +74,9 @@ void lvk_cov_symmetrize(lvk_context* ctx, double* P, int ld, int n);
 // be_landmark.hip
 bool lvk_landmark_job_ok(const lvk_landmark_job* j, int n);
 lvk_status lvk_launch_landmark_cov(lvk_context* ctx, const double* d_P, int ldp, const lvk_landmark_job* d_jobs, int n_jobs, double* d_cov9);
+// be_landmark_rel.hip
+bool lvk_landmark_rel_job_ok(const lvk_landmark_rel_job* j, int n);
+lvk_status lvk_launch_landmark_rel_cov(lvk_context* ctx, const double* d_P, int ldp, const lvk_landmark_rel_job* d_jobs, int n_jobs, double* d_out12);
 // be_pose_rel.hip
 bool lvk_pose_rel_job_ok(const lvk_pose_rel_job* j, int n);
 lvk_status lvk_launch_pose_rel_cov(lvk_context* ctx, const double* d_P, int ldp, const lvk_pose_rel_job* d_jobs, int n_jobs, double* d_cov36);

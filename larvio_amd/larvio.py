@@ -70,6 +70,7 @@ def _L():
         L.lvk_ekf_take_off_stamp.argtypes = [vp]; L.lvk_ekf_take_off_stamp.restype = C.c_double
         L.lvk_ekf_take_lost_features.argtypes = [vp, vp, vp, i]; L.lvk_ekf_take_lost_features.restype = i
         L.lvk_ekf_get_feature_cov.argtypes = [vp, vp, vp, vp, vp, i, pi]; L.lvk_ekf_get_feature_cov.restype = i
+        L.lvk_ekf_get_feature_rel.argtypes = [vp, C.c_int64, vp, vp, vp, vp, i, pi]; L.lvk_ekf_get_feature_rel.restype = i
         L.lvk_ekf_set_lost_feature_cov.argtypes = [vp, i]; L.lvk_ekf_set_lost_feature_cov.restype = i
         L.lvk_ekf_take_lost_features_cov.argtypes = [vp, vp, vp, vp, i]; L.lvk_ekf_take_lost_features_cov.restype = i
         L.lvk_ekf_set_msckf_points.argtypes = [vp, i]; L.lvk_ekf_set_msckf_points.restype = i
@@ -498,6 +499,17 @@ class LarVio:
         cap = 4096
         ids = np.zeros(cap, np.int64); anc = np.zeros(cap, np.int64); pos = np.zeros((cap, 3)); cov = np.zeros((cap, 3, 3)); n = C.c_int(0)
         self.ctx.check(_L().lvk_ekf_get_feature_cov(self._h, _p(ids), _p(anc), _p(pos), _p(cov), cap, C.byref(n)))
+        n = n.value
+        return ids[:n].copy(), anc[:n].copy(), pos[:n].copy(), cov[:n].copy()
+
+    def get_features_in_camera(self, to_clone_id=-1):
+        """lvk_ekf_get_feature_rel: (ids, anchor clone ids, positions (n, 3) in the camera frame of the target pose, Sigma (n, 3, 3)
+        there) of the in-state features, in the order of features().  to_clone_id -1: the current IMU state; otherwise the id of a clone
+        of clones() (an id outside the window raises LvkError, the filter stays usable).  Position and Sigma are all NaN for a feature
+        whose anchor clone has left the window.  The depth sigma of point k is sqrt(Sigma[k, 2, 2])."""
+        cap = 4096
+        ids = np.zeros(cap, np.int64); anc = np.zeros(cap, np.int64); pos = np.zeros((cap, 3)); cov = np.zeros((cap, 3, 3)); n = C.c_int(0)
+        self.ctx.check(_L().lvk_ekf_get_feature_rel(self._h, int(to_clone_id), _p(ids), _p(anc), _p(pos), _p(cov), cap, C.byref(n)))
         n = n.value
         return ids[:n].copy(), anc[:n].copy(), pos[:n].copy(), cov[:n].copy()
 

@@ -231,6 +231,24 @@ def pose_rel_cov(ctx, P, jobs, n=None):
     return out
 
 
+LANDMARK_REL_JOB = np.dtype(LANDMARK_JOB.descr + [("b_theta_col", np.int32), ("b_p_col", np.int32), ("q_b", np.float64, 4), ("p_b", np.float64, 3),
+                                                 ("p_anchor", np.float64, 3)])
+
+
+def landmark_rel_cov(ctx, P, jobs, n=None):
+    """lvk_ekf_landmark_rel_cov: every LANDMARK_REL_JOB record's point in the camera frame of the job's target pose and its 3 x 3
+    covariance there, read off the covariance P.  P: a whole row-major buffer (its row length is the leading dimension, contents go to
+    the device as they are) whose leading n x n block (default: all rows) is the covariance.  -> (p_c (n_jobs, 3), Sigma (n_jobs, 3, 3))"""
+    P = np.ascontiguousarray(P, np.float64); jobs = np.ascontiguousarray(jobs, LANDMARK_REL_JOB)
+    n = P.shape[0] if n is None else int(n)
+    out = np.full((len(jobs), 12), np.nan)
+    L = lib()
+    L.lvk_ekf_landmark_rel_cov.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]; L.lvk_ekf_landmark_rel_cov.restype = C.c_int
+    dP = ctx.to_device(P)
+    ctx.check(L.lvk_ekf_landmark_rel_cov(ctx.h, _p(dP), P.shape[1], n, _p(jobs), len(jobs), _p(out)))
+    return np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3:]).reshape(-1, 3, 3)
+
+
 MSCKF_POINT_JOB = np.dtype([("n_obs", np.int32), ("obs_off", np.int32), ("p_w", np.float64, 3)])
 
 
