@@ -1,6 +1,8 @@
-// be_filter.h — the filter object as its own translation units see it (backend.hip, be_export.hip, be_pipe.hip): the host records,
-// struct lvk_ekf with its deferred-update worker, the row-job record, and the few inline helpers that more than one of those files
-// needs.  Nothing here is visible outside liblvk_hip.so; what the files call in one another is declared in be_host.h.
+// be_filter.h — the filter object as its own translation units see it (backend.hip and the stages it runs: be_propagate.hip,
+// be_triangulate.hip, be_update.hip, be_prune.hip, be_initialize.hip; be_export.hip, be_pipe.hip): the host records, struct lvk_ekf
+// with its deferred-update worker, the records the stages pass one another (row jobs, triangulation requests), the phase tracer, and
+// the few inline helpers that more than one of those files needs.  Nothing here is visible outside liblvk_hip.so; what the files
+// call in one another is declared in be_host.h.
 #pragma once
 #include "lvk_internal.h"
 #include "be_dev.h"
@@ -16,6 +18,7 @@
 #include <thread>
 #include <mutex>
 #include <condition_variable>
+#include <chrono>
 namespace lvk_init { struct DynInit; }
 
 #define LEG (e->leg)           // LEG_DIM: 22, or 46 with online IMU-intrinsics calibration (larvio.cpp:158-161)
@@ -267,7 +270,7 @@ struct lvk_ekf {
     // hand the next frame's front-end the right buffer view while this update is still running
     void (*on_consumed)(void*, int) = nullptr; void* on_consumed_user = nullptr;
     // one update with the sticky failure state kept (backend.hip's ekf_process_guarded, set by lvk_ekf_create; fetch, when given, delivers
-    // the message once the IMU batch is counted).  be_pipe.hip calls it through the handle: no object needs a symbol of backend.o
+    // the message once the IMU batch is counted).  be_pipe.hip calls it through the handle: no object calls a function of backend.o
     lvk_status (*process)(lvk_ekf* e, double ts, const lvk_feature_obs* feats, int n_feats, const lvk_imu* imu, int n_imu, int* n_consumed, int* updated, lvk_feats_fn fetch, void* fetch_user) = nullptr;
     // optional HIP-event bracket around the H P GEMM of every update (bench: MFMA utilisation of the P H^T contraction)
     bool prof_on = false; double prof_ms = 0, prof_flops = 0; long prof_n = 0;
@@ -380,3 +383,132 @@ template <typename T> static inline void drain_append(std::vector<T>& list, cons
 // caller's batch) whose result the row kernel consumes on the device (FJ_TRI_PENDING) and the host reads after the update
 struct RowJob { Feature* f; int type; std::vector<long long> sids; bool want_gate; int dof; FeatJob dev; FeatResult res; FeatJob* hdev = nullptr; int tri = -1; };
 struct RowObs { const int* rank = nullptr; const double *z = nullptr, *zv = nullptr; };      // where a batch's observations lie on the device (FeatJob::obs_off indexes them)
+
+// ------------------------------------------------------------------------- host-side phase tracer (LVK_EKF_TRACE=1)
+// one instance for all the filter's files (backend.hip defines it, with the names its report prints)
+enum { TR_IMU, TR_PROP, TR_FETCH, TR_ADDOBS, TR_ZUPT, TR_RLF_PRE, TR_RLF_TRI, TR_RLF_TRIAGE, TR_RLF_ROWS, TR_RLF_UPD, TR_RLF_DX, TR_RLF_INJ,
+       TR_PR_PRE, TR_PR_TRI, TR_PR_ROWS, TR_PR_UPD, TR_PR_DX, TR_PR_END, TR_FINAL, TR_N };
+struct EkfTrace {
+    bool on = false; double acc[TR_N] = {0}; long n = 0;
+    double sub_acc[8] = {0}; std::chrono::steady_clock::time_point last_sub; long cnt[4] = {0, 0, 0, 0};      // cnt: updates above 160 rows / plans drawn up / compressions taken / rows of those updates      // finer marks inside one phase (TRS): time since the previous mark of either kind
+    double cur[TR_N] = {0};                              // this update's phases: an update above LVK_EKF_TRACE_SLOW_US is printed on its own
+    std::chrono::steady_clock::time_point last;
+    void start() { if (on) { last = last_sub = std::chrono::steady_clock::now(); for (int i = 0; i < TR_N; ++i) cur[i] = 0; } }
+    void mark(int slot) { if (!on) return; auto t = std::chrono::steady_clock::now(); const double d = std::chrono::duration<double, std::micro>(t - last).count(); acc[slot] += d; cur[slot] += d; last = t; last_sub = t; }
+    void sub(int k) { if (!on) return; auto t = std::chrono::steady_clock::now(); sub_acc[k] += std::chrono::duration<double, std::micro>(t - last_sub).count(); last_sub = t; }
+    void end_update(const char* const* names)
+    {
+        static const double slow = [] { const char* v = getenv("LVK_EKF_TRACE_SLOW_US"); return v ? atof(v) : 0.0; }();
+        if (!on || slow <= 0) return;
+        double tot = 0; for (int i = 0; i < TR_N; ++i) tot += cur[i];
+        if (tot < slow) return;
+        fprintf(stderr, "[lvk_ekf trace] slow update %ld: %.0f us:", n, tot);
+        for (int i = 0; i < TR_N; ++i) if (cur[i] > 0.02 * tot) fprintf(stderr, " %s %.0f;", names[i], cur[i]);
+        fprintf(stderr, "\n");
+    }
+};
+extern EkfTrace g_tr;
+#define TR(slot) g_tr.mark(slot)
+#define TRS(k) g_tr.sub(k)
+
+// ------------------------------------------------------------------------- helpers of more than one stage
+static void update_imu_mx(lvk_ekf* e)
+{   // larvio.cpp:3803-3846
+    const double *T1 = e->imx, *T2 = e->imx + 3, *T3 = e->imx + 6, *A1 = e->imx + 9, *A2 = e->imx + 12, *A3 = e->imx + 15, *M1 = e->imx + 18, *M2 = e->imx + 21;
+    double* Tg = e->Tg; double* As = e->As; double* Ma = e->Ma;
+    Tg[0] = T2[0]; Tg[1] = T3[0]; Tg[2] = T3[1]; Tg[3] = T1[0]; Tg[4] = T2[1]; Tg[5] = T3[2]; Tg[6] = T1[1]; Tg[7] = T1[2]; Tg[8] = T2[2];
+    As[0] = A2[0]; As[1] = A3[0]; As[2] = A3[1]; As[3] = A1[0]; As[4] = A2[1]; As[5] = A3[2]; As[6] = A1[1]; As[7] = A1[2]; As[8] = A2[2];
+    Ma[0] = M2[0]; Ma[1] = 0; Ma[2] = 0; Ma[3] = M1[0]; Ma[4] = M2[1]; Ma[5] = 0; Ma[6] = M1[1]; Ma[7] = M1[2]; Ma[8] = M2[2];
+}
+// P <- P[idx, idx] (ping-pong)
+static lvk_status cov_gather(lvk_ekf* e, const std::vector<int>& idx)
+{
+    int* h = up_alloc<int>(e, idx.size());
+    if (!h) return lvk_set_error(e->ctx, LVK_ERR_CAPACITY, "upload arena exhausted");
+    memcpy(h, idx.data(), sizeof(int) * idx.size());
+    double* src = e->dP[e->cur]; double* dst = e->dP[e->cur ^ 1];
+    const int* d_idx = dev(e, h); const int n = (int)idx.size();
+    lvk_status st = run_or_defer(e, [=]() { return lvk_cov_gather(e->ctx, src, e->ld, dst, e->ld, d_idx, n); });
+    if (st != LVK_OK) return st;
+    e->cur ^= 1; e->N = n;
+    return LVK_OK;
+}
+// P loses the rows / columns marked in drop (N flags)
+static lvk_status cov_drop(lvk_ekf* e, const std::vector<char>& drop)
+{
+    std::vector<int> idx; idx.reserve(e->N);
+    for (int i = 0; i < e->N; ++i) if (!drop[i]) idx.push_back(i);
+    return cov_gather(e, idx);
+}
+
+// ------------------------------------------------------------------------- device job batches: the records and small helpers the stages share
+// one triangulation request: its views live in the filter's request pools (tri_ranks / tri_z) at [off, off + n) - no per-request
+// vectors (at configs[4] an update issues hundreds of requests)
+struct TriReq { Feature* f; int mode; int off, n; long long last_id; bool use_pos; int slot = -1; };   // slot >= 0: the row job that takes the result on the device (lvk_ekf_launch_triangulation)
+struct TriAns { bool ok; double position[3], inv_depth, obs_anchor[3]; long long id_anchor; };
+static void apply_tri(Feature* f, int mode, const TriAns& a)
+{   // feature.hpp:537-546 incl. the FEJ quirk (position_FEJ takes the OLD position of a first-time feature)
+    if (!a.ok) return;
+    if (!f->is_initialized) memcpy(f->position_fej, f->position, 24);
+    f->is_initialized = true;
+    memcpy(f->position, a.position, 24);
+    f->id_anchor = a.id_anchor;
+    f->inv_depth = a.inv_depth; memcpy(f->obs_anchor, a.obs_anchor, 24);
+    if (mode == 2) f->ekf_feature = true;
+}
+static TriAns tri_answer(const lvk_ekf* e, const TriReq& rq, size_t slot)
+{   // after a stream sync that covers the batch: d_triout IS the mapped view of h_down
+    const TriResult& o = ((const TriResult*)e->h_down)[slot];
+    TriAns a; a.ok = o.ok != 0; memcpy(a.position, o.position, 24); a.inv_depth = o.inv_depth; memcpy(a.obs_anchor, o.obs_anchor, 24); a.id_anchor = rq.last_id;
+    return a;
+}
+// One feature-rows job (rows on the device) ------------------------------------------------------------
+// the job of an MSCKF feature over the given observations, or over all it has
+static RowJob msckf_job(Feature* f, std::vector<long long> sids, int tri = -1)
+{
+    RowJob r; r.f = f; r.type = JOB_MSCKF; r.want_gate = true; r.dof = 2 * (int)sids.size() - 3; r.tri = tri; r.sids = std::move(sids);
+    return r;
+}
+static RowJob msckf_job(Feature* f, int tri = -1)
+{
+    std::vector<long long> sids; sids.reserve(f->obs.size()); for (const Obs& o : f->obs) sids.push_back(o.sid);
+    return msckf_job(f, std::move(sids), tri);
+}
+// row layout of a job, known before it runs: MSCKF blocks lose the 3 rows of the null-space projection, a new in-state
+// feature's block keeps its range row first, a tracked in-state feature contributes its 2 rows as they are
+static int job_first_row(const RowJob& j) { return fj_first_row(j.type); }
+static int job_rows(const RowJob& j) { return fj_rows(j.type, (int)j.sids.size()); }
+static bool gate_ok(lvk_ekf* e, const RowJob& j)
+{
+    const bool ok = j.res.gamma < lvk_chi2_005(j.dof);
+    e->counters[ok ? 4 : 5]++;
+    return ok;
+}
+static void drop_observations(lvk_ekf* e, const long long* sids, int n) { for (auto kv : e->map) for (int k = 0; k < n; ++k) kv.second.erase(sids[k]); }
+// ... and its effect on the host state, when any row passed its gate; counter: 0 feature update, 1 pruning update
+static void gated_update_apply(lvk_ekf* e, const std::vector<double>& dx, int accepted, int counter)
+{
+    if (accepted <= 0) return;
+    lvk_ekf_inject(e, dx.data());
+    e->last_update_time = e->s.t;
+    e->counters[counter]++;
+    e->counters[2] = accepted;
+}
+// What a gated update leaves to the host, after its sync.  The MSCKF jobs [order[0]) in ascending order: a job whose triangulation
+// was consumed on the device (RowJob::tri) has its answer read and applied in `mode`, and one whose triangulation failed is not used
+// (its rows were zeroed on the device); the others pass through gate_ok and are recorded as MSCKF points.  retire(job, tri_ok) is
+// the caller's bookkeeping for each of them.  Then the tracked in-state jobs [order[1]), two rows each.  Returns the accepted rows.
+template <class Retire>
+static int settle_update(lvk_ekf* e, const std::vector<RowJob>& jobs, const size_t (&order)[2][2], const std::vector<TriReq>& reqs, int mode, Retire retire)
+{
+    int accepted = 0;
+    for (size_t k = order[0][0]; k < order[0][1]; ++k) {
+        const RowJob& j = jobs[k];
+        bool tri_ok = true;
+        if (j.tri >= 0) { const TriAns a = tri_answer(e, reqs[(size_t)j.tri], k); apply_tri(j.f, mode, a); tri_ok = a.ok; }
+        if (tri_ok && gate_ok(e, j)) { accepted += job_rows(j); lvk_ekf_msckf_point_record(e, j, k); }
+        retire(j, tri_ok);
+    }
+    for (size_t k = order[1][0]; k < order[1][1]; ++k) if (gate_ok(e, jobs[k])) accepted += 2;
+    return accepted;
+}

@@ -2,7 +2,9 @@
 // prototype of every lvk_* function that one be_*.hip / backend.hip defines and another calls.  Definers include it as well, so
 // the compiler checks each definition against the prototype its callers see.  (The structure-aware compression has be_qr.h; the
 // filter object itself, which backend.hip shares with the exports of be_export.hip and the pipelined driver of be_pipe.hip, has
-// be_filter.h; no other object calls into backend.o - the pipelined driver reaches the update through lvk_ekf::process.)
+// be_filter.h.  backend.hip runs one message through the stages declared at the end of this file and defines the one phase tracer
+// they all mark (g_tr, be_filter.h); no function of backend.o is called from another object - the pipelined driver reaches the
+// update through lvk_ekf::process.)
 #pragma once
 #include "lvk_internal.h"
 #include "be_dev.h"
@@ -104,3 +106,29 @@ lvk_status lvk_ekf_keyframes_queue(lvk_ekf* e, const long long* rm, int nrm);
 lvk_status lvk_ekf_exports_attach(lvk_ekf* e);
 lvk_status lvk_ekf_msckf_points_queue(lvk_ekf* e, const std::vector<RowJob>& jobs, size_t lo, size_t hi, const RowObs& obs);
 void lvk_ekf_msckf_point_record(lvk_ekf* e, const RowJob& j, size_t k);
+// The stages of one message (backend.hip's ekf_process_impl runs them; be_filter.h has their records)
+// be_initialize.hip
+bool lvk_ekf_static_try_init(lvk_ekf* e, double ts, const lvk_feature_obs* f, int n, const lvk_imu* imu, int n_imu, int* n_erased);
+bool lvk_ekf_dynamic_try_init(lvk_ekf* e, double ts, const lvk_feature_obs* f, int n, const lvk_imu* imu, int n_imu, int* n_erased);
+// be_propagate.hip
+int lvk_ekf_batch_imu(lvk_ekf* e, double time_bound, const lvk_imu* imu, int n_imu);
+lvk_status lvk_ekf_state_augmentation(lvk_ekf* e);
+void lvk_ekf_add_observations(lvk_ekf* e, const lvk_feature_obs* f, int n);
+void lvk_ekf_inject(lvk_ekf* e, const double* dx);
+// be_triangulate.hip
+struct Feature; struct TriReq; struct TriAns;
+lvk_status lvk_ekf_upload_clones(lvk_ekf* e);
+void lvk_ekf_make_tri_req(lvk_ekf* e, Feature* f, int mode, TriReq* rq);
+lvk_status lvk_ekf_launch_triangulation(lvk_ekf* e, std::vector<TriReq>& reqs);
+lvk_status lvk_ekf_run_triangulation(lvk_ekf* e, std::vector<TriReq>& reqs, std::vector<TriAns>& ans);
+bool lvk_ekf_check_motion(const lvk_ekf* e, const Feature& f, bool if_tracked);
+// be_update.hip
+struct RowGroup;
+lvk_status lvk_ekf_d2h_sync(lvk_ekf* e, void* dst, const void* src, size_t bytes);
+lvk_status lvk_ekf_dense_update(lvk_ekf* e, int m, std::vector<double>& dx, int extra, const std::vector<RowGroup>* groups = nullptr);
+lvk_status lvk_ekf_gated_update(lvk_ekf* e, std::vector<RowJob>& jobs, const size_t (&order)[2][2], const int (&tr)[3], std::vector<double>& dx,
+                                const long long* retire = nullptr, int n_retire = 0, size_t mp_lo = 0, size_t mp_hi = 0);
+lvk_status lvk_ekf_remove_lost_features(lvk_ekf* e);
+// be_prune.hip
+lvk_status lvk_ekf_check_zupt(lvk_ekf* e, bool* out);
+lvk_status lvk_ekf_prune_imu_state_buffer(lvk_ekf* e);

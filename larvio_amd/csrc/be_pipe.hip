@@ -334,4 +334,27 @@ lvk_status lvk_vio_pipe_drain(lvk_vio_pipe* p, long* n_updates, long* n_msgs)
     return p->st;
 }
 
+// one frame through both halves: the front-end waits for its feature message, `process` (lvk_ekf_process, or lvk_ekf_process_async: what
+// the adapter classes do under the reference's blocking drivers, processImage returning the message to the caller) takes it
+static lvk_status vio_step(lvk_frontend* fe, lvk_ekf* ekf, const lvk_image* img, double ts, const lvk_imu* h_imu, int n_imu, int* n_consumed, int* has_msg, int* updated,
+                           lvk_status (*process)(lvk_ekf*, double, const lvk_feature_obs*, int, const lvk_imu*, int, int*, int*))
+{
+    if (!fe || !ekf || !n_consumed || !has_msg || !updated) return LVK_ERR_ARG;
+    *n_consumed = 0; *updated = 0; *has_msg = 0;
+    static thread_local std::vector<lvk_feature_obs> msg;
+    if (msg.size() < 8192) msg.resize(8192);
+    int n_out = 0;
+    lvk_status st = lvk_frontend_process(fe, img, ts, h_imu, n_imu, msg.data(), (int)msg.size(), &n_out, has_msg);
+    if (st != LVK_OK || !*has_msg) return st;
+    return process(ekf, ts, msg.data(), n_out, h_imu, n_imu, n_consumed, updated);
+}
+lvk_status lvk_vio_process(lvk_frontend* fe, lvk_ekf* ekf, const lvk_image* img, double ts, const lvk_imu* h_imu, int n_imu, int* n_consumed, int* has_msg, int* updated)
+{
+    return vio_step(fe, ekf, img, ts, h_imu, n_imu, n_consumed, has_msg, updated, lvk_ekf_process);
+}
+lvk_status lvk_vio_process_deferred(lvk_frontend* fe, lvk_ekf* ekf, const lvk_image* img, double ts, const lvk_imu* h_imu, int n_imu, int* n_consumed, int* has_msg, int* will_update)
+{
+    return vio_step(fe, ekf, img, ts, h_imu, n_imu, n_consumed, has_msg, will_update, lvk_ekf_process_async);
+}
+
 }  // extern "C"

@@ -170,6 +170,9 @@ lvk_status lvk_set_error(lvk_context* ctx, lvk_status code, const char* fmt, ...
 
 #define LVK_LAUNCH_CHECK(ctx) LVK_HIP(ctx, hipGetLastError())
 
+// n elements of device memory (never an empty allocation)
+template <typename T> static bool dalloc(T** p, size_t n) { return hipMalloc((void**)p, sizeof(T) * (n ? n : 1)) == hipSuccess; }
+
 // ---- compile-time instrumentation (make CXXFLAGS+=-DLVK_BE_TIMING; tools/gpu/be_ticks.py): thread 0 of ONE chosen workgroup of a kernel
 // stores the 100 MHz wall clock at its phase boundaries into a per-file device array; off, the macros vanish
 #ifdef LVK_BE_TIMING

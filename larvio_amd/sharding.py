@@ -9,7 +9,7 @@ once; latency-bound), and every rank QR-reduces the rank-ordered stack [R_0; ...
 identical update on its replica of P.  Rank order fixes the reduction order, so replicas stay bit-identical.
 At the north-star size (150 tracks) this does not pay: bench.py runs replicas instead.
 
-The PRODUCT path is inside liblvk_hip.so (lvk_ekf_set_shard, backend.hip shard_stage1, be_shard.hip): per-rank feature rows ->
+The PRODUCT path is inside liblvk_hip.so (lvk_ekf_set_shard, be_update.hip shard_stage1, be_shard.hip): per-rank feature rows ->
 structure-aware TSQR -> pack kernel -> ncclAllGather on the filter's stream, device buffers in place -> unpack kernel -> replicated
 second stage and update.  What crosses the wire is the rank's compressed block as rows (k_g x (N + 1) doubles, k_g ~ 50..200 at
 configs[4]) plus the gate results of its features - smaller than the n x n triangle above, which the early-design helpers at the

@@ -1,7 +1,7 @@
 // Host-only check of backend.hip's per-feature observation list (std::map<StateIDType, ...> in the reference, a sorted vector with
 // newest-first / bisection lookups here) and of add_observations' cursor walk over the feature map: random operation sequences against
 // plain std::map models.  Prints "ok" or "MISMATCH ...".
-#include "../../larvio_amd/csrc/backend.hip"
+#include "../../larvio_amd/csrc/be_propagate.hip"
 #include <random>
 
 static int check_feature_obs()
@@ -41,7 +41,7 @@ static int check_add_observations()
         std::vector<long long> order = live; if (msg % 17 == 5) std::shuffle(order.begin(), order.end(), rng);
         std::vector<lvk_feature_obs> feats(order.size());
         for (size_t i = 0; i < order.size(); ++i) { memset(&feats[i], 0, sizeof feats[i]); feats[i].id = (uint64_t)order[i]; feats[i].u = (double)order[i]; feats[i].v = msg; feats[i].u_init = -1; feats[i].v_init = -1; }
-        add_observations(e, feats.data(), (int)feats.size());
+        lvk_ekf_add_observations(e, feats.data(), (int)feats.size());
         for (long long id : order) model[id] += 1;
         if (msg % 5 == 4 && !e->map.empty()) {            // erase a few features, as the filter does after using them
             for (int k = 0; k < 3 && !e->map.empty(); ++k) { auto it = e->map.begin(); std::advance(it, (long)(rng() % e->map.size())); const long long id = it->first; e->map.erase(it); model.erase(id);

@@ -2,7 +2,7 @@
 // compose_transition<L> (structure-aware, vectorisable loop nests) must equal the plain dense recurrences
 //     Phi_tot <- Phi Phi_tot ;  Q_tot <- Phi Q_tot Phi^T + (Phi G) Qc (Phi G)^T dt
 // bit for bit (larvio.cpp:520-578 does them densely).  Prints "ok <checksum>" or "MISMATCH ...".
-#include "../../larvio_amd/csrc/backend.hip"
+#include "../../larvio_amd/csrc/be_propagate.hip"
 
 template <int L> static void dense_step(const lvk_ekf* e, const double* Phi, double dt, const double* C, double* Pt, double* Qt, bool first)
 {

@@ -1,8 +1,9 @@
 """Host arithmetic of the product that runs on the CPU by design (larvio.cpp:520-578: the IMU samples of a frame are integrated on
 the host and composed into one (Phi, Q) pair that a single kernel applies).  The product's composition skips structurally-zero
-blocks and nests its loops for vectorisation; tests/host/imu_compose_check.hip recompiles backend.hip's host code (no GPU is touched)
+blocks and nests its loops for vectorisation; tests/host/imu_compose_check.hip recompiles be_propagate.hip's host code (no GPU is touched)
 and requires it to equal the dense recurrences bit for bit, with and without IMU-intrinsics calibration (L = 22 / 46)."""
 import os
+import re
 import shutil
 import subprocess
 
@@ -12,14 +13,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _run_host_check(tmp_path, name):
-    """compile tests/host/<name>.hip (it #includes backend.hip: host code only is exercised) against the built objects and run it"""
+    """compile tests/host/<name>.hip (it #includes be_propagate.hip: host code only is exercised) against the built objects and run it"""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     csrc = os.path.join(ROOT, "larvio_amd", "csrc")
     subprocess.check_call(["make", "-C", csrc, "-j8", "-s"])                      # the objects the check links against (no-op when built)
     obj = str(tmp_path / (name + ".o")); exe = str(tmp_path / name)
     flags = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-Xarch_host", "-mavx2", "-w", "-I", csrc]
     subprocess.check_call([hipcc] + flags + ["-c", os.path.join(ROOT, "tests", "host", name + ".hip"), "-o", obj])
-    objs = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith(".o") and f != "backend.o"]
+    own = {m + ".o" for m in re.findall(r'csrc/(\w+)\.hip"', open(os.path.join(ROOT, "tests", "host", name + ".hip")).read())}     # the library source the check includes
+    objs = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith(".o") and f not in own]
     subprocess.check_call([hipcc, "--offload-arch=gfx950", obj] + objs + ["-pthread", "-o", exe])
     return subprocess.run([exe], capture_output=True, text=True, timeout=120)
 
