@@ -1,6 +1,6 @@
 // be_landmark.hip — first-order position covariance of anchored inverse-depth landmarks (lvk_ekf_landmark_cov, include/lvk_c.h).
 // Sigma = J P_s J^T, P_s the 13 x 13 sub-block of the filter's covariance over [extrinsics 15..20 | the anchor clone's six columns |
-// the feature's column], J the 3 x 13 derivative of Feature::position under the filter's own state injection (backend.hip, inject()).
+// the feature's column], J the 3 x 13 derivative of Feature::position under the filter's own state injection (be_propagate.hip, lvk_ekf_inject).
 #include "be_host.h"
 #include <math.h>
 

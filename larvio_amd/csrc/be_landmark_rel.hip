@@ -1,7 +1,7 @@
 // be_landmark_rel.hip — anchored inverse-depth landmarks in the camera frame of a target pose, with their first-order covariance
 // (lvk_ekf_landmark_rel_cov, include/lvk_c.h).  Sigma = J P_s J^T, P_s the 19 x 19 sub-block of the filter's covariance over
 // [extrinsics 15..20 | the anchor clone's six columns | the target's d_theta and d_p columns | the feature's column], J the 3 x 19
-// derivative of p_c = R_b2c (R_b^T (p_w - p_b) - t_c_b) under the filter's own state injection (backend.hip, inject()).
+// derivative of p_c = R_b2c (R_b^T (p_w - p_b) - t_c_b) under the filter's own state injection (be_propagate.hip, lvk_ekf_inject).
 #include "be_host.h"
 #include <math.h>
 

@@ -264,7 +264,7 @@ lvk_status lvk_stage_copy2(lvk_context* ctx, void* d_dst0, const void* d_src0, s
 BE_TICK_DECL(g_la_tick);
 BE_TICK_GETTER(lvk_debug_ticks_linalg, g_la_tick)
 __device__ __forceinline__ int cpg_src(int a, int pose_rows) { return a < pose_rows ? a : a < pose_rows + 6 ? (a - pose_rows < 3 ? a - pose_rows : a - pose_rows + 3) : a - 6; }
-// The composed transition of a frame has structure (backend.hip, compose_transition): rows 9.. of Phi are identity rows and Q is zero
+// The composed transition of a frame has structure (be_propagate.hip, compose_transition): rows 9.. of Phi are identity rows and Q is zero
 // outside its leading 15 x 15 block.  For the 22-dimensional IMU block that is 9 x 22 + 15 x 15 doubles = 3.4 KB: it travels BY VALUE in
 // the kernel arguments (device memory with HIP_FORCE_DEV_KERNARG=1, which the runtime section of INTEGRATION.md prescribes) instead of
 // being fetched from the pinned arena by nine workgroups (6.8 us of the kernel's 16, profiles/r4_d_be_ticks.json).  With IMU-intrinsics

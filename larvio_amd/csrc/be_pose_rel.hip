@@ -1,7 +1,7 @@
 // be_pose_rel.hip — first-order covariance of one pose relative to another, and the absolute 6 x 6 block of one pose
 // (lvk_ekf_pose_rel_cov, include/lvk_c.h).  Sigma_rel = J P_s J^T, P_s the 12 x 12 sub-block of the filter's covariance over
 // [d_theta_a d_p_a d_theta_b d_p_b], J the 6 x 12 derivative of (R_a^T R_b, R_a^T (p_b - p_a)) under the filter's own state injection
-// (backend.hip, inject()).
+// (be_propagate.hip, lvk_ekf_inject).
 #include "be_host.h"
 #include <math.h>
 

@@ -6,30 +6,7 @@
 // the stencils and as few dependent launches as possible (each costs ~1.5-2 us on MI355X).
 #include "lvk_internal.h"
 #include <vector>
-#include <stdarg.h>
 #include <algorithm>
-
-lvk_status lvk_set_error(lvk_context* ctx, lvk_status code, const char* fmt, ...)
-{
-    if (ctx) {
-        va_list ap; va_start(ap, fmt);
-        vsnprintf(ctx->err, sizeof ctx->err, fmt, ap);
-        va_end(ap);
-    }
-    return code;
-}
-
-void* lvk_ctx_scratch(lvk_context* ctx, int slot, size_t bytes)
-{
-    if (slot < 0 || slot >= LVK_SCRATCH_SLOTS) return nullptr;
-    if (ctx->scratch_bytes[slot] >= bytes && ctx->scratch[slot]) return ctx->scratch[slot];
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return nullptr;
-    if (ctx->scratch[slot]) hipFree(ctx->scratch[slot]);
-    ctx->scratch[slot] = nullptr; ctx->scratch_bytes[slot] = 0;
-    if (hipMalloc(&ctx->scratch[slot], bytes) != hipSuccess) return nullptr;
-    ctx->scratch_bytes[slot] = bytes;
-    return ctx->scratch[slot];
-}
 
 // =========================================================================== CLAHE
 // Histogram of one tile in LDS (one sub-histogram per wave), clip + redistribute, inclusive scan -> LUT.  [cv::CLAHE CLAHE_CalcLut_Body]

@@ -91,14 +91,12 @@ lvk_status lvk_lk_track(lvk_context* ctx, const lvk_pyramid* prev, const lvk_pyr
         return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_lk_track: bad argument");
     if (prev->pad != next->pad) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_lk_track: pyramids built with different windows");
     if (n == 0) return LVK_OK;
-    int max_count = max_iter < 0 ? 0 : max_iter > 100 ? 100 : max_iter;
-    double epsilon = eps < 0. ? 0. : eps > 10. ? 10. : eps;
-    epsilon *= epsilon;
+    const LkTerm term = lvk_lk_term(max_iter, eps);
     PyrView a = make_view(prev), b = make_view(next);
     switch (prev->pad) {
-        case 21: launch_lk<21>(ctx, a, b, d_prev_pts, d_next_pts, d_status, n, max_count, epsilon, d_iters); break;
-        case 15: launch_lk<15>(ctx, a, b, d_prev_pts, d_next_pts, d_status, n, max_count, epsilon, d_iters); break;
-        case 31: launch_lk<31>(ctx, a, b, d_prev_pts, d_next_pts, d_status, n, max_count, epsilon, d_iters); break;
+        case 21: launch_lk<21>(ctx, a, b, d_prev_pts, d_next_pts, d_status, n, term.max_count, term.epsilon, d_iters); break;
+        case 15: launch_lk<15>(ctx, a, b, d_prev_pts, d_next_pts, d_status, n, term.max_count, term.epsilon, d_iters); break;
+        case 31: launch_lk<31>(ctx, a, b, d_prev_pts, d_next_pts, d_status, n, term.max_count, term.epsilon, d_iters); break;
         default: return lvk_set_error(ctx, LVK_ERR_UNSUPPORTED, "LK window %d not instantiated (15, 21, 31)", prev->pad);
     }
     LVK_LAUNCH_CHECK(ctx);
@@ -144,9 +142,10 @@ static lvk_status fm_launch(lvk_context* ctx, const lvk_pt2f* p1, const lvk_pt2f
 {
     if (!ctx || n < 0 || (n > 0 && (!p1 || !p2 || !mask))) return lvk_set_error(ctx, LVK_ERR_ARG, "fundamental: bad argument");
     if (n > FM_MAX_N) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "fundamental: n=%d exceeds %d", n, FM_MAX_N);
-    // same split as the frame path (frontend.hip: commit): the wide workgroup for point sets the per-point loops dominate
-    if (n > FM_WIDE_FROM) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fundamental_mask<FM_THREADS_WIDE>), dim3(1), dim3(FM_THREADS_WIDE), 0, ctx->stream, p1, p2, n, thresh, conf, max_iters, force_ransac, mask, info, model);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fundamental_mask<FM_THREADS>), dim3(1), dim3(FM_THREADS), 0, ctx->stream, p1, p2, n, thresh, conf, max_iters, force_ransac, mask, info, model);
+    // same split as the frame path (fe_frame.hip: commit): the wide workgroup for point sets the per-point loops dominate
+#define FM_LAUNCH(NT) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fundamental_mask<NT>), dim3(1), dim3(NT), 0, ctx->stream, p1, p2, n, thresh, conf, max_iters, force_ransac, mask, info, model)
+    if (n > FM_WIDE_FROM) FM_LAUNCH(FM_THREADS_WIDE); else FM_LAUNCH(FM_THREADS);
+#undef FM_LAUNCH
     LVK_LAUNCH_CHECK(ctx);
     return LVK_OK;
 }

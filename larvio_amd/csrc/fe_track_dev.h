@@ -1,5 +1,5 @@
 // fe_track_dev.h — device functions shared by the stage-level kernels (fe_track.hip) and the
-// frame-level kernels (frontend.hip).  wave64 only.
+// frame-level kernels (fe_frame.hip).  wave64 only.
 #pragma once
 #include "lvk_internal.h"
 #include <float.h>
@@ -254,7 +254,7 @@ __device__ __forceinline__ LkLdsAcc lk_acc_init(unsigned long long* lds4)
 
 // ---- debug builds
 #ifdef LVK_LK_TIMING
-static __device__ unsigned long long g_lk_tick[4096][12];    // -DLVK_LK_TIMING=1: the kernel's spans only (LkSpan, frontend.hip); =2: this phase account too
+static __device__ unsigned long long g_lk_tick[4096][12];    // -DLVK_LK_TIMING=1: the kernel's spans only (LkSpan, fe_frame.hip); =2: this phase account too
 #endif
 // per-block phase account of the LK wavefront of k_fe_lk_both (variants/lkt.so, tools/gpu/lk_ticks.py): shader-clock cycles by category
 // 0 level set-up (template blends incl. the wait for the fetched bytes)  1 A sums  2 eigen test / inverse  3 iteration: origin, weights,
@@ -280,7 +280,7 @@ struct LkTicks {
 };
 #endif
 // -DLVK_LK_BOUNDS (debug builds only): every window load of the row-segment kernels is checked against the level's padded plane; the
-// first violation is recorded (frontend.hip prints it when the front-end is destroyed) and the load skipped
+// first violation is recorded (fe_frame.hip prints it when the front-end is destroyed) and the load skipped
 #ifdef LVK_LK_BOUNDS
 static __device__ int g_lk_oob[16];
 __device__ __forceinline__ bool lk_in_bounds(const PyrView& V, int level, int row, int col, int tag, float fx, float fy)
@@ -482,14 +482,13 @@ __device__ __forceinline__ int lk_point_rs21_lds(const PyrView& prev, const PyrV
     return total_it;
 }
 
-// ---- the levels' templates built by OTHER wavefronts of the block (k_fe_lk_pipe, frontend.hip).
+// ---- the levels' templates built by OTHER wavefronts of the block (k_fe_lk_pipe, fe_frame.hip).
 // What a track costs is one wavefront's dependent instruction stream (profiles/r6_e_*: fewer instructions in one phase did not make it
 // shorter), and a third of that stream - per level: six loads, 21 bilinear blends, three exact sums, a square root and two divisions,
 // ~1.7 us - does not depend on what the iterations find: the template of a level is a function of the point in the FIRST image alone.
 // So the wavefront that iterates no longer builds it: three builder wavefronts (levels l, l + 3, ...) do, at once, before the pass
 // starts, and leave per lane the 21 shorts (I, Ix, Iy of its seven pixels) and per level A11, A12, A22, 1 / D and the verdict of the
 // eigenvalue test in LDS.  The same building blocks as above, so the same bits.
-#define LK_PIPE_MAX_LEVELS 4
 struct LkTplLevel {
     unsigned long long px[64][6];       // per lane: Iv[7], Ixv[7], Iyv[7] (21 shorts, 48 bytes)
     float A11, A12, A22, Dinv;
@@ -561,7 +560,7 @@ __device__ __forceinline__ int lk_pass_iterate21(const PyrView& next, int n_leve
 // The LK kernels (A/B records in profiles/; the wave-wide sums by DPP + v_readlane of rounds 3-5, once variant 0, are gone):
 //   lk_point_rs21_lds  one wavefront per pass: k_lk_track<21>, k_fe_lk_both<21> (LVK_LK_VARIANT=1, and 0 selects it too)
 //   lk_tpl_build21 + lk_pass_iterate21  the same arithmetic with the levels' templates built by three more wavefronts of the block:
-//                      k_fe_lk_pipe (frontend.hip; LVK_LK_VARIANT=2)
+//                      k_fe_lk_pipe (fe_frame.hip; LVK_LK_VARIANT=2)
 // (tried and dropped, profiles/r6_e_*: sums by DPP + one FP64 MFMA; touching the next image's lines of all levels at the start of a pass)
 // Which of the two a frame uses when LVK_LK_VARIANT is unset: lvk_lk_variant(), lvk_internal.h.
 // LVK_LK_GENERIC (compile-time): the one-pixel-per-lane-slot path for every window size

@@ -21,7 +21,7 @@
 #define LVK_STORE_FENCE() __atomic_thread_fence(__ATOMIC_SEQ_CST)
 #endif
 
-// May this process push host writes into device memory through the PCIe BAR on `device`?  frontend.hip: LVK_BAR_PUSH=0 says no; a
+// May this process push host writes into device memory through the PCIe BAR on `device`?  lvk_context.hip: LVK_BAR_PUSH=0 says no; a
 // device without a large BAR says no; otherwise a self-test decides, once per device and process - the host writes a pattern into a
 // fine-grained device buffer, a kernel reads it, the host REWRITES the same addresses, a second kernel reads again: a stale second
 // read (L2 lines of the first read surviving the kernel boundary under this driver's MTYPE / partition settings) says no.
@@ -195,6 +195,28 @@ inline int lvk_lk_variant()
 {
     static const int v = [] { const char* e = getenv("LVK_LK_VARIANT"); const int x = e ? atoi(e) : -1; return x < -1 || x > 2 ? -1 : x == 0 ? 1 : x; }();
     return v;
+}
+#define LK_PIPE_MAX_LEVELS 4            // pyramid levels k_fe_lk_pipe keeps templates for in LDS (LkTplLevel, fe_track_dev.h)
+// Which LK kernel the frames of a front-end launch (its patch size, its track slots, the levels of the two pyramids of a frame), and may
+// the frame's two track sets share ONE launch.  pipe: k_fe_lk_pipe<21>, otherwise k_fe_lk_both<patch_size>.  merged is opt-in
+// (LVK_LK_MERGED=1, read once per process): built and measured in round 6 - bit-exact, and SLOWER in the pipelined driver (10,260 against
+// 10,640 frames/s, LK launch 28.2 against 25.9 us: the launch then waits for the previous frame's detection on the side stream, and
+// carries twice the blocks), +0.5 % through the adapter's schedule; profiles/r6_o_lk_merged_launch_ab.json
+struct LkChoice { bool pipe, merged; };
+inline LkChoice lvk_lk_choice(int patch_size, int slots, int levels_prev, int levels_curr)
+{
+    static const bool merged_on = [] { const char* e = getenv("LVK_LK_MERGED"); return e && !strcmp(e, "1"); }();
+    int var = lvk_lk_variant();
+    if (var < 0) var = slots <= LVK_LK_PIPE_MAX_TRACKS ? 2 : 1;
+    const bool pipe = patch_size == 21 && var == 2 && levels_prev <= LK_PIPE_MAX_LEVELS && levels_curr <= LK_PIPE_MAX_LEVELS;
+    return LkChoice{pipe, pipe && merged_on};
+}
+// cv::calcOpticalFlowPyrLK's termination criteria as it clamps them: the count to [0, 100], epsilon to [0, 10] and squared
+struct LkTerm { int max_count; double epsilon; };
+inline LkTerm lvk_lk_term(int max_iter, double eps)
+{
+    const double e = eps < 0. ? 0. : eps > 10. ? 10. : eps;
+    return LkTerm{max_iter < 0 ? 0 : max_iter > 100 ? 100 : max_iter, e * e};
 }
 
 // ---- device helpers shared by the kernels --------------------------------------------------

@@ -1,4 +1,4 @@
-"""lvk_runtime_env and GPU_MAX_HW_QUEUES (include/lvk_c.h, larvio_amd/csrc/frontend.hip): an explicit call with LVK_RT_HW_QUEUES raises
+"""lvk_runtime_env and GPU_MAX_HW_QUEUES (include/lvk_c.h, larvio_amd/csrc/lvk_context.hip): an explicit call with LVK_RT_HW_QUEUES raises
 a preset number below 8 to 8 and reports the flag; 8 or more is left alone; the implicit call of lvk_context_create never overrides a
 variable the user has set.  No GPU is needed: the environment is settled before the process's first HIP call, and each case runs in
 a child process of its own that only loads the library (the environment is process-wide state, read once by the runtime)."""

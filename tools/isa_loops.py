@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Static picture of a kernel's loops from the compiler's assembly: for every back edge, the instructions between its target and
 its branch, by class.  usage:
-  hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-fast-math --cuda-device-only -S -o fe.s larvio_amd/csrc/frontend.hip
+  hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-fast-math --cuda-device-only -S -o fe.s larvio_amd/csrc/fe_frame.hip
   tools/isa_loops.py fe.s k_fe_lk_bothILi21E [--dump <first label> <last label>]
 (what the LK iteration costs in issue slots, next to what the event-bracketed launch time says it costs in microseconds)"""
 import re
