@@ -59,6 +59,13 @@ class LarVio {
     // lvk_c.h); cov9: 9 doubles per point, row-major, NaN where the anchor clone has left the window
     bool getFeaturesInCamera(std::vector<FeatureIDType>& ids, std::vector<Eigen::Vector3d>& positions_c, std::vector<double>& cov9, long long to_clone_id = -1);
 
+    // not in the reference: external position / pose fixes on a clone of the window, expressed in the filter's world frame
+    // (lvk_ekf_add_fix / lvk_ekf_set_fix_options / lvk_ekf_take_fix_reports, lvk_c.h: models, target clone, gate, refusals); the next
+    // processFeatures that holds the clone applies a queued fix, takeFixReports says what became of each (drained on read)
+    bool addFix(const lvk_fix& fix);
+    bool setFixOptions(double gate_scale, double max_gap_s);
+    void takeFixReports(std::vector<lvk_fix_report>& reports);
+
     typedef boost::shared_ptr<LarVio> Ptr;
     typedef boost::shared_ptr<const LarVio> ConstPtr;
 

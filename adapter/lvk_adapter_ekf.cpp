@@ -225,6 +225,30 @@ void LarVio::takeKeyframes(std::vector<lvk_keyframe>& keyframes)
     }
 }
 
+bool LarVio::addFix(const lvk_fix& fix)
+{
+    finish();                                             // (a fix queued behind a deferred update that nobody has waited for is refused)
+    return ekf && lvk_ekf_add_fix(ekf, &fix) == LVK_OK;
+}
+
+bool LarVio::setFixOptions(double gate_scale, double max_gap_s)
+{
+    finish();
+    return ekf && lvk_ekf_set_fix_options(ekf, gate_scale, max_gap_s) == LVK_OK;
+}
+
+void LarVio::takeFixReports(std::vector<lvk_fix_report>& reports)
+{
+    finish();
+    reports.clear();
+    std::vector<lvk_fix_report> buf(256);
+    for (;;) {
+        const int n = lvk_ekf_take_fix_reports(ekf, buf.data(), 256);
+        reports.insert(reports.end(), buf.begin(), buf.begin() + n);
+        if (n < 256) break;
+    }
+}
+
 bool LarVio::getWindowCov(std::vector<long long>& ids, std::vector<double>& cov_abs36, std::vector<double>& cov_rel36)
 {
     finish();

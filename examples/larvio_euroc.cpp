@@ -2,7 +2,7 @@
 // Pangolin): same command line, same loop, same log files (msckf_2_state.txt / msckf_2_takeoff.txt in the configuration's
 // output_dir, written by lvk::LarVio as larvio.cpp:388,446-453 does), running on liblvk_hip.so.
 //
-//   larvio_euroc path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE] [--keyframes-out FILE] [--depth-out FILE]
+//   larvio_euroc path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE] [--keyframes-out FILE] [--depth-out FILE] [--fixes FILE] [--fix-max-gap S]
 //
 // --mask restricts corner detection to the non-zero pixels of an 8-bit PNG of the configured resolution (ImageProcessor::setMask:
 // a fisheye vignette, the vehicle's own body); a mask of another size is an error.
@@ -18,6 +18,12 @@
 // --depth-out writes, after every pose, one line per in-state feature: "timestamp id x y z s00 s01 s02 s11 s12 s22" - the point in the
 // camera frame of that pose and the upper triangle of its 3 x 3 covariance there (LarVio::getFeaturesInCamera; lvk_c.h,
 // lvk_ekf_landmark_rel_cov): s22 is the depth variance.  A getter only: the filter's outputs do not notice it.
+// --fixes reads external position / pose fixes (LarVio::addFix; lvk_c.h, lvk_ekf_add_fix) from a csv file with the columns
+// "time,kind,px,py,pz,qx,qy,qz,qw,sigma_p,sigma_theta[,lx,ly,lz]" (kind 0 position / 1 pose; time on the IMU clock, ascending; the fix
+// in the FILTER's world frame - aligning another frame is the caller's job; lines that do not parse are skipped) and queues each line
+// before the first frame whose stamp reaches its time; the filter applies it on the clone with exactly that time, or - with
+// --fix-max-gap S - between two adjacent clones at most S seconds apart.  A last line "fixes queued .. applied .." reports the outcome.
+// Not with --pipelined (the pipeline takes fixes only between a drain and the next frame).
 // --tum writes "t x y z qx qy qz qw" (body in world, absolute stamps, 17 significant digits) for tools/traj_rmse.py.
 // --pipelined runs the same loop through lvk::VioPipeline: the filter update of a message overlaps the front-end of the next
 // frames on a second HIP stream; the trajectory is the same, written from the filter thread's odometry callback.
@@ -100,6 +106,31 @@ struct DepthOut {
     void close() { if (f) { std::fclose(f); f = nullptr; } }
 };
 
+// --fixes: the file's lines in order; next = the first one not queued yet
+struct Fixes {
+    std::vector<lvk_fix> all; size_t next; long refused;
+    bool load(const std::string& path)
+    {
+        FILE* f = std::fopen(path.c_str(), "r");
+        if (!f) return false;
+        char line[1024];
+        while (std::fgets(line, sizeof line, f)) {
+            double v[14];
+            if (!lvk::parse_fix_line(line, v)) continue;
+            lvk_fix x = lvk_fix();
+            x.tag = (int64_t)all.size(); x.kind = (int)v[1]; x.clone_id = -1; x.time = v[0];
+            for (int i = 0; i < 3; ++i) { x.p[i] = v[2 + i]; x.lever[i] = v[11 + i]; }
+            for (int i = 0; i < 4; ++i) x.q[i] = v[5 + i];
+            if (x.kind == LVK_FIX_POSE) for (int i = 0; i < 3; ++i) { x.cov[7 * i] = v[10] * v[10]; x.cov[7 * (3 + i)] = v[9] * v[9]; }
+            else for (int i = 0; i < 3; ++i) x.cov[7 * i] = v[9] * v[9];
+            all.push_back(x);
+        }
+        std::fclose(f);
+        return true;
+    }
+    void queue_up_to(lvk::LarVio& Estimator, double stamp) { for (; next < all.size() && all[next].time <= stamp; ++next) if (!Estimator.addFix(all[next])) ++refused; }
+};
+
 struct OdometrySink { FILE* tum; long n_odo; DepthOut* depth; };
 static void on_odometry(void* user, double, const lvk::LarVio& Estimator)
 {
@@ -152,7 +183,7 @@ static int run_pipelined(const char* image_dir, const std::vector<lvk::ImuData>&
 int main(int argc, char** argv)
 {
     if (argc < 5) {
-        std::fprintf(stderr, "Usage: %s path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE] [--keyframes-out FILE] [--depth-out FILE]\n", argv[0]);
+        std::fprintf(stderr, "Usage: %s path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE] [--keyframes-out FILE] [--depth-out FILE] [--fixes FILE] [--fix-max-gap S]\n", argv[0]);
         return 1;
     }
     lvk::EurocArgs opt; std::string bad;
@@ -206,6 +237,12 @@ int main(int argc, char** argv)
     }
     DepthOut depth_out = {nullptr, 0};
     if (!opt.depth_out.empty() && !(depth_out.f = std::fopen(opt.depth_out.c_str(), "w"))) { std::perror(opt.depth_out.c_str()); return 1; }
+    Fixes fixes = {std::vector<lvk_fix>(), 0, 0};
+    if (!opt.fixes.empty()) {
+        if (pipelined) { std::fprintf(stderr, "larvio_euroc: --fixes is not available with --pipelined\n"); return 1; }
+        if (!fixes.load(opt.fixes)) { std::perror(opt.fixes.c_str()); return 1; }
+        if (!Estimator.setFixOptions(1.0, opt.fix_max_gap)) { std::fprintf(stderr, "larvio_euroc: %s\n", ctx.error()); return 1; }
+    }
     if (pipelined) return run_pipelined(argv[3], allImuData, allImgInfo, max_frames, ImgProcesser, Estimator, tum, map_out, msckf_out, kf_out, depth_out);
 
     typedef std::chrono::steady_clock Clock;
@@ -230,6 +267,7 @@ int main(int argc, char** argv)
         const bool bProcess = ImgProcesser.processImage(msg, imu_msg_buffer, &features);
         const Clock::time_point t2 = Clock::now();
         bool bPubOdo = false;
+        fixes.queue_up_to(Estimator, ts);
         if (bProcess) bPubOdo = Estimator.processFeatures(&features, imu_msg_buffer);
         const Clock::time_point t3 = Clock::now();
         t_io += std::chrono::duration<double>(t1 - t0).count();
@@ -252,5 +290,10 @@ int main(int argc, char** argv)
     std::printf("front-end %.3f ms/frame   back-end %.3f ms/message   image read+decode %.3f ms/frame\n", n_fe ? 1e3 * t_fe / n_fe : 0.0,
                 n_be ? 1e3 * t_be / n_be : 0.0, n_fe ? 1e3 * t_io / n_fe : 0.0);
     if (t_fe + t_be > 0) std::printf("processing rate %.1f frames/s (front-end + back-end, sequential, host buffers)\n", n_fe / (t_fe + t_be));
+    if (!opt.fixes.empty()) {
+        long st[8]; lvk_ekf_fix_stats(Estimator.handle(), st);
+        std::printf("fixes read %zu refused %ld queued %ld applied %ld gated %ld not_pd %ld stale %ld no_clone %ld waiting %ld interpolated %ld\n", fixes.all.size(), fixes.refused,
+                    st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]);
+    }
     return 0;
 }

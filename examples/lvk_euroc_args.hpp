@@ -8,7 +8,8 @@
 
 namespace lvk {
 
-struct EurocArgs { std::string tum, mask, map_out, msckf_out, keyframes_out, depth_out; long max_frames; bool pipelined; EurocArgs() : max_frames(-1), pipelined(false) {} };
+struct EurocArgs { std::string tum, mask, map_out, msckf_out, keyframes_out, depth_out, fixes; long max_frames; bool pipelined; double fix_max_gap;
+                   EurocArgs() : max_frames(-1), pipelined(false), fix_max_gap(0.0) {} };
 
 // argv[first..]: false, with the offending word in *bad, on an unknown option or an option without its value
 inline bool parse_euroc_args(int argc, char** argv, int first, EurocArgs* o, std::string* bad)
@@ -22,6 +23,8 @@ inline bool parse_euroc_args(int argc, char** argv, int first, EurocArgs* o, std
         else if (!std::strcmp(argv[a], "--msckf-out") && a + 1 < argc) o->msckf_out = argv[++a];
         else if (!std::strcmp(argv[a], "--keyframes-out") && a + 1 < argc) o->keyframes_out = argv[++a];
         else if (!std::strcmp(argv[a], "--depth-out") && a + 1 < argc) o->depth_out = argv[++a];
+        else if (!std::strcmp(argv[a], "--fixes") && a + 1 < argc) o->fixes = argv[++a];
+        else if (!std::strcmp(argv[a], "--fix-max-gap") && a + 1 < argc) o->fix_max_gap = std::atof(argv[++a]);
         else { if (bad) *bad = argv[a]; return false; }
     }
     return true;
@@ -49,6 +52,24 @@ inline void write_keyframe(FILE* f, long long id, long long to_id, const double*
 inline void write_depth_point(FILE* f, double t, long long id, const double* p, const double* c)
 {
     std::fprintf(f, "%.9f %lld %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", t, id, p[0], p[1], p[2], c[0], c[1], c[2], c[4], c[5], c[8]);
+}
+
+// one --fixes line: "time,kind,px,py,pz,qx,qy,qz,qw,sigma_p,sigma_theta[,lx,ly,lz]" - kind 0 position / 1 pose, the fix in the filter's
+// world frame at `time` on the IMU clock, isotropic standard deviations (m, rad), an optional lever arm in the body frame.  v: the 14
+// numbers in that order (the lever arm zero when absent).  false: not such a line (a comment, a header, too few fields).
+inline bool parse_fix_line(const char* line, double v[14])
+{
+    for (int i = 0; i < 14; ++i) v[i] = 0.0;
+    int n = 0; const char* p = line;
+    while (n < 14) {
+        char* end = nullptr; const double x = std::strtod(p, &end);
+        if (end == p) break;
+        v[n++] = x; p = end;
+        while (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n') ++p;
+        if (*p != ',') break;
+        ++p;
+    }
+    return (n == 11 || n == 14) && (v[1] == 0.0 || v[1] == 1.0);
 }
 
 }   // namespace lvk

@@ -443,6 +443,34 @@ typedef struct { int anchor_col, feat_col, pad0, pad1;      /* as lvk_landmark_j
                  double q_b[4], p_b[3], p_anchor[3]; } lvk_landmark_rel_job;   /* the target's pose; the anchor clone's position as lvk_clone.p */
 lvk_status lvk_ekf_landmark_rel_cov(lvk_context* ctx, const double* d_P, int ldp, int n, const lvk_landmark_rel_job* h_jobs, int n_jobs, double* h_out12);
 
+/* lvk_ekf_update_sparse: one measurement of 3 or 6 rows that touches at most 12 columns of the state and carries a full noise
+ * covariance, applied to a device-resident covariance (n x n, row-major, leading dimension ldp) without a dense H, a GEMM or a whitening
+ * step - the update an external position or pose fix needs (lvk_ekf_add_fix).  No reference counterpart: the reference has no such input.
+ *   S = H P[cols, cols] H^T + R = L L^T,   gamma = r^T S^-1 r,   W = L^-1 H P[cols, :],   dx = W^T L^-1 r,   P <- P - W^T W.
+ * H is m x ncols, packed row-major (row stride ncols); R is m x m, packed row-major (row stride m), and only its upper triangle,
+ * diagonal included, is read - S is formed as its upper triangle and mirrored.  Entries of cols and H beyond ncols, of r beyond m and
+ * of R beyond m x m are never read and may hold anything.
+ * Two launches and one wait.  The first forms, in every workgroup by itself and therefore with the same bits everywhere, S from the
+ * ncols x ncols sub-block of P, its Cholesky factor, gamma and the status, then its own 64 columns of W (to a work space) and of dx.
+ * The second subtracts W^T W, one entry of P per thread, and does nothing unless the status is 0: the gate is decided on the device.
+ * No kernel writes what a sibling workgroup of the same launch reads.  Every sum runs in a fixed order (the same input gives the
+ * same bits), and P[i][j] and P[j][i] are formed from the same operands in the same order: a symmetric P stays symmetric bit for bit.
+ * Nothing of P outside [0, n) x [0, n) is read or written: the padding of a wider ldp keeps its bytes.
+ * h_dx: n doubles.  h_info4: [0] status - 0 applied, 1 gated out (gate > 0 and not gamma <= gate), 2 S not positive definite (a
+ * pivot that is not > 0); [1] gamma (0 with status 2); [2] the smallest pivot met (the diagonal entry of the reduced S whose square
+ * root is L_ii; with status 2 the failing one); [3] 0.  With status 1 or 2 not one byte of P changes and dx is all zeros.
+ * LVK_ERR_ARG, with nothing launched and the context still usable: a null pointer, m not 3 or 6, ncols outside 1..12, columns that
+ * do not ascend strictly or leave [0, n), ldp < n, or a value that is not finite among gate and the entries of H, r and R that are read. */
+typedef struct { int m;            /* 3 or 6 rows */
+                 int ncols;        /* 1..12 distinct columns, ascending */
+                 int cols[12];
+                 double H[6*12];   /* row-major m x ncols */
+                 double r[6], R[36];  /* residual; full SPD noise covariance, m x m row-major */
+                 double gate; }    /* accept iff r' S^-1 r <= gate; <= 0: no gate */
+        lvk_sparse_update;
+lvk_status lvk_ekf_update_sparse(lvk_context* ctx, double* d_P, int ldp, int n, const lvk_sparse_update* h_u,
+                                 double* h_dx /* n */, double* h_info4);
+
 typedef struct {
     /* names and meaning as LarVio::loadParameters reads them (larvio.cpp:58-311, config/euroc.yaml) */
     int if_fej, estimate_extrin, estimate_td, if_zupt_valid;
@@ -637,6 +665,69 @@ typedef struct { int64_t id, to_id; double time, to_time;
 lvk_status lvk_ekf_set_keyframe_export(lvk_ekf* e, int on);
 int        lvk_ekf_take_keyframes(lvk_ekf* e, lvk_keyframe* h_out, int cap);
 lvk_status lvk_ekf_get_window_cov(lvk_ekf* e, int64_t* h_ids, double* h_cov_abs36, double* h_cov_rel36, int cap, int* n_out);
+/* External fixes: the way back INTO the filter.  Global position and yaw are unobservable for a VIO and their block of the covariance
+ * grows without bound (see lvk_ekf_pose_rel_cov); a caller that has GNSS, motion capture or a pose graph over lvk_ekf_take_keyframes
+ * hands its result back as a measurement of a CLONE that is still in the window - a delayed measurement on a stochastic clone, so a
+ * late result is fused correctly with no re-propagation.  No reference counterpart.
+ * Conventions (those of lvk_ekf_pose_rel_cov): R(q) maps body to world, the injection is R <- (I + [d_theta]x) R, p <- p + d_p, clone
+ * c has columns leg + 6 c (d_theta) and leg + 6 c + 3 (d_p), times are on the IMU clock as lvk_clone.time.  A fix is expressed in the
+ * FILTER's world frame: aligning an external frame (yaw and translation) is the caller's job.
+ *   LVK_FIX_POSITION   z = p_i + R_i lever + n,  n ~ N(0, cov[0:3, 0:3]) (cov is 6 x 6 row-major storage; the upper-left 3 x 3 is used);
+ *                      r = z - (p_i + R_i lever),  H_theta = -[R_i lever]x,  H_p = I                                  (3 rows, 6 columns)
+ *   ... between two adjacent clones i, j, a = (t - t_i) / (t_j - t_i): the prediction is (1 - a)(p_i + R_i lever) + a (p_j + R_j lever)
+ *                      and the two clones' blocks are scaled by 1 - a and a                                           (3 rows, 12 columns)
+ *   LVK_FIX_POSE       three more rows in front: r_theta = 2 vec(q_z * q_i^-1), the sign taken so that w >= 0, H_theta = I on clone i;
+ *                      cov is the 6 x 6 covariance in the order [d_theta; p]                                          (6 rows, 6 columns)
+ * (The signs were confirmed against the injection by central differences: tests/fix_ref.py.)
+ * lvk_ekf_add_fix queues a fix (at most 64 wait at a time: LVK_ERR_CAPACITY beyond).  Every update (lvk_ekf_process and its deferred
+ * and pipelined forms) applies the queue at one place: after the zero-velocity check and before the lost-feature update - the
+ * message's own clone exists, no clone has been pruned yet - in queue order, each fix one lvk_ekf_update_sparse on the filter's
+ * covariance followed by the state injection.  An empty queue costs nothing: the filter then launches exactly the kernels it
+ * launched before these entry points existed.  Each applied fix costs two launches and one stream wait.  The target clone:
+ *   clone_id >= 0                that clone; an id that is not in the window (pruned, or never handed out): LVK_FIX_STALE
+ *   clone_id == -1, by time      a clone whose time equals (==) the fix's: that clone; older than the oldest clone: LVK_FIX_STALE; newer
+ *                                than the newest clone: the fix stays queued; strictly between two adjacent clones: a POSITION fix
+ *                                with t_j - t_i <= max_gap_s is interpolated, anything else is LVK_FIX_NO_CLONE.
+ * max_gap_s defaults to 0 - no interpolation unless the caller asks for it and picks the gap: after pruning, adjacent clones can be far
+ * apart, and the library invents no bound.  The chi-square gate of a fix is gate_scale times the filter's own table entry for 3 or 6
+ * degrees of freedom - the table of the feature gate (larvio.cpp:353-357), the reference's 5 % quantiles: 0.3518 and 1.6354 - so the
+ * default scale of 1 is as strict as the filter is with its features; a caller who wants the usual 99.9 % gate passes
+ * 16.27 / 0.3518 = 46.2 (3 rows) or 22.46 / 1.6354 = 13.7 (6 rows).  A scale <= 0 disables the gate; a NaN is LVK_ERR_ARG.
+ * One lvk_fix_report per consumed fix (lvk_ekf_take_fix_reports drains them in order, up to cap per call, and returns the count; the
+ * list holds at most 65536 records: the oldest half goes when it is full): tag, kind, status, gamma = r^T S^-1 r (0 unless APPLIED or
+ * GATED), the ids of the clones used (clone_j = -1 unless interpolated; both -1 for STALE and NO_CLONE) and a (0 unless interpolated).
+ * lvk_ekf_fix_stats: [0] fixes queued so far [1] applied [2] gated [3] not positive definite [4] stale [5] no clone [6] waiting now
+ * [7] of the applied ones, interpolated.  lvk_ekf_counters and lvk_ekf_last_update are unchanged by a fix, and lvk_ekf_config keeps its size.
+ * A gated or not-positive-definite fix leaves state and covariance exactly as they were.
+ * Refusals and limits:
+ *   lvk_ekf_add_fix is LVK_ERR_UNSUPPORTED while a shard transport is set (lvk_ekf_set_shard), and a transport is refused while fixes
+ *     wait: the sharded update does not apply fixes;
+ *   LVK_ERR_ARG for a value that is not finite (time, p, lever, the part of cov that is used, q of a POSE fix), a cov block that is not
+ *     symmetric positive definite (a Cholesky factorisation on the host), a POSE fix whose |q| differs from 1 by more than 1e-6, a kind
+ *     other than the two, a clone_id below -1;
+ *   a deferred update (lvk_ekf_process_async) consumes what was queued when it was issued; lvk_ekf_add_fix between the issue and
+ *     lvk_ekf_wait (or any other call that waits for it: every getter does) is LVK_ERR_ARG, whether or not the update has finished
+ *     meanwhile, as for lvk_ekf_set_cov;
+ *   with a lvk_vio_pipe, fixes are legal only between lvk_vio_pipe_drain and the next lvk_vio_pipe_submit. */
+#define LVK_FIX_POSITION 0
+#define LVK_FIX_POSE     1
+#define LVK_FIX_APPLIED  0
+#define LVK_FIX_GATED    1
+#define LVK_FIX_NOT_PD   2
+#define LVK_FIX_STALE    3
+#define LVK_FIX_NO_CLONE 4
+typedef struct { int64_t tag;       /* caller's, echoed in the report */
+                 int kind;          /* LVK_FIX_POSITION 0, LVK_FIX_POSE 1 */
+                 int64_t clone_id;  /* >= 0: this clone; -1: by time */
+                 double time;       /* IMU clock, as lvk_clone.time */
+                 double p[3], q[4], lever[3];
+                 double cov[36]; }  /* POSITION: upper-left 3x3 used, order [p]; POSE: order [dtheta; p] */
+        lvk_fix;
+typedef struct { int64_t tag; int kind, status; double gamma; int64_t clone_i, clone_j; double a; } lvk_fix_report;
+lvk_status lvk_ekf_add_fix(lvk_ekf* e, const lvk_fix* h_fix);              /* queue, cap 64: LVK_ERR_CAPACITY beyond */
+lvk_status lvk_ekf_set_fix_options(lvk_ekf* e, double gate_scale, double max_gap_s);
+int        lvk_ekf_take_fix_reports(lvk_ekf* e, lvk_fix_report* h_out, int cap);
+void       lvk_ekf_fix_stats(const lvk_ekf* e, long* h_out8);
 /* What the moving-start initialiser (FlexibleInitializer.cpp:11-25 -> DynamicInitializer.cpp) handed to the filter, with the intermediate
  * results of the successful attempt - for parity tests against an independent restatement fed the same messages:
  *   valid        1 once the dynamic initialiser has succeeded on this handle (0: never ran, or the static one fired)

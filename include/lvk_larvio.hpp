@@ -243,6 +243,18 @@ public:
         ids.resize((size_t)n); cov_abs.resize((size_t)36 * n); cov_rel.resize((size_t)36 * n);
         return ok;
     }
+    // External fixes (lvk_ekf_add_fix / lvk_ekf_set_fix_options / lvk_ekf_take_fix_reports; models, target clone, gate and refusals in
+    // lvk_c.h): addFix queues a position or pose fix, expressed in the filter's world frame, on a clone of the window - by id or by
+    // time - and the next processFeatures that holds the clone applies it; takeFixReports hands out what became of each (up to 256
+    // per call).  With a VioPipeline call addFix only between drain() and the next processImage.
+    bool addFix(const lvk_fix& fix) { return ekf_ && lvk_ekf_add_fix(ekf_, &fix) == LVK_OK; }
+    bool setFixOptions(double gate_scale, double max_gap_s) { return ekf_ && lvk_ekf_set_fix_options(ekf_, gate_scale, max_gap_s) == LVK_OK; }
+    void takeFixReports(std::vector<lvk_fix_report>& out)
+    {
+        out.resize(256);
+        const int n = ekf_ ? lvk_ekf_take_fix_reports(ekf_, out.data(), 256) : 0;
+        out.resize((size_t)n);
+    }
     lvk_ekf* handle() const { return ekf_; }
 private:
     friend class VioPipeline;

@@ -198,6 +198,12 @@ struct lvk_ekf {
     // download buffer (down_kf), its relative one in slot 2 i + 1 - attached like the lost-feature covariance (kf_mark as lost_cov_mark)
     std::vector<lvk_keyframe> keyframes;
     bool keyframes_on = false; size_t down_kf = 0; int kf_pending = 0, kf_mark = 0;
+    // lvk_ekf_add_fix: external position / pose fixes waiting for their clone (at most FIX_CAP), applied by lvk_ekf_apply_fixes
+    // (be_fix.hip) once per message; one report per consumed fix (drained on read).  fix_stats: [0] queued so far [1] applied [2] gated
+    // [3] not positive definite [4] stale [5] no clone [7] interpolated among the applied ([6], waiting, is fix_queue.size())
+    enum { FIX_CAP = 64 };
+    std::vector<lvk_fix> fix_queue; std::vector<lvk_fix_report> fix_reports;
+    double fix_gate_scale = 1.0, fix_max_gap = 0.0; long fix_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     double sigma2, zupt_v2, zupt_p2, zupt_q2, imu_img_time_th, Qc[12];
     double x_min, y_min, grid_w, grid_h;
     std::vector<int> grid_count;

@@ -129,6 +129,8 @@ lvk_status lvk_ekf_dense_update(lvk_ekf* e, int m, std::vector<double>& dx, int 
 lvk_status lvk_ekf_gated_update(lvk_ekf* e, std::vector<RowJob>& jobs, const size_t (&order)[2][2], const int (&tr)[3], std::vector<double>& dx,
                                 const long long* retire = nullptr, int n_retire = 0, size_t mp_lo = 0, size_t mp_hi = 0);
 lvk_status lvk_ekf_remove_lost_features(lvk_ekf* e);
+// be_fix.hip
+lvk_status lvk_ekf_apply_fixes(lvk_ekf* e);
 // be_prune.hip
 lvk_status lvk_ekf_check_zupt(lvk_ekf* e, bool* out);
 lvk_status lvk_ekf_prune_imu_state_buffer(lvk_ekf* e);

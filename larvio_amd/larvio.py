@@ -18,6 +18,14 @@ CLONE = np.dtype([("id", np.int64), ("time", np.float64), ("dt", np.float64), ("
 KEYFRAME = np.dtype([("id", np.int64), ("to_id", np.int64), ("time", np.float64), ("to_time", np.float64), ("q", np.float64, 4), ("p", np.float64, 3),
                      ("rel_q", np.float64, 4), ("rel_p", np.float64, 3), ("cov_abs", np.float64, (6, 6)), ("cov_rel", np.float64, (6, 6))])
 
+# lvk_fix / lvk_fix_report (include/lvk_c.h)
+FIX = np.dtype([("tag", np.int64), ("kind", np.int32), ("pad", np.int32), ("clone_id", np.int64), ("time", np.float64), ("p", np.float64, 3), ("q", np.float64, 4),
+                ("lever", np.float64, 3), ("cov", np.float64, (6, 6))])
+FIX_REPORT = np.dtype([("tag", np.int64), ("kind", np.int32), ("status", np.int32), ("gamma", np.float64), ("clone_i", np.int64), ("clone_j", np.int64),
+                       ("a", np.float64)])
+FIX_POSITION, FIX_POSE = 0, 1
+FIX_APPLIED, FIX_GATED, FIX_NOT_PD, FIX_STALE, FIX_NO_CLONE = 0, 1, 2, 3, 4
+
 _CFG_INT = ["if_fej", "estimate_extrin", "estimate_td", "if_zupt_valid", "sw_size", "max_track_len", "least_observation_number",
             "max_features_in_one_grid", "aug_grid_rows", "aug_grid_cols", "width", "height"]
 _CFG_DBL = ["td", "pub_frequency", "imu_rate", "noise_gyro", "noise_acc", "noise_gyro_bias", "noise_acc_bias", "noise_feature",
@@ -78,6 +86,10 @@ def _L():
         L.lvk_ekf_set_keyframe_export.argtypes = [vp, i]; L.lvk_ekf_set_keyframe_export.restype = i
         L.lvk_ekf_take_keyframes.argtypes = [vp, vp, i]; L.lvk_ekf_take_keyframes.restype = i
         L.lvk_ekf_get_window_cov.argtypes = [vp, vp, vp, vp, i, pi]; L.lvk_ekf_get_window_cov.restype = i
+        L.lvk_ekf_add_fix.argtypes = [vp, vp]; L.lvk_ekf_add_fix.restype = i
+        L.lvk_ekf_set_fix_options.argtypes = [vp, d, d]; L.lvk_ekf_set_fix_options.restype = i
+        L.lvk_ekf_take_fix_reports.argtypes = [vp, vp, i]; L.lvk_ekf_take_fix_reports.restype = i
+        L.lvk_ekf_fix_stats.argtypes = [vp, vp]; L.lvk_ekf_fix_stats.restype = None
         L.lvk_ekf_get_state.argtypes = [vp, vp]; L.lvk_ekf_get_state.restype = i
         L.lvk_ekf_get_cov.argtypes = [vp, vp]; L.lvk_ekf_get_cov.restype = i
         L.lvk_ekf_get_cov_imu.argtypes = [vp, i, vp]; L.lvk_ekf_get_cov_imu.restype = i
@@ -568,6 +580,40 @@ class LarVio:
         self.ctx.check(_L().lvk_ekf_get_window_cov(self._h, _p(ids), _p(ca), _p(cr), cap, C.byref(n)))
         n = n.value
         return ids[:n].copy(), ca[:n].copy(), cr[:n].copy()
+
+    def add_fix(self, p, cov, time=0.0, clone_id=-1, q=None, lever=(0.0, 0.0, 0.0), tag=0):
+        """lvk_ekf_add_fix: queue an external fix, expressed in the filter's world frame, on the clone `clone_id` or (clone_id -1) on the
+        clone at `time` (IMU clock, as clones()["time"]).  q None: a POSITION fix, p the position of the point at `lever` (body frame),
+        cov its 3 x 3 covariance; with q ([x y z w], body to world): a POSE fix, cov 6 x 6 in the order [d_theta; p].  Applied by the next
+        update that holds the clone; take_fix_reports() says what became of it.  Raises LvkError for what the header lists as refused."""
+        f = np.zeros(1, FIX)
+        cov = np.asarray(cov, np.float64); m = 3 if q is None else 6
+        if cov.shape != (m, m):
+            raise ValueError("add_fix: cov must be %d x %d" % (m, m))
+        f["tag"] = tag; f["kind"] = FIX_POSITION if q is None else FIX_POSE; f["clone_id"] = clone_id; f["time"] = time
+        f["p"] = p; f["lever"] = lever; f["q"] = (0, 0, 0, 1) if q is None else q; f["cov"][0, :m, :m] = cov
+        self.ctx.check(_L().lvk_ekf_add_fix(self._h, _p(f)))
+
+    def set_fix_options(self, gate_scale=1.0, max_gap_s=0.0):
+        """lvk_ekf_set_fix_options: the gate of a fix is gate_scale times the filter's own chi-square table entry (<= 0: no gate);
+        max_gap_s: a POSITION fix between two adjacent clones at most this far apart is interpolated (0: never)"""
+        self.ctx.check(_L().lvk_ekf_set_fix_options(self._h, float(gate_scale), float(max_gap_s)))
+
+    def take_fix_reports(self):
+        """lvk_ekf_take_fix_reports: a structured array (dtype FIX_REPORT), one record per fix consumed since the last call, in order"""
+        out = []
+        while True:
+            buf = np.zeros(256, FIX_REPORT)
+            n = _L().lvk_ekf_take_fix_reports(self._h, _p(buf), 256)
+            out.append(buf[:n].copy())
+            if n < 256:
+                break
+        return np.concatenate(out)
+
+    def fix_stats(self):
+        o = np.zeros(8, np.int64); _L().lvk_ekf_fix_stats(self._h, _p(o))
+        return dict(queued=int(o[0]), applied=int(o[1]), gated=int(o[2]), not_pd=int(o[3]), stale=int(o[4]), no_clone=int(o[5]), waiting=int(o[6]),
+                    interpolated=int(o[7]))
 
     def set_shard(self, rank, world, fn, user, keepalive=None):
         """lvk_ekf_set_shard: this filter does the per-feature device work of rank `rank` of `world`; fn/user = the all-gather

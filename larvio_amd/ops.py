@@ -269,3 +269,34 @@ def msckf_point_cov(ctx, P, clones, jobs, clone_rank, obs, obs_vel, leg_dim=22, 
     ctx.check(L.lvk_ekf_msckf_point_cov(ctx.h, _p(dP), P.shape[1], n, _p(clones), len(clones), _p(jobs), len(jobs), _p(rk), _p(z), _p(zv),
                                         int(leg_dim), int(bool(if_fej)), int(bool(estimate_td)), float(sigma2), _p(out), _p(ok)))
     return out, ok
+
+
+# lvk_sparse_update (include/lvk_c.h): H is m x ncols packed row-major at the front of its 72 doubles, R m x m packed at the front of its 36
+SPARSE_UPDATE = np.dtype([("m", np.int32), ("ncols", np.int32), ("cols", np.int32, 12), ("H", np.float64, 72), ("r", np.float64, 6), ("R", np.float64, 36),
+                          ("gate", np.float64)])
+
+
+def sparse_update_record(cols, H, r, R, gate=0.0, fill=0.0):
+    """one SPARSE_UPDATE record from H (m x ncols), r (m), R (m x m); fill: what the entries the call never reads hold"""
+    H = np.asarray(H, np.float64); r = np.asarray(r, np.float64); R = np.asarray(R, np.float64)
+    m, nc = H.shape
+    u = np.zeros(1, SPARSE_UPDATE)
+    u["cols"] = -1 if np.isnan(fill) else 0
+    u["H"] = fill; u["r"] = fill; u["R"] = fill
+    u["m"] = m; u["ncols"] = nc; u["cols"][0, :nc] = cols
+    u["H"][0, :m * nc] = H.ravel(); u["r"][0, :m] = r; u["R"][0, :m * m] = R.ravel(); u["gate"] = gate
+    return u
+
+
+def update_sparse(ctx, P, u, n=None):
+    """lvk_ekf_update_sparse: one SPARSE_UPDATE record applied to the covariance P.  P: a whole row-major buffer (its row length is
+    the leading dimension, contents go to the device as they are) whose leading n x n block (default: all rows) is the covariance.
+    -> (dx (n,), the whole P buffer after the call, info (4,): status, gamma, smallest pivot, 0)"""
+    P = np.ascontiguousarray(P, np.float64); u = np.ascontiguousarray(u, SPARSE_UPDATE)
+    n = P.shape[0] if n is None else int(n)
+    dx = np.full(n, np.nan); info = np.full(4, np.nan)
+    L = lib()
+    L.lvk_ekf_update_sparse.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]; L.lvk_ekf_update_sparse.restype = C.c_int
+    dP = ctx.to_device(P)
+    ctx.check(L.lvk_ekf_update_sparse(ctx.h, _p(dP), P.shape[1], n, _p(u), _p(dx), _p(info)))
+    return dx, ctx.to_host(dP, np.float64, P.shape), info
