@@ -259,6 +259,74 @@ lvk_status lvk_frontend_profile_enable(lvk_frontend* fe, unsigned stage_mask);
 lvk_status lvk_frontend_profile_read(lvk_frontend* fe, double ms_sum[LVK_FE_STAGES], uint64_t launches[LVK_FE_STAGES], int reset);
 const char* lvk_frontend_stage_name(int stage);
 
+/* ------------------------------------------------------------------ stage entries of the frame path
+ * The three kinds of launch a steady-state frame queues, each on a caller's HOST arrays through the very launch code lvk_frontend_process
+ * uses (stage parity; no reference counterpart beyond the functions cited).  Each call checks everything on the host before it queues
+ * anything, allocates its device buffers for the call, and returns after a wait for the context's stream.  Refusals leave every output
+ * array untouched and the context usable.  Status codes in the per-point status byte: 0 alive, 1 lost by the forward pass, 2 by the
+ * reverse pass, 3 by the descriptor gate.
+ *
+ * lvk_fe_track_stage: forward LK from the H-predicted start, in-image test, reverse LK, <= 1 px round trip, descriptor gate (> 58 bits
+ * fails) and the K -> K undistorted pair of every point (trackFeatures image_processor.cpp:558-712, trackNewFeatures :830-943) in ONE
+ * launch: variant 1 = k_fe_lk_both<patch_size> (two wavefronts per point), variant 2 = k_fe_lk_pipe<21> (five).  The variant is the
+ * caller's, LVK_LK_VARIANT is not read.  prev / next: built pyramids of width x height created with win = patch_size; d_*_ext / d_*_blur:
+ * their lvk_orb_prepare planes.  A set is n points in `grid` slots (= blocks; the frame path launches one per track slot): blocks >= n
+ * must write nothing, which a caller sees because every output array is filled with fill_byte before the launch.  is_new = 0: the gate
+ * compares with h_stored_desc (n x 4 words); 1: with the previous-image descriptor, which is written to h_desc (grid x 4).  Per slot:
+ * h_curr = the forward result whatever the status, h_und[2p] = the undistorted source point, h_und[2p + 1] = the undistorted forward
+ * result - written only when the forward pass succeeded.  set1 (may be NULL, variant 2 only): a second set in the same launch, blocks
+ * [grid0, grid0 + grid1) - the frame path's LVK_LK_MERGED launch.  h_counters[2]: lk_point_levels and lk_iterations, in / out.
+ * LVK_ERR_ARG: a null pointer that is needed, n < 0 or n > grid, is_new not 0 / 1, pyramids not width x height or not built with win =
+ * patch_size, a variant other than 1 / 2, a second set with variant 1, H or the camera not finite, a model other than 0 / 1, a source
+ * point that is not finite or outside [0, width - 1] x [0, height - 1] (the descriptor wavefront reads the mosaic around it
+ * unconditionally).  LVK_ERR_CAPACITY: grid > 4096.  LVK_ERR_UNSUPPORTED: patch_size not 15 / 21 / 31, variant 2 with another window
+ * than 21 or with a pyramid of more than 4 levels (the templates it keeps in LDS). */
+typedef struct {
+    int n, grid, is_new;
+    const lvk_pt2f* h_src_pts;          /* n */
+    const uint64_t* h_stored_desc;      /* n x 4, is_new = 0 */
+    lvk_pt2f* h_curr;                   /* out, grid */
+    uint8_t*  h_status;                 /* out, grid */
+    lvk_pt2f* h_und;                    /* out, grid x 2 */
+    uint64_t* h_desc;                   /* out, grid x 4, is_new = 1 */
+} lvk_fe_track_io;
+lvk_status lvk_fe_track_stage(lvk_context* ctx, const lvk_pyramid* prev, const lvk_pyramid* next, const uint8_t* d_prev_ext, const uint8_t* d_prev_blur,
+                              const uint8_t* d_next_ext, const uint8_t* d_next_blur, int width, int height, int patch_size, int variant, const float H[9],
+                              int model, const double intr[4], const double dist[4], int max_iteration, double track_precision, int fill_byte,
+                              const lvk_fe_track_io* set0, const lvk_fe_track_io* set1, uint64_t h_counters[2]);
+
+/* lvk_fe_commit_stage: k_fe_ransac_commit - ordered compaction of the alive points, the modes' failure rules, the cv::findFundamentalMat
+ * mask on their undistorted pairs (fewer than 7: none, everything is kept; 7: all ones; 8..14 LMedS; 15 and more RANSAC) and the ordered
+ * write of the destination set.  mode 0 = old tracks (trackFeatures :701-808: the set is replaced, id and init carried, life + 1),
+ * 1 = new points appended behind dst_n (trackNewFeatures :932-1001: fails - nothing changes - with fewer than 20 alive or none kept),
+ * 2 = bootstrap (initializeFirstFeatures :464-536: needs 20 after the forward pass, after the reverse pass, after the gate and after the
+ * mask; boot_ok says which way it went, failure leaves dst_n = 0).  One workgroup: 512 threads when cap > 512, otherwise 256 - by the
+ * slot count cap, as the frame path chooses, not by n.  All source arrays hold n entries (h_und n x 2, h_src_desc n x 4; h_src_id,
+ * h_src_init, h_src_life: mode 0 only), h_dst's arrays cap slots each, in / out.  h_state in / out; in modes 1 and 2 the kernel's count
+ * IS n_new, as in a frame, so n_new must equal n on entry.
+ * Mode 1 at a full set: slots >= cap are never written and dst_n stops at cap, but next_id advances by the UNCLIPPED count of kept points
+ * - ids are consumed by points that found no slot.  (The frame path never gets there: detection asks for cap - dst_n corners at most.)
+ * LVK_ERR_ARG: mode outside 0..2, cap < 1, n < 0, a null pointer that is needed, dst_n outside [0, cap], n_new != n in modes 1 / 2, a
+ * status byte above 3, an undistorted point that is not finite.  LVK_ERR_CAPACITY: cap > 4096 (the kernel's LDS), n > cap. */
+typedef struct {                        /* a track set in host arrays */
+    uint64_t* id; lvk_pt2f* pts; lvk_pt2f* ppts; lvk_pt2f* init; int* life;
+    uint64_t* desc;                     /* 4 words per slot */
+} lvk_fe_track_arrays;
+typedef struct { uint64_t next_id; int dst_n, n_new, boot_ok; } lvk_fe_commit_state;
+lvk_status lvk_fe_commit_stage(lvk_context* ctx, int mode, int cap, int n, const lvk_pt2f* h_src_pts, const lvk_pt2f* h_curr, const uint8_t* h_status, const lvk_pt2f* h_und,
+                               const uint64_t* h_src_id, const lvk_pt2f* h_src_init, const int* h_src_life, const uint64_t* h_src_desc,
+                               const lvk_fe_track_arrays* h_dst, lvk_fe_commit_state* h_state);
+
+/* lvk_fe_msg_stage: k_fe_msg - getFeatureMsg (:1076-1128) of the first n of a set's cap slots, ceil(cap / 64) blocks of 64 threads as the
+ * frame path launches it.  Reads h_set's id, pts, ppts and init (cap entries each; life and desc may be NULL); writes h_out[i] for i < n
+ * (h_out: cap entries, filled with fill_byte before the launch) and resets init[i] to (-1, -1) where it was a real point.  h_state in /
+ * out: n_msg and n_host become n, msg_features grows by n, msg_count by one.
+ * LVK_ERR_ARG: cap < 1, n < 0, a null pointer, prev_is_last not 0 / 1, a dt or the camera not finite, a model other than 0 / 1.
+ * LVK_ERR_CAPACITY: cap > 4096, n > cap. */
+typedef struct { int n_msg, n_host; uint64_t msg_features, msg_count; } lvk_fe_msg_state;
+lvk_status lvk_fe_msg_stage(lvk_context* ctx, const lvk_fe_track_arrays* h_set, int cap, int n, int model, const double intr[4], const double dist[4],
+                            double dt_1, double dt_2, int prev_is_last, int fill_byte, lvk_feature_obs* h_out, lvk_fe_msg_state* h_state);
+
 /* ==================================================================== back-end: EKF measurement update
  * replaces larvio::LarVio (include/larvio/larvio.h:37-90).  feature_idp_dim = 1, use_schmidt = 0,
  * calib_imu_instrinsic = 0 or 1 (config/euroc.yaml:8-10,105,108) are implemented; other values are refused.

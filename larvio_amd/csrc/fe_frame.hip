@@ -1,10 +1,13 @@
 // fe_frame.hip — the kernels of a steady-state frame and their launchers: LK forward + reverse with the ORB descriptor gate in their
 // shadow (k_fe_lk_both, k_fe_lk_pipe), RANSAC + commit of a track set (k_fe_ransac_commit), the feature message (k_fe_msg).
-// frontend.hip decides what a frame queues and on which stream; the launches themselves are here, next to the kernels (fe_frontend.h).
+// frontend.hip decides what a frame queues and on which stream; the launches themselves are here, next to the kernels (fe_frontend.h),
+// and so are the three stage entries that run one such launch on a caller's host arrays (lvk_fe_track_stage, lvk_fe_commit_stage,
+// lvk_fe_msg_stage, include/lvk_c.h).
 #include "lvk_internal.h"
 #include "fe_track_dev.h"
 #include "fe_frontend.h"
 #include <math.h>
+#include <cmath>
 
 __device__ __forceinline__ lvk_pt2f apply_h(const HMat& H, lvk_pt2f p)
 {   // predictFeatureTracking (:285-290): Matx33f * Vec3f, s = 0; s += H(i,k)*p(k)
@@ -397,38 +400,68 @@ static LkSet lk_set(const lvk_pt2f* src_pts, const int* n_ptr, lvk_pt2f* w_curr,
     return LkSet{src_pts, n_ptr, w_curr, w_status, stored_desc, w_desc, w_und, is_new, 0};
 }
 
+// ---- the launch code itself: ONE place per kernel, for the frame path (an lvk_frontend owns the buffers) and the stage entries (a caller does)
+struct LkFrame {        // what an LK launch reads besides its track sets
+    hipStream_t stream; PyrView pv, cv; int width, height; LkTerm term; FeDev* dev;
+    const uint8_t *cur_ext, *cur_blur, *prv_ext, *prv_blur; CamParams cam;
+};
+// pipe: k_fe_lk_pipe<21> over `grid` blocks, [0, grid0) set a, the rest set b (one set: b = a, grid = grid0); otherwise k_fe_lk_both<WIN> over set a's grid0
 template <int WIN>
-static void launch_track_chain(lvk_frontend* fe, hipStream_t s, const PyrView& pv, const PyrView& cv, const lvk_pt2f* src_pts, const int* n_ptr, int grid,
-                               const HMat& H, lvk_pt2f* w_curr, uint8_t* w_status, const unsigned long long* stored_desc,
-                               unsigned long long* w_desc, int is_new, int max_count, double epsilon)
+static void lk_launch(const LkFrame& f, bool pipe, const LkSet& a, const LkSet& b, int grid0, int grid, const HMat& H)
 {
-    const int W = fe->cfg.width, Hh = fe->cfg.height;
-    if (fe->pyr_event) hipStreamWaitEvent(s, fe->ev_orb, 0);      // the frame start waited for the pyramid only: the ORB planes (read by the kernel's second wavefront) follow it on the image stream
-    ProfScope ps(fe, 2, s);
-    lvk_pt2f* const w_und = w_curr == fe->w_curr ? fe->w_und : fe->wn_und;
     if constexpr (WIN == 21) {
-        if (lvk_lk_choice(WIN, fe->cap, pv.n_levels, cv.n_levels).pipe) {
-            const LkSet a = lk_set(src_pts, n_ptr, w_curr, w_status, stored_desc, w_desc, w_und, is_new);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fe_lk_pipe<21>), dim3(grid), dim3(320), 0, s, pv, cv, a, a, grid, H, W, Hh, max_count, epsilon, fe->dev,
-                               (const uint8_t*)fe->ext[1], (const uint8_t*)fe->blur[1], (const uint8_t*)fe->ext[0], (const uint8_t*)fe->blur[0], fe->cam);
+        if (pipe) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fe_lk_pipe<21>), dim3(grid), dim3(320), 0, f.stream, f.pv, f.cv, a, b, grid0, H, f.width, f.height, f.term.max_count, f.term.epsilon, f.dev,
+                               f.cur_ext, f.cur_blur, f.prv_ext, f.prv_blur, f.cam);
             return;
         }
     }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fe_lk_both<WIN>), dim3(grid), dim3(128), 0, s, pv, cv, src_pts, n_ptr, H, W, Hh, max_count, epsilon, w_curr, w_status, fe->dev,
-                       (const uint8_t*)fe->ext[1], (const uint8_t*)fe->blur[1], (const uint8_t*)fe->ext[0], (const uint8_t*)fe->blur[0], stored_desc, w_desc, is_new,
-                       fe->cam, w_und);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fe_lk_both<WIN>), dim3(grid0), dim3(128), 0, f.stream, f.pv, f.cv, a.src_pts, a.n_ptr, H, f.width, f.height, f.term.max_count, f.term.epsilon,
+                       a.w_curr, a.w_status, f.dev, f.cur_ext, f.cur_blur, f.prv_ext, f.prv_blur, a.stored_desc, a.w_desc, a.is_new, f.cam, a.w_und);
+}
+static bool lk_launch_window(int patch_size, const LkFrame& f, bool pipe, const LkSet& a, const LkSet& b, int grid0, int grid, const HMat& H)
+{   // false: window not instantiated, nothing launched
+    switch (patch_size) {
+        case 21: lk_launch<21>(f, pipe, a, b, grid0, grid, H); return true;
+        case 15: lk_launch<15>(f, false, a, b, grid0, grid, H); return true;
+        case 31: lk_launch<31>(f, false, a, b, grid0, grid, H); return true;
+        default: return false;
+    }
+}
+// one workgroup either way: FM_THREADS_WIDE threads when the per-point loops (compaction, scoring, mask) are what the call costs - by the slot count, not by n
+static void commit_launch(hipStream_t stream, int mode, int cap, const lvk_pt2f* src_pts, const int* n_ptr, const lvk_pt2f* w_curr, const uint8_t* w_status, const lvk_pt2f* w_und,
+                          const unsigned long long* src_id, const lvk_pt2f* src_init, const int* src_life, const unsigned long long* desc_src,
+                          const TrackSet& dst, int* dst_n, FeDev* dev)
+{
+#define COMMIT_LAUNCH(NT) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fe_ransac_commit<NT>), dim3(1), dim3(NT), 0, stream, mode, cap, src_pts, n_ptr, w_curr, w_status, w_und, \
+                           src_id, src_init, src_life, desc_src, dst, dst_n, dev)
+    if (cap > FM_WIDE_FROM) COMMIT_LAUNCH(FM_THREADS_WIDE); else COMMIT_LAUNCH(FM_THREADS);
+#undef COMMIT_LAUNCH
+}
+static void msg_launch(hipStream_t stream, int cap, const TrackSet& ts, const int* n_ptr, const CamParams& cam, double dt_1, double dt_2, int prev_is_last,
+                       lvk_feature_obs* out, FeDev* dev, int* n_host)
+{
+    hipLaunchKernelGGL(k_fe_msg, dim3((cap + 63) / 64), dim3(64), 0, stream, ts, n_ptr, cam, dt_1, dt_2, prev_is_last, out, dev, n_host);
+}
+
+// ---- the frame path's side of it
+static LkFrame lk_frame_of(const lvk_frontend* fe, hipStream_t stream)
+{
+    return LkFrame{stream, make_view(fe->pyr[0]), make_view(fe->pyr[1]), fe->cfg.width, fe->cfg.height, lvk_lk_term(fe->cfg.max_iteration, fe->cfg.track_precision), fe->dev,
+                   fe->ext[1], fe->blur[1], fe->ext[0], fe->blur[0], fe->cam};
 }
 
 lvk_status track_chain(lvk_frontend* fe, hipStream_t stream, const lvk_pt2f* src_pts, const int* n_ptr, const HMat& H, lvk_pt2f* w_curr, uint8_t* w_status,
                        const unsigned long long* stored_desc, unsigned long long* w_desc, int is_new)
 {
-    const LkTerm term = lvk_lk_term(fe->cfg.max_iteration, fe->cfg.track_precision);
-    PyrView pv = make_view(fe->pyr[0]), cv = make_view(fe->pyr[1]);
-    switch (fe->cfg.patch_size) {
-        case 21: launch_track_chain<21>(fe, stream, pv, cv, src_pts, n_ptr, fe->cap, H, w_curr, w_status, stored_desc, w_desc, is_new, term.max_count, term.epsilon); break;
-        case 15: launch_track_chain<15>(fe, stream, pv, cv, src_pts, n_ptr, fe->cap, H, w_curr, w_status, stored_desc, w_desc, is_new, term.max_count, term.epsilon); break;
-        case 31: launch_track_chain<31>(fe, stream, pv, cv, src_pts, n_ptr, fe->cap, H, w_curr, w_status, stored_desc, w_desc, is_new, term.max_count, term.epsilon); break;
-        default: return lvk_set_error(fe->ctx, LVK_ERR_UNSUPPORTED, "patch_size %d not instantiated (15, 21, 31)", fe->cfg.patch_size);
+    const LkFrame f = lk_frame_of(fe, stream);
+    const LkSet a = lk_set(src_pts, n_ptr, w_curr, w_status, stored_desc, w_desc, w_curr == fe->w_curr ? fe->w_und : fe->wn_und, is_new);
+    const bool pipe = lvk_lk_choice(fe->cfg.patch_size, fe->cap, f.pv.n_levels, f.cv.n_levels).pipe;
+    if (fe->pyr_event) hipStreamWaitEvent(stream, fe->ev_orb, 0);      // the frame start waited for the pyramid only: the ORB planes (read by the kernel's second wavefront) follow it on the image stream
+    {
+        ProfScope ps(fe, 2, stream);
+        if (!lk_launch_window(fe->cfg.patch_size, f, pipe, a, a, fe->cap, fe->cap, H))
+            return lvk_set_error(fe->ctx, LVK_ERR_UNSUPPORTED, "patch_size %d not instantiated (15, 21, 31)", fe->cfg.patch_size);
     }
     LVK_LAUNCH_CHECK(fe->ctx);
     return LVK_OK;
@@ -437,15 +470,13 @@ lvk_status track_chain(lvk_frontend* fe, hipStream_t stream, const lvk_pt2f* src
 // trackFeatures' and trackNewFeatures' LK + descriptor gate in one launch on `stream`: blocks [0, cap) the old tracks of set `src`, [cap, 2 cap) the new points
 lvk_status track_chain_merged(lvk_frontend* fe, hipStream_t stream, int src, const HMat& H)
 {
-    const LkTerm term = lvk_lk_term(fe->cfg.max_iteration, fe->cfg.track_precision);
-    PyrView pv = make_view(fe->pyr[0]), cv = make_view(fe->pyr[1]);
+    const LkFrame f = lk_frame_of(fe, stream);
     const LkSet a = lk_set(fe->set[src].pts, &fe->dev->n_tracks[src], fe->w_curr, fe->w_status, fe->set[src].desc, nullptr, fe->w_und, 0);
     const LkSet b = lk_set(fe->new_pts, &fe->dev->n_new, fe->wn_curr, fe->wn_status, nullptr, fe->wn_desc, fe->wn_und, 1);
     if (fe->pyr_event) hipStreamWaitEvent(stream, fe->ev_orb, 0);
     {
         ProfScope ps(fe, 2, stream);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fe_lk_pipe<21>), dim3(2 * fe->cap), dim3(320), 0, stream, pv, cv, a, b, fe->cap, H, fe->cfg.width, fe->cfg.height, term.max_count, term.epsilon, fe->dev,
-                           (const uint8_t*)fe->ext[1], (const uint8_t*)fe->blur[1], (const uint8_t*)fe->ext[0], (const uint8_t*)fe->blur[0], fe->cam);
+        lk_launch<21>(f, true, a, b, fe->cap, 2 * fe->cap, H);
     }
     LVK_LAUNCH_CHECK(fe->ctx);
     return LVK_OK;
@@ -455,13 +486,8 @@ lvk_status commit(lvk_frontend* fe, int mode, const lvk_pt2f* src_pts, const int
                   const TrackSet* src, const unsigned long long* desc_src, int dst_set)
 {
     ProfScope ps(fe, 5);
-    const lvk_pt2f* w_und = w_curr == fe->w_curr ? fe->w_und : fe->wn_und;
-    // one workgroup either way: 1024 threads when the per-point loops (compaction, scoring, mask) are what the call costs
-#define COMMIT_LAUNCH(NT) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fe_ransac_commit<NT>), dim3(1), dim3(NT), 0, fe->ctx->stream, mode, fe->cap, src_pts, n_ptr, w_curr, w_status, w_und, \
-                           (const unsigned long long*)(src ? src->id : nullptr), (const lvk_pt2f*)(src ? src->init : nullptr),                                                       \
-                           (const int*)(src ? src->life : nullptr), desc_src, fe->set[dst_set], &fe->dev->n_tracks[dst_set], fe->dev)
-    if (fe->cap > FM_WIDE_FROM) COMMIT_LAUNCH(FM_THREADS_WIDE); else COMMIT_LAUNCH(FM_THREADS);
-#undef COMMIT_LAUNCH
+    commit_launch(fe->ctx->stream, mode, fe->cap, src_pts, n_ptr, w_curr, w_status, w_curr == fe->w_curr ? fe->w_und : fe->wn_und,
+                  src ? src->id : nullptr, src ? src->init : nullptr, src ? src->life : nullptr, desc_src, fe->set[dst_set], &fe->dev->n_tracks[dst_set], fe->dev);
     LVK_LAUNCH_CHECK(fe->ctx);
     return LVK_OK;
 }
@@ -470,11 +496,182 @@ lvk_status commit(lvk_frontend* fe, int mode, const lvk_pt2f* src_pts, const int
 lvk_status fe_msg_launch(lvk_frontend* fe, int dst, const FeMsgArgs& m)
 {
     ProfScope ps8(fe, 8);
-    hipLaunchKernelGGL(k_fe_msg, dim3((fe->cap + 63) / 64), dim3(64), 0, fe->ctx->stream, fe->set[dst], (const int*)&fe->dev->n_tracks[dst], fe->cam, m.dt_1, m.dt_2,
-                       m.prev_is_last, m.out, fe->dev, m.n_host);
+    msg_launch(fe->ctx->stream, fe->cap, fe->set[dst], &fe->dev->n_tracks[dst], fe->cam, m.dt_1, m.dt_2, m.prev_is_last, m.out, fe->dev, m.n_host);
     LVK_LAUNCH_CHECK(fe->ctx);
     return LVK_OK;
 }
+
+// =========================================================================== stage entries (include/lvk_c.h): the same launches on a caller's host arrays
+// Everything is checked on the host before anything is queued; buffers live for the call and every entry ends with a wait for the stream.
+namespace {
+struct StageBufs {      // device buffers of one stage call
+    lvk_context* ctx; std::vector<void*> all; bool ok = true;
+    explicit StageBufs(lvk_context* c) : ctx(c) { }
+    ~StageBufs() { for (void* p : all) hipFree(p); }
+    template <typename T> T* get(size_t n) { T* p = nullptr; if (!dalloc(&p, n)) { ok = false; (void)hipGetLastError(); return nullptr; } all.push_back(p); return p; }
+    template <typename T> T* filled(size_t n, int byte) { T* p = get<T>(n); if (p && hipMemsetAsync(p, byte, sizeof(T) * (n ? n : 1), ctx->stream) != hipSuccess) ok = false; return p; }
+    template <typename T> T* up(const T* h, size_t n) { T* p = get<T>(n); if (p && n && hipMemcpyAsync(p, h, sizeof(T) * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) ok = false; return p; }
+    template <typename T> void down(T* h, const T* d, size_t n) { if (ok && n && hipMemcpyAsync(h, d, sizeof(T) * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) ok = false; }
+};
+bool pt_finite(lvk_pt2f p) { return std::isfinite(p.x) && std::isfinite(p.y); }
+bool stage_cam(CamParams* cam, int model, const double* intr, const double* dist, int width, int height)
+{
+    if ((model != 0 && model != 1) || !intr || !dist) return false;
+    memset(cam, 0, sizeof *cam);
+    for (int i = 0; i < 4; ++i) { if (!std::isfinite(intr[i]) || !std::isfinite(dist[i])) return false; cam->intr[i] = intr[i]; cam->dist[i] = dist[i]; }
+    cam->model = model; cam->width = width; cam->height = height;
+    return true;
+}
+const char* track_set_refusal(const lvk_fe_track_io* s, int width, int height, lvk_status* code)
+{
+    *code = LVK_ERR_ARG;
+    if (s->n < 0 || s->grid < 0 || s->n > s->grid) return "0 <= n <= grid required";
+    if (s->grid > FM_MAX_N) { *code = LVK_ERR_CAPACITY; return "more slots than a front-end can have"; }
+    if (s->is_new != 0 && s->is_new != 1) return "is_new must be 0 or 1";
+    if (s->grid > 0 && (!s->h_curr || !s->h_status || !s->h_und || (s->is_new && !s->h_desc))) return "null output array";
+    if (s->n > 0 && (!s->h_src_pts || (!s->is_new && !s->h_stored_desc))) return "null input array";
+    for (int i = 0; i < s->n; ++i) {
+        const lvk_pt2f p = s->h_src_pts[i];
+        if (!pt_finite(p) || p.x < 0 || p.x > width - 1 || p.y < 0 || p.y > height - 1) return "a source point outside the image";
+    }
+    return nullptr;
+}
+}   // namespace
+
+extern "C" {
+
+lvk_status lvk_fe_track_stage(lvk_context* ctx, const lvk_pyramid* prev, const lvk_pyramid* next, const uint8_t* d_prev_ext, const uint8_t* d_prev_blur,
+                              const uint8_t* d_next_ext, const uint8_t* d_next_blur, int width, int height, int patch_size, int variant, const float H[9],
+                              int model, const double intr[4], const double dist[4], int max_iteration, double track_precision, int fill_byte,
+                              const lvk_fe_track_io* set0, const lvk_fe_track_io* set1, uint64_t h_counters[2])
+{
+    if (!ctx) return LVK_ERR_ARG;
+    if (!prev || !next || !d_prev_ext || !d_prev_blur || !d_next_ext || !d_next_blur || !H || !set0 || !h_counters) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_track_stage: null pointer");
+    if (width < 1 || height < 1 || prev->w[0] != width || prev->h[0] != height || next->w[0] != width || next->h[0] != height)
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_track_stage: pyramids are not %d x %d", width, height);
+    if (patch_size != 15 && patch_size != 21 && patch_size != 31) return lvk_set_error(ctx, LVK_ERR_UNSUPPORTED, "lvk_fe_track_stage: patch_size %d not instantiated (15, 21, 31)", patch_size);
+    if (prev->pad != patch_size || next->pad != patch_size) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_track_stage: pyramids not built for window %d", patch_size);
+    if (prev->n_levels < 1 || next->n_levels < 1) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_track_stage: a pyramid has not been built");
+    if (variant != 1 && variant != 2) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_track_stage: variant must be 1 (k_fe_lk_both) or 2 (k_fe_lk_pipe)");
+    if (variant == 2 && patch_size != 21) return lvk_set_error(ctx, LVK_ERR_UNSUPPORTED, "lvk_fe_track_stage: the five-wavefront kernel has the 21 x 21 window only");
+    if (variant == 2 && (prev->n_levels > LK_PIPE_MAX_LEVELS || next->n_levels > LK_PIPE_MAX_LEVELS))
+        return lvk_set_error(ctx, LVK_ERR_UNSUPPORTED, "lvk_fe_track_stage: the five-wavefront kernel keeps templates for %d levels", LK_PIPE_MAX_LEVELS);
+    if (variant == 1 && set1) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_track_stage: the two-set launch is the five-wavefront kernel's");
+    for (int i = 0; i < 9; ++i) if (!std::isfinite(H[i])) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_track_stage: H is not finite");
+    LkFrame f;
+    if (!stage_cam(&f.cam, model, intr, dist, width, height)) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_track_stage: bad camera");
+    const lvk_fe_track_io* io[2] = {set0, set1};
+    const int n_sets = set1 ? 2 : 1;
+    for (int k = 0; k < n_sets; ++k) {
+        lvk_status code;
+        if (const char* why = track_set_refusal(io[k], width, height, &code)) return lvk_set_error(ctx, code, "lvk_fe_track_stage: set %d: %s", k, why);
+    }
+    StageBufs B(ctx);
+    FeDev hd; memset(&hd, 0, sizeof hd);
+    hd.lk_point_levels = h_counters[0]; hd.lk_iterations = h_counters[1]; hd.n_tracks[0] = set0->n; hd.n_new = set1 ? set1->n : 0;
+    FeDev* dev = B.up(&hd, 1);
+    LkSet ls[2];
+    for (int k = 0; k < n_sets && B.ok; ++k) {
+        const lvk_fe_track_io* s = io[k];
+        ls[k] = lk_set(B.up(s->h_src_pts, s->n), k ? &dev->n_new : &dev->n_tracks[0], B.filled<lvk_pt2f>(s->grid, fill_byte), B.filled<uint8_t>(s->grid, fill_byte),
+                       s->is_new ? nullptr : (const unsigned long long*)B.up(s->h_stored_desc, (size_t)s->n * 4),
+                       s->is_new ? B.filled<unsigned long long>((size_t)s->grid * 4, fill_byte) : nullptr, B.filled<lvk_pt2f>((size_t)s->grid * 2, fill_byte), s->is_new);
+    }
+    if (!B.ok) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_fe_track_stage: allocation or copy failed");
+    const int grid0 = set0->grid, grid = grid0 + (set1 ? set1->grid : 0);
+    f.stream = ctx->stream; f.pv = make_view(prev); f.cv = make_view(next); f.width = width; f.height = height; f.term = lvk_lk_term(max_iteration, track_precision); f.dev = dev;
+    f.cur_ext = d_next_ext; f.cur_blur = d_next_blur; f.prv_ext = d_prev_ext; f.prv_blur = d_prev_blur;
+    HMat Hm; memcpy(Hm.h, H, sizeof Hm.h);
+    if (grid > 0) {                     // no slots, no launch
+        lk_launch_window(patch_size, f, variant == 2, ls[0], ls[n_sets - 1], grid0, grid, Hm);
+        LVK_LAUNCH_CHECK(ctx);
+    }
+    for (int k = 0; k < n_sets; ++k) {
+        const lvk_fe_track_io* s = io[k];
+        B.down(s->h_curr, ls[k].w_curr, s->grid); B.down(s->h_status, ls[k].w_status, s->grid); B.down(s->h_und, ls[k].w_und, (size_t)s->grid * 2);
+        if (s->is_new) B.down((unsigned long long*)s->h_desc, ls[k].w_desc, (size_t)s->grid * 4);
+    }
+    B.down(&hd, dev, 1);
+    if (!B.ok) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_fe_track_stage: copy failed");
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    h_counters[0] = hd.lk_point_levels; h_counters[1] = hd.lk_iterations;
+    return LVK_OK;
+}
+
+lvk_status lvk_fe_commit_stage(lvk_context* ctx, int mode, int cap, int n, const lvk_pt2f* h_src_pts, const lvk_pt2f* h_curr, const uint8_t* h_status, const lvk_pt2f* h_und,
+                               const uint64_t* h_src_id, const lvk_pt2f* h_src_init, const int* h_src_life, const uint64_t* h_src_desc,
+                               const lvk_fe_track_arrays* h_dst, lvk_fe_commit_state* h_state)
+{
+    if (!ctx) return LVK_ERR_ARG;
+    if (mode < 0 || mode > 2) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_commit_stage: mode must be 0, 1 or 2");
+    if (cap < 1 || n < 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_commit_stage: cap >= 1 and n >= 0 required");
+    if (cap > FM_MAX_N) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_fe_commit_stage: cap %d beyond the %d points the kernel has LDS for", cap, FM_MAX_N);
+    if (n > cap) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_fe_commit_stage: n %d beyond cap %d", n, cap);
+    if (!h_dst || !h_state || !h_dst->id || !h_dst->pts || !h_dst->ppts || !h_dst->init || !h_dst->life || !h_dst->desc) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_commit_stage: null pointer");
+    if (n > 0 && (!h_src_pts || !h_curr || !h_status || !h_und || !h_src_desc || (mode == 0 && (!h_src_id || !h_src_init || !h_src_life))))
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_commit_stage: null input array");
+    if (h_state->dst_n < 0 || h_state->dst_n > cap) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_commit_stage: dst_n %d outside [0, cap]", h_state->dst_n);
+    if (mode != 0 && h_state->n_new != n) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_commit_stage: modes 1 and 2 commit the n_new new points: n_new must equal n");
+    for (int i = 0; i < n; ++i) {
+        if (h_status[i] > ST_ORB) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_commit_stage: status byte %d of point %d", (int)h_status[i], i);
+        if (!pt_finite(h_und[2 * i]) || !pt_finite(h_und[2 * i + 1])) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_commit_stage: undistorted pair %d is not finite", i);
+    }
+    StageBufs B(ctx);
+    FeDev hd; memset(&hd, 0, sizeof hd);
+    hd.next_id = h_state->next_id; hd.n_new = h_state->n_new; hd.boot_ok = h_state->boot_ok;
+    hd.n_tracks[0] = n; hd.n_tracks[1] = h_state->dst_n;                                     // as a frame has them: the source count in n_tracks[src] (mode 0) or n_new, the destination's in n_tracks[dst]
+    FeDev* dev = B.up(&hd, 1);
+    TrackSet dst;
+    dst.id = (unsigned long long*)B.up(h_dst->id, cap); dst.pts = B.up(h_dst->pts, cap); dst.ppts = B.up(h_dst->ppts, cap); dst.init = B.up(h_dst->init, cap);
+    dst.life = B.up(h_dst->life, cap); dst.desc = (unsigned long long*)B.up(h_dst->desc, (size_t)cap * 4);
+    const lvk_pt2f* src_pts = B.up(h_src_pts, n); const lvk_pt2f* w_curr = B.up(h_curr, n); const uint8_t* w_status = B.up(h_status, n); const lvk_pt2f* w_und = B.up(h_und, (size_t)n * 2);
+    const unsigned long long* src_desc = (const unsigned long long*)B.up(h_src_desc, (size_t)n * 4);
+    const unsigned long long* src_id = mode == 0 ? (const unsigned long long*)B.up(h_src_id, n) : nullptr;
+    const lvk_pt2f* src_init = mode == 0 ? B.up(h_src_init, n) : nullptr;
+    const int* src_life = mode == 0 ? B.up(h_src_life, n) : nullptr;
+    if (!B.ok) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_fe_commit_stage: allocation or copy failed");
+    commit_launch(ctx->stream, mode, cap, src_pts, mode == 0 ? &dev->n_tracks[0] : &dev->n_new, w_curr, w_status, w_und, src_id, src_init, src_life, src_desc, dst, &dev->n_tracks[1], dev);
+    LVK_LAUNCH_CHECK(ctx);
+    B.down((unsigned long long*)h_dst->id, dst.id, cap); B.down(h_dst->pts, dst.pts, cap); B.down(h_dst->ppts, dst.ppts, cap); B.down(h_dst->init, dst.init, cap);
+    B.down(h_dst->life, dst.life, cap); B.down((unsigned long long*)h_dst->desc, dst.desc, (size_t)cap * 4);
+    B.down(&hd, dev, 1);
+    if (!B.ok) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_fe_commit_stage: copy failed");
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    h_state->next_id = hd.next_id; h_state->dst_n = hd.n_tracks[1]; h_state->n_new = hd.n_new; h_state->boot_ok = hd.boot_ok;
+    return LVK_OK;
+}
+
+lvk_status lvk_fe_msg_stage(lvk_context* ctx, const lvk_fe_track_arrays* h_set, int cap, int n, int model, const double intr[4], const double dist[4],
+                            double dt_1, double dt_2, int prev_is_last, int fill_byte, lvk_feature_obs* h_out, lvk_fe_msg_state* h_state)
+{
+    if (!ctx) return LVK_ERR_ARG;
+    if (cap < 1 || n < 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_msg_stage: cap >= 1 and n >= 0 required");
+    if (cap > FM_MAX_N) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_fe_msg_stage: cap %d beyond the %d slots a front-end can have", cap, FM_MAX_N);
+    if (n > cap) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_fe_msg_stage: n %d beyond cap %d", n, cap);
+    if (!h_set || !h_out || !h_state || !h_set->id || !h_set->pts || !h_set->ppts || !h_set->init) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_msg_stage: null pointer");
+    if (prev_is_last != 0 && prev_is_last != 1) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_msg_stage: prev_is_last must be 0 or 1");
+    if (!std::isfinite(dt_1) || !std::isfinite(dt_2)) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_msg_stage: dt is not finite");
+    CamParams cam;
+    if (!stage_cam(&cam, model, intr, dist, 0, 0)) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_fe_msg_stage: bad camera");
+    StageBufs B(ctx);
+    FeDev hd; memset(&hd, 0, sizeof hd);
+    hd.n_tracks[0] = n; hd.n_msg = h_state->n_msg; hd.msg_features = h_state->msg_features; hd.msg_count = h_state->msg_count;
+    FeDev* dev = B.up(&hd, 1);
+    TrackSet ts; memset(&ts, 0, sizeof ts);                                                    // the message reads id, pts, ppts and init, and resets init
+    ts.id = (unsigned long long*)B.up(h_set->id, cap); ts.pts = B.up(h_set->pts, cap); ts.ppts = B.up(h_set->ppts, cap); ts.init = B.up(h_set->init, cap);
+    lvk_feature_obs* out = B.filled<lvk_feature_obs>(cap, fill_byte);
+    int* n_host = B.up(&h_state->n_host, 1);
+    if (!B.ok) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_fe_msg_stage: allocation or copy failed");
+    msg_launch(ctx->stream, cap, ts, &dev->n_tracks[0], cam, dt_1, dt_2, prev_is_last, out, dev, n_host);
+    LVK_LAUNCH_CHECK(ctx);
+    B.down(h_out, out, cap); B.down(h_set->init, ts.init, cap); B.down(&h_state->n_host, n_host, 1); B.down(&hd, dev, 1);
+    if (!B.ok) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_fe_msg_stage: copy failed");
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    h_state->n_msg = hd.n_msg; h_state->msg_features = hd.msg_features; h_state->msg_count = hd.msg_count;
+    return LVK_OK;
+}
+
+}   // extern "C"
 
 // ---- readers of the instrumentation arrays: each is one copy per file, so what reads one lives with the kernels that write it
 #ifdef LVK_LK_TIMING

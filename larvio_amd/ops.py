@@ -300,3 +300,114 @@ def update_sparse(ctx, P, u, n=None):
     dP = ctx.to_device(P)
     ctx.check(L.lvk_ekf_update_sparse(ctx.h, _p(dP), P.shape[1], n, _p(u), _p(dx), _p(info)))
     return dx, ctx.to_host(dP, np.float64, P.shape), info
+
+
+# ---- stage entries of the frame path (include/lvk_c.h: lvk_fe_track_stage, lvk_fe_commit_stage, lvk_fe_msg_stage)
+class FeTrackIo(C.Structure):
+    _fields_ = [("n", C.c_int), ("grid", C.c_int), ("is_new", C.c_int), ("h_src_pts", C.c_void_p), ("h_stored_desc", C.c_void_p),
+                ("h_curr", C.c_void_p), ("h_status", C.c_void_p), ("h_und", C.c_void_p), ("h_desc", C.c_void_p)]
+
+
+class FeTrackArrays(C.Structure):
+    _fields_ = [("id", C.c_void_p), ("pts", C.c_void_p), ("ppts", C.c_void_p), ("init", C.c_void_p), ("life", C.c_void_p), ("desc", C.c_void_p)]
+
+
+class FeCommitState(C.Structure):
+    _fields_ = [("next_id", C.c_uint64), ("dst_n", C.c_int), ("n_new", C.c_int), ("boot_ok", C.c_int)]
+
+
+class FeMsgState(C.Structure):
+    _fields_ = [("n_msg", C.c_int), ("n_host", C.c_int), ("msg_features", C.c_uint64), ("msg_count", C.c_uint64)]
+
+
+def _hp(a):
+    return a.ctypes.data if a is not None else None
+
+
+def _finish(ctx, st, check):
+    if check:
+        ctx.check(st)
+    return st
+
+
+def fe_track_stage(ctx, prev, nxt, sets, patch_size, variant, H, model, intr, dist, max_iteration=30, track_precision=0.01,
+                   fill=0xA5, counters=(0, 0), width=None, height=None, check=True):
+    """lvk_fe_track_stage.  prev / nxt: built Pyramids whose orb_prepare() has run.  sets: one or two dicts with pts (n, 2), grid (slots,
+    default n), is_new and - for old tracks - stored_desc (n, 32) uint8; a key `n` overrides the count.  -> (status, [dict(curr (grid, 2), status (grid,),
+    und (grid, 2, 2), desc (grid, 32) or None)], (point_levels, iterations)); every output array starts as the byte `fill`."""
+    L = lib()
+    vp, i, d = C.c_void_p, C.c_int, C.c_double
+    L.lvk_fe_track_stage.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp, i, vp, vp, i, d, i, vp, vp, vp]; L.lvk_fe_track_stage.restype = i
+    ios, outs, keep = [], [], []
+    for s in sets:
+        p = _pts(s["pts"]); n = int(s.get("n", len(p))); grid = int(s.get("grid", len(p))); is_new = int(s["is_new"])
+        sd = None if s.get("stored_desc") is None else np.ascontiguousarray(s["stored_desc"], np.uint8)
+        g = max(grid, 1)
+        o = dict(curr=np.full((g, 2), 0, np.float32), status=np.full(g, fill, np.uint8), und=np.zeros((g, 2, 2), np.float32),
+                 desc=np.full((g, 32), fill, np.uint8) if is_new == 1 else None)
+        o["curr"].view(np.uint8)[...] = fill; o["und"].view(np.uint8)[...] = fill
+        if s.get("null_out"):
+            o["curr"] = None
+        ios.append(FeTrackIo(n, grid, is_new, _hp(p), _hp(sd), _hp(o["curr"]), _hp(o["status"]), _hp(o["und"]), _hp(o["desc"])))
+        keep += [p, sd]; outs.append(o)
+    Hc = None if H is None else np.ascontiguousarray(H, np.float32).reshape(9)
+    a = np.asarray(intr, np.float64); dd = np.asarray(dist, np.float64)
+    cnt = np.array(counters, np.uint64)
+    st = L.lvk_fe_track_stage(ctx.h, prev.h_, nxt.h_, _p(prev.d_ext), _p(prev.d_blur), _p(nxt.d_ext), _p(nxt.d_blur),
+                              prev.w if width is None else width, prev.h if height is None else height, patch_size, variant, _p(Hc), model, _p(a), _p(dd),
+                              max_iteration, track_precision, fill, C.byref(ios[0]), C.byref(ios[1]) if len(ios) > 1 else None, _p(cnt))
+    _finish(ctx, st, check)
+    for o, s in zip(outs, ios):
+        for k in ("curr", "status", "und", "desc"):
+            if o[k] is not None:
+                o[k] = o[k][:s.grid]
+    return st, outs, (int(cnt[0]), int(cnt[1]))
+
+
+def track_set_arrays(cap, fill=0xA5):
+    """a track set of cap slots whose every byte is `fill`: dict(id, pts, ppts, init, life, desc)"""
+    t = dict(id=np.zeros(cap, np.uint64), pts=np.zeros((cap, 2), np.float32), ppts=np.zeros((cap, 2), np.float32), init=np.zeros((cap, 2), np.float32),
+             life=np.zeros(cap, np.int32), desc=np.zeros((cap, 32), np.uint8))
+    for v in t.values():
+        v.view(np.uint8)[...] = fill
+    return t
+
+
+def _track_arrays(t):
+    return FeTrackArrays(*[_hp(t.get(k)) for k in ("id", "pts", "ppts", "init", "life", "desc")])
+
+
+def fe_commit_stage(ctx, mode, cap, src, dst, state, n=None, check=True):
+    """lvk_fe_commit_stage.  src: dict(pts (n, 2), curr (n, 2), status (n,), und (n, 2, 2), desc (n, 32) and, mode 0, id, init, life); dst: a
+    track_set_arrays(cap) dict, updated in place; state: dict(next_id, dst_n, n_new, boot_ok), a new one is returned.  -> (status, state)"""
+    L = lib()
+    vp, i = C.c_void_p, C.c_int
+    L.lvk_fe_commit_stage.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]; L.lvk_fe_commit_stage.restype = i
+    f32 = lambda k, shape: None if src.get(k) is None else np.ascontiguousarray(src[k], np.float32).reshape(shape)
+    p, c, u, ini = f32("pts", (-1, 2)), f32("curr", (-1, 2)), f32("und", (-1, 2, 2)), f32("init", (-1, 2))
+    stt = None if src.get("status") is None else np.ascontiguousarray(src["status"], np.uint8)
+    ids = None if src.get("id") is None else np.ascontiguousarray(src["id"], np.uint64)
+    life = None if src.get("life") is None else np.ascontiguousarray(src["life"], np.int32)
+    desc = None if src.get("desc") is None else np.ascontiguousarray(src["desc"], np.uint8)
+    n = len(stt) if n is None else int(n)
+    cs = FeCommitState(int(state["next_id"]), int(state["dst_n"]), int(state["n_new"]), int(state["boot_ok"]))
+    ta = _track_arrays(dst)
+    st = L.lvk_fe_commit_stage(ctx.h, mode, cap, n, _hp(p), _hp(c), _hp(stt), _hp(u), _hp(ids), _hp(ini), _hp(life), _hp(desc), C.byref(ta), C.byref(cs))
+    _finish(ctx, st, check)
+    return st, dict(next_id=int(cs.next_id), dst_n=cs.dst_n, n_new=cs.n_new, boot_ok=cs.boot_ok)
+
+
+def fe_msg_stage(ctx, tset, cap, n, model, intr, dist, dt_1, dt_2, prev_is_last, state, fill=0xA5, check=True):
+    """lvk_fe_msg_stage.  tset: dict(id, pts, ppts, init) of cap slots, init updated in place; state: dict(n_msg, n_host, msg_features,
+    msg_count), a new one is returned.  -> (status, message (cap,) OBS records whose slots >= n keep the byte `fill`, state)"""
+    from ._lib import OBS
+    L = lib()
+    vp, i, d = C.c_void_p, C.c_int, C.c_double
+    L.lvk_fe_msg_stage.argtypes = [vp, vp, i, i, i, vp, vp, d, d, i, i, vp, vp]; L.lvk_fe_msg_stage.restype = i
+    out = np.zeros(max(cap, 1), OBS); out.view(np.uint8)[...] = fill
+    ms = FeMsgState(int(state["n_msg"]), int(state["n_host"]), int(state["msg_features"]), int(state["msg_count"]))
+    ta = _track_arrays(tset)
+    a = np.asarray(intr, np.float64); dd = np.asarray(dist, np.float64)
+    st = L.lvk_fe_msg_stage(ctx.h, C.byref(ta), cap, n, model, _p(a), _p(dd), dt_1, dt_2, prev_is_last, fill, _p(out), C.byref(ms))
+    _finish(ctx, st, check)
+    return st, out[:max(cap, 0)], dict(n_msg=ms.n_msg, n_host=ms.n_host, msg_features=int(ms.msg_features), msg_count=int(ms.msg_count))
