@@ -65,6 +65,12 @@ class LarVio {
     bool addFix(const lvk_fix& fix);
     bool setFixOptions(double gate_scale, double max_gap_s);
     void takeFixReports(std::vector<lvk_fix_report>& reports);
+    // not in the reference: image observations of points whose world position is known, all made in one image, fused on that image's
+    // clone (lvk_ekf_add_landmark_obs / lvk_ekf_set_landmark_options / lvk_ekf_take_landmark_reports / lvk_ekf_landmark_stats, lvk_c.h)
+    bool addLandmarkObs(long long tag, long long clone_id, double time, const std::vector<lvk_landmark_obs>& obs);
+    bool setLandmarkOptions(double gate_scale, double min_depth);
+    void takeLandmarkReports(std::vector<lvk_landmark_report>& reports);
+    void landmarkStats(long out12[12]);
 
     typedef boost::shared_ptr<LarVio> Ptr;
     typedef boost::shared_ptr<const LarVio> ConstPtr;

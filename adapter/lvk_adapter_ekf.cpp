@@ -249,6 +249,37 @@ void LarVio::takeFixReports(std::vector<lvk_fix_report>& reports)
     }
 }
 
+bool LarVio::addLandmarkObs(long long tag, long long clone_id, double time, const std::vector<lvk_landmark_obs>& obs)
+{
+    finish();                                             // (a batch queued behind a deferred update that nobody has waited for is refused)
+    return ekf && lvk_ekf_add_landmark_obs(ekf, tag, clone_id, time, obs.data(), (int)obs.size()) == LVK_OK;
+}
+
+bool LarVio::setLandmarkOptions(double gate_scale, double min_depth)
+{
+    finish();
+    return ekf && lvk_ekf_set_landmark_options(ekf, gate_scale, min_depth) == LVK_OK;
+}
+
+void LarVio::takeLandmarkReports(std::vector<lvk_landmark_report>& reports)
+{
+    finish();
+    reports.clear();
+    std::vector<lvk_landmark_report> buf(64);
+    for (;;) {
+        const int n = ekf ? lvk_ekf_take_landmark_reports(ekf, buf.data(), 64) : 0;
+        reports.insert(reports.end(), buf.begin(), buf.begin() + n);
+        if (n < 64) break;
+    }
+}
+
+void LarVio::landmarkStats(long out12[12])
+{
+    finish();
+    for (int i = 0; i < 12; ++i) out12[i] = 0;
+    if (ekf) lvk_ekf_landmark_stats(ekf, out12);
+}
+
 bool LarVio::getWindowCov(std::vector<long long>& ids, std::vector<double>& cov_abs36, std::vector<double>& cov_rel36)
 {
     finish();

@@ -87,7 +87,7 @@ int main(int argc, char** argv)
         lvk::EurocArgs o; std::string bad;
         if (!lvk::parse_euroc_args(argc, argv, 3, &o, &bad)) { std::fprintf(stderr, "unknown option %s\n", bad.c_str()); return 1; }
         const struct { const char* name; std::string value; } all[] = {{"tum", o.tum}, {"mask", o.mask}, {"map_out", o.map_out}, {"msckf_out", o.msckf_out},
-            {"keyframes_out", o.keyframes_out}, {"depth_out", o.depth_out}, {"fixes", o.fixes}, {"fix_max_gap", std::to_string(o.fix_max_gap)}, {"max_frames", std::to_string(o.max_frames)}, {"pipelined", o.pipelined ? "1" : "0"}};
+            {"keyframes_out", o.keyframes_out}, {"depth_out", o.depth_out}, {"fixes", o.fixes}, {"fix_max_gap", std::to_string(o.fix_max_gap)}, {"landmarks", o.landmarks}, {"max_frames", std::to_string(o.max_frames)}, {"pipelined", o.pipelined ? "1" : "0"}};
         const std::string want = argv[2];
         for (size_t lo = 0; lo <= want.size();) {
             size_t hi = want.find(',', lo); if (hi == std::string::npos) hi = want.size();
@@ -109,6 +109,15 @@ int main(int argc, char** argv)
         for (int i = 0; i < 14; ++i) std::printf("%.17g%c", v[i], i == 13 ? '\n' : ' ');
         return 0;
     }
+    if (argc == 3 && !std::strcmp(argv[1], "landmark-batches")) {      // "batch b time t n k" per batch, then every line's 8 numbers
+        lvk::LandmarkFile lf;
+        if (!lf.load(argv[2])) { std::perror(argv[2]); return 1; }
+        for (size_t b = 0; b < lf.batches(); ++b) {
+            std::printf("batch %zu time %.17g n %zu\n", b, lf.rows[8 * lf.first[b]], lf.first[b + 1] - lf.first[b]);
+            for (size_t k = lf.first[b]; k < lf.first[b + 1]; ++k) for (int i = 0; i < 8; ++i) std::printf("%.17g%c", lf.rows[8 * k + i], i == 7 ? '\n' : ' ');
+        }
+        return 0;
+    }
     if (argc == 92 && !std::strcmp(argv[1], "keyframe-line")) {
         double v[88]; for (int i = 0; i < 88; ++i) v[i] = std::strtod(argv[4 + i], nullptr);
         lvk::write_keyframe(stdout, std::atoll(argv[2]), std::atoll(argv[3]), v);
@@ -119,6 +128,6 @@ int main(int argc, char** argv)
         lvk::write_msckf_point(stdout, std::atoll(argv[2]), v, v + 3, std::atoi(argv[15]));
         return 0;
     }
-    std::fprintf(stderr, "usage: host_tools config|png|imu|images|euroc-args|euroc-args-all|euroc-args-fields|msckf-line|keyframe-line|depth-line|fix-line ...\n");
+    std::fprintf(stderr, "usage: host_tools config|png|imu|images|euroc-args|euroc-args-all|euroc-args-fields|msckf-line|keyframe-line|depth-line|fix-line|landmark-batches ...\n");
     return 2;
 }

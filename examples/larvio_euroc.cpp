@@ -2,7 +2,7 @@
 // Pangolin): same command line, same loop, same log files (msckf_2_state.txt / msckf_2_takeoff.txt in the configuration's
 // output_dir, written by lvk::LarVio as larvio.cpp:388,446-453 does), running on liblvk_hip.so.
 //
-//   larvio_euroc path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE] [--keyframes-out FILE] [--depth-out FILE] [--fixes FILE] [--fix-max-gap S]
+//   larvio_euroc path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE] [--keyframes-out FILE] [--depth-out FILE] [--fixes FILE] [--fix-max-gap S] [--landmarks FILE]
 //
 // --mask restricts corner detection to the non-zero pixels of an 8-bit PNG of the configured resolution (ImageProcessor::setMask:
 // a fisheye vignette, the vehicle's own body); a mask of another size is an error.
@@ -106,6 +106,27 @@ struct DepthOut {
     void close() { if (f) { std::fclose(f); f = nullptr; } }
 };
 
+// --landmarks reads image observations of points whose position in the filter's world frame is known (LarVio::addLandmarkObs; lvk_c.h,
+// lvk_ekf_add_landmark_obs) from a csv file with the columns "time,px,py,pz,u,v,sigma[,sigma_w]" (time on the IMU clock, ascending;
+// u, v normalised).  Consecutive lines with equal time form one batch, queued by time before the first frame whose stamp reaches it.  A
+// last line "landmarks batches .. applied .." reports the outcome.  Not with --pipelined, as --fixes.
+struct Landmarks {
+    lvk::LandmarkFile file; size_t next; long refused;
+    void queue_up_to(lvk::LarVio& Estimator, double stamp)
+    {
+        for (; next < file.batches() && file.rows[8 * file.first[next]] <= stamp; ++next) {
+            std::vector<lvk_landmark_obs> obs;
+            for (size_t k = file.first[next]; k < file.first[next + 1]; ++k) {
+                const double* v = &file.rows[8 * k];
+                lvk_landmark_obs o = lvk_landmark_obs();
+                for (int i = 0; i < 3; ++i) { o.p_w[i] = v[1 + i]; o.cov_w[4 * i] = v[7] * v[7]; }
+                o.uv[0] = v[4]; o.uv[1] = v[5]; o.sigma = v[6];
+                obs.push_back(o);
+            }
+            if (!Estimator.addLandmarkObs((long long)next, -1, file.rows[8 * file.first[next]], obs)) ++refused;
+        }
+    }
+};
 // --fixes: the file's lines in order; next = the first one not queued yet
 struct Fixes {
     std::vector<lvk_fix> all; size_t next; long refused;
@@ -183,7 +204,7 @@ static int run_pipelined(const char* image_dir, const std::vector<lvk::ImuData>&
 int main(int argc, char** argv)
 {
     if (argc < 5) {
-        std::fprintf(stderr, "Usage: %s path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE] [--keyframes-out FILE] [--depth-out FILE] [--fixes FILE] [--fix-max-gap S]\n", argv[0]);
+        std::fprintf(stderr, "Usage: %s path_to_imu/data.csv path_to_cam0/data.csv path_to_cam0/data config_file_path [--tum traj.txt] [--max-frames N] [--pipelined] [--mask FILE.png] [--map-out FILE] [--msckf-out FILE] [--keyframes-out FILE] [--depth-out FILE] [--fixes FILE] [--fix-max-gap S] [--landmarks FILE]\n", argv[0]);
         return 1;
     }
     lvk::EurocArgs opt; std::string bad;
@@ -237,6 +258,11 @@ int main(int argc, char** argv)
     }
     DepthOut depth_out = {nullptr, 0};
     if (!opt.depth_out.empty() && !(depth_out.f = std::fopen(opt.depth_out.c_str(), "w"))) { std::perror(opt.depth_out.c_str()); return 1; }
+    Landmarks landmarks = {lvk::LandmarkFile(), 0, 0};
+    if (!opt.landmarks.empty()) {
+        if (pipelined) { std::fprintf(stderr, "larvio_euroc: --landmarks is not available with --pipelined\n"); return 1; }
+        if (!landmarks.file.load(opt.landmarks)) { std::perror(opt.landmarks.c_str()); return 1; }
+    }
     Fixes fixes = {std::vector<lvk_fix>(), 0, 0};
     if (!opt.fixes.empty()) {
         if (pipelined) { std::fprintf(stderr, "larvio_euroc: --fixes is not available with --pipelined\n"); return 1; }
@@ -268,6 +294,7 @@ int main(int argc, char** argv)
         const Clock::time_point t2 = Clock::now();
         bool bPubOdo = false;
         fixes.queue_up_to(Estimator, ts);
+        landmarks.queue_up_to(Estimator, ts);
         if (bProcess) bPubOdo = Estimator.processFeatures(&features, imu_msg_buffer);
         const Clock::time_point t3 = Clock::now();
         t_io += std::chrono::duration<double>(t1 - t0).count();
@@ -290,6 +317,11 @@ int main(int argc, char** argv)
     std::printf("front-end %.3f ms/frame   back-end %.3f ms/message   image read+decode %.3f ms/frame\n", n_fe ? 1e3 * t_fe / n_fe : 0.0,
                 n_be ? 1e3 * t_be / n_be : 0.0, n_fe ? 1e3 * t_io / n_fe : 0.0);
     if (t_fe + t_be > 0) std::printf("processing rate %.1f frames/s (front-end + back-end, sequential, host buffers)\n", n_fe / (t_fe + t_be));
+    if (!opt.landmarks.empty()) {
+        long st[12]; Estimator.landmarkStats(st);
+        std::printf("landmarks batches %zu refused %ld queued %ld applied %ld all_rejected %ld not_pd %ld stale %ld no_clone %ld waiting %ld obs %ld used %ld gated %ld behind %ld\n",
+                    landmarks.file.batches(), landmarks.refused, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9], st[10]);
+    }
     if (!opt.fixes.empty()) {
         long st[8]; lvk_ekf_fix_stats(Estimator.handle(), st);
         std::printf("fixes read %zu refused %ld queued %ld applied %ld gated %ld not_pd %ld stale %ld no_clone %ld waiting %ld interpolated %ld\n", fixes.all.size(), fixes.refused,

@@ -5,10 +5,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 namespace lvk {
 
-struct EurocArgs { std::string tum, mask, map_out, msckf_out, keyframes_out, depth_out, fixes; long max_frames; bool pipelined; double fix_max_gap;
+struct EurocArgs { std::string tum, mask, map_out, msckf_out, keyframes_out, depth_out, fixes, landmarks; long max_frames; bool pipelined; double fix_max_gap;
                    EurocArgs() : max_frames(-1), pipelined(false), fix_max_gap(0.0) {} };
 
 // argv[first..]: false, with the offending word in *bad, on an unknown option or an option without its value
@@ -25,6 +26,7 @@ inline bool parse_euroc_args(int argc, char** argv, int first, EurocArgs* o, std
         else if (!std::strcmp(argv[a], "--depth-out") && a + 1 < argc) o->depth_out = argv[++a];
         else if (!std::strcmp(argv[a], "--fixes") && a + 1 < argc) o->fixes = argv[++a];
         else if (!std::strcmp(argv[a], "--fix-max-gap") && a + 1 < argc) o->fix_max_gap = std::atof(argv[++a]);
+        else if (!std::strcmp(argv[a], "--landmarks") && a + 1 < argc) o->landmarks = argv[++a];
         else { if (bad) *bad = argv[a]; return false; }
     }
     return true;
@@ -71,5 +73,45 @@ inline bool parse_fix_line(const char* line, double v[14])
     }
     return (n == 11 || n == 14) && (v[1] == 0.0 || v[1] == 1.0);
 }
+
+// one --landmarks line: "time,px,py,pz,u,v,sigma[,sigma_w]" - an observation (u, v, normalised image coordinates, standard deviation
+// sigma) made in the image at `time` (IMU clock) of the point (px, py, pz) of the filter's world frame, known to an isotropic standard
+// deviation sigma_w (0 when absent).  v: the 8 numbers in that order.  false: not such a line (a comment, a header, too few fields).
+inline bool parse_landmark_line(const char* line, double v[8])
+{
+    for (int i = 0; i < 8; ++i) v[i] = 0.0;
+    int n = 0; const char* p = line;
+    while (n < 8) {
+        char* end = nullptr; const double x = std::strtod(p, &end);
+        if (end == p) break;
+        v[n++] = x; p = end;
+        while (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n') ++p;
+        if (*p != ',') break;
+        ++p;
+    }
+    return n == 7 || n == 8;
+}
+
+// the batches of a --landmarks file: consecutive lines with equal time form one batch.  rows: 8 doubles per line as parse_landmark_line
+// gives them, in file order; first[b] .. first[b + 1]: the lines of batch b
+struct LandmarkFile {
+    std::vector<double> rows; std::vector<size_t> first;
+    size_t batches() const { return first.empty() ? 0 : first.size() - 1; }
+    bool load(const std::string& path)
+    {
+        FILE* f = std::fopen(path.c_str(), "r");
+        if (!f) return false;
+        char line[1024]; size_t n = 0;
+        while (std::fgets(line, sizeof line, f)) {
+            double v[8];
+            if (!parse_landmark_line(line, v)) continue;
+            if (n == 0 || v[0] != rows[8 * (n - 1)]) first.push_back(n);
+            rows.insert(rows.end(), v, v + 8); ++n;
+        }
+        std::fclose(f);
+        if (n) first.push_back(n);
+        return true;
+    }
+};
 
 }   // namespace lvk

@@ -539,6 +539,70 @@ typedef struct { int m;            /* 3 or 6 rows */
 lvk_status lvk_ekf_update_sparse(lvk_context* ctx, double* d_P, int ldp, int n, const lvk_sparse_update* h_u,
                                  double* h_dx /* n */, double* h_info4);
 
+/* lvk_ekf_update_landmarks: up to 1024 image observations, all made in ONE image - of one clone b of the window - of points whose world
+ * position is known (surveyed fiducials, the points of an earlier session, a prior map), fused directly into a device-resident
+ * covariance (n x n, row-major, leading dimension ldp) - the update behind lvk_ekf_add_landmark_obs.  No reference counterpart.
+ * Conventions (those of lvk_ekf_landmark_rel_cov and lvk_ekf_pose_rel_cov): R(q) maps body to world, the injection is
+ * R_b <- (I + [d_theta_b]x) R_b, p_b <- p_b + d_p_b, R_b2c <- R_b2c R(d_theta_e)^T, t_c_b <- t_c_b + d_t; the clone has columns
+ * clone_col .. clone_col + 5 (d_theta_b, d_p_b), the extrinsics 15..20 (d_theta_e, d_t).  For a world point p_w with covariance
+ * Sigma_w, a normalised image observation z = (u, v) and pixel noise sigma (in normalised units):
+ *   g = p_w - p_b,   y = R_b^T g - t_c_b,   p_c = R_b2c y,   h = (p_c.x / p_c.z, p_c.y / p_c.z),   r = z - h
+ * (g is that subtraction before anything else: the size of the world coordinates stays out of the rounding).  Twelve columns of P
+ * matter, in ascending order: 15..20, then the clone's six.  With M = R_b2c R_b^T the derivative of p_c is that of
+ * lvk_ekf_landmark_rel_cov with the anchor terms dropped,
+ *   d p_c = [R_b2c [y]x | -R_b2c | M [g]x | -M] [d_theta_e; d_t; d_theta_b; d_p_b],   d p_c / d p_w = M,
+ *   H = J (d p_c) (2 x 12),  J = [1/z 0 -x/z^2; 0 1/z -y/z^2],   R_k = sigma^2 I + J M Sigma_w M^T J^T
+ * (Sigma_w may be all zeros; only its upper triangle, diagonal included, is read).  The extrinsics columns are always named: when
+ * the extrinsics are not estimated their block of P is zero and they drop out.  (The signs were confirmed against the injection by
+ * central differences: tests/landmark_fix_ref.py.)
+ * On the covariance as it is before the batch, observation by observation: p_c.z <= min_depth: BEHIND, nothing else is computed for
+ * it (no division, no NaN), gamma_k = 0.  Otherwise gamma_k = r^T (H P_s H^T + R_k)^-1 r (P_s: the 12 x 12 sub-block), and with
+ * gate > 0 the observation is USED iff gamma_k <= gate, else GATED (a pivot of that 2 x 2 that is not > 0 - possible only with an
+ * indefinite P - counts as GATED with gamma_k = 0, and so does a pivot of R_k that is not > 0: a Sigma_w so many orders above sigma^2
+ * that rounding leaves R_k indefinite).  The rows of a used observation are whitened by the Cholesky factor of R_k (unit
+ * noise) and stacked, in the batch's order, as 2 n_used x 12 with the residual as a thirteenth column.  More than 12 rows are
+ * compressed by Householder reflections applied to [0 (12 x 13); A]: reflection j involves row j of the zero block and all of A
+ * (so its arithmetic is a_j.a_k / |a_j| for the new row and a_k - (a_j.a_k / a_j.a_j) a_j for what remains: no Gram matrix is formed
+ * or factored, PARITY.md records why not).  The twelve columns act through the camera's pose alone, so the rows have rank 6 at the
+ * most, and the rank is decided on the device: a column of which the reflections before it have left no more than 2^-60 of its
+ * squared norm depends on them and gives no row (what it keeps is rounding, 1e-30 of the squared norm; an independent direction keeps
+ * 1e-6 and more).  The compressed system has as many rows as the stacked one has rank - 6 for points in general position - and none
+ * of rounding noise.  The part of the residual outside the range of the rows is dropped, as in every compression of the filter: the
+ * batch's gamma of a compressed batch is that of the part inside it.
+ * Then, m <= 12 rows:  S = H P_s H^T + I = L L^T,  W = L^-1 H P[cols, :],  dx = W^T L^-1 r,  P <- P - W^T W.
+ * Three launches and one wait.  The first, one workgroup with one lane per observation, forms rows, gates, whitens and compresses;
+ * the second (one wavefront per 64 columns, every workgroup forming S, L and y by itself with the same bits) writes W and dx; the
+ * third subtracts W^T W.  Every sum runs in a fixed order: the same input gives the same bits, the per-observation results do not
+ * depend on where an observation stands in the batch, and the compressed system depends on the used observations and their order
+ * only - a batch and the same batch without its gated and behind observations give the same dx and P bit for bit.  No floating-point
+ * atomics.  P[i][j] and P[j][i] are formed from the same operands in the same order: a symmetric P stays symmetric bit for bit.  No
+ * kernel writes what a sibling workgroup of the same launch reads.  "Nothing to apply" is decided on the device: with n_used = 0 or a
+ * pivot of S that is not > 0 not one byte of P changes and dx is all zeros.  Before the second launch nothing of P outside the twelve
+ * rows AND columns is read (and with nothing to apply nothing ever is); nothing outside [0, n) x [0, n) is read or written at all.
+ * h_dx: n doubles.  h_info8: [0] batch status - 0 applied, 1 all rejected (n_used = 0), 2 S not positive definite; [1] the batch's
+ * gamma = |L^-1 r|^2 of the system that was applied (0 unless applied); [2] the smallest pivot of S (with status 2 the failing one, 0
+ * with status 1); [3] n_used [4] n_gated [5] n_behind [6] rows m after compression (2 n_used up to 6 used observations, else the rank) [7] 0.
+ * h_status[n_obs]: 0 used, 1 gated, 2 behind.  h_gamma[n_obs]: gamma_k.
+ * At most 1024 observations: LVK_ERR_CAPACITY beyond.  n_obs == 0 is LVK_OK, launches nothing and writes nothing (h_obs may be null).
+ * LVK_ERR_ARG, with nothing launched and the context still usable: a null pointer, ldp < n, clone_col < 21 or clone_col + 6 > n, a
+ * value that is read and is not finite, sigma <= 0, a cov_w whose upper triangle is not positive semi-definite (its principal minors,
+ * on the host), |q_b| off 1 by more than 1e-6, min_depth < 0. */
+#define LVK_LANDMARK_USED   0
+#define LVK_LANDMARK_GATED  1
+#define LVK_LANDMARK_BEHIND 2
+typedef struct { int clone_col, pad0;            /* first of the clone's six columns */
+                 double q_b[4], p_b[3];          /* the clone's pose */
+                 double R_b2c[9], t_c_b[3];      /* the extrinsics, as lvk_ekf_get_state hands them out */
+                 double gate;                    /* an observation is used iff gamma_k <= gate; <= 0: no gate */
+                 double min_depth; }             /* p_c.z <= min_depth: behind */
+        lvk_landmark_fix_job;
+typedef struct { double p_w[3], cov_w[9];        /* world point and its covariance (row-major; the upper triangle is read) */
+                 double uv[2], sigma; }          /* normalised image observation and its standard deviation */
+        lvk_landmark_obs;
+lvk_status lvk_ekf_update_landmarks(lvk_context* ctx, double* d_P, int ldp, int n, const lvk_landmark_fix_job* h_job,
+                                    const lvk_landmark_obs* h_obs, int n_obs, double* h_dx /* n */, double* h_info8,
+                                    int* h_status /* n_obs */, double* h_gamma /* n_obs */);
+
 typedef struct {
     /* names and meaning as LarVio::loadParameters reads them (larvio.cpp:58-311, config/euroc.yaml) */
     int if_fej, estimate_extrin, estimate_td, if_zupt_valid;
@@ -796,6 +860,44 @@ lvk_status lvk_ekf_add_fix(lvk_ekf* e, const lvk_fix* h_fix);              /* qu
 lvk_status lvk_ekf_set_fix_options(lvk_ekf* e, double gate_scale, double max_gap_s);
 int        lvk_ekf_take_fix_reports(lvk_ekf* e, lvk_fix_report* h_out, int cap);
 void       lvk_ekf_fix_stats(const lvk_ekf* e, long* h_out8);
+/* Observations of known landmarks: localising against a prior map.  Where lvk_ekf_add_fix takes a finished pose with a covariance, this
+ * takes what a vision caller has before any PnP: image observations (normalised coordinates, as the filter's own features) of points
+ * whose position in the FILTER's world frame is known, each with its own covariance - surveyed fiducial corners, the output of
+ * lvk_ekf_take_msckf_points / lvk_ekf_take_lost_features_cov of an earlier lap, a prior map.  The filter fuses them directly
+ * (lvk_ekf_update_landmarks: measurement model, gate, compression), correlation with the extrinsics included, and five points or
+ * fewer - where a PnP has no answer - still count.  No reference counterpart.
+ * lvk_ekf_add_landmark_obs queues one BATCH: the observations made in one image, i.e. of one clone (at most 1024 observations per
+ * batch and 16 batches waiting: LVK_ERR_CAPACITY beyond; n_obs = 0 is a legal, empty batch).  The target clone follows the rules of
+ * lvk_ekf_add_fix without the interpolation: clone_id >= 0 names it (not in the window: LVK_LANDMARKS_STALE); clone_id == -1 goes by
+ * time - equal (==) to a clone's time: that clone; older than the oldest clone: STALE; newer than the newest: the batch stays queued;
+ * anything else, strictly between two clones included: LVK_LANDMARKS_NO_CLONE.
+ * Every update applies the queue right behind the fix queue - after the zero-velocity check, before the lost-feature update - in queue
+ * order, each batch one lvk_ekf_update_landmarks on the filter's covariance (three launches, one wait) plus the state injection.  An
+ * empty queue costs nothing, an empty batch launches nothing, and a run that never queues a batch keeps its bits.
+ * lvk_ekf_set_landmark_options: the gate of one observation is gate_scale times the filter's own table entry for 2 degrees of freedom
+ * (the reference's 5 % quantile, 0.1026): the default scale of 1 is as strict as the filter is with its features; the usual 99.9 %
+ * gate is 13.816 / 0.1026 = 134.7.  A scale <= 0 disables the gate; a NaN is LVK_ERR_ARG.  min_depth (default 0.1, >= 0) is the depth
+ * in the camera frame at or below which an observation counts as behind the camera.
+ * One lvk_landmark_report per consumed batch (lvk_ekf_take_landmark_reports drains them in order, up to cap per call, and returns the
+ * count; the list is capped like the fix reports): tag, status, the clone's id (-1 for STALE and NO_CLONE), n_obs, n_used, n_gated,
+ * n_behind and the batch's gamma (0 unless APPLIED).  ALL_REJECTED (no observation was used; an empty batch too) and NOT_PD leave state
+ * and covariance exactly as they were.  lvk_ekf_landmark_stats: [0] batches queued so far [1] applied [2] all rejected [3] not positive
+ * definite [4] stale [5] no clone [6] waiting now [7] observations in consumed batches [8] used [9] gated [10] behind [11] 0.
+ * lvk_ekf_counters, lvk_ekf_last_update and lvk_ekf_config are unchanged.
+ * Refusals: LVK_ERR_UNSUPPORTED while a shard transport is set, and a transport is refused while batches wait; LVK_ERR_ARG for what
+ * lvk_ekf_update_landmarks refuses in an observation, a time that is not finite, a clone_id below -1; between lvk_ekf_process_async
+ * and the call that waits for it an add is LVK_ERR_ARG, as for fixes; with a lvk_vio_pipe, adds are legal only between
+ * lvk_vio_pipe_drain and the next lvk_vio_pipe_submit. */
+#define LVK_LANDMARKS_APPLIED      0
+#define LVK_LANDMARKS_ALL_REJECTED 1
+#define LVK_LANDMARKS_NOT_PD       2
+#define LVK_LANDMARKS_STALE        3
+#define LVK_LANDMARKS_NO_CLONE     4
+typedef struct { int64_t tag; int status, n_obs; int64_t clone_id; int n_used, n_gated, n_behind, pad0; double gamma; } lvk_landmark_report;
+lvk_status lvk_ekf_add_landmark_obs(lvk_ekf* e, int64_t tag, int64_t clone_id, double time, const lvk_landmark_obs* h_obs, int n_obs);
+lvk_status lvk_ekf_set_landmark_options(lvk_ekf* e, double gate_scale, double min_depth);
+int        lvk_ekf_take_landmark_reports(lvk_ekf* e, lvk_landmark_report* h_out, int cap);
+void       lvk_ekf_landmark_stats(const lvk_ekf* e, long* h_out12);
 /* What the moving-start initialiser (FlexibleInitializer.cpp:11-25 -> DynamicInitializer.cpp) handed to the filter, with the intermediate
  * results of the successful attempt - for parity tests against an independent restatement fed the same messages:
  *   valid        1 once the dynamic initialiser has succeeded on this handle (0: never ran, or the static one fired)

@@ -255,6 +255,23 @@ public:
         const int n = ekf_ ? lvk_ekf_take_fix_reports(ekf_, out.data(), 256) : 0;
         out.resize((size_t)n);
     }
+    // Observations of known landmarks (lvk_ekf_add_landmark_obs / lvk_ekf_set_landmark_options / lvk_ekf_take_landmark_reports; the
+    // measurement model, target clone, gate and refusals in lvk_c.h): addLandmarkObs queues the observations made in ONE image of
+    // points whose position in the filter's world frame is known, on a clone of the window - by id or (clone_id -1) by time - and the
+    // next processFeatures that holds the clone applies them; takeLandmarkReports hands out what became of each batch (up to 64 per
+    // call).  With a VioPipeline call addLandmarkObs only between drain() and the next processImage.
+    bool addLandmarkObs(long long tag, long long clone_id, double time, const std::vector<lvk_landmark_obs>& obs)
+    {
+        return ekf_ && lvk_ekf_add_landmark_obs(ekf_, tag, clone_id, time, obs.data(), (int)obs.size()) == LVK_OK;
+    }
+    bool setLandmarkOptions(double gate_scale, double min_depth) { return ekf_ && lvk_ekf_set_landmark_options(ekf_, gate_scale, min_depth) == LVK_OK; }
+    void takeLandmarkReports(std::vector<lvk_landmark_report>& out)
+    {
+        out.resize(64);
+        const int n = ekf_ ? lvk_ekf_take_landmark_reports(ekf_, out.data(), 64) : 0;
+        out.resize((size_t)n);
+    }
+    void landmarkStats(long out12[12]) const { for (int i = 0; i < 12; ++i) out12[i] = 0; if (ekf_) lvk_ekf_landmark_stats(ekf_, out12); }
     lvk_ekf* handle() const { return ekf_; }
 private:
     friend class VioPipeline;

@@ -100,6 +100,7 @@ static lvk_status ekf_process_impl(lvk_ekf* e, double ts, const lvk_feature_obs*
     if (e->cfg.if_zupt_valid) { bool z = false; st = lvk_ekf_check_zupt(e, &z); if (st != LVK_OK) return st; e->if_zupt = z; }
     TR(TR_ZUPT);
     if (!e->fix_queue.empty()) { st = lvk_ekf_apply_fixes(e); if (st != LVK_OK) return st; }      // external fixes (lvk_ekf_add_fix): the message's clone exists, none is pruned yet
+    if (!e->lm_queue.empty()) { st = lvk_ekf_apply_landmarks(e); if (st != LVK_OK) return st; }   // observations of known landmarks (lvk_ekf_add_landmark_obs), behind the fixes
     st = lvk_ekf_remove_lost_features(e);
     if (st != LVK_OK) return st;
     st = lvk_ekf_prune_imu_state_buffer(e);
@@ -390,6 +391,7 @@ lvk_status lvk_ekf_set_shard(lvk_ekf* e, int rank, int world, lvk_exchange_fn fn
     if (fn && e->msckf_points_on) return lvk_set_error(e->ctx, LVK_ERR_UNSUPPORTED, "lvk_ekf_set_shard: the sharded update does not export MSCKF points (lvk_ekf_set_msckf_points is on)");
     if (fn && e->keyframes_on) return lvk_set_error(e->ctx, LVK_ERR_UNSUPPORTED, "lvk_ekf_set_shard: the sharded update does not export keyframes (lvk_ekf_set_keyframe_export is on)");
     if (fn && !e->fix_queue.empty()) return lvk_set_error(e->ctx, LVK_ERR_UNSUPPORTED, "lvk_ekf_set_shard: the sharded update does not apply fixes (%zu wait, lvk_ekf_add_fix)", e->fix_queue.size());
+    if (fn && !e->lm_queue.empty()) return lvk_set_error(e->ctx, LVK_ERR_UNSUPPORTED, "lvk_ekf_set_shard: the sharded update does not apply landmark observations (%zu batches wait, lvk_ekf_add_landmark_obs)", e->lm_queue.size());
     EKF_HIP(hipStreamSynchronize(e->ctx->stream));
     if (S.d_send) hipFree(S.d_send); if (S.d_recv) hipFree(S.d_recv);
     S.d_send = S.d_recv = nullptr; S.cap = 0; S.xk_cap = 0;

@@ -204,6 +204,13 @@ struct lvk_ekf {
     enum { FIX_CAP = 64 };
     std::vector<lvk_fix> fix_queue; std::vector<lvk_fix_report> fix_reports;
     double fix_gate_scale = 1.0, fix_max_gap = 0.0; long fix_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // lvk_ekf_add_landmark_obs: batches of observations of known landmarks waiting for their clone (at most LM_CAP), applied by
+    // lvk_ekf_apply_landmarks (be_landmark_fix.hip) behind the fixes; one report per consumed batch (drained on read).  lm_stats: as
+    // lvk_ekf_landmark_stats hands them out ([6], waiting, is lm_queue.size())
+    enum { LM_CAP = 16 };
+    struct LmBatch { long long tag, clone_id; double time; std::vector<lvk_landmark_obs> obs; };
+    std::vector<LmBatch> lm_queue; std::vector<lvk_landmark_report> lm_reports;
+    double lm_gate_scale = 1.0, lm_min_depth = 0.1; long lm_stats[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     double sigma2, zupt_v2, zupt_p2, zupt_q2, imu_img_time_th, Qc[12];
     double x_min, y_min, grid_w, grid_h;
     std::vector<int> grid_count;

@@ -131,6 +131,8 @@ lvk_status lvk_ekf_gated_update(lvk_ekf* e, std::vector<RowJob>& jobs, const siz
 lvk_status lvk_ekf_remove_lost_features(lvk_ekf* e);
 // be_fix.hip
 lvk_status lvk_ekf_apply_fixes(lvk_ekf* e);
+// be_landmark_fix.hip
+lvk_status lvk_ekf_apply_landmarks(lvk_ekf* e);
 // be_prune.hip
 lvk_status lvk_ekf_check_zupt(lvk_ekf* e, bool* out);
 lvk_status lvk_ekf_prune_imu_state_buffer(lvk_ekf* e);

@@ -25,6 +25,10 @@ FIX_REPORT = np.dtype([("tag", np.int64), ("kind", np.int32), ("status", np.int3
                        ("a", np.float64)])
 FIX_POSITION, FIX_POSE = 0, 1
 FIX_APPLIED, FIX_GATED, FIX_NOT_PD, FIX_STALE, FIX_NO_CLONE = 0, 1, 2, 3, 4
+# lvk_landmark_report (include/lvk_c.h; the observation record lvk_landmark_obs is ops.LANDMARK_OBS)
+LANDMARK_REPORT = np.dtype([("tag", np.int64), ("status", np.int32), ("n_obs", np.int32), ("clone_id", np.int64), ("n_used", np.int32), ("n_gated", np.int32),
+                            ("n_behind", np.int32), ("pad0", np.int32), ("gamma", np.float64)])
+LANDMARKS_APPLIED, LANDMARKS_ALL_REJECTED, LANDMARKS_NOT_PD, LANDMARKS_STALE, LANDMARKS_NO_CLONE = 0, 1, 2, 3, 4
 
 _CFG_INT = ["if_fej", "estimate_extrin", "estimate_td", "if_zupt_valid", "sw_size", "max_track_len", "least_observation_number",
             "max_features_in_one_grid", "aug_grid_rows", "aug_grid_cols", "width", "height"]
@@ -90,6 +94,10 @@ def _L():
         L.lvk_ekf_set_fix_options.argtypes = [vp, d, d]; L.lvk_ekf_set_fix_options.restype = i
         L.lvk_ekf_take_fix_reports.argtypes = [vp, vp, i]; L.lvk_ekf_take_fix_reports.restype = i
         L.lvk_ekf_fix_stats.argtypes = [vp, vp]; L.lvk_ekf_fix_stats.restype = None
+        L.lvk_ekf_add_landmark_obs.argtypes = [vp, C.c_int64, C.c_int64, d, vp, i]; L.lvk_ekf_add_landmark_obs.restype = i
+        L.lvk_ekf_set_landmark_options.argtypes = [vp, d, d]; L.lvk_ekf_set_landmark_options.restype = i
+        L.lvk_ekf_take_landmark_reports.argtypes = [vp, vp, i]; L.lvk_ekf_take_landmark_reports.restype = i
+        L.lvk_ekf_landmark_stats.argtypes = [vp, vp]; L.lvk_ekf_landmark_stats.restype = None
         L.lvk_ekf_get_state.argtypes = [vp, vp]; L.lvk_ekf_get_state.restype = i
         L.lvk_ekf_get_cov.argtypes = [vp, vp]; L.lvk_ekf_get_cov.restype = i
         L.lvk_ekf_get_cov_imu.argtypes = [vp, i, vp]; L.lvk_ekf_get_cov_imu.restype = i
@@ -614,6 +622,40 @@ class LarVio:
         o = np.zeros(8, np.int64); _L().lvk_ekf_fix_stats(self._h, _p(o))
         return dict(queued=int(o[0]), applied=int(o[1]), gated=int(o[2]), not_pd=int(o[3]), stale=int(o[4]), no_clone=int(o[5]), waiting=int(o[6]),
                     interpolated=int(o[7]))
+
+    def add_landmark_obs(self, p_w, uv, sigma, cov_w=None, time=0.0, clone_id=-1, tag=0):
+        """lvk_ekf_add_landmark_obs: queue one batch - the observations uv (k x 2, normalised image coordinates, standard deviation sigma:
+        a number or k of them) made in ONE image of the known world points p_w (k x 3, the filter's world frame; cov_w: None, one 3 x 3
+        or k of them) - on the clone `clone_id` or (clone_id -1) on the clone at `time`.  Applied by the next update that holds the clone;
+        take_landmark_reports() says what became of it.  Raises LvkError for what the header lists as refused."""
+        p_w = np.asarray(p_w, np.float64).reshape(-1, 3); k = len(p_w)
+        from .ops import LANDMARK_OBS
+        o = np.zeros(k, LANDMARK_OBS)
+        o["p_w"] = p_w; o["uv"] = np.asarray(uv, np.float64).reshape(k, 2); o["sigma"] = sigma
+        if cov_w is not None:
+            o["cov_w"] = np.asarray(cov_w, np.float64).reshape(-1, 9)
+        self.ctx.check(_L().lvk_ekf_add_landmark_obs(self._h, int(tag), int(clone_id), float(time), _p(o) if k else None, k))
+
+    def set_landmark_options(self, gate_scale=1.0, min_depth=0.1):
+        """lvk_ekf_set_landmark_options: the gate of one observation is gate_scale times the filter's own chi-square table entry for 2
+        degrees of freedom (<= 0: no gate); an observation whose depth in the camera is <= min_depth counts as behind"""
+        self.ctx.check(_L().lvk_ekf_set_landmark_options(self._h, float(gate_scale), float(min_depth)))
+
+    def take_landmark_reports(self):
+        """lvk_ekf_take_landmark_reports: a structured array (dtype LANDMARK_REPORT), one record per batch consumed since the last call"""
+        out = []
+        while True:
+            buf = np.zeros(64, LANDMARK_REPORT)
+            n = _L().lvk_ekf_take_landmark_reports(self._h, _p(buf), 64)
+            out.append(buf[:n].copy())
+            if n < 64:
+                break
+        return np.concatenate(out)
+
+    def landmark_stats(self):
+        o = np.zeros(12, np.int64); _L().lvk_ekf_landmark_stats(self._h, _p(o))
+        return dict(queued=int(o[0]), applied=int(o[1]), all_rejected=int(o[2]), not_pd=int(o[3]), stale=int(o[4]), no_clone=int(o[5]), waiting=int(o[6]),
+                    obs=int(o[7]), used=int(o[8]), gated=int(o[9]), behind=int(o[10]))
 
     def set_shard(self, rank, world, fn, user, keepalive=None):
         """lvk_ekf_set_shard: this filter does the per-feature device work of rank `rank` of `world`; fn/user = the all-gather

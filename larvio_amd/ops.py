@@ -411,3 +411,24 @@ def fe_msg_stage(ctx, tset, cap, n, model, intr, dist, dt_1, dt_2, prev_is_last,
     st = L.lvk_fe_msg_stage(ctx.h, C.byref(ta), cap, n, model, _p(a), _p(dd), dt_1, dt_2, prev_is_last, fill, _p(out), C.byref(ms))
     _finish(ctx, st, check)
     return st, out[:max(cap, 0)], dict(n_msg=ms.n_msg, n_host=ms.n_host, msg_features=int(ms.msg_features), msg_count=int(ms.msg_count))
+
+
+# lvk_landmark_fix_job / lvk_landmark_obs (include/lvk_c.h)
+LANDMARK_FIX_JOB = np.dtype([("clone_col", np.int32), ("pad0", np.int32), ("q_b", np.float64, 4), ("p_b", np.float64, 3), ("R_b2c", np.float64, 9), ("t_c_b", np.float64, 3),
+                             ("gate", np.float64), ("min_depth", np.float64)])
+LANDMARK_OBS = np.dtype([("p_w", np.float64, 3), ("cov_w", np.float64, 9), ("uv", np.float64, 2), ("sigma", np.float64)])
+
+
+def update_landmarks(ctx, P, job, obs, n=None):
+    """lvk_ekf_update_landmarks: one LANDMARK_FIX_JOB record and a LANDMARK_OBS array applied to the covariance P.  P: a whole row-major
+    buffer (its row length is the leading dimension, contents go to the device as they are) whose leading n x n block (default: all
+    rows) is the covariance.  -> (dx (n,), the whole P buffer after the call, info (8,), status (n_obs,), gamma (n_obs,))"""
+    P = np.ascontiguousarray(P, np.float64); job = np.ascontiguousarray(job, LANDMARK_FIX_JOB); obs = np.ascontiguousarray(obs, LANDMARK_OBS)
+    n = P.shape[0] if n is None else int(n)
+    dx = np.full(n, np.nan); info = np.full(8, np.nan); st = np.full(max(len(obs), 1), -1, np.int32); g = np.full(max(len(obs), 1), np.nan)
+    L = lib()
+    vp, i = C.c_void_p, C.c_int
+    L.lvk_ekf_update_landmarks.argtypes = [vp, vp, i, i, vp, vp, i, vp, vp, vp, vp]; L.lvk_ekf_update_landmarks.restype = i
+    dP = ctx.to_device(P)
+    ctx.check(L.lvk_ekf_update_landmarks(ctx.h, _p(dP), P.shape[1], n, _p(job), _p(obs) if len(obs) else None, len(obs), _p(dx), _p(info), _p(st), _p(g)))
+    return dx, ctx.to_host(dP, np.float64, P.shape), info, st[:len(obs)], g[:len(obs)]
