@@ -179,6 +179,35 @@ lvk_status lvk_find_fundamental(lvk_context* ctx, const lvk_pt2f* d_p1, const lv
 /* the RANSAC branch alone for any n >= 8 (stage parity) */
 lvk_status lvk_ransac_fundamental(lvk_context* ctx, const lvk_pt2f* d_p1, const lvk_pt2f* d_p2, int n,
                                   double thresh, double conf, int max_iters, uint8_t* d_mask, int* d_info);
+/* Stage entry: guided ORB matching - for each of n_q queries (a predicted pixel, a search radius and a 256-bit descriptor) the described
+ * corner of the frame that is the query's map point, or the reason there is none.  No reference counterpart: the reference never looks a
+ * known point up in a frame.  All integer except the window test, which is float32 exactly as written (no contraction), so every field
+ * has one right value:
+ *   window     candidate c is in the window of query q iff  dx = cx - qx; dy = cy - qy; dx*dx + dy*dy <= radius*radius.  A NaN anywhere
+ *              makes the comparison false (an infinite x or y too: the query then has no candidate; an infinite radius holds every finite
+ *              candidate).  n_window = candidates in the window.
+ *   best       the in-window candidate with the smallest Hamming distance, ties to the lowest candidate index: cand, dist.
+ *   second     the smallest distance over the in-window candidates other than best, -1 when there is none.
+ *   status     the first rule that applies: NO_CANDIDATE when n_window == 0 (cand = dist = second = -1); TOO_FAR when dist > max_dist;
+ *              AMBIGUOUS when second >= 0 and 100 * dist > ratio_pct * second (ratio_pct 100 switches the test off); otherwise the query
+ *              is provisionally matched.  A candidate claimed by several provisionally matched queries goes to the smallest (dist, query
+ *              index): that query is OK, the others are CONFLICT, keep their cand and dist and are NOT moved to their second choice.
+ * d_cand_pts / d_cand_desc: n_cand points and 32-byte descriptors (lvk_orb_describe's layout); d_q / d_q_desc: n_q queries and their
+ * descriptors; d_out: n_q results, pad written as 0.  Both descriptor pointers must be 8-byte aligned.  Two launches (match, then the
+ * resolve pass of the claims) behind a clear of the claim words on the context's stream, not waited for.
+ * LVK_ERR_ARG, with nothing launched and the context still usable: a null pointer where its count is positive, a negative count, max_dist
+ * outside 0..256, ratio_pct outside 1..100, a descriptor pointer that is not 8-byte aligned.  LVK_ERR_CAPACITY: n_cand > 4096 (the
+ * positions are staged in LDS) or n_q > 1024.  n_q == 0: LVK_OK, nothing launched.  n_cand == 0: every query NO_CANDIDATE. */
+#define LVK_MATCH_OK           0
+#define LVK_MATCH_NO_CANDIDATE 1
+#define LVK_MATCH_TOO_FAR      2
+#define LVK_MATCH_AMBIGUOUS    3
+#define LVK_MATCH_CONFLICT     4
+typedef struct { float x, y, radius, pad; } lvk_match_query;   /* predicted pixel, search radius in pixels */
+typedef struct { int cand, dist, second, n_window, status, pad; } lvk_match_result;
+lvk_status lvk_orb_match_guided(lvk_context* ctx, const lvk_pt2f* d_cand_pts, const uint8_t* d_cand_desc, int n_cand,
+                                const lvk_match_query* d_q, const uint8_t* d_q_desc, int n_q,
+                                int max_dist, int ratio_pct, lvk_match_result* d_out);
 /* replaces integrateImuData + predictFeatureTracking's matrix (image_processor.cpp:222-293): host math */
 lvk_status lvk_predict_homography(const lvk_imu* h_imu, int n_imu, double t_prev, double t_curr,
                                   const double R_cam_imu[9], const double intr[4], float H[9]);
@@ -242,6 +271,31 @@ int        lvk_frontend_has_mask(const lvk_frontend* fe);
  * conversion kernel.  With a lvk_vio_pipe attached, call it before the first lvk_vio_pipe_submit or after lvk_vio_pipe_drain. */
 lvk_status lvk_frontend_set_input_format(lvk_frontend* fe, int format, int shift);
 int        lvk_frontend_input_format(const lvk_frontend* fe);
+/* Where in the last processed frame are these map points?  No reference counterpart.  h_q: n_q predicted pixels with their search radii,
+ * h_desc: their 32-byte descriptors (e.g. the first-seen descriptor lvk_frontend_tracks returned for the point's feature id), at most 1024.
+ * The call waits for the front-end's own streams, as lvk_frontend_tracks does, then runs on the main stream, on the pyramid and ORB planes
+ * of the last processed frame: lvk_min_eigen_map into a buffer of its own (allocated on first use; nothing the detection owns is touched),
+ * lvk_good_features_from_map with no mask at all (max_candidates, quality, min_distance), lvk_orb_describe of those corners,
+ * lvk_orb_match_guided (max_dist, ratio_pct), lvk_undistort_points of the matched pixels with unit intrinsics - as the feature message does
+ * it -, and one copy of the n_q records back.  Per query: status, dist, second and n_window as lvk_orb_match_guided states them; px = the
+ * candidate's pixel, und = its normalised coordinate (what lvk_landmark_obs takes as uv); both (0, 0) for NO_CANDIDATE, and set for every
+ * other status, OK or not.  *n_cand_out (may be NULL) = corners the selection found.  The call is off the per-frame path: it waits for the
+ * GPU twice (the corner count, the records) and changes nothing a later frame reads - a run with these calls publishes the bits of a run
+ * without them.
+ * opt may be NULL; a zero field takes its default: max_candidates 4096 (1..4096), quality 0.01, min_distance the configured
+ * min_distance - the spacing the map's own points were detected at -, max_dist 58 (the front-end's own descriptor gate; 1..256 here, 0
+ * being the default's spelling), ratio_pct 100 = no ratio test (1..100).
+ * LVK_ERR_ARG, with nothing launched: a null pointer that is needed, n_q < 0, a field of opt outside its range or not finite, a call
+ * before the first processed frame, a call between lvk_frontend_begin and the lvk_frontend_process of the same frame.  LVK_ERR_CAPACITY:
+ * n_q > 1024, max_candidates > 4096, and the selection's own refusal (its cell grid does not fit the LDS: lvk_good_features_from_map),
+ * passed through unchanged; its LVK_ERR_UNSUPPORTED for a min_distance outside 1..32767 likewise.  None of these is sticky: the handle
+ * goes on.  On a handle that has failed the call returns the failure, as lvk_frontend_process does.  n_q == 0 is legal and still reports
+ * *n_cand_out.  With a lvk_vio_pipe attached, call it only between lvk_vio_pipe_drain and the next lvk_vio_pipe_submit - never between
+ * a submit and the drain that follows. */
+typedef struct { int max_candidates; double quality, min_distance; int max_dist, ratio_pct; } lvk_match_options;  /* zeros = defaults */
+typedef struct { int status, dist, second, n_window; lvk_pt2f px, und; } lvk_landmark_match;
+lvk_status lvk_frontend_match_landmarks(lvk_frontend* fe, const lvk_match_query* h_q, const uint8_t* h_desc, int n_q,
+                                        const lvk_match_options* opt, lvk_landmark_match* h_out, int* n_cand_out);
 /* cumulative LK work: point-levels processed and iterations executed (SURVEY §8d byte model) */
 lvk_status lvk_frontend_lk_stats(lvk_frontend* fe, uint64_t* point_levels, uint64_t* iterations);
 /* feature messages published so far (getFeatureMsg, image_processor.cpp:1076-1128) and the features they carried in total:

@@ -97,6 +97,19 @@ public:
         if (lvk_frontend_set_input_format(fe_, format, shift) != LVK_OK) { std::fprintf(stderr, "ImageProcessor::setInputFormat: %s\n", lvk_last_error(ctx_)); return false; }
         return true;
     }
+    // where in the last processed frame are these map points (lvk_frontend_match_landmarks; the reference has no such call)?  queries: the
+    // predicted pixel and search radius of each, desc: 32 bytes per query; opt may be null (defaults).  out[i].status == LVK_MATCH_OK marks a
+    // match, out[i].und is what lvk_landmark_obs takes as uv.  With a VioPipeline only after drain().  false = refused.
+    bool matchLandmarks(const std::vector<lvk_match_query>& queries, const std::vector<uint8_t>& desc, std::vector<lvk_landmark_match>& out,
+                        const lvk_match_options* opt = nullptr, int* n_candidates = nullptr)
+    {
+        if (!fe_ || desc.size() != queries.size() * 32) return false;
+        out.resize(queries.size());
+        if (lvk_frontend_match_landmarks(fe_, queries.data(), desc.data(), (int)queries.size(), opt, out.data(), n_candidates) != LVK_OK) {
+            std::fprintf(stderr, "ImageProcessor::matchLandmarks: %s\n", lvk_last_error(ctx_)); return false;
+        }
+        return true;
+    }
     lvk_frontend* handle() const { return fe_; }
 private:
     ImageProcessor(const ImageProcessor&); ImageProcessor& operator=(const ImageProcessor&);

@@ -21,9 +21,9 @@ ABI_SYMBOLS = [
     "lvk_clahe_u8", "lvk_pyramid_create", "lvk_pyramid_destroy", "lvk_pyramid_build", "lvk_pyramid_build_clahe",
     "lvk_pyramid_levels", "lvk_pyramid_level", "lvk_orb_prepare", "lvk_image_to_gray", "lvk_min_eigen_map", "lvk_good_features", "lvk_good_features_from_map",
     "lvk_lk_track", "lvk_orb_describe", "lvk_hamming256_rows", "lvk_undistort_points", "lvk_find_fundamental_mask", "lvk_find_fundamental",
-    "lvk_ransac_fundamental", "lvk_predict_homography",
+    "lvk_ransac_fundamental", "lvk_orb_match_guided", "lvk_predict_homography",
     "lvk_frontend_create", "lvk_frontend_destroy", "lvk_frontend_process", "lvk_frontend_tracks", "lvk_frontend_new_pts",
-    "lvk_frontend_set_mask", "lvk_frontend_has_mask", "lvk_frontend_set_input_format", "lvk_frontend_input_format",
+    "lvk_frontend_set_mask", "lvk_frontend_has_mask", "lvk_frontend_set_input_format", "lvk_frontend_input_format", "lvk_frontend_match_landmarks",
     "lvk_frontend_state", "lvk_frontend_lk_stats", "lvk_frontend_msg_stats", "lvk_frontend_profile_enable", "lvk_frontend_profile_read",
     "lvk_frontend_stage_name", "lvk_fe_track_stage", "lvk_fe_commit_stage", "lvk_fe_msg_stage",
     "lvk_ekf_compress_qr", "lvk_ekf_compress_qr_groups", "lvk_ekf_qr_plan", "lvk_ekf_update", "lvk_ekf_update_ldlt", "lvk_ekf_update_ldlt_perm", "lvk_dgemm", "lvk_dgemm_ex", "lvk_chol_solve", "lvk_ekf_cov_propagate_augment", "lvk_ekf_cov_gather", "lvk_ekf_cov_reanchor", "lvk_ekf_cov_append_features", "lvk_ekf_landmark_cov", "lvk_ekf_pose_rel_cov", "lvk_ekf_landmark_rel_cov", "lvk_ekf_msckf_point_cov", "lvk_ekf_update_sparse", "lvk_ekf_update_landmarks", "lvk_ekf_create", "lvk_ekf_destroy", "lvk_ekf_process", "lvk_ekf_process_async", "lvk_ekf_wait", "lvk_ekf_set_state",
@@ -92,6 +92,17 @@ class FeConfig(C.Structure):
                 ("R_cam_imu", C.c_double * 9)]
 
 
+# lvk_match_query / lvk_match_result / lvk_landmark_match / lvk_match_options of include/lvk_c.h, and the LVK_MATCH_* status codes by name
+MATCH_QUERY = np.dtype([("x", np.float32), ("y", np.float32), ("radius", np.float32), ("pad", np.float32)])
+MATCH_RESULT = np.dtype([("cand", np.int32), ("dist", np.int32), ("second", np.int32), ("n_window", np.int32), ("status", np.int32), ("pad", np.int32)])
+LANDMARK_MATCH = np.dtype([("status", np.int32), ("dist", np.int32), ("second", np.int32), ("n_window", np.int32), ("px", np.float32, 2), ("und", np.float32, 2)])
+MATCH_OK, MATCH_NO_CANDIDATE, MATCH_TOO_FAR, MATCH_AMBIGUOUS, MATCH_CONFLICT = 0, 1, 2, 3, 4
+
+
+class MatchOptions(C.Structure):
+    _fields_ = [("max_candidates", C.c_int), ("quality", C.c_double), ("min_distance", C.c_double), ("max_dist", C.c_int), ("ratio_pct", C.c_int)]
+
+
 def lib():
     """Load liblvk_hip.so.  Fails loudly when the HIP extension has not been built."""
     global _LIB
@@ -124,6 +135,7 @@ def lib():
             "lvk_find_fundamental_mask": ([vp, vp, vp, i, d, d, vp, vp], i),
             "lvk_find_fundamental": ([vp, vp, vp, i, d, d, vp, vp, vp], i),
             "lvk_ransac_fundamental": ([vp, vp, vp, i, d, d, i, vp, vp], i),
+            "lvk_orb_match_guided": ([vp, vp, vp, i, vp, vp, i, i, i, vp], i),
             "lvk_predict_homography": ([vp, i, d, d, vp, vp, vp], i),
             "lvk_frontend_create": ([vp, C.POINTER(FeConfig), C.POINTER(vp)], i), "lvk_frontend_destroy": ([vp], None),
             "lvk_frontend_process": ([vp, C.POINTER(Image), d, vp, i, vp, i, pi, pi], i),
@@ -132,6 +144,7 @@ def lib():
             "lvk_frontend_set_mask": ([vp, C.POINTER(Image)], i), "lvk_frontend_has_mask": ([vp], i),
             "lvk_image_to_gray": ([vp, vp, i, i, i, i, i, vp, i], i),
             "lvk_frontend_set_input_format": ([vp, i, i], i), "lvk_frontend_input_format": ([vp], i),
+            "lvk_frontend_match_landmarks": ([vp, vp, vp, i, C.POINTER(MatchOptions), vp, pi], i),
             "lvk_frontend_lk_stats": ([vp, vp, vp], i),
             "lvk_frontend_msg_stats": ([vp, vp, vp], i),
             "lvk_frontend_profile_enable": ([vp, C.c_uint], i), "lvk_frontend_profile_read": ([vp, vp, vp, i], i),

@@ -109,6 +109,13 @@ struct lvk_frontend {
     // stream -> main), ev_commit (main -> side), ev_tail (bootstrap only), ev_main / ev_side (end of a frame on either stream)
     hipEvent_t ev_pyr, ev_orb, ev_new, ev_commit, ev_tail;
     bool ev_trim = true;                                 // LVK_FE_EVENT_TRIM=0: queue every event record / stream wait as rounds 1-4 did (A/B switch)
+    // lvk_frontend_match_landmarks' own buffers, allocated by its first call (null in a front-end that never matches): response map, the
+    // corners, their count and descriptors, then the queries, their descriptors, the matcher's results, the matched pixels, their
+    // normalised coordinates and the records the host reads
+    struct Match {
+        float* eig; lvk_pt2f* cand_pts; int* n_cand; uint8_t* cand_desc;
+        lvk_match_query* q; uint8_t* q_desc; lvk_match_result* res; lvk_pt2f *px, *und; lvk_landmark_match* out;
+    } match = {};
     // sticky: a frame that failed AFTER its image stage was queued (device error, ring overrun) leaves the buffer-set rotation and the
     // end-of-frame events out of step with the frame count; the handle then refuses further frames instead of racing on its buffers
     lvk_status failed = LVK_OK; char failed_msg[200] = {0};
@@ -157,6 +164,9 @@ lvk_status commit(lvk_frontend* fe, int mode, const lvk_pt2f* src_pts, const int
                   const TrackSet* src, const unsigned long long* desc_src, int dst_set);
 // the feature message of set `dst` on the main stream
 lvk_status fe_msg_launch(lvk_frontend* fe, int dst, const FeMsgArgs& m);
+// fe_match.hip: matched pixels, their normalised coordinates and the host's records behind lvk_orb_match_guided, on the context's stream
+lvk_status fe_match_finish(lvk_context* ctx, const CamParams& cam, const lvk_match_result* d_res, const lvk_pt2f* d_cand_pts, int n_q, lvk_pt2f* d_px, lvk_pt2f* d_und,
+                           lvk_landmark_match* d_out);
 #ifdef LVK_LK_BOUNDS
-void fe_lk_bounds_report();                              // prints what the frame path's kernels recorded in THEIR copy of g_lk_oob
+void fe_lk_bounds_report();                             // prints what the frame path's kernels recorded in THEIR copy of g_lk_oob
 #endif

@@ -125,7 +125,8 @@ void lvk_frontend_destroy(lvk_frontend* fe)
         if (i < 2) set_free(fe->set[i]);
     }
     void* ptrs[] = {fe->d_img, fe->w_curr, fe->wn_curr, fe->w_und, fe->wn_und, fe->new_pts, fe->w_status, fe->wn_status, fe->wn_desc, fe->eig, fe->mask,
-                    fe->gf_scratch, fe->gf_cands, fe->dev, fe->user_mask, fe->d_gray};
+                    fe->gf_scratch, fe->gf_cands, fe->dev, fe->user_mask, fe->d_gray,
+                    fe->match.eig, fe->match.cand_pts, fe->match.n_cand, fe->match.cand_desc, fe->match.q, fe->match.q_desc, fe->match.res, fe->match.px, fe->match.und, fe->match.out};
     for (void* p : ptrs) if (p) hipFree(p);
     for (int i = 0; i < 3; ++i) { if (fe->h_stage[i]) hipHostFree(fe->h_stage[i]); if (fe->d_ring[i]) hipFree(fe->d_ring[i]); if (fe->ev_img[i]) hipEventDestroy(fe->ev_img[i]); }
     for (int i = 0; i < LVK_MSG_SLOTS; ++i) if (fe->ev_msg[i]) hipEventDestroy(fe->ev_msg[i]);
@@ -696,6 +697,72 @@ lvk_status lvk_frontend_set_input_format(lvk_frontend* fe, int format, int shift
     return LVK_OK;
 }
 int lvk_frontend_input_format(const lvk_frontend* fe) { return fe ? fe->pix_format : -1; }
+
+// Map points in the last processed frame (no reference counterpart): fresh corners of that frame without any mask, their descriptors, the
+// guided matcher, the matched pixels normalised.  After the rotation the frame's pyramid and ORB planes are pyr[0], ext[0], blur[0]; the next
+// frame's image stage writes set [1], so nothing here races with a frame queued later on the main stream, and every buffer written is the
+// call's own (fe->match) or the main context's stage scratch: the detection's eig / mask / scratch on side[0] are not touched.
+#define FE_MATCH_MAX_CAND 4096
+#define FE_MATCH_MAX_Q    1024
+lvk_status lvk_frontend_match_landmarks(lvk_frontend* fe, const lvk_match_query* h_q, const uint8_t* h_desc, int n_q, const lvk_match_options* opt,
+                                        lvk_landmark_match* h_out, int* n_cand_out)
+{
+    if (!fe) return LVK_ERR_ARG;
+    lvk_context* ctx = fe->ctx;
+    { lvk_status fs = fe_check_failed(fe); if (fs != LVK_OK) return fs; }
+    if (n_q < 0 || (n_q > 0 && (!h_q || !h_desc || !h_out))) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: bad argument");
+    if (n_q > FE_MATCH_MAX_Q) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_frontend_match_landmarks: %d queries, at most %d", n_q, FE_MATCH_MAX_Q);
+    lvk_match_options o = {0, 0., 0., 0, 0};
+    if (opt) o = *opt;
+    if (o.max_candidates == 0) o.max_candidates = FE_MATCH_MAX_CAND;
+    if (o.quality == 0.) o.quality = 0.01;
+    if (o.min_distance == 0.) o.min_distance = (double)fe->cfg.min_distance;
+    if (o.max_dist == 0) o.max_dist = 58;
+    if (o.ratio_pct == 0) o.ratio_pct = 100;
+    if (o.max_candidates < 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: max_candidates %d", o.max_candidates);
+    if (o.max_candidates > FE_MATCH_MAX_CAND) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_frontend_match_landmarks: max_candidates %d, at most %d", o.max_candidates, FE_MATCH_MAX_CAND);
+    if (!(o.quality > 0. && o.quality <= 1.)) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: quality must be in (0, 1]");
+    if (!std::isfinite(o.min_distance) || o.min_distance < 0.) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: min_distance is negative or not finite");
+    if (o.max_dist < 0 || o.max_dist > 256) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: max_dist %d outside 1..256", o.max_dist);
+    if (o.ratio_pct < 1 || o.ratio_pct > 100) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: ratio_pct %d outside 1..100", o.ratio_pct);
+    if (fe->n_img == 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: no frame has been processed yet");
+    if (fe->image_done)
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: the image stage of t = %.6f is still waiting for its lvk_frontend_process", fe->image_done_ts);
+    const int w = fe->cfg.width, h = fe->cfg.height;
+    lvk_frontend::Match& m = fe->match;
+    if (!m.eig) {
+        lvk_frontend::Match a = {};
+        const bool ok = dalloc(&a.eig, (size_t)w * h) && dalloc(&a.cand_pts, FE_MATCH_MAX_CAND) && dalloc(&a.n_cand, 1) && dalloc(&a.cand_desc, (size_t)32 * FE_MATCH_MAX_CAND) &&
+                        dalloc(&a.q, FE_MATCH_MAX_Q) && dalloc(&a.q_desc, (size_t)32 * FE_MATCH_MAX_Q) && dalloc(&a.res, FE_MATCH_MAX_Q) && dalloc(&a.px, FE_MATCH_MAX_Q) &&
+                        dalloc(&a.und, FE_MATCH_MAX_Q) && dalloc(&a.out, FE_MATCH_MAX_Q);
+        if (!ok) {
+            (void)hipGetLastError();
+            void* ptrs[] = {a.eig, a.cand_pts, a.n_cand, a.cand_desc, a.q, a.q_desc, a.res, a.px, a.und, a.out};
+            for (void* p : ptrs) if (p) hipFree(p);
+            return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_frontend_match_landmarks: allocation failed");
+        }
+        m = a;
+    }
+    { lvk_status qs = fe_quiesce(fe); if (qs != LVK_OK) return qs; }
+    lvk_status st = lvk_min_eigen_map(ctx, fe->pyr[0], m.eig);
+    if (st == LVK_OK) st = lvk_good_features_from_map(ctx, m.eig, nullptr, w, h, o.max_candidates, o.quality, o.min_distance, m.cand_pts, FE_MATCH_MAX_CAND, m.n_cand);
+    if (st != LVK_OK) return st;
+    int n_cand = 0;
+    LVK_HIP(ctx, hipMemcpyAsync(&n_cand, m.n_cand, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_cand < 0 || n_cand > FE_MATCH_MAX_CAND) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_frontend_match_landmarks: the selection reported %d corners", n_cand);
+    if (n_cand_out) *n_cand_out = n_cand;
+    if (n_q == 0) return LVK_OK;
+    LVK_HIP(ctx, hipMemcpyAsync(m.q, h_q, sizeof(lvk_match_query) * (size_t)n_q, hipMemcpyHostToDevice, ctx->stream));
+    LVK_HIP(ctx, hipMemcpyAsync(m.q_desc, h_desc, (size_t)32 * n_q, hipMemcpyHostToDevice, ctx->stream));
+    st = lvk_orb_describe(ctx, fe->ext[0], fe->blur[0], w, h, m.cand_pts, n_cand, m.cand_desc, nullptr);
+    if (st == LVK_OK) st = lvk_orb_match_guided(ctx, m.cand_pts, m.cand_desc, n_cand, m.q, m.q_desc, n_q, o.max_dist, o.ratio_pct, m.res);
+    if (st == LVK_OK) st = fe_match_finish(ctx, fe->cam, m.res, m.cand_pts, n_q, m.px, m.und, m.out);
+    if (st != LVK_OK) return st;
+    LVK_HIP(ctx, hipMemcpyAsync(h_out, m.out, sizeof(lvk_landmark_match) * (size_t)n_q, hipMemcpyDeviceToHost, ctx->stream));
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));     // (h_q and h_desc are the caller's pageable arrays: their copies are done too)
+    return LVK_OK;
+}
 
 lvk_status lvk_frontend_profile_enable(lvk_frontend* fe, unsigned stage_mask)
 {

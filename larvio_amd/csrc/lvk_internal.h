@@ -66,6 +66,7 @@ enum lvk_scratch_slot {
     LVK_SCR_STAGE_IN, LVK_SCR_STAGE_MID, LVK_SCR_STAGE_OUT,   // shared by every stage entry (input blob, staging, output blob): each ends with a stream wait
     LVK_SCR_CHOL_WS,                    // fused Cholesky: diagonal-block inverses and the panel flag (lvk_context::chol_epoch)
     LVK_SCR_LDLT_WS,                    // LDL^T update: pivot-ordered copies of [HP | r] and X, D, the permutation, the counters
+    LVK_SCR_MATCH_CLAIM,                // guided ORB matching: one claim word per candidate
     LVK_SCRATCH_SLOTS
 };
 #define LVK_LDS_OPTIN_KERNELS 24        // kernels that ask for more dynamic LDS than the default (fewer than that today)

@@ -131,6 +131,28 @@ class ImageProcessor:
         v = lib().lvk_frontend_input_format(self._h)
         return next(k for k, n in PIX_FORMATS.items() if n == v)
 
+    def match_landmarks(self, pred_px, radius, desc, max_candidates=0, quality=0.0, min_distance=0.0, max_dist=0, ratio_pct=0):
+        """lvk_frontend_match_landmarks: where in the last processed frame are these map points?  pred_px (n, 2): their predicted pixels
+        (larvio_amd.localize.predict_pixels), radius: the search radius in pixels (a number or n of them), desc (n, 32) uint8: their
+        descriptors (tracks()["desc"] of the run that mapped them).  Options left at zero take the library's defaults: 4096 candidates,
+        quality 0.01, the configured min_distance, max_dist 58, ratio_pct 100 (no ratio test).  -> a structured array (dtype
+        LANDMARK_MATCH: status, dist, second, n_window, px, und) of n records - status MATCH_OK (0) marks a match, und is what
+        LarVio.add_landmark_obs takes as uv; self.last_match_candidates = the corners the frame offered.  With a VioPipeline call it only
+        after drain()."""
+        from ._lib import MATCH_QUERY, LANDMARK_MATCH, MatchOptions
+        if self._h is None:
+            raise LvkError("ImageProcessor.initialize() has not succeeded")
+        p = np.ascontiguousarray(np.asarray(pred_px, np.float32).reshape(-1, 2)); n = len(p)
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        if len(d) != n:
+            raise ValueError(f"{n} predicted pixels but {len(d)} descriptors")
+        q = np.zeros(n, MATCH_QUERY); q["x"] = p[:, 0]; q["y"] = p[:, 1]; q["radius"] = radius
+        out = np.zeros(n, LANDMARK_MATCH); nc = C.c_int(0)
+        o = MatchOptions(int(max_candidates), float(quality), float(min_distance), int(max_dist), int(ratio_pct))
+        self.ctx.check(lib().lvk_frontend_match_landmarks(self._h, _p(q) if n else None, _p(d) if n else None, n, C.byref(o), _p(out) if n else None, C.byref(nc)))
+        self.last_match_candidates = nc.value
+        return out
+
     @property
     def state(self):
         return lib().lvk_frontend_state(self._h)

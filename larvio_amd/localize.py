@@ -1,0 +1,74 @@
+"""Localising against a prior map: the two host steps around ImageProcessor.match_landmarks (plain numpy, nothing here runs on the GPU).
+
+    px, ok = predict_pixels(p_w, R_wc, p_wc, fe_config)                # where the map's points should appear, from a pose prediction
+    m = image_processor.match_landmarks(px[ok], radius, desc[ok])      # which corner of the frame each of them is
+    obs, idx = landmark_obs(m, p_w[ok], cov_w[ok], sigma_px, fe_config)
+    larvio.add_landmark_obs(obs["p_w"], obs["uv"], obs["sigma"], obs["cov_w"], time=ts)
+
+The library itself only ever UNdistorts (lvk_undistort_points); predict_pixels is the forward camera model the map side needs."""
+import numpy as np
+
+from ._lib import MATCH_OK
+from .ops import LANDMARK_OBS
+
+
+def distort(xy, model, dist):
+    """forward distortion of normalised image coordinates (n, 2): model 0 = radtan (k1, k2, p1, p2), 1 = equidistant (k1..k4)"""
+    xy = np.asarray(xy, np.float64).reshape(-1, 2)
+    x, y = xy[:, 0], xy[:, 1]
+    r2 = x * x + y * y
+    if model == 0:
+        k1, k2, p1, p2 = dist
+        rad = 1.0 + (k2 * r2 + k1) * r2
+        xd = x * rad + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)
+        yd = y * rad + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y
+    elif model == 1:
+        r = np.sqrt(r2)
+        th = np.arctan(r); t2 = th * th
+        thd = th * (1.0 + t2 * (dist[0] + t2 * (dist[1] + t2 * (dist[2] + t2 * dist[3]))))
+        s = np.where(r > 1e-8, thd / np.maximum(r, 1e-300), 1.0)
+        xd, yd = x * s, y * s
+    else:
+        raise ValueError("distortion_model must be 0 (radtan) or 1 (equidistant)")
+    return np.stack([xd, yd], -1)
+
+
+def project(xy, fe_config):
+    """normalised undistorted coordinates (n, 2) -> pixels (n, 2) float64 of the configured camera"""
+    fx, fy, cx, cy = fe_config["intrinsics"]
+    d = distort(xy, fe_config["distortion_model"], fe_config["distortion"])
+    return np.stack([fx * d[:, 0] + cx, fy * d[:, 1] + cy], -1)
+
+
+def predict_pixels(p_w, R_wc, p_wc, fe_config, min_depth=0.1):
+    """World points p_w (n, 3) seen from the camera pose (R_wc: camera-to-world rotation, p_wc: camera position in the world) through the
+    front-end's camera (fe_config: the ImageProcessor's configuration dict).  -> (pixels (n, 2) float32, ok (n,) bool); ok is False for a
+    point behind the camera (depth <= min_depth) or outside the image - its pixel is NaN, which match_landmarks answers with NO_CANDIDATE."""
+    p_w = np.asarray(p_w, np.float64).reshape(-1, 3)
+    p_c = (p_w - np.asarray(p_wc, np.float64).reshape(1, 3)) @ np.asarray(R_wc, np.float64).reshape(3, 3)      # rows: R_wc^T (p_w - p_wc)
+    front = p_c[:, 2] > min_depth
+    z = np.where(front, p_c[:, 2], 1.0)
+    px = project(p_c[:, :2] / z[:, None], fe_config)
+    ok = front & (px[:, 0] >= 0) & (px[:, 0] <= fe_config["width"] - 1) & (px[:, 1] >= 0) & (px[:, 1] <= fe_config["height"] - 1)
+    px[~ok] = np.nan
+    return px.astype(np.float32), ok
+
+
+def landmark_obs(matches, p_w, cov_w, sigma_px, fe_config):
+    """The observation rows of the matches whose status is MATCH_OK.  matches: what match_landmarks returned for the points p_w (n, 3) with
+    covariances cov_w (None, one 3 x 3, or n of them); sigma_px: the standard deviation of a matched corner in pixels, turned into
+    normalised units with the mean focal length of fe_config.  -> (obs: an ops.LANDMARK_OBS array (p_w, cov_w, uv, sigma), idx: the rows of
+    `matches` they came from); feed obs["p_w"], obs["uv"], obs["sigma"], obs["cov_w"] to LarVio.add_landmark_obs."""
+    p_w = np.asarray(p_w, np.float64).reshape(-1, 3)
+    if len(matches) != len(p_w):
+        raise ValueError(f"{len(matches)} matches for {len(p_w)} points")
+    idx = np.nonzero(matches["status"] == MATCH_OK)[0]
+    fx, fy = fe_config["intrinsics"][:2]
+    obs = np.zeros(len(idx), LANDMARK_OBS)
+    obs["p_w"] = p_w[idx]
+    obs["uv"] = matches["und"][idx].astype(np.float64)
+    obs["sigma"] = float(sigma_px) / (0.5 * (fx + fy))
+    if cov_w is not None:
+        c = np.asarray(cov_w, np.float64)
+        obs["cov_w"] = c.reshape(1, 9) if c.size == 9 else c.reshape(-1, 9)[idx]
+    return obs, idx

@@ -152,6 +152,26 @@ def hamming_rows(ctx, a, b):
     return ctx.to_host(dd, np.int32, (n,))
 
 
+def orb_match_guided(ctx, cand_pts, cand_desc, q_px, q_radius, q_desc, max_dist=58, ratio_pct=100, check=True):
+    """lvk_orb_match_guided: n_q queries (predicted pixel q_px (n_q, 2), search radius q_radius: a number or n_q of them, descriptor q_desc
+    (n_q, 32) uint8) against n_cand described corners (cand_pts (n_cand, 2), cand_desc (n_cand, 32)).  -> a MATCH_RESULT array (cand, dist,
+    second, n_window, status, pad) whose every byte starts as 0xA5; check=False returns (status code, that array) instead of raising."""
+    from ._lib import MATCH_QUERY, MATCH_RESULT
+    cp = _pts(cand_pts); cd = np.ascontiguousarray(cand_desc, np.uint8).reshape(-1, 32)
+    qp = _pts(q_px); qd = np.ascontiguousarray(q_desc, np.uint8).reshape(-1, 32)
+    nc, nq = len(cp), len(qp)
+    assert len(cd) == nc and len(qd) == nq
+    q = np.zeros(nq, MATCH_QUERY); q["x"] = qp[:, 0]; q["y"] = qp[:, 1]; q["radius"] = q_radius
+    res = np.zeros(max(nq, 1), MATCH_RESULT); res.view(np.uint8)[...] = 0xA5
+    d_cp = ctx.to_device(cp); d_cd = ctx.to_device(cd); d_q = ctx.to_device(q); d_qd = ctx.to_device(qd); d_res = ctx.to_device(res)
+    st = lib().lvk_orb_match_guided(ctx.h, _p(d_cp) if nc else None, _p(d_cd) if nc else None, nc, _p(d_q) if nq else None, _p(d_qd) if nq else None, nq,
+                                    int(max_dist), int(ratio_pct), _p(d_res) if nq else None)
+    if check:
+        ctx.check(st)
+    out = ctx.to_host(d_res, MATCH_RESULT, (max(nq, 1),))[:nq].copy() if st == 0 else res[:nq]
+    return out if check else (st, out)
+
+
 def undistort(ctx, points, intr, model, dist, new_intr):
     p = _pts(points); n = len(p)
     a = np.asarray(intr, np.float64); d = np.asarray(dist, np.float64); k = np.asarray(new_intr, np.float64)
