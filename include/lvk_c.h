@@ -208,6 +208,67 @@ typedef struct { int cand, dist, second, n_window, status, pad; } lvk_match_resu
 lvk_status lvk_orb_match_guided(lvk_context* ctx, const lvk_pt2f* d_cand_pts, const uint8_t* d_cand_desc, int n_cand,
                                 const lvk_match_query* d_q, const uint8_t* d_q_desc, int n_q,
                                 int max_dist, int ratio_pct, lvk_match_result* d_out);
+/* Stage entry: relocalisation against a prior map - the yaw and translation that take a map's frame into the filter's world frame, from
+ * n putative 2D-3D matches, many of them wrong, by two-point RANSAC over n_pairs given pairs.  No reference counterpart.  Both frames
+ * have z along gravity (roll and pitch are observable in either session), so four numbers are sought: c = cos psi, s = sin psi and t, with
+ * p_w = Rz(psi) X + t,  Rz X = (c X_x - s X_y, s X_x + c X_y, X_z).  Match k carries the map point X_k (map frame) and the normalised
+ * undistorted observation (u_k, v_k) (lvk_landmark_match.und); R_wc (row-major, camera to world) and p_wc are the camera pose of that image
+ * in the filter's world frame; d_k = R_wc (u_k, v_k, 1)^T.  FP64 throughout, no contraction, no atan2 / sin / cos.
+ *   solver     pair (i, j): a = X_i - X_j, rho2 = a_x^2 + a_y^2; the constraint is Rz a = l_i d_i - l_j d_j.  p = i when |d_i,z| >= |d_j,z|,
+ *              else j, q the other.  No model when i == j, when an index is outside 0..n-1 (nothing is read), when rho2 is not > 0, when
+ *              |d_p,z| < min_dz.  The z row gives l_p = alpha + beta l_q:  p = i: alpha = a_z / d_i,z, beta = d_j,z / d_i,z,
+ *              e = alpha d_i,xy, f = beta d_i,xy - d_j,xy;  p = j: alpha = -a_z / d_j,z, beta = d_i,z / d_j,z, e = -alpha d_j,xy,
+ *              f = d_i,xy - beta d_j,xy.  With w = e + mu f (mu = l_q), |w|^2 = rho2 is A mu^2 + 2 B mu + C = 0, A = f.f, B = e.f,
+ *              C = e.e - rho2, disc = B B - A C.  No model unless A > 0 and disc >= 0.  Root 0 is mu = (-B - sqrt(disc)) / A, root 1
+ *              mu = (-B + sqrt(disc)) / A; a root is a model iff mu > 0 and l_p > 0.  Its dot = a_xy . w, crs = a_x w_y - a_y w_x,
+ *              nrm = sqrt(dot^2 + crs^2), c = dot / nrm, s = crs / nrm, t = (p_wc + l_i d_i) - Rz X_i.  At most two models, root 0 first.
+ *   score      match k is an inlier of a model iff p_c = R_wc^T ((Rz X_k + t) - p_wc) has p_c.z > min_depth and
+ *              (p_c.x / p_c.z - u_k)^2 + (p_c.y / p_c.z - v_k)^2 <= thresh^2; count = the inliers, the pair's own two included or not as
+ *              the test says.
+ *   winner     the model with the largest count; ties to the lowest hypothesis index, then to the lower root.  d_mask[k] = 1 for its
+ *              inliers, 0 otherwise; the mask is NOT scored again after the refinement (lvk_find_fundamental does not refit either).
+ *   refinement Gauss-Newton on (dpsi, dt) over the winner's inliers, minimising sum |r_k|^2, r_k = (p_c.x / p_c.z - u_k, p_c.y / p_c.z - v_k),
+ *              from the winner: A = sum J^T J (4 x 4, order psi, t_x, t_y, t_z), g = sum J^T r, A d = -g by Cholesky; t += dt and the yaw by the
+ *              half-angle form h = dpsi / 2, (c, s) <- (c, s) rotated by ((1 - h^2) / (1 + h^2), 2 h / (1 + h^2)).  Stop rule: behind the
+ *              first step with dpsi^2 + |dt|^2 <= 1e-20, or behind max_refine_iters steps.  A and rms = sqrt(sum |r_k|^2 / n_inliers) are
+ *              evaluated at the model that is returned; the caller inverts A and scales by their variance in normalised units - the
+ *              library invents no covariance.  A pivot at or below 1e-12 of its diagonal entry of A counts as non-positive (rounding
+ *              leaves a rank-deficient A with pivots of either sign at 1e-16 of it).
+ *   status     the first rule that applies: NO_MODEL no pair gave a model (hyp = root = pair_i = pair_j = -1, c = c0 = 1, all else 0, mask
+ *              zeroed); FEW_INLIERS the best count is below min_inliers (c0, s0, t0 = c, s, t = the winner, the mask is the winner's,
+ *              A = rms = iters = 0); SINGULAR the solve met a non-positive pivot (c, s, t = the winner again, A and rms those of the
+ *              iterate whose solve failed); OK.
+ * d_m: n matches; d_pairs: n_pairs pairs; d_hyp: NULL or n_pairs records - n_models, then the models in root order, slots beyond
+ * n_models and both pads zero; d_mask: n bytes; d_out: one record.  Matches beyond n and records beyond n_pairs are not read.  Two
+ * launches on the context's stream (hypotheses; arg-max, mask and refinement), not waited for.
+ * opt may be NULL; a zero field takes its default: thresh 0.01 (normalised units), min_depth 0.1, min_dz 1e-6, min_inliers 6 (2..1024),
+ * max_refine_iters 10 (1..100).  LVK_ERR_ARG, with nothing launched and the context still usable: a null pointer that is needed, a
+ * negative count, an option that is not finite, not positive or outside its range, a non-finite entry of R_wc or p_wc.
+ * LVK_ERR_CAPACITY: n > 1024 (the matches are staged in LDS) or n_pairs > 4096.  n < 2 or n_pairs == 0: NO_MODEL, the mask zeroed,
+ * the hypotheses kernel not launched. */
+#define LVK_ALIGN_OK          0
+#define LVK_ALIGN_NO_MODEL    1
+#define LVK_ALIGN_FEW_INLIERS 2
+#define LVK_ALIGN_SINGULAR    3
+#define LVK_ALIGN_DEFAULT_SEED 0xFFFFFFFFu      /* what a seed of 0 means to lvk_align_draw_pairs */
+typedef struct { double X[3]; double u, v; } lvk_align_match;
+typedef struct { int i, j; } lvk_align_pair;
+typedef struct { int count, root; double c, s, t[3]; } lvk_align_model;
+typedef struct { int n_models, pad; lvk_align_model m[2]; } lvk_align_hyp;
+typedef struct { double thresh, min_depth, min_dz; int min_inliers, max_refine_iters; } lvk_align_options;   /* zeros = defaults */
+typedef struct { int status, n_inliers, hyp, root, pair_i, pair_j, iters, pad;
+                 double c, s, t[3];        /* refined */
+                 double c0, s0, t0[3];     /* the winner of the minimal solver */
+                 double A[16], rms; } lvk_align_result;
+lvk_status lvk_align_ransac_2pt(lvk_context* ctx, const lvk_align_match* d_m, int n, const lvk_align_pair* d_pairs, int n_pairs,
+                                const double R_wc[9], const double p_wc[3], const lvk_align_options* opt, lvk_align_hyp* d_hyp,
+                                uint8_t* d_mask, lvk_align_result* d_out);
+/* The pairs lvk_frontend_align_landmarks tries (host only, so that a caller can reproduce them): when n (n - 1) / 2 <= max_hypotheses
+ * (0 = the cap, 4096) every pair i < j in lexicographic order; otherwise hypothesis h takes i = r() % n, j = r() % (n - 1), j += (j >= i),
+ * r() the low word of x <- (uint32) x * 4164903690 + (x >> 32) (the multiply-with-carry generator of the RANSAC stage), x starting at seed,
+ * or at LVK_ALIGN_DEFAULT_SEED for a seed of 0.  Returns the number of pairs written (0 for n < 2; h_pairs holds min(n (n - 1) / 2,
+ * max_hypotheses)), -1 for a negative n, max_hypotheses outside 0..4096 or a null pointer. */
+int        lvk_align_draw_pairs(int n, int max_hypotheses, uint32_t seed, lvk_align_pair* h_pairs);
 /* replaces integrateImuData + predictFeatureTracking's matrix (image_processor.cpp:222-293): host math */
 lvk_status lvk_predict_homography(const lvk_imu* h_imu, int n_imu, double t_prev, double t_curr,
                                   const double R_cam_imu[9], const double intr[4], float H[9]);
@@ -296,6 +357,20 @@ typedef struct { int max_candidates; double quality, min_distance; int max_dist,
 typedef struct { int status, dist, second, n_window; lvk_pt2f px, und; } lvk_landmark_match;
 lvk_status lvk_frontend_match_landmarks(lvk_frontend* fe, const lvk_match_query* h_q, const uint8_t* h_desc, int n_q,
                                         const lvk_match_options* opt, lvk_landmark_match* h_out, int* n_cand_out);
+/* The first link of that chain: a map from another session has its own origin and yaw, and lvk_frontend_match_landmarks can only be asked
+ * once the map is in the filter's world frame.  Match the map's descriptors with an infinite radius and a ratio test, hand the OK
+ * records here (h_m: X = the map point, u, v = lvk_landmark_match.und; n <= 1024) with the camera pose of that frame in the filter's world
+ * frame, and the call returns the yaw and translation of the map (lvk_align_ransac_2pt states all of it).  It waits for the front-end's own
+ * streams, as lvk_frontend_match_landmarks does, draws the pairs (lvk_align_draw_pairs with max_hypotheses - 0 = 4096, the cap - and seed),
+ * uploads, runs the stage entry on the main stream in buffers of its own (allocated on first use) and copies the result and the n mask
+ * bytes back (h_mask may be NULL).  Off the per-frame path; it changes nothing a later frame reads - a run with these calls publishes the
+ * bits of a run without them.  LVK_ERR_ARG, with nothing launched: a null pointer that is needed, n < 0, max_hypotheses < 0, the
+ * stage entry's own refusals, a call before the first processed frame or between lvk_frontend_begin and the lvk_frontend_process of
+ * the same frame.  LVK_ERR_CAPACITY: n > 1024, max_hypotheses > 4096.  None is sticky.  With a lvk_vio_pipe attached, call it only
+ * between lvk_vio_pipe_drain and the next lvk_vio_pipe_submit. */
+lvk_status lvk_frontend_align_landmarks(lvk_frontend* fe, const lvk_align_match* h_m, int n, const double R_wc[9], const double p_wc[3],
+                                        const lvk_align_options* opt, int max_hypotheses, uint32_t seed, lvk_align_result* h_out,
+                                        uint8_t* h_mask);
 /* cumulative LK work: point-levels processed and iterations executed (SURVEY §8d byte model) */
 lvk_status lvk_frontend_lk_stats(lvk_frontend* fe, uint64_t* point_levels, uint64_t* iterations);
 /* feature messages published so far (getFeatureMsg, image_processor.cpp:1076-1128) and the features they carried in total:
@@ -857,7 +932,8 @@ lvk_status lvk_ekf_get_window_cov(lvk_ekf* e, int64_t* h_ids, double* h_cov_abs3
  * late result is fused correctly with no re-propagation.  No reference counterpart.
  * Conventions (those of lvk_ekf_pose_rel_cov): R(q) maps body to world, the injection is R <- (I + [d_theta]x) R, p <- p + d_p, clone
  * c has columns leg + 6 c (d_theta) and leg + 6 c + 3 (d_p), times are on the IMU clock as lvk_clone.time.  A fix is expressed in the
- * FILTER's world frame: aligning an external frame (yaw and translation) is the caller's job.
+ * FILTER's world frame: aligning an external frame (yaw and translation) is the caller's job (for a map of points seen in a frame,
+ * lvk_frontend_align_landmarks estimates exactly those four numbers; a frame that differs by more stays the caller's).
  *   LVK_FIX_POSITION   z = p_i + R_i lever + n,  n ~ N(0, cov[0:3, 0:3]) (cov is 6 x 6 row-major storage; the upper-left 3 x 3 is used);
  *                      r = z - (p_i + R_i lever),  H_theta = -[R_i lever]x,  H_p = I                                  (3 rows, 6 columns)
  *   ... between two adjacent clones i, j, a = (t - t_i) / (t_j - t_i): the prediction is (1 - a)(p_i + R_i lever) + a (p_j + R_j lever)
@@ -917,7 +993,8 @@ void       lvk_ekf_fix_stats(const lvk_ekf* e, long* h_out8);
 /* Observations of known landmarks: localising against a prior map.  Where lvk_ekf_add_fix takes a finished pose with a covariance, this
  * takes what a vision caller has before any PnP: image observations (normalised coordinates, as the filter's own features) of points
  * whose position in the FILTER's world frame is known, each with its own covariance - surveyed fiducial corners, the output of
- * lvk_ekf_take_msckf_points / lvk_ekf_take_lost_features_cov of an earlier lap, a prior map.  The filter fuses them directly
+ * lvk_ekf_take_msckf_points / lvk_ekf_take_lost_features_cov of an earlier lap, a prior map (one with its own origin and yaw is
+ * brought into this frame by lvk_frontend_align_landmarks first).  The filter fuses them directly
  * (lvk_ekf_update_landmarks: measurement model, gate, compression), correlation with the extrinsics included, and five points or
  * fewer - where a PnP has no answer - still count.  No reference counterpart.
  * lvk_ekf_add_landmark_obs queues one BATCH: the observations made in one image, i.e. of one clone (at most 1024 observations per

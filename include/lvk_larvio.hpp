@@ -110,6 +110,21 @@ public:
         }
         return true;
     }
+    // the yaw and translation that take a prior map's frame into the filter's world frame (lvk_frontend_align_landmarks; the reference has no
+    // such call): matches = (map point, normalised observation) pairs of the last processed frame, many of them possibly wrong; R_wc, p_wc =
+    // that frame's camera pose in the filter's world frame; opt may be null (defaults).  out.status == LVK_ALIGN_OK marks success, mask[k]
+    // the winner's inliers.  With a VioPipeline only after drain().  false = refused.
+    bool alignLandmarks(const std::vector<lvk_align_match>& matches, const double R_wc[9], const double p_wc[3], lvk_align_result& out,
+                        std::vector<uint8_t>* mask = nullptr, const lvk_align_options* opt = nullptr, int max_hypotheses = 0, uint32_t seed = 0)
+    {
+        if (!fe_) return false;
+        if (mask) mask->assign(matches.size(), 0);
+        if (lvk_frontend_align_landmarks(fe_, matches.data(), (int)matches.size(), R_wc, p_wc, opt, max_hypotheses, seed, &out,
+                                         mask && !mask->empty() ? mask->data() : nullptr) != LVK_OK) {
+            std::fprintf(stderr, "ImageProcessor::alignLandmarks: %s\n", lvk_last_error(ctx_)); return false;
+        }
+        return true;
+    }
     lvk_frontend* handle() const { return fe_; }
 private:
     ImageProcessor(const ImageProcessor&); ImageProcessor& operator=(const ImageProcessor&);

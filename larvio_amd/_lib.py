@@ -21,9 +21,9 @@ ABI_SYMBOLS = [
     "lvk_clahe_u8", "lvk_pyramid_create", "lvk_pyramid_destroy", "lvk_pyramid_build", "lvk_pyramid_build_clahe",
     "lvk_pyramid_levels", "lvk_pyramid_level", "lvk_orb_prepare", "lvk_image_to_gray", "lvk_min_eigen_map", "lvk_good_features", "lvk_good_features_from_map",
     "lvk_lk_track", "lvk_orb_describe", "lvk_hamming256_rows", "lvk_undistort_points", "lvk_find_fundamental_mask", "lvk_find_fundamental",
-    "lvk_ransac_fundamental", "lvk_orb_match_guided", "lvk_predict_homography",
+    "lvk_ransac_fundamental", "lvk_orb_match_guided", "lvk_align_ransac_2pt", "lvk_align_draw_pairs", "lvk_predict_homography",
     "lvk_frontend_create", "lvk_frontend_destroy", "lvk_frontend_process", "lvk_frontend_tracks", "lvk_frontend_new_pts",
-    "lvk_frontend_set_mask", "lvk_frontend_has_mask", "lvk_frontend_set_input_format", "lvk_frontend_input_format", "lvk_frontend_match_landmarks",
+    "lvk_frontend_set_mask", "lvk_frontend_has_mask", "lvk_frontend_set_input_format", "lvk_frontend_input_format", "lvk_frontend_match_landmarks", "lvk_frontend_align_landmarks",
     "lvk_frontend_state", "lvk_frontend_lk_stats", "lvk_frontend_msg_stats", "lvk_frontend_profile_enable", "lvk_frontend_profile_read",
     "lvk_frontend_stage_name", "lvk_fe_track_stage", "lvk_fe_commit_stage", "lvk_fe_msg_stage",
     "lvk_ekf_compress_qr", "lvk_ekf_compress_qr_groups", "lvk_ekf_qr_plan", "lvk_ekf_update", "lvk_ekf_update_ldlt", "lvk_ekf_update_ldlt_perm", "lvk_dgemm", "lvk_dgemm_ex", "lvk_chol_solve", "lvk_ekf_cov_propagate_augment", "lvk_ekf_cov_gather", "lvk_ekf_cov_reanchor", "lvk_ekf_cov_append_features", "lvk_ekf_landmark_cov", "lvk_ekf_pose_rel_cov", "lvk_ekf_landmark_rel_cov", "lvk_ekf_msckf_point_cov", "lvk_ekf_update_sparse", "lvk_ekf_update_landmarks", "lvk_ekf_create", "lvk_ekf_destroy", "lvk_ekf_process", "lvk_ekf_process_async", "lvk_ekf_wait", "lvk_ekf_set_state",
@@ -103,6 +103,24 @@ class MatchOptions(C.Structure):
     _fields_ = [("max_candidates", C.c_int), ("quality", C.c_double), ("min_distance", C.c_double), ("max_dist", C.c_int), ("ratio_pct", C.c_int)]
 
 
+# lvk_align_match / lvk_align_pair / lvk_align_model / lvk_align_hyp / lvk_align_result / lvk_align_options of include/lvk_c.h, the
+# LVK_ALIGN_* status codes and the seed a 0 stands for
+ALIGN_MATCH = np.dtype([("X", np.float64, 3), ("u", np.float64), ("v", np.float64)])
+ALIGN_PAIR = np.dtype([("i", np.int32), ("j", np.int32)])
+ALIGN_MODEL = np.dtype([("count", np.int32), ("root", np.int32), ("c", np.float64), ("s", np.float64), ("t", np.float64, 3)])
+ALIGN_HYP = np.dtype([("n_models", np.int32), ("pad", np.int32), ("m", ALIGN_MODEL, 2)])
+ALIGN_RESULT = np.dtype([("status", np.int32), ("n_inliers", np.int32), ("hyp", np.int32), ("root", np.int32), ("pair_i", np.int32), ("pair_j", np.int32),
+                         ("iters", np.int32), ("pad", np.int32), ("c", np.float64), ("s", np.float64), ("t", np.float64, 3),
+                         ("c0", np.float64), ("s0", np.float64), ("t0", np.float64, 3), ("A", np.float64, (4, 4)), ("rms", np.float64)])
+ALIGN_OK, ALIGN_NO_MODEL, ALIGN_FEW_INLIERS, ALIGN_SINGULAR = 0, 1, 2, 3
+ALIGN_DEFAULT_SEED = 0xFFFFFFFF
+ALIGN_MAX_MATCHES, ALIGN_MAX_PAIRS = 1024, 4096
+
+
+class AlignOptions(C.Structure):
+    _fields_ = [("thresh", C.c_double), ("min_depth", C.c_double), ("min_dz", C.c_double), ("min_inliers", C.c_int), ("max_refine_iters", C.c_int)]
+
+
 def lib():
     """Load liblvk_hip.so.  Fails loudly when the HIP extension has not been built."""
     global _LIB
@@ -136,6 +154,8 @@ def lib():
             "lvk_find_fundamental": ([vp, vp, vp, i, d, d, vp, vp, vp], i),
             "lvk_ransac_fundamental": ([vp, vp, vp, i, d, d, i, vp, vp], i),
             "lvk_orb_match_guided": ([vp, vp, vp, i, vp, vp, i, i, i, vp], i),
+            "lvk_align_ransac_2pt": ([vp, vp, i, vp, i, vp, vp, C.POINTER(AlignOptions), vp, vp, vp], i),
+            "lvk_align_draw_pairs": ([i, i, C.c_uint32, vp], i),
             "lvk_predict_homography": ([vp, i, d, d, vp, vp, vp], i),
             "lvk_frontend_create": ([vp, C.POINTER(FeConfig), C.POINTER(vp)], i), "lvk_frontend_destroy": ([vp], None),
             "lvk_frontend_process": ([vp, C.POINTER(Image), d, vp, i, vp, i, pi, pi], i),
@@ -145,6 +165,7 @@ def lib():
             "lvk_image_to_gray": ([vp, vp, i, i, i, i, i, vp, i], i),
             "lvk_frontend_set_input_format": ([vp, i, i], i), "lvk_frontend_input_format": ([vp], i),
             "lvk_frontend_match_landmarks": ([vp, vp, vp, i, C.POINTER(MatchOptions), vp, pi], i),
+            "lvk_frontend_align_landmarks": ([vp, vp, i, vp, vp, C.POINTER(AlignOptions), i, C.c_uint32, vp, vp], i),
             "lvk_frontend_lk_stats": ([vp, vp, vp], i),
             "lvk_frontend_msg_stats": ([vp, vp, vp], i),
             "lvk_frontend_profile_enable": ([vp, C.c_uint], i), "lvk_frontend_profile_read": ([vp, vp, vp, i], i),

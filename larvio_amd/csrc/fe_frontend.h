@@ -116,6 +116,8 @@ struct lvk_frontend {
         float* eig; lvk_pt2f* cand_pts; int* n_cand; uint8_t* cand_desc;
         lvk_match_query* q; uint8_t* q_desc; lvk_match_result* res; lvk_pt2f *px, *und; lvk_landmark_match* out;
     } match = {};
+    // lvk_frontend_align_landmarks' own buffers, allocated by its first call: the matches, the pairs, the mask and the result
+    struct Align { lvk_align_match* m; lvk_align_pair* pairs; uint8_t* mask; lvk_align_result* out; } align = {};
     // sticky: a frame that failed AFTER its image stage was queued (device error, ring overrun) leaves the buffer-set rotation and the
     // end-of-frame events out of step with the frame count; the handle then refuses further frames instead of racing on its buffers
     lvk_status failed = LVK_OK; char failed_msg[200] = {0};

@@ -126,7 +126,8 @@ void lvk_frontend_destroy(lvk_frontend* fe)
     }
     void* ptrs[] = {fe->d_img, fe->w_curr, fe->wn_curr, fe->w_und, fe->wn_und, fe->new_pts, fe->w_status, fe->wn_status, fe->wn_desc, fe->eig, fe->mask,
                     fe->gf_scratch, fe->gf_cands, fe->dev, fe->user_mask, fe->d_gray,
-                    fe->match.eig, fe->match.cand_pts, fe->match.n_cand, fe->match.cand_desc, fe->match.q, fe->match.q_desc, fe->match.res, fe->match.px, fe->match.und, fe->match.out};
+                    fe->match.eig, fe->match.cand_pts, fe->match.n_cand, fe->match.cand_desc, fe->match.q, fe->match.q_desc, fe->match.res, fe->match.px, fe->match.und, fe->match.out,
+                    fe->align.m, fe->align.pairs, fe->align.mask, fe->align.out};
     for (void* p : ptrs) if (p) hipFree(p);
     for (int i = 0; i < 3; ++i) { if (fe->h_stage[i]) hipHostFree(fe->h_stage[i]); if (fe->d_ring[i]) hipFree(fe->d_ring[i]); if (fe->ev_img[i]) hipEventDestroy(fe->ev_img[i]); }
     for (int i = 0; i < LVK_MSG_SLOTS; ++i) if (fe->ev_msg[i]) hipEventDestroy(fe->ev_msg[i]);
@@ -761,6 +762,48 @@ lvk_status lvk_frontend_match_landmarks(lvk_frontend* fe, const lvk_match_query*
     if (st != LVK_OK) return st;
     LVK_HIP(ctx, hipMemcpyAsync(h_out, m.out, sizeof(lvk_landmark_match) * (size_t)n_q, hipMemcpyDeviceToHost, ctx->stream));
     LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));     // (h_q and h_desc are the caller's pageable arrays: their copies are done too)
+    return LVK_OK;
+}
+
+// The yaw and translation of a prior map from its matches in the last processed frame (no reference counterpart): the pairs are drawn
+// on the host, the matches and pairs go up, lvk_align_ransac_2pt runs on the main stream in buffers the call owns, the result and the
+// mask come back.  Nothing a frame reads or writes is touched.
+#define FE_ALIGN_MAX_N     1024
+#define FE_ALIGN_MAX_PAIRS 4096
+lvk_status lvk_frontend_align_landmarks(lvk_frontend* fe, const lvk_align_match* h_m, int n, const double* R_wc, const double* p_wc, const lvk_align_options* opt,
+                                        int max_hypotheses, uint32_t seed, lvk_align_result* h_out, uint8_t* h_mask)
+{
+    if (!fe) return LVK_ERR_ARG;
+    lvk_context* ctx = fe->ctx;
+    { lvk_status fs = fe_check_failed(fe); if (fs != LVK_OK) return fs; }
+    if (n < 0 || max_hypotheses < 0 || !R_wc || !p_wc || !h_out || (n > 0 && !h_m)) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_align_landmarks: bad argument");
+    if (n > FE_ALIGN_MAX_N) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_frontend_align_landmarks: %d matches, at most %d", n, FE_ALIGN_MAX_N);
+    if (max_hypotheses > FE_ALIGN_MAX_PAIRS) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_frontend_align_landmarks: max_hypotheses %d, at most %d", max_hypotheses, FE_ALIGN_MAX_PAIRS);
+    if (fe->n_img == 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_align_landmarks: no frame has been processed yet");
+    if (fe->image_done)
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_align_landmarks: the image stage of t = %.6f is still waiting for its lvk_frontend_process", fe->image_done_ts);
+    lvk_frontend::Align& a = fe->align;
+    if (!a.m) {
+        lvk_frontend::Align b = {};
+        if (!(dalloc(&b.m, FE_ALIGN_MAX_N) && dalloc(&b.pairs, FE_ALIGN_MAX_PAIRS) && dalloc(&b.mask, FE_ALIGN_MAX_N) && dalloc(&b.out, 1))) {
+            (void)hipGetLastError();
+            void* ptrs[] = {b.m, b.pairs, b.mask, b.out};
+            for (void* p : ptrs) if (p) hipFree(p);
+            return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_frontend_align_landmarks: allocation failed");
+        }
+        a = b;
+    }
+    std::vector<lvk_align_pair> pairs(FE_ALIGN_MAX_PAIRS);
+    const int n_pairs = lvk_align_draw_pairs(n, max_hypotheses, seed, pairs.data());
+    if (n_pairs < 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_align_landmarks: the pairs could not be drawn");
+    { lvk_status qs = fe_quiesce(fe); if (qs != LVK_OK) return qs; }
+    if (n > 0) LVK_HIP(ctx, hipMemcpyAsync(a.m, h_m, sizeof(lvk_align_match) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    if (n_pairs > 0) LVK_HIP(ctx, hipMemcpyAsync(a.pairs, pairs.data(), sizeof(lvk_align_pair) * (size_t)n_pairs, hipMemcpyHostToDevice, ctx->stream));
+    const lvk_status st = lvk_align_ransac_2pt(ctx, a.m, n, a.pairs, n_pairs, R_wc, p_wc, opt, nullptr, a.mask, a.out);
+    if (st != LVK_OK) { (void)hipStreamSynchronize(ctx->stream); return st; }      // (the uploads read this call's own vector)
+    LVK_HIP(ctx, hipMemcpyAsync(h_out, a.out, sizeof(lvk_align_result), hipMemcpyDeviceToHost, ctx->stream));
+    if (h_mask && n > 0) LVK_HIP(ctx, hipMemcpyAsync(h_mask, a.mask, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LVK_OK;
 }
 

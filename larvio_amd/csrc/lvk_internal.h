@@ -67,6 +67,7 @@ enum lvk_scratch_slot {
     LVK_SCR_CHOL_WS,                    // fused Cholesky: diagonal-block inverses and the panel flag (lvk_context::chol_epoch)
     LVK_SCR_LDLT_WS,                    // LDL^T update: pivot-ordered copies of [HP | r] and X, D, the permutation, the counters
     LVK_SCR_MATCH_CLAIM,                // guided ORB matching: one claim word per candidate
+    LVK_SCR_ALIGN_HYP,                  // two-point alignment: the hypothesis records when the caller keeps none
     LVK_SCRATCH_SLOTS
 };
 #define LVK_LDS_OPTIN_KERNELS 24        // kernels that ask for more dynamic LDS than the default (fewer than that today)

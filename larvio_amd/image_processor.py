@@ -153,6 +153,26 @@ class ImageProcessor:
         self.last_match_candidates = nc.value
         return out
 
+    def align_landmarks(self, matches, R_wc, p_wc, thresh=0.0, min_depth=0.0, min_dz=0.0, min_inliers=0, max_refine_iters=0, max_hypotheses=0, seed=0):
+        """lvk_frontend_align_landmarks: the yaw and translation that take a prior map's frame into the filter's world frame, p_w = Rz X + t,
+        from putative matches of the map's points in the last processed frame.  matches: an ALIGN_MATCH array (X: the map point, u, v: the
+        normalised observation - larvio_amd.localize.align_matches builds it from match_landmarks' records), at most 1024; R_wc, p_wc: the
+        camera pose of that frame in the filter's world frame (camera-to-world rotation, camera position).  Options left at zero take the
+        library's defaults: thresh 0.01, min_depth 0.1, min_dz 1e-6, min_inliers 6, max_refine_iters 10, 4096 hypotheses, the header's
+        seed.  -> (result: one ALIGN_RESULT record - status ALIGN_OK (0) marks success; c, s, t the refined alignment, A the normal
+        matrix, rms, iters -, mask: (n,) uint8, the winner's inliers).  larvio_amd.localize.apply_alignment takes the result.  With a
+        VioPipeline call it only after drain()."""
+        from ._lib import ALIGN_MATCH, ALIGN_RESULT, AlignOptions
+        if self._h is None:
+            raise LvkError("ImageProcessor.initialize() has not succeeded")
+        m = np.ascontiguousarray(matches, ALIGN_MATCH); n = len(m)
+        R = np.ascontiguousarray(R_wc, np.float64).reshape(9); p = np.ascontiguousarray(p_wc, np.float64).reshape(3)
+        out = np.zeros(1, ALIGN_RESULT); mask = np.zeros(max(n, 1), np.uint8)
+        o = AlignOptions(float(thresh), float(min_depth), float(min_dz), int(min_inliers), int(max_refine_iters))
+        self.ctx.check(lib().lvk_frontend_align_landmarks(self._h, _p(m) if n else None, n, _p(R), _p(p), C.byref(o), int(max_hypotheses), int(seed) & 0xFFFFFFFF,
+                                                          _p(out), _p(mask)))
+        return out[0], mask[:n]
+
     @property
     def state(self):
         return lib().lvk_frontend_state(self._h)

@@ -1,4 +1,16 @@
-"""Localising against a prior map: the two host steps around ImageProcessor.match_landmarks (plain numpy, nothing here runs on the GPU).
+"""Localising against a prior map: the host steps around ImageProcessor.align_landmarks and ImageProcessor.match_landmarks (plain numpy,
+nothing here runs on the GPU).
+
+A map from another session has its own origin and yaw (gravity fixes roll and pitch in both), so relocalise first - once, or whenever
+the alignment is lost:
+
+    m0 = image_processor.match_landmarks(any_px, np.inf, desc, ratio_pct=80)   # an infinite radius: a global descriptor search
+    am, idx = align_matches(m0, X_map)                                  # the OK records as (X, u, v)
+    res, mask = image_processor.align_landmarks(am, R_wc, p_wc)         # yaw and translation of the map, RANSAC over pairs
+    p_w, cov_w = apply_alignment(res, X_map, cov_map)                   # the map in the filter's world frame (if res["status"] == ALIGN_OK)
+    cov_psi_t = alignment_cov(res, sigma_px, fe_config)                 # sigma^2 A^-1 of (psi, t), if the caller wants it
+
+then, per frame to localise on:
 
     px, ok = predict_pixels(p_w, R_wc, p_wc, fe_config)                # where the map's points should appear, from a pose prediction
     m = image_processor.match_landmarks(px[ok], radius, desc[ok])      # which corner of the frame each of them is
@@ -8,7 +20,7 @@
 The library itself only ever UNdistorts (lvk_undistort_points); predict_pixels is the forward camera model the map side needs."""
 import numpy as np
 
-from ._lib import MATCH_OK
+from ._lib import MATCH_OK, ALIGN_MATCH
 from .ops import LANDMARK_OBS
 
 
@@ -72,3 +84,37 @@ def landmark_obs(matches, p_w, cov_w, sigma_px, fe_config):
         c = np.asarray(cov_w, np.float64)
         obs["cov_w"] = c.reshape(1, 9) if c.size == 9 else c.reshape(-1, 9)[idx]
     return obs, idx
+
+
+def align_matches(matches, X_map):
+    """The ALIGN_MATCH records (X, u, v) of the matches whose status is MATCH_OK.  matches: what match_landmarks (or ops.orb_match_guided
+    with `und` filled in) returned for the map points X_map (n, 3), in the map's own frame.  -> (records, idx: the rows they came from)"""
+    X_map = np.asarray(X_map, np.float64).reshape(-1, 3)
+    if len(matches) != len(X_map):
+        raise ValueError(f"{len(matches)} matches for {len(X_map)} points")
+    idx = np.nonzero(matches["status"] == MATCH_OK)[0]
+    out = np.zeros(len(idx), ALIGN_MATCH)
+    out["X"] = X_map[idx]
+    out["u"] = matches["und"][idx, 0].astype(np.float64); out["v"] = matches["und"][idx, 1].astype(np.float64)
+    return out, idx
+
+
+def apply_alignment(result, X_map, cov_map=None):
+    """p_w = Rz X + t for the map points X_map (n, 3) with the refined (c, s, t) of an ALIGN_RESULT record, and their covariances
+    (None, one 3 x 3 or n of them) rotated by Rz: what predict_pixels and landmark_obs take.  -> (p_w (n, 3), cov_w (n, 3, 3) or None)"""
+    c, s = float(result["c"]), float(result["s"])
+    Rz = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+    X_map = np.asarray(X_map, np.float64).reshape(-1, 3)
+    p_w = X_map @ Rz.T + np.asarray(result["t"], np.float64).reshape(1, 3)
+    if cov_map is None:
+        return p_w, None
+    cov = np.asarray(cov_map, np.float64).reshape(-1, 3, 3)
+    return p_w, Rz @ cov @ Rz.T
+
+
+def alignment_cov(result, sigma_px, fe_config):
+    """sigma^2 A^-1: the covariance of (psi, t_x, t_y, t_z) from the refinement's normal matrix, for corners with a standard deviation of
+    sigma_px pixels (turned into normalised units with the mean focal length of fe_config, as landmark_obs does)"""
+    fx, fy = fe_config["intrinsics"][:2]
+    sigma = float(sigma_px) / (0.5 * (fx + fy))
+    return sigma * sigma * np.linalg.inv(np.asarray(result["A"], np.float64).reshape(4, 4))

@@ -172,6 +172,50 @@ def orb_match_guided(ctx, cand_pts, cand_desc, q_px, q_radius, q_desc, max_dist=
     return out if check else (st, out)
 
 
+def align_options(thresh=0.0, min_depth=0.0, min_dz=0.0, min_inliers=0, max_refine_iters=0):
+    """lvk_align_options; a zero field takes the library's default (0.01, 0.1, 1e-6, 6, 10)"""
+    from ._lib import AlignOptions
+    return AlignOptions(float(thresh), float(min_depth), float(min_dz), int(min_inliers), int(max_refine_iters))
+
+
+def align_draw_pairs(n, max_hypotheses=0, seed=0):
+    """lvk_align_draw_pairs (host code): the pairs ImageProcessor.align_landmarks tries for n matches -> an ALIGN_PAIR array"""
+    from ._lib import ALIGN_PAIR, ALIGN_MAX_PAIRS
+    buf = np.zeros(ALIGN_MAX_PAIRS, ALIGN_PAIR)
+    k = lib().lvk_align_draw_pairs(int(n), int(max_hypotheses), int(seed) & 0xFFFFFFFF, _p(buf))
+    if k < 0:
+        raise ValueError(f"lvk_align_draw_pairs refused n = {n}, max_hypotheses = {max_hypotheses}")
+    return buf[:k].copy()
+
+
+ALIGN_GUARD = 64        # sentinel bytes (0xA5) align_ransac_2pt keeps on either side of the records, the mask and the result
+
+
+def align_ransac_2pt(ctx, matches, pairs, R_wc, p_wc, options=None, n=None, n_pairs=None, want_hyp=True, check=True):
+    """lvk_align_ransac_2pt: matches (an ALIGN_MATCH array: X, u, v) and pairs (ALIGN_PAIR) against the camera pose (R_wc 3 x 3 camera to
+    world, p_wc); options: align_options(...) or None.  n / n_pairs default to the arrays' lengths (smaller values leave the tails unread).
+    -> dict(hyp: the n_pairs ALIGN_HYP records (None unless want_hyp), mask: n bytes, result: one ALIGN_RESULT record, and hyp_raw,
+    mask_raw, result_raw: the device buffers as bytes with ALIGN_GUARD sentinel bytes of 0xA5 on either side, every output byte starting
+    as 0xA5 too).  check=False returns (status code, that dict) instead of raising."""
+    from ._lib import ALIGN_MATCH, ALIGN_PAIR, ALIGN_HYP, ALIGN_RESULT
+    m = np.ascontiguousarray(matches, ALIGN_MATCH); pr = np.ascontiguousarray(pairs, ALIGN_PAIR)
+    n = len(m) if n is None else int(n); npr = len(pr) if n_pairs is None else int(n_pairs)
+    R = np.ascontiguousarray(R_wc, np.float64).reshape(9); p = np.ascontiguousarray(p_wc, np.float64).reshape(3)
+    G = ALIGN_GUARD
+    sizes = dict(hyp=ALIGN_HYP.itemsize * max(npr, 0), mask=max(n, 0), result=ALIGN_RESULT.itemsize)
+    bufs = {k: ctx.to_device(np.full(v + 2 * G, 0xA5, np.uint8)) for k, v in sizes.items()}
+    d_m = ctx.to_device(m.view(np.uint8) if len(m) else np.zeros(8, np.uint8)); d_pr = ctx.to_device(pr.view(np.uint8) if len(pr) else np.zeros(8, np.uint8))
+    st = lib().lvk_align_ransac_2pt(ctx.h, _p(d_m), n, _p(d_pr), npr, _p(R), _p(p), C.byref(options) if options is not None else None,
+                                    C.c_void_p(bufs["hyp"].ptr + G) if want_hyp else None, C.c_void_p(bufs["mask"].ptr + G), C.c_void_p(bufs["result"].ptr + G))
+    if check:
+        ctx.check(st)
+    ctx.sync()
+    raw = {k: ctx.to_host(bufs[k], np.uint8, (sizes[k] + 2 * G,)).copy() for k in sizes}
+    out = dict(hyp=raw["hyp"][G:G + sizes["hyp"]].view(ALIGN_HYP) if want_hyp else None, mask=raw["mask"][G:G + sizes["mask"]],
+               result=raw["result"][G:G + sizes["result"]].view(ALIGN_RESULT)[0], hyp_raw=raw["hyp"], mask_raw=raw["mask"], result_raw=raw["result"])
+    return out if check else (st, out)
+
+
 def undistort(ctx, points, intr, model, dist, new_intr):
     p = _pts(points); n = len(p)
     a = np.asarray(intr, np.float64); d = np.asarray(dist, np.float64); k = np.asarray(new_intr, np.float64)
