@@ -269,6 +269,66 @@ lvk_status lvk_align_ransac_2pt(lvk_context* ctx, const lvk_align_match* d_m, in
  * or at LVK_ALIGN_DEFAULT_SEED for a seed of 0.  Returns the number of pairs written (0 for n < 2; h_pairs holds min(n (n - 1) / 2,
  * max_hypotheses)), -1 for a negative n, max_hypotheses outside 0..4096 or a null pointer. */
 int        lvk_align_draw_pairs(int n, int max_hypotheses, uint32_t seed, lvk_align_pair* h_pairs);
+/* Stage entry: the per-frame link of that chain - where should each point of a device-resident prior map appear from a pose prediction, how
+ * far may the matcher look for it, and which at most 1024 points are worth asking lvk_orb_match_guided about.  No reference counterpart.
+ * d_X: n points (3 doubles each) in the map's own frame; d_cov: NULL or their covariances (9 doubles each, row-major, map frame); d_desc:
+ * NULL or their 32-byte descriptors; cam: the camera (intr = fx fy cx cy; model 0 radtan k1 k2 p1 p2, 1 equidistant k1..k4, as
+ * lvk_undistort_points; width, height in pixels); align: the map's alignment - only c, s, t of the record are read, NULL = identity
+ * (c = 1, s = 0, t = 0 through the same expressions); R_wc (row-major, camera to world) and p_wc as lvk_align_ransac_2pt takes them;
+ * cov_cam: NULL or the 6 x 6 covariance (row-major) of the camera pose in the order [dtheta dp]: the rotation error is on the camera side,
+ * R_true = R_wc (I + [dtheta]x), dp is in the world frame.  Turning the filter's IMU-pose block (lvk_ekf_get_window_cov) into that with the
+ * extrinsics is the caller's job.  FP64 throughout, no contraction, every expression in the order written here (a product chain a b c is
+ * (a b) c, a sum of products runs over its index upwards from the first product), so every field has one right value:
+ *   pose       q = (c X_x - s X_y, s X_x + c X_y);  g = ((q_x + t_x) - p_wc,x, (q_y + t_y) - p_wc,y, (X_z + t_z) - p_wc,z);
+ *              p_c,i = (R_wc[0][i] g_0 + R_wc[1][i] g_1) + R_wc[2][i] g_2 (= R_wc^T (Rz X + t - p_wc));  x = p_c,x / p_c,z, y = p_c,y / p_c,z,
+ *              r2 = x x + y y.
+ *   model      radtan: rad = 1 + (k2 r2 + k1) r2;  xd = x rad + 2 p1 x y + p2 (r2 + 2 x x);  yd = y rad + p1 (r2 + 2 y y) + 2 p2 x y.
+ *              equidistant: r = sqrt(r2), th = atan(r), t2 = th th, thd = th (1 + t2 (k1 + t2 (k2 + t2 (k3 + t2 k4)))), s = thd / r when
+ *              r > 1e-8, else 1;  xd = x s, yd = y s.  px = fx xd + cx, py = fy yd + cy.  (The library's first forward model; everything
+ *              else undistorts.)
+ *   status     the first rule that applies: BEHIND unless p_c,z > min_depth (a NaN lands here); FAR when p_c,z > max_depth; OUTSIDE unless
+ *              r2 <= max_r2; OUTSIDE unless margin <= px <= (width - 1) - margin and margin <= py <= (height - 1) - margin (a NaN pixel lands
+ *              here); otherwise VISIBLE.  A radtan model folds back beyond its range: max_r2 is the guard (larvio_amd.localize.view_limit).
+ *   radius     S = 0.  With d_cov: R = Rz^T R_wc (R[0][j] = c R_wc[0][j] + s R_wc[1][j], R[1][j] = c R_wc[1][j] - s R_wc[0][j], R[2][j] =
+ *              R_wc[2][j]), M = Sigma_X R, S = R^T M - the point's covariance in the camera frame.  With cov_cam: G = [ [p_c]x | -R_wc^T ]
+ *              (3 x 6), T = G cov_cam, K = T G^T, and S = S + K (S = K without d_cov).  u_j = S[0][j] - x S[2][j], v_j = S[1][j] - y S[2][j];
+ *              e00 = u_0 - u_2 x, e01 = u_1 - u_2 y, e10 = v_0 - v_2 x, e11 = v_1 - v_2 y (= z^2 J S J^T, J = (1 / p_c,z) [[1, 0, -x],
+ *              [0, 1, -y]]);  sx = fx / p_c,z, sy = fy / p_c,z;  a = (sx sx) e00, d = (sy sy) e11, b = ((sx sy) e01 + (sx sy) e10) / 2;
+ *              lambda = (a + d) / 2 + sqrt(((a - d) / 2)^2 + b^2), the larger eigenvalue of the pixel covariance; lambda = 0 with neither
+ *              covariance.  radius = k_sigma sqrt(lambda + sigma_px^2), clamped to [r_min, r_max]; r_max when lambda is negative or not
+ *              finite.  The distortion's own Jacobian is left out on purpose: the radius is a gate, not a measurement.
+ *   cell       col = min(cols - 1, (int)((px cols) / width)), row = min(rows - 1, (int)((py rows) / height)), from the FP64 pixel;
+ *              cell = row cols + col.
+ *   selection  every cell keeps its `quota` VISIBLE points with the lowest map index; the output is ordered by (cell, map index), both
+ *              ascending.  The map's order is its priority: sort it best-first once, at upload.  Nothing in the rule depends on the
+ *              order in which anything ran: two runs on the same input give the same bytes.
+ * px, py, radius and p_c,z are rounded to float32 once, at the end.  d_sel: the selected points' records; d_q: the same as lvk_match_query
+ * (pad 0), ready for lvk_orb_match_guided; d_q_desc: their descriptors, gathered from d_desc (required when d_desc is given, not touched
+ * otherwise) - all three with room for rows cols quota records; d_info: n_selected and the count per status (n_candidates 0, pad 0);
+ * d_status: NULL or n bytes, the status with bit 7 set on a selected point.  Records beyond n_selected are not written.  Three launches on
+ * the context's stream (project and count; scan the chunk x cell table; ordered scatter and gather), not waited for; the covariances are
+ * read for the selected points only.
+ * opt may be NULL; a zero field takes its default: min_depth 0.1, max_depth +inf, max_r2 +inf (no test), margin 0, k_sigma 3, sigma_px 1,
+ * r_min 4, r_max 40, rows x cols 4 x 5 (1..16 each), quota 1024 / (rows cols) rounded down.
+ * LVK_ERR_ARG, with nothing launched and the context still usable: a null pointer that is needed, a negative count, a non-finite entry of
+ * R_wc, p_wc, the alignment or the camera, width or height < 1, a model other than 0 or 1, an option that is NaN, a negative margin, r_min
+ * > r_max, rows or cols outside 1..16, quota < 1, rows cols quota > 1024, a descriptor pointer that is not 8-byte aligned.
+ * LVK_ERR_CAPACITY: n > 1,048,576.  n == 0: LVK_OK, d_info zeroed, nothing launched. */
+#define LVK_MAP_VISIBLE  0
+#define LVK_MAP_BEHIND   1
+#define LVK_MAP_FAR      2
+#define LVK_MAP_OUTSIDE  3
+#define LVK_MAP_SELECTED 0x80                    /* bit 7 of a d_status byte */
+#define LVK_MAP_MAX_POINTS  1048576
+#define LVK_MAP_MAX_QUERIES 1024
+typedef struct { double intr[4]; int model, width, height, pad; double dist[4]; } lvk_map_camera;
+typedef struct { double min_depth, max_depth, max_r2, margin, k_sigma, sigma_px, r_min, r_max; int rows, cols, quota, pad; } lvk_map_select_options;   /* zeros = defaults */
+typedef struct { int index, cell; float x, y, radius, depth; } lvk_map_sel;
+typedef struct { int n_selected, n_visible, n_behind, n_far, n_outside, n_candidates, pad[2]; } lvk_map_info;
+lvk_status lvk_map_select_queries(lvk_context* ctx, const double* d_X, const double* d_cov, const uint8_t* d_desc, int n,
+                                  const lvk_map_camera* cam, const lvk_align_result* align, const double R_wc[9], const double p_wc[3],
+                                  const double cov_cam[36], const lvk_map_select_options* opt, lvk_map_sel* d_sel, lvk_match_query* d_q,
+                                  uint8_t* d_q_desc, lvk_map_info* d_info, uint8_t* d_status);
 /* replaces integrateImuData + predictFeatureTracking's matrix (image_processor.cpp:222-293): host math */
 lvk_status lvk_predict_homography(const lvk_imu* h_imu, int n_imu, double t_prev, double t_curr,
                                   const double R_cam_imu[9], const double intr[4], float H[9]);
@@ -371,6 +431,31 @@ lvk_status lvk_frontend_match_landmarks(lvk_frontend* fe, const lvk_match_query*
 lvk_status lvk_frontend_align_landmarks(lvk_frontend* fe, const lvk_align_match* h_m, int n, const double R_wc[9], const double p_wc[3],
                                         const lvk_align_options* opt, int max_hypotheses, uint32_t seed, lvk_align_result* h_out,
                                         uint8_t* h_mask);
+/* The per-frame link of that chain with the map resident on the device.  lvk_frontend_set_map copies a prior map - n points h_X (3 doubles
+ * each, the map's own frame), their covariances h_cov9 (9 doubles each, may be NULL) and their 32-byte descriptors h_desc (required) - into
+ * device buffers the front-end owns; it replaces a previous map, n == 0 frees it (the pointers may then be NULL).  The map's order is its
+ * priority (lvk_map_select_queries).  It waits for the front-end's own streams and for the copies.  LVK_ERR_ARG: a null pointer that is
+ * needed, n < 0, a call between lvk_frontend_begin and the lvk_frontend_process of the same frame; LVK_ERR_CAPACITY: n > 1,048,576;
+ * LVK_ERR_DEVICE when the buffers cannot be had - in each case the map in force stays.  lvk_frontend_map_size = the points of the map in
+ * force (0: none).
+ * lvk_frontend_match_map runs lvk_map_select_queries on that map with the configured camera (align, R_wc, p_wc, cov_cam36, select_opt as
+ * the stage entry takes them), reads n_selected back, then runs exactly the device chain of lvk_frontend_match_landmarks (match_opt: its
+ * options) on the selected queries and their gathered descriptors, and copies n_selected records back: index and cell of the map point,
+ * the query q the matcher was given, the point's depth, and m, the record lvk_frontend_match_landmarks returns for that query.  cap: the
+ * room in h_out, at least rows cols quota of select_opt (1020 with the defaults); *n_out = n_selected; h_info (may be NULL): the stage
+ * entry's counts with n_candidates = the corners the frame offered.  The same preconditions, waits (three here: the selection's count,
+ * the corner count, the records) and promise as lvk_frontend_match_landmarks: off the per-frame path, it changes nothing a later frame
+ * reads - a run with these calls publishes the bits of a run without them - and a front-end that never calls them launches what it
+ * launched before.  LVK_ERR_ARG, with nothing launched: no map is set, a null pointer that is needed, a call before the first processed
+ * frame or between lvk_frontend_begin and the lvk_frontend_process of the same frame, and the refusals of the stage entry and of
+ * lvk_frontend_match_landmarks; LVK_ERR_CAPACITY: cap < rows cols quota, and what lvk_frontend_match_landmarks passes through.  None is
+ * sticky.  With a lvk_vio_pipe attached, call either only between lvk_vio_pipe_drain and the next lvk_vio_pipe_submit. */
+typedef struct { int index, cell; lvk_match_query q; float depth, pad; lvk_landmark_match m; } lvk_map_match;
+lvk_status lvk_frontend_set_map(lvk_frontend* fe, const double* h_X, const double* h_cov9, const uint8_t* h_desc, int n);
+int        lvk_frontend_map_size(const lvk_frontend* fe);
+lvk_status lvk_frontend_match_map(lvk_frontend* fe, const lvk_align_result* align, const double R_wc[9], const double p_wc[3],
+                                  const double cov_cam36[36], const lvk_map_select_options* select_opt, const lvk_match_options* match_opt,
+                                  lvk_map_match* h_out, int cap, int* n_out, lvk_map_info* h_info);
 /* cumulative LK work: point-levels processed and iterations executed (SURVEY §8d byte model) */
 lvk_status lvk_frontend_lk_stats(lvk_frontend* fe, uint64_t* point_levels, uint64_t* iterations);
 /* feature messages published so far (getFeatureMsg, image_processor.cpp:1076-1128) and the features they carried in total:

@@ -125,6 +125,35 @@ public:
         }
         return true;
     }
+    // keep a prior map on the device (lvk_frontend_set_map; the reference has no such call): X = 3 doubles per point in the map's own frame,
+    // best first - the order is the priority matchMap selects by -, cov9 = 9 doubles per point or empty, desc = 32 bytes per point.  Replaces
+    // a previous map, an empty X frees it.  With a VioPipeline only after drain().  false = refused.
+    bool setMap(const std::vector<double>& X, const std::vector<double>& cov9, const std::vector<uint8_t>& desc)
+    {
+        const size_t n = X.size() / 3;
+        if (!fe_ || X.size() != 3 * n || desc.size() != 32 * n || (!cov9.empty() && cov9.size() != 9 * n)) return false;
+        if (lvk_frontend_set_map(fe_, n ? X.data() : nullptr, cov9.empty() ? nullptr : cov9.data(), n ? desc.data() : nullptr, (int)n) != LVK_OK) {
+            std::fprintf(stderr, "ImageProcessor::setMap: %s\n", lvk_last_error(ctx_)); return false;
+        }
+        return true;
+    }
+    // the resident map's points in the last processed frame (lvk_frontend_match_map): projected from the pose prediction R_wc, p_wc (align:
+    // the map's alignment or null, cov_cam36: the pose covariance [dtheta dp] or null), culled, at most 1024 picked cell by cell and
+    // matched.  out[i].index is the map point, out[i].m.status == LVK_MATCH_OK marks a match.  With a VioPipeline only after drain().
+    bool matchMap(const double R_wc[9], const double p_wc[3], std::vector<lvk_map_match>& out, const lvk_align_result* align = nullptr,
+                  const double* cov_cam36 = nullptr, const lvk_map_select_options* select_opt = nullptr, const lvk_match_options* match_opt = nullptr,
+                  lvk_map_info* info = nullptr)
+    {
+        if (!fe_) return false;
+        out.resize(LVK_MAP_MAX_QUERIES);
+        int n = 0;
+        if (lvk_frontend_match_map(fe_, align, R_wc, p_wc, cov_cam36, select_opt, match_opt, out.data(), (int)out.size(), &n, info) != LVK_OK) {
+            out.clear();
+            std::fprintf(stderr, "ImageProcessor::matchMap: %s\n", lvk_last_error(ctx_)); return false;
+        }
+        out.resize((size_t)n);
+        return true;
+    }
     lvk_frontend* handle() const { return fe_; }
 private:
     ImageProcessor(const ImageProcessor&); ImageProcessor& operator=(const ImageProcessor&);

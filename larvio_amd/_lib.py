@@ -21,9 +21,10 @@ ABI_SYMBOLS = [
     "lvk_clahe_u8", "lvk_pyramid_create", "lvk_pyramid_destroy", "lvk_pyramid_build", "lvk_pyramid_build_clahe",
     "lvk_pyramid_levels", "lvk_pyramid_level", "lvk_orb_prepare", "lvk_image_to_gray", "lvk_min_eigen_map", "lvk_good_features", "lvk_good_features_from_map",
     "lvk_lk_track", "lvk_orb_describe", "lvk_hamming256_rows", "lvk_undistort_points", "lvk_find_fundamental_mask", "lvk_find_fundamental",
-    "lvk_ransac_fundamental", "lvk_orb_match_guided", "lvk_align_ransac_2pt", "lvk_align_draw_pairs", "lvk_predict_homography",
+    "lvk_ransac_fundamental", "lvk_orb_match_guided", "lvk_align_ransac_2pt", "lvk_align_draw_pairs", "lvk_map_select_queries", "lvk_predict_homography",
     "lvk_frontend_create", "lvk_frontend_destroy", "lvk_frontend_process", "lvk_frontend_tracks", "lvk_frontend_new_pts",
     "lvk_frontend_set_mask", "lvk_frontend_has_mask", "lvk_frontend_set_input_format", "lvk_frontend_input_format", "lvk_frontend_match_landmarks", "lvk_frontend_align_landmarks",
+    "lvk_frontend_set_map", "lvk_frontend_map_size", "lvk_frontend_match_map",
     "lvk_frontend_state", "lvk_frontend_lk_stats", "lvk_frontend_msg_stats", "lvk_frontend_profile_enable", "lvk_frontend_profile_read",
     "lvk_frontend_stage_name", "lvk_fe_track_stage", "lvk_fe_commit_stage", "lvk_fe_msg_stage",
     "lvk_ekf_compress_qr", "lvk_ekf_compress_qr_groups", "lvk_ekf_qr_plan", "lvk_ekf_update", "lvk_ekf_update_ldlt", "lvk_ekf_update_ldlt_perm", "lvk_dgemm", "lvk_dgemm_ex", "lvk_chol_solve", "lvk_ekf_cov_propagate_augment", "lvk_ekf_cov_gather", "lvk_ekf_cov_reanchor", "lvk_ekf_cov_append_features", "lvk_ekf_landmark_cov", "lvk_ekf_pose_rel_cov", "lvk_ekf_landmark_rel_cov", "lvk_ekf_msckf_point_cov", "lvk_ekf_update_sparse", "lvk_ekf_update_landmarks", "lvk_ekf_create", "lvk_ekf_destroy", "lvk_ekf_process", "lvk_ekf_process_async", "lvk_ekf_wait", "lvk_ekf_set_state",
@@ -121,6 +122,26 @@ class AlignOptions(C.Structure):
     _fields_ = [("thresh", C.c_double), ("min_depth", C.c_double), ("min_dz", C.c_double), ("min_inliers", C.c_int), ("max_refine_iters", C.c_int)]
 
 
+# lvk_map_sel / lvk_map_info / lvk_map_match / lvk_map_camera / lvk_map_select_options of include/lvk_c.h, the LVK_MAP_* status codes, the bit
+# a selected point carries in its status byte and the two caps
+MAP_SEL = np.dtype([("index", np.int32), ("cell", np.int32), ("x", np.float32), ("y", np.float32), ("radius", np.float32), ("depth", np.float32)])
+MAP_INFO = np.dtype([("n_selected", np.int32), ("n_visible", np.int32), ("n_behind", np.int32), ("n_far", np.int32), ("n_outside", np.int32),
+                     ("n_candidates", np.int32), ("pad", np.int32, 2)])
+MAP_MATCH = np.dtype([("index", np.int32), ("cell", np.int32), ("q", MATCH_QUERY), ("depth", np.float32), ("pad", np.float32), ("m", LANDMARK_MATCH)])
+MAP_VISIBLE, MAP_BEHIND, MAP_FAR, MAP_OUTSIDE = 0, 1, 2, 3
+MAP_SELECTED = 0x80
+MAP_MAX_POINTS, MAP_MAX_QUERIES = 1 << 20, 1024
+
+
+class MapCamera(C.Structure):
+    _fields_ = [("intr", C.c_double * 4), ("model", C.c_int), ("width", C.c_int), ("height", C.c_int), ("pad", C.c_int), ("dist", C.c_double * 4)]
+
+
+class MapSelectOptions(C.Structure):
+    _fields_ = [("min_depth", C.c_double), ("max_depth", C.c_double), ("max_r2", C.c_double), ("margin", C.c_double), ("k_sigma", C.c_double),
+                ("sigma_px", C.c_double), ("r_min", C.c_double), ("r_max", C.c_double), ("rows", C.c_int), ("cols", C.c_int), ("quota", C.c_int), ("pad", C.c_int)]
+
+
 def lib():
     """Load liblvk_hip.so.  Fails loudly when the HIP extension has not been built."""
     global _LIB
@@ -156,6 +177,7 @@ def lib():
             "lvk_orb_match_guided": ([vp, vp, vp, i, vp, vp, i, i, i, vp], i),
             "lvk_align_ransac_2pt": ([vp, vp, i, vp, i, vp, vp, C.POINTER(AlignOptions), vp, vp, vp], i),
             "lvk_align_draw_pairs": ([i, i, C.c_uint32, vp], i),
+            "lvk_map_select_queries": ([vp, vp, vp, vp, i, C.POINTER(MapCamera), vp, vp, vp, vp, C.POINTER(MapSelectOptions), vp, vp, vp, vp, vp], i),
             "lvk_predict_homography": ([vp, i, d, d, vp, vp, vp], i),
             "lvk_frontend_create": ([vp, C.POINTER(FeConfig), C.POINTER(vp)], i), "lvk_frontend_destroy": ([vp], None),
             "lvk_frontend_process": ([vp, C.POINTER(Image), d, vp, i, vp, i, pi, pi], i),
@@ -166,6 +188,8 @@ def lib():
             "lvk_frontend_set_input_format": ([vp, i, i], i), "lvk_frontend_input_format": ([vp], i),
             "lvk_frontend_match_landmarks": ([vp, vp, vp, i, C.POINTER(MatchOptions), vp, pi], i),
             "lvk_frontend_align_landmarks": ([vp, vp, i, vp, vp, C.POINTER(AlignOptions), i, C.c_uint32, vp, vp], i),
+            "lvk_frontend_set_map": ([vp, vp, vp, vp, i], i), "lvk_frontend_map_size": ([vp], i),
+            "lvk_frontend_match_map": ([vp, vp, vp, vp, vp, C.POINTER(MapSelectOptions), C.POINTER(MatchOptions), vp, i, pi, vp], i),
             "lvk_frontend_lk_stats": ([vp, vp, vp], i),
             "lvk_frontend_msg_stats": ([vp, vp, vp], i),
             "lvk_frontend_profile_enable": ([vp, C.c_uint], i), "lvk_frontend_profile_read": ([vp, vp, vp, i], i),

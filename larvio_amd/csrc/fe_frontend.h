@@ -118,6 +118,9 @@ struct lvk_frontend {
     } match = {};
     // lvk_frontend_align_landmarks' own buffers, allocated by its first call: the matches, the pairs, the mask and the result
     struct Align { lvk_align_match* m; lvk_align_pair* pairs; uint8_t* mask; lvk_align_result* out; } align = {};
+    // the prior map of lvk_frontend_set_map (null in a front-end without one): its n points, their covariances (or null) and descriptors,
+    // and lvk_frontend_match_map's own buffers, allocated with the map: the selected points' records and the counts
+    struct Map { double *X, *cov; uint8_t* desc; int n; lvk_map_sel* sel; lvk_map_info* info; } map = {};
     // sticky: a frame that failed AFTER its image stage was queued (device error, ring overrun) leaves the buffer-set rotation and the
     // end-of-frame events out of step with the frame count; the handle then refuses further frames instead of racing on its buffers
     lvk_status failed = LVK_OK; char failed_msg[200] = {0};
@@ -169,6 +172,8 @@ lvk_status fe_msg_launch(lvk_frontend* fe, int dst, const FeMsgArgs& m);
 // fe_match.hip: matched pixels, their normalised coordinates and the host's records behind lvk_orb_match_guided, on the context's stream
 lvk_status fe_match_finish(lvk_context* ctx, const CamParams& cam, const lvk_match_result* d_res, const lvk_pt2f* d_cand_pts, int n_q, lvk_pt2f* d_px, lvk_pt2f* d_und,
                            lvk_landmark_match* d_out);
+// fe_map.hip: rows * cols * quota of the options as lvk_map_select_queries reads them, -1 when it refuses them
+int fe_map_max_selected(const lvk_map_select_options* opt);
 #ifdef LVK_LK_BOUNDS
 void fe_lk_bounds_report();                             // prints what the frame path's kernels recorded in THEIR copy of g_lk_oob
 #endif

@@ -127,7 +127,7 @@ void lvk_frontend_destroy(lvk_frontend* fe)
     void* ptrs[] = {fe->d_img, fe->w_curr, fe->wn_curr, fe->w_und, fe->wn_und, fe->new_pts, fe->w_status, fe->wn_status, fe->wn_desc, fe->eig, fe->mask,
                     fe->gf_scratch, fe->gf_cands, fe->dev, fe->user_mask, fe->d_gray,
                     fe->match.eig, fe->match.cand_pts, fe->match.n_cand, fe->match.cand_desc, fe->match.q, fe->match.q_desc, fe->match.res, fe->match.px, fe->match.und, fe->match.out,
-                    fe->align.m, fe->align.pairs, fe->align.mask, fe->align.out};
+                    fe->align.m, fe->align.pairs, fe->align.mask, fe->align.out, fe->map.X, fe->map.cov, fe->map.desc, fe->map.sel, fe->map.info};
     for (void* p : ptrs) if (p) hipFree(p);
     for (int i = 0; i < 3; ++i) { if (fe->h_stage[i]) hipHostFree(fe->h_stage[i]); if (fe->d_ring[i]) hipFree(fe->d_ring[i]); if (fe->ev_img[i]) hipEventDestroy(fe->ev_img[i]); }
     for (int i = 0; i < LVK_MSG_SLOTS; ++i) if (fe->ev_msg[i]) hipEventDestroy(fe->ev_msg[i]);
@@ -705,14 +705,10 @@ int lvk_frontend_input_format(const lvk_frontend* fe) { return fe ? fe->pix_form
 // call's own (fe->match) or the main context's stage scratch: the detection's eig / mask / scratch on side[0] are not touched.
 #define FE_MATCH_MAX_CAND 4096
 #define FE_MATCH_MAX_Q    1024
-lvk_status lvk_frontend_match_landmarks(lvk_frontend* fe, const lvk_match_query* h_q, const uint8_t* h_desc, int n_q, const lvk_match_options* opt,
-                                        lvk_landmark_match* h_out, int* n_cand_out)
+// the options with their defaults filled in and their ranges checked, as lvk_frontend_match_landmarks states them
+static lvk_status fe_match_options(lvk_frontend* fe, const lvk_match_options* opt, lvk_match_options* out)
 {
-    if (!fe) return LVK_ERR_ARG;
     lvk_context* ctx = fe->ctx;
-    { lvk_status fs = fe_check_failed(fe); if (fs != LVK_OK) return fs; }
-    if (n_q < 0 || (n_q > 0 && (!h_q || !h_desc || !h_out))) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: bad argument");
-    if (n_q > FE_MATCH_MAX_Q) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_frontend_match_landmarks: %d queries, at most %d", n_q, FE_MATCH_MAX_Q);
     lvk_match_options o = {0, 0., 0., 0, 0};
     if (opt) o = *opt;
     if (o.max_candidates == 0) o.max_candidates = FE_MATCH_MAX_CAND;
@@ -729,22 +725,35 @@ lvk_status lvk_frontend_match_landmarks(lvk_frontend* fe, const lvk_match_query*
     if (fe->n_img == 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: no frame has been processed yet");
     if (fe->image_done)
         return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: the image stage of t = %.6f is still waiting for its lvk_frontend_process", fe->image_done_ts);
+    *out = o;
+    return LVK_OK;
+}
+// the matcher's buffers, allocated by the first call that needs them
+static lvk_status fe_match_buffers(lvk_frontend* fe)
+{
+    if (fe->match.eig) return LVK_OK;
+    const int w = fe->cfg.width, h = fe->cfg.height;
+    lvk_frontend::Match a = {};
+    const bool ok = dalloc(&a.eig, (size_t)w * h) && dalloc(&a.cand_pts, FE_MATCH_MAX_CAND) && dalloc(&a.n_cand, 1) && dalloc(&a.cand_desc, (size_t)32 * FE_MATCH_MAX_CAND) &&
+                    dalloc(&a.q, FE_MATCH_MAX_Q) && dalloc(&a.q_desc, (size_t)32 * FE_MATCH_MAX_Q) && dalloc(&a.res, FE_MATCH_MAX_Q) && dalloc(&a.px, FE_MATCH_MAX_Q) &&
+                    dalloc(&a.und, FE_MATCH_MAX_Q) && dalloc(&a.out, FE_MATCH_MAX_Q);
+    if (!ok) {
+        (void)hipGetLastError();
+        void* ptrs[] = {a.eig, a.cand_pts, a.n_cand, a.cand_desc, a.q, a.q_desc, a.res, a.px, a.und, a.out};
+        for (void* p : ptrs) if (p) hipFree(p);
+        return lvk_set_error(fe->ctx, LVK_ERR_DEVICE, "lvk_frontend_match_landmarks: allocation failed");
+    }
+    fe->match = a;
+    return LVK_OK;
+}
+// The device chain of lvk_frontend_match_landmarks on n_q queries that are already in fe->match.q / q_desc (their upload, or the kernels
+// that wrote them, queued on the main stream): corners of the last processed frame, their descriptors, the matcher, the records in
+// fe->match.out.  Waits once, for the corner count; the records are not waited for.
+static lvk_status fe_match_chain(lvk_frontend* fe, const lvk_match_options& o, int n_q, int* n_cand_out)
+{
+    lvk_context* ctx = fe->ctx;
     const int w = fe->cfg.width, h = fe->cfg.height;
     lvk_frontend::Match& m = fe->match;
-    if (!m.eig) {
-        lvk_frontend::Match a = {};
-        const bool ok = dalloc(&a.eig, (size_t)w * h) && dalloc(&a.cand_pts, FE_MATCH_MAX_CAND) && dalloc(&a.n_cand, 1) && dalloc(&a.cand_desc, (size_t)32 * FE_MATCH_MAX_CAND) &&
-                        dalloc(&a.q, FE_MATCH_MAX_Q) && dalloc(&a.q_desc, (size_t)32 * FE_MATCH_MAX_Q) && dalloc(&a.res, FE_MATCH_MAX_Q) && dalloc(&a.px, FE_MATCH_MAX_Q) &&
-                        dalloc(&a.und, FE_MATCH_MAX_Q) && dalloc(&a.out, FE_MATCH_MAX_Q);
-        if (!ok) {
-            (void)hipGetLastError();
-            void* ptrs[] = {a.eig, a.cand_pts, a.n_cand, a.cand_desc, a.q, a.q_desc, a.res, a.px, a.und, a.out};
-            for (void* p : ptrs) if (p) hipFree(p);
-            return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_frontend_match_landmarks: allocation failed");
-        }
-        m = a;
-    }
-    { lvk_status qs = fe_quiesce(fe); if (qs != LVK_OK) return qs; }
     lvk_status st = lvk_min_eigen_map(ctx, fe->pyr[0], m.eig);
     if (st == LVK_OK) st = lvk_good_features_from_map(ctx, m.eig, nullptr, w, h, o.max_candidates, o.quality, o.min_distance, m.cand_pts, FE_MATCH_MAX_CAND, m.n_cand);
     if (st != LVK_OK) return st;
@@ -754,14 +763,122 @@ lvk_status lvk_frontend_match_landmarks(lvk_frontend* fe, const lvk_match_query*
     if (n_cand < 0 || n_cand > FE_MATCH_MAX_CAND) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_frontend_match_landmarks: the selection reported %d corners", n_cand);
     if (n_cand_out) *n_cand_out = n_cand;
     if (n_q == 0) return LVK_OK;
-    LVK_HIP(ctx, hipMemcpyAsync(m.q, h_q, sizeof(lvk_match_query) * (size_t)n_q, hipMemcpyHostToDevice, ctx->stream));
-    LVK_HIP(ctx, hipMemcpyAsync(m.q_desc, h_desc, (size_t)32 * n_q, hipMemcpyHostToDevice, ctx->stream));
     st = lvk_orb_describe(ctx, fe->ext[0], fe->blur[0], w, h, m.cand_pts, n_cand, m.cand_desc, nullptr);
     if (st == LVK_OK) st = lvk_orb_match_guided(ctx, m.cand_pts, m.cand_desc, n_cand, m.q, m.q_desc, n_q, o.max_dist, o.ratio_pct, m.res);
     if (st == LVK_OK) st = fe_match_finish(ctx, fe->cam, m.res, m.cand_pts, n_q, m.px, m.und, m.out);
+    return st;
+}
+
+lvk_status lvk_frontend_match_landmarks(lvk_frontend* fe, const lvk_match_query* h_q, const uint8_t* h_desc, int n_q, const lvk_match_options* opt,
+                                        lvk_landmark_match* h_out, int* n_cand_out)
+{
+    if (!fe) return LVK_ERR_ARG;
+    lvk_context* ctx = fe->ctx;
+    { lvk_status fs = fe_check_failed(fe); if (fs != LVK_OK) return fs; }
+    if (n_q < 0 || (n_q > 0 && (!h_q || !h_desc || !h_out))) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: bad argument");
+    if (n_q > FE_MATCH_MAX_Q) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_frontend_match_landmarks: %d queries, at most %d", n_q, FE_MATCH_MAX_Q);
+    lvk_match_options o;
+    lvk_status st = fe_match_options(fe, opt, &o);
+    if (st == LVK_OK) st = fe_match_buffers(fe);
     if (st != LVK_OK) return st;
+    lvk_frontend::Match& m = fe->match;
+    { lvk_status qs = fe_quiesce(fe); if (qs != LVK_OK) return qs; }
+    if (n_q > 0) {
+        LVK_HIP(ctx, hipMemcpyAsync(m.q, h_q, sizeof(lvk_match_query) * (size_t)n_q, hipMemcpyHostToDevice, ctx->stream));
+        LVK_HIP(ctx, hipMemcpyAsync(m.q_desc, h_desc, (size_t)32 * n_q, hipMemcpyHostToDevice, ctx->stream));
+    }
+    st = fe_match_chain(fe, o, n_q, n_cand_out);
+    if (st != LVK_OK) { (void)hipStreamSynchronize(ctx->stream); return st; }      // (the uploads read the caller's arrays)
+    if (n_q == 0) return LVK_OK;
     LVK_HIP(ctx, hipMemcpyAsync(h_out, m.out, sizeof(lvk_landmark_match) * (size_t)n_q, hipMemcpyDeviceToHost, ctx->stream));
     LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));     // (h_q and h_desc are the caller's pageable arrays: their copies are done too)
+    return LVK_OK;
+}
+
+// The prior map, resident on the device (no reference counterpart).  New buffers are filled before the old ones go, so a refusal leaves
+// the map in force; lvk_frontend_match_map always returns with its work done, so nothing reads the old buffers when they are freed.
+lvk_status lvk_frontend_set_map(lvk_frontend* fe, const double* h_X, const double* h_cov9, const uint8_t* h_desc, int n)
+{
+    if (!fe) return LVK_ERR_ARG;
+    lvk_context* ctx = fe->ctx;
+    { lvk_status fs = fe_check_failed(fe); if (fs != LVK_OK) return fs; }
+    if (n < 0 || (n > 0 && (!h_X || !h_desc))) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_set_map: bad argument");
+    if (n > LVK_MAP_MAX_POINTS) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_frontend_set_map: %d points, at most %d", n, LVK_MAP_MAX_POINTS);
+    if (fe->image_done)
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_set_map: the image stage of t = %.6f is still waiting for its lvk_frontend_process", fe->image_done_ts);
+    lvk_frontend::Map b = {};
+    if (n > 0) {
+        const bool ok = dalloc(&b.X, (size_t)3 * n) && (!h_cov9 || dalloc(&b.cov, (size_t)9 * n)) && dalloc(&b.desc, (size_t)32 * n) && dalloc(&b.sel, LVK_MAP_MAX_QUERIES) &&
+                        dalloc(&b.info, 1);
+        hipError_t e = ok ? hipMemcpyAsync(b.X, h_X, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream) : hipErrorOutOfMemory;
+        if (e == hipSuccess && h_cov9) e = hipMemcpyAsync(b.cov, h_cov9, sizeof(double) * 9 * (size_t)n, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(b.desc, h_desc, (size_t)32 * n, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            void* ptrs[] = {b.X, b.cov, b.desc, b.sel, b.info};
+            for (void* p : ptrs) if (p) hipFree(p);
+            return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_frontend_set_map: %s", ok ? hipGetErrorString(e) : "allocation failed");
+        }
+        b.n = n;
+    }
+    { lvk_status qs = fe_quiesce(fe); if (qs != LVK_OK) return qs; }
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    void* old[] = {fe->map.X, fe->map.cov, fe->map.desc, fe->map.sel, fe->map.info};
+    for (void* p : old) if (p) hipFree(p);
+    fe->map = b;
+    return LVK_OK;
+}
+int lvk_frontend_map_size(const lvk_frontend* fe) { return fe ? fe->map.n : -1; }
+
+// The map's points in the last processed frame: lvk_map_select_queries writes the queries and their descriptors straight into the
+// matcher's buffers, the chain of lvk_frontend_match_landmarks runs on them, the host joins the two record arrays.
+lvk_status lvk_frontend_match_map(lvk_frontend* fe, const lvk_align_result* align, const double* R_wc, const double* p_wc, const double* cov_cam36,
+                                  const lvk_map_select_options* select_opt, const lvk_match_options* match_opt, lvk_map_match* h_out, int cap, int* n_out,
+                                  lvk_map_info* h_info)
+{
+    if (!fe) return LVK_ERR_ARG;
+    lvk_context* ctx = fe->ctx;
+    { lvk_status fs = fe_check_failed(fe); if (fs != LVK_OK) return fs; }
+    if (!R_wc || !p_wc || !h_out || !n_out || cap < 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_map: bad argument");
+    if (fe->map.n == 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_map: no map is set (lvk_frontend_set_map)");
+    const int most = fe_map_max_selected(select_opt);
+    if (most >= 0 && cap < most) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_frontend_match_map: room for %d records, the options can select %d", cap, most);
+    lvk_match_options o;
+    lvk_status st = fe_match_options(fe, match_opt, &o);
+    if (st == LVK_OK) st = fe_match_buffers(fe);
+    if (st != LVK_OK) return st;
+    lvk_frontend::Match& m = fe->match;
+    lvk_frontend::Map& mp = fe->map;
+    lvk_map_camera cam;
+    memset(&cam, 0, sizeof cam);
+    for (int k = 0; k < 4; ++k) { cam.intr[k] = fe->cam.intr[k]; cam.dist[k] = fe->cam.dist[k]; }
+    cam.model = fe->cam.model; cam.width = fe->cam.width; cam.height = fe->cam.height;
+    { lvk_status qs = fe_quiesce(fe); if (qs != LVK_OK) return qs; }
+    st = lvk_map_select_queries(ctx, mp.X, mp.cov, mp.desc, mp.n, &cam, align, R_wc, p_wc, cov_cam36, select_opt, mp.sel, m.q, m.q_desc, mp.info, nullptr);
+    if (st != LVK_OK) return st;
+    lvk_map_info info;
+    LVK_HIP(ctx, hipMemcpyAsync(&info, mp.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int n_q = info.n_selected;
+    if (n_q < 0 || n_q > most) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_frontend_match_map: the selection reported %d points", n_q);
+    st = fe_match_chain(fe, o, n_q, &info.n_candidates);
+    if (st != LVK_OK) return st;
+    *n_out = n_q;
+    if (h_info) *h_info = info;
+    if (n_q == 0) return LVK_OK;
+    std::vector<lvk_map_sel> sel((size_t)n_q);
+    std::vector<lvk_landmark_match> res((size_t)n_q);
+    LVK_HIP(ctx, hipMemcpyAsync(sel.data(), mp.sel, sizeof(lvk_map_sel) * (size_t)n_q, hipMemcpyDeviceToHost, ctx->stream));
+    LVK_HIP(ctx, hipMemcpyAsync(res.data(), m.out, sizeof(lvk_landmark_match) * (size_t)n_q, hipMemcpyDeviceToHost, ctx->stream));
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < n_q; ++k) {
+        lvk_map_match& r = h_out[k];
+        r.index = sel[k].index; r.cell = sel[k].cell;
+        r.q.x = sel[k].x; r.q.y = sel[k].y; r.q.radius = sel[k].radius; r.q.pad = 0.f;
+        r.depth = sel[k].depth; r.pad = 0.f;
+        r.m = res[k];
+    }
     return LVK_OK;
 }
 

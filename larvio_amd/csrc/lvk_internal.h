@@ -68,6 +68,7 @@ enum lvk_scratch_slot {
     LVK_SCR_LDLT_WS,                    // LDL^T update: pivot-ordered copies of [HP | r] and X, D, the permutation, the counters
     LVK_SCR_MATCH_CLAIM,                // guided ORB matching: one claim word per candidate
     LVK_SCR_ALIGN_HYP,                  // two-point alignment: the hypothesis records when the caller keeps none
+    LVK_SCR_MAP_WORK,                   // prior-map selection: the chunk x cell table, the cells' offsets, the points' status and cell
     LVK_SCRATCH_SLOTS
 };
 #define LVK_LDS_OPTIN_KERNELS 24        // kernels that ask for more dynamic LDS than the default (fewer than that today)

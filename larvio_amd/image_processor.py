@@ -173,6 +173,45 @@ class ImageProcessor:
                                                           _p(out), _p(mask)))
         return out[0], mask[:n]
 
+    def set_map(self, X_map, cov_map, desc):
+        """lvk_frontend_set_map: keep a prior map on the device.  X_map (n, 3): its points in the map's own frame, best first - the order
+        is the priority match_map selects by -, cov_map: their covariances (n, 3, 3) or None, desc (n, 32) uint8: their descriptors.  Replaces
+        a previous map; an empty X_map (or None) frees it.  With a VioPipeline call it only after drain()."""
+        if self._h is None:
+            raise LvkError("ImageProcessor.initialize() has not succeeded")
+        X = np.zeros((0, 3)) if X_map is None else np.ascontiguousarray(X_map, np.float64).reshape(-1, 3)
+        n = len(X)
+        cv = None if cov_map is None or n == 0 else np.ascontiguousarray(cov_map, np.float64).reshape(-1, 9)
+        d = None if n == 0 else np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        if n and (len(d) != n or (cv is not None and len(cv) != n)):
+            raise ValueError(f"{n} map points but {len(d)} descriptors" + ("" if cv is None else f" and {len(cv)} covariances"))
+        self.ctx.check(lib().lvk_frontend_set_map(self._h, _p(X) if n else None, _p(cv), _p(d), n))
+
+    @property
+    def map_size(self):
+        """points of the map in force (lvk_frontend_map_size); 0: none"""
+        return lib().lvk_frontend_map_size(self._h)
+
+    def match_map(self, R_wc, p_wc, align=None, cov_cam=None, select=None, max_candidates=0, quality=0.0, min_distance=0.0, max_dist=0, ratio_pct=0):
+        """lvk_frontend_match_map: the resident map's points in the last processed frame.  R_wc, p_wc: the predicted camera pose in the
+        filter's world frame; align: the map's alignment - None (the map is in the world frame), the ALIGN_RESULT record of
+        align_landmarks, or (c, s, t); cov_cam: None or the 6 x 6 covariance of that pose in the order [dtheta (camera side), dp (world)];
+        select: larvio_amd.ops.map_select_options(...) or None; the rest are match_landmarks' options.  -> (records: a MAP_MATCH array -
+        index into the map, cell, q: the query the matcher was given, depth, m: the LANDMARK_MATCH record -, info: one MAP_INFO record).
+        larvio_amd.localize.map_obs turns the OK records into observations.  With a VioPipeline call it only after drain()."""
+        from ._lib import MAP_MATCH, MAP_INFO, MAP_MAX_QUERIES, MatchOptions
+        from .ops import align_record
+        if self._h is None:
+            raise LvkError("ImageProcessor.initialize() has not succeeded")
+        R = np.ascontiguousarray(R_wc, np.float64).reshape(9); p = np.ascontiguousarray(p_wc, np.float64).reshape(3)
+        cc = None if cov_cam is None else np.ascontiguousarray(cov_cam, np.float64).reshape(36)
+        al = align_record(align)
+        out = np.zeros(MAP_MAX_QUERIES, MAP_MATCH); info = np.zeros(1, MAP_INFO); n = C.c_int(0)
+        o = MatchOptions(int(max_candidates), float(quality), float(min_distance), int(max_dist), int(ratio_pct))
+        self.ctx.check(lib().lvk_frontend_match_map(self._h, _p(al), _p(R), _p(p), _p(cc), C.byref(select) if select is not None else None, C.byref(o), _p(out),
+                                                    len(out), C.byref(n), _p(info)))
+        return out[:n.value].copy(), info[0]
+
     @property
     def state(self):
         return lib().lvk_frontend_state(self._h)

@@ -1,5 +1,5 @@
-"""Localising against a prior map: the host steps around ImageProcessor.align_landmarks and ImageProcessor.match_landmarks (plain numpy,
-nothing here runs on the GPU).
+"""Localising against a prior map: the host steps around ImageProcessor.align_landmarks, ImageProcessor.match_landmarks and
+ImageProcessor.match_map (plain numpy, nothing here runs on the GPU).
 
 A map from another session has its own origin and yaw (gravity fixes roll and pitch in both), so relocalise first - once, or whenever
 the alignment is lost:
@@ -10,14 +10,27 @@ the alignment is lost:
     p_w, cov_w = apply_alignment(res, X_map, cov_map)                   # the map in the filter's world frame (if res["status"] == ALIGN_OK)
     cov_psi_t = alignment_cov(res, sigma_px, fe_config)                 # sigma^2 A^-1 of (psi, t), if the caller wants it
 
-then, per frame to localise on:
+then keep the map on the device, best points first - once:
+
+    image_processor.set_map(X_map, cov_map, desc)
+    sel = ops.map_select_options(max_r2=view_limit(fe_config))          # the guard against a radtan model folding back
+
+and per frame to localise on:
+
+    rec, info = image_processor.match_map(R_wc, p_wc, align=res, cov_cam=cov_cam, select=sel)   # project, cull, pick <= 1024, match
+    obs, idx = map_obs(rec, X_map, cov_map, res, sigma_px, fe_config)
+    larvio.add_landmark_obs(obs["p_w"], obs["uv"], obs["sigma"], obs["cov_w"], time=ts)
+
+match_map projects the whole map on the GPU, takes each search radius from the point's and the pose's covariance (cov_cam: order
+[dtheta dp], rotation error on the camera side, dp in the world frame - converting the filter's IMU-pose block of LarVio.window_cov with
+the extrinsics is the caller's job) and spreads its at most 1024 queries over a grid of image cells.  The same on the host, for a small
+map or a check:
 
     px, ok = predict_pixels(p_w, R_wc, p_wc, fe_config)                # where the map's points should appear, from a pose prediction
     m = image_processor.match_landmarks(px[ok], radius, desc[ok])      # which corner of the frame each of them is
     obs, idx = landmark_obs(m, p_w[ok], cov_w[ok], sigma_px, fe_config)
-    larvio.add_landmark_obs(obs["p_w"], obs["uv"], obs["sigma"], obs["cov_w"], time=ts)
 
-The library itself only ever UNdistorts (lvk_undistort_points); predict_pixels is the forward camera model the map side needs."""
+distort / project / predict_pixels are the forward camera model in numpy; the library's own is in lvk_map_select_queries."""
 import numpy as np
 
 from ._lib import MATCH_OK, ALIGN_MATCH
@@ -84,6 +97,66 @@ def landmark_obs(matches, p_w, cov_w, sigma_px, fe_config):
         c = np.asarray(cov_w, np.float64)
         obs["cov_w"] = c.reshape(1, 9) if c.size == 9 else c.reshape(-1, 9)[idx]
     return obs, idx
+
+
+def map_obs(records, X_map, cov_map, result, sigma_px, fe_config):
+    """The observation rows of match_map's records whose match is MATCH_OK.  records: the MAP_MATCH array match_map returned for the map
+    X_map (n, 3) with covariances cov_map (None, one 3 x 3, or n of them), both in the map's own frame; result: the alignment match_map
+    was given (an ALIGN_RESULT record, or None for a map already in the world frame) - it is applied to X[index] and cov[index];
+    sigma_px as landmark_obs takes it.  -> (obs: an ops.LANDMARK_OBS array, idx: the rows of `records` they came from)"""
+    X_map = np.asarray(X_map, np.float64).reshape(-1, 3)
+    idx = np.nonzero(records["m"]["status"] == MATCH_OK)[0]
+    k = records["index"][idx]
+    cov = None if cov_map is None else np.asarray(cov_map, np.float64)
+    if cov is not None:
+        cov = cov.reshape(1, 3, 3) if cov.size == 9 else cov.reshape(-1, 3, 3)[k]
+    if result is None:
+        p_w, cov_w = X_map[k], cov
+    else:
+        p_w, cov_w = apply_alignment(result, X_map[k], cov)
+    fx, fy = fe_config["intrinsics"][:2]
+    obs = np.zeros(len(idx), LANDMARK_OBS)
+    obs["p_w"] = p_w
+    obs["uv"] = records["m"]["und"][idx].astype(np.float64)
+    obs["sigma"] = float(sigma_px) / (0.5 * (fx + fy))
+    if cov_w is not None:
+        obs["cov_w"] = cov_w.reshape(-1, 9)
+    return obs, idx
+
+
+def view_limit(fe_config, r_max=20.0, step=0.01):
+    """The value to pass as max_r2 to match_map / ops.map_select_queries: the largest r2 = x^2 + y^2 of a normalised point, along the rays
+    from the principal point towards the four image corners and the four edge midpoints, up to which the forward model is still
+    increasing (the distorted radius grows with the undistorted one) and lands inside the image.  Beyond it a radtan model with a
+    negative k1 folds back and can put a point far outside the field of view into the image.  Found per ray by a scan in steps of
+    `step` up to the radius r_max and then bisection on `distort`; the largest of the eight."""
+    fx, fy, cx, cy = fe_config["intrinsics"]
+    w, h = fe_config["width"], fe_config["height"]
+    model, dist = fe_config["distortion_model"], fe_config["distortion"]
+    best = 0.0
+    for u, v in ((0, 0), (w - 1, 0), (0, h - 1), (w - 1, h - 1), (0.5 * (w - 1), 0), (0.5 * (w - 1), h - 1), (0, 0.5 * (h - 1)), (w - 1, 0.5 * (h - 1))):
+        d = np.array([(u - cx) / fx, (v - cy) / fy])
+        nd = float(np.linalg.norm(d))
+        if nd == 0.0:
+            continue
+        d = d / nd
+
+        def good(rho):
+            a = distort(rho * d, model, dist)[0]; b = distort(rho * (1.0 + 1e-6) * d, model, dist)[0]
+            px, py = fx * a[0] + cx, fy * a[1] + cy
+            return bool(np.hypot(*b) > np.hypot(*a) and 0 <= px <= w - 1 and 0 <= py <= h - 1)
+        lo, hi = 0.0, None
+        for k in range(1, int(round(r_max / step)) + 1):
+            if not good(k * step):
+                hi = k * step
+                break
+            lo = k * step
+        if hi is not None:
+            for _ in range(60):
+                mid = 0.5 * (lo + hi)
+                lo, hi = (mid, hi) if good(mid) else (lo, mid)
+        best = max(best, lo * lo)
+    return best
 
 
 def align_matches(matches, X_map):

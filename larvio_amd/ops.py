@@ -216,6 +216,67 @@ def align_ransac_2pt(ctx, matches, pairs, R_wc, p_wc, options=None, n=None, n_pa
     return out if check else (st, out)
 
 
+def map_select_options(min_depth=0.0, max_depth=0.0, max_r2=0.0, margin=0.0, k_sigma=0.0, sigma_px=0.0, r_min=0.0, r_max=0.0, rows=0, cols=0, quota=0):
+    """lvk_map_select_options; a zero field takes the library's default (0.1, inf, inf, 0, 3, 1, 4, 40, 4 x 5, 1024 / (rows cols))"""
+    from ._lib import MapSelectOptions
+    return MapSelectOptions(float(min_depth), float(max_depth), float(max_r2), float(margin), float(k_sigma), float(sigma_px), float(r_min), float(r_max),
+                            int(rows), int(cols), int(quota), 0)
+
+
+def map_camera(fe_config):
+    """lvk_map_camera of a front-end configuration dict (intrinsics, distortion_model, distortion, width, height)"""
+    from ._lib import MapCamera
+    return MapCamera((C.c_double * 4)(*fe_config["intrinsics"]), int(fe_config["distortion_model"]), int(fe_config["width"]), int(fe_config["height"]), 0,
+                     (C.c_double * 4)(*fe_config["distortion"]))
+
+
+def align_record(align):
+    """an ALIGN_RESULT record for an alignment given as one (returned as it is), as (c, s, t) or as None (-> None: identity)"""
+    from ._lib import ALIGN_RESULT
+    if align is None or (isinstance(align, (np.ndarray, np.void)) and align.dtype == ALIGN_RESULT):
+        return None if align is None else np.ascontiguousarray(align, ALIGN_RESULT).reshape(1)
+    r = np.zeros(1, ALIGN_RESULT)
+    r["c"], r["s"], r["t"] = float(align[0]), float(align[1]), np.asarray(align[2], np.float64).reshape(3)
+    return r
+
+
+MAP_GUARD = 64          # sentinel bytes (0xA5) map_select_queries keeps on either side of every output buffer
+
+
+def map_select_queries(ctx, X, cov, desc, fe_config, R_wc, p_wc, align=None, cov_cam=None, options=None, want_status=True, check=True):
+    """lvk_map_select_queries over host arrays: X (n, 3) map points, cov (n, 3, 3) or None, desc (n, 32) uint8 or None, the camera of
+    fe_config, the pose (R_wc 3 x 3 camera to world, p_wc), align: None, an ALIGN_RESULT record or (c, s, t), cov_cam: None or 6 x 6,
+    options: map_select_options(...) or None.  -> dict(info: one MAP_INFO record, sel: the n_selected MAP_SEL records, q: the MATCH_QUERY
+    records, q_desc: (n_selected, 32) uint8 or None, status: (n,) uint8 or None, and sel_raw, q_raw, q_desc_raw, info_raw, status_raw: the
+    device buffers as bytes, sized for 1024 records, with MAP_GUARD sentinel bytes of 0xA5 on either side, every output byte starting as
+    0xA5 too).  check=False returns (status code, that dict) instead of raising."""
+    from ._lib import MAP_SEL, MAP_INFO, MATCH_QUERY, MAP_MAX_QUERIES
+    X = np.ascontiguousarray(X, np.float64).reshape(-1, 3); n = len(X)
+    cv = None if cov is None else np.ascontiguousarray(cov, np.float64).reshape(-1, 9)
+    ds = None if desc is None else np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+    assert (cv is None or len(cv) == n) and (ds is None or len(ds) == n)
+    R = np.ascontiguousarray(R_wc, np.float64).reshape(9); p = np.ascontiguousarray(p_wc, np.float64).reshape(3)
+    cc = None if cov_cam is None else np.ascontiguousarray(cov_cam, np.float64).reshape(36)
+    al = align_record(align); cam = map_camera(fe_config)
+    G = MAP_GUARD
+    sizes = dict(sel=MAP_SEL.itemsize * MAP_MAX_QUERIES, q=MATCH_QUERY.itemsize * MAP_MAX_QUERIES, q_desc=32 * MAP_MAX_QUERIES, info=MAP_INFO.itemsize, status=n)
+    bufs = {k: ctx.to_device(np.full(v + 2 * G, 0xA5, np.uint8)) for k, v in sizes.items()}
+    at = lambda k: C.c_void_p(bufs[k].ptr + G)
+    d_X = ctx.to_device(X) if n else None; d_cov = ctx.to_device(cv) if cv is not None and n else None; d_desc = ctx.to_device(ds) if ds is not None and n else None
+    st = lib().lvk_map_select_queries(ctx.h, _p(d_X), _p(d_cov), _p(d_desc), n, C.byref(cam), _p(al), _p(R), _p(p), _p(cc), C.byref(options) if options is not None else None,
+                                      at("sel"), at("q"), at("q_desc") if ds is not None else None, at("info"), at("status") if want_status else None)
+    if check:
+        ctx.check(st)
+    ctx.sync()
+    raw = {k: ctx.to_host(bufs[k], np.uint8, (sizes[k] + 2 * G,)).copy() for k in sizes}
+    body = lambda k: raw[k][G:G + sizes[k]]
+    info = body("info").view(MAP_INFO)[0]
+    ns = int(info["n_selected"]) if st == 0 else 0
+    out = dict(info=info, sel=body("sel").view(MAP_SEL)[:ns], q=body("q").view(MATCH_QUERY)[:ns], q_desc=body("q_desc").reshape(-1, 32)[:ns] if ds is not None else None,
+               status=body("status") if want_status else None, **{k + "_raw": v for k, v in raw.items()})
+    return out if check else (st, out)
+
+
 def undistort(ctx, points, intr, model, dist, new_intr):
     p = _pts(points); n = len(p)
     a = np.asarray(intr, np.float64); d = np.asarray(dist, np.float64); k = np.asarray(new_intr, np.float64)
