@@ -329,6 +329,37 @@ lvk_status lvk_map_select_queries(lvk_context* ctx, const double* d_X, const dou
                                   const lvk_map_camera* cam, const lvk_align_result* align, const double R_wc[9], const double p_wc[3],
                                   const double cov_cam[36], const lvk_map_select_options* opt, lvk_map_sel* d_sel, lvk_match_query* d_q,
                                   uint8_t* d_q_desc, lvk_map_info* d_info, uint8_t* d_status);
+/* Stage entry: global ORB search of a device-resident map - the first link of that chain at the map's full size.  The search runs the other
+ * way round from lvk_orb_match_guided: the n_cand described corners of the frame are the queries (descriptor of corner c at d_cand_desc +
+ * 32 c) and the n_map map points are the database; there is no window.  No reference counterpart.  Everything is integer, so every field
+ * has one right value:
+ *   best       for corner c, the map point with the smallest Hamming distance over all n_map points, ties to the lowest map index:
+ *              d_best[c].cand = that MAP INDEX (the field keeps the name it has in lvk_match_result), dist = its distance,
+ *              n_window = n_map, pad = 0.
+ *   second     the smallest distance over the map points other than best, -1 when n_map == 1.
+ *   status     the first rule of lvk_orb_match_guided that applies, unchanged: NO_CANDIDATE when n_map == 0 (cand = dist = second = -1);
+ *              TOO_FAR when dist > max_dist; AMBIGUOUS when second >= 0 and 100 * dist > ratio_pct * second - two exact duplicates at
+ *              distance 0 are therefore NOT ambiguous (0 > 0 is false), as in the guided matcher; otherwise the corner is provisionally
+ *              matched.  A map point claimed by several provisionally matched corners goes to the smallest (dist, corner index): that
+ *              corner is OK, the others are CONFLICT, keep their cand and dist and are NOT moved to their second choice.
+ *   selection  the OK corners in ascending (dist, corner index) order; the first n_selected = min(n_ok, max_matches) of them are written to
+ *              d_sel[0 .. n_selected) as (cand = the corner, index = the map point, dist, second).  Records beyond n_selected are not touched.
+ *   info       n_ok, n_no_candidate, n_too_far, n_ambiguous, n_conflict: the corners per status (they sum to n_cand); n_selected; pad 0.
+ * Nothing in the rule depends on how the work is cut into slices of the map or tiles of corners, nor on the order in which anything ran.
+ * d_best: n_cand records; d_sel: max_matches records; d_info: one record, written by the kernels of every call that launches (no host
+ * clear).  Both descriptor pointers must be 8-byte aligned.  Four launches on the context's stream (search: two smallest keys dist << 20 |
+ * index per slice of the map and corner; pick: the two smallest over the slices, status, and a reset of the claim words that can be
+ * touched - never of one word per map point; claim: a 64-bit atomicMin of dist << 32 | corner; select: resolve, count, order - one
+ * workgroup), not waited for.
+ * LVK_ERR_ARG, with nothing launched and the context still usable: a null pointer where its count is positive (d_best, d_sel and d_info
+ * go with n_cand), a negative count, max_dist outside 0..256, ratio_pct outside 1..100, max_matches outside 1..1024, a descriptor pointer
+ * that is not 8-byte aligned.  LVK_ERR_CAPACITY: n_cand > 4096 or n_map > LVK_MAP_MAX_POINTS.  n_cand == 0: LVK_OK, nothing launched,
+ * nothing written.  n_map == 0: every corner NO_CANDIDATE. */
+typedef struct { int cand, index, dist, second; } lvk_global_match;
+typedef struct { int n_ok, n_no_candidate, n_too_far, n_ambiguous, n_conflict, n_selected, pad[2]; } lvk_global_info;
+lvk_status lvk_orb_match_global(lvk_context* ctx, const uint8_t* d_map_desc, int n_map, const uint8_t* d_cand_desc, int n_cand,
+                                int max_dist, int ratio_pct, int max_matches, lvk_match_result* d_best, lvk_global_match* d_sel,
+                                lvk_global_info* d_info);
 /* replaces integrateImuData + predictFeatureTracking's matrix (image_processor.cpp:222-293): host math */
 lvk_status lvk_predict_homography(const lvk_imu* h_imu, int n_imu, double t_prev, double t_curr,
                                   const double R_cam_imu[9], const double intr[4], float H[9]);
@@ -456,6 +487,29 @@ int        lvk_frontend_map_size(const lvk_frontend* fe);
 lvk_status lvk_frontend_match_map(lvk_frontend* fe, const lvk_align_result* align, const double R_wc[9], const double p_wc[3],
                                   const double cov_cam36[36], const lvk_map_select_options* select_opt, const lvk_match_options* match_opt,
                                   lvk_map_match* h_out, int cap, int* n_out, lvk_map_info* h_info);
+/* The first link of that chain with the map resident on the device: from "last processed frame + map in force + camera pose" to the map's
+ * yaw and translation in one call, whatever the map's size.  It detects and describes the frame's corners exactly as
+ * lvk_frontend_match_landmarks does (lvk_min_eigen_map, lvk_good_features_from_map with no mask, a wait for the count, lvk_orb_describe;
+ * match_opt's max_candidates, quality, min_distance), runs lvk_orb_match_global of the map's descriptors against them (match_opt's
+ * max_dist and ratio_pct - zero fields take lvk_frontend_match_landmarks' defaults, so ratio_pct stays 100: 80 is recommended here -;
+ * max_matches, 0 = 1024), waits for n_selected, draws the pairs on the host (lvk_align_draw_pairs(n_selected, max_hypotheses, seed)),
+ * gathers the lvk_align_match records on the device (X = map point `index`, (u, v) = the corner's pixel through lvk_undistort_points with
+ * unit intrinsics), runs lvk_align_ransac_2pt (align_opt) and makes one copy back: h_out = the result, h_matches[0 .. n_selected) = the
+ * selection's records in its order with the corner's pixel px, its normalised coordinate und, inlier = the mask byte and pad = 0,
+ * h_info (may be NULL) = the search's counts.  *n_out = n_selected; cap = the room in h_matches, at least min(max_matches, 1024).
+ * n_selected < 2 gives LVK_ALIGN_NO_MODEL through the stage entry's own rule and is no error.
+ * The same preconditions, waits (three: the corner count, n_selected, the records) and promise as lvk_frontend_match_map: off the per-frame
+ * path, it waits for the front-end's own streams, works in buffers of its own (allocated on first use) and the matcher's corner buffers,
+ * changes nothing a later frame reads - a run with these calls publishes the bits of a run without them - and a front-end that never calls
+ * it allocates and launches what it did before.  LVK_ERR_ARG: no map is set, a null pointer that is needed, max_matches outside 0..1024 (as
+ * the stage entry refuses it), max_hypotheses negative, a call before the first processed frame or between lvk_frontend_begin and the lvk_frontend_process of the same frame, and the
+ * refusals of lvk_frontend_match_landmarks' options and of the stage entries, passed through; LVK_ERR_CAPACITY: cap < min(max_matches,
+ * 1024), max_hypotheses > 4096, and what the stage entries pass through.  None is sticky.  With a lvk_vio_pipe attached,
+ * call it only between lvk_vio_pipe_drain and the next lvk_vio_pipe_submit. */
+typedef struct { int cand, index, dist, second; lvk_pt2f px, und; int inlier, pad; } lvk_reloc_match;
+lvk_status lvk_frontend_relocalise_map(lvk_frontend* fe, const double R_wc[9], const double p_wc[3], const lvk_match_options* match_opt,
+                                       const lvk_align_options* align_opt, int max_matches, int max_hypotheses, uint32_t seed,
+                                       lvk_align_result* h_out, lvk_reloc_match* h_matches, int cap, int* n_out, lvk_global_info* h_info);
 /* cumulative LK work: point-levels processed and iterations executed (SURVEY §8d byte model) */
 lvk_status lvk_frontend_lk_stats(lvk_frontend* fe, uint64_t* point_levels, uint64_t* iterations);
 /* feature messages published so far (getFeatureMsg, image_processor.cpp:1076-1128) and the features they carried in total:

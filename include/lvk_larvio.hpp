@@ -154,6 +154,26 @@ public:
         out.resize((size_t)n);
         return true;
     }
+    // the resident map's yaw and translation from the last processed frame in one call, whatever the map's size
+    // (lvk_frontend_relocalise_map): the frame's corners searched in the whole map, the best max_matches (0 = 1024) matches into the
+    // two-point RANSAC.  R_wc, p_wc = that frame's camera pose in the filter's world frame; the options may be null (ratio_pct 80 is
+    // recommended in match_opt).  out.status == LVK_ALIGN_OK marks success; matches[k].inlier the winner's inliers; matchMap takes out as
+    // align.  With a VioPipeline only after drain().  false = refused.
+    bool relocaliseMap(const double R_wc[9], const double p_wc[3], lvk_align_result& out, std::vector<lvk_reloc_match>* matches = nullptr,
+                       const lvk_match_options* match_opt = nullptr, const lvk_align_options* align_opt = nullptr, int max_matches = 0,
+                       int max_hypotheses = 0, uint32_t seed = 0, lvk_global_info* info = nullptr)
+    {
+        if (!fe_) return false;
+        std::vector<lvk_reloc_match> m(1024);
+        int n = 0;
+        if (lvk_frontend_relocalise_map(fe_, R_wc, p_wc, match_opt, align_opt, max_matches, max_hypotheses, seed, &out, m.data(), (int)m.size(), &n, info) != LVK_OK) {
+            if (matches) matches->clear();
+            std::fprintf(stderr, "ImageProcessor::relocaliseMap: %s\n", lvk_last_error(ctx_)); return false;
+        }
+        m.resize((size_t)n);
+        if (matches) matches->swap(m);
+        return true;
+    }
     lvk_frontend* handle() const { return fe_; }
 private:
     ImageProcessor(const ImageProcessor&); ImageProcessor& operator=(const ImageProcessor&);

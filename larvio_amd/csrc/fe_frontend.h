@@ -121,6 +121,10 @@ struct lvk_frontend {
     // the prior map of lvk_frontend_set_map (null in a front-end without one): its n points, their covariances (or null) and descriptors,
     // and lvk_frontend_match_map's own buffers, allocated with the map: the selected points' records and the counts
     struct Map { double *X, *cov; uint8_t* desc; int n; lvk_map_sel* sel; lvk_map_info* info; } map = {};
+    // lvk_frontend_relocalise_map's own buffers, allocated by its first call: the search's records per corner and its selection, the selected
+    // corners' pixels and normalised coordinates, and the blob that goes back in one copy (RelocBlob: result, counts, match records)
+    struct RelocBlob { lvk_align_result res; lvk_global_info info; lvk_reloc_match m[1024]; };
+    struct Reloc { lvk_match_result* best; lvk_global_match* sel; lvk_pt2f *px, *und; RelocBlob* blob; } reloc = {};
     // sticky: a frame that failed AFTER its image stage was queued (device error, ring overrun) leaves the buffer-set rotation and the
     // end-of-frame events out of step with the frame count; the handle then refuses further frames instead of racing on its buffers
     lvk_status failed = LVK_OK; char failed_msg[200] = {0};
@@ -174,6 +178,11 @@ lvk_status fe_match_finish(lvk_context* ctx, const CamParams& cam, const lvk_mat
                            lvk_landmark_match* d_out);
 // fe_map.hip: rows * cols * quota of the options as lvk_map_select_queries reads them, -1 when it refuses them
 int fe_map_max_selected(const lvk_map_select_options* opt);
+// fe_global.hip: behind lvk_orb_match_global on the context's stream - the n selected corners' pixels, their normalised coordinates, the
+// alignment's match records and the host's records (inlier 0); then, behind lvk_align_ransac_2pt, inlier = the mask byte
+lvk_status fe_reloc_gather(lvk_context* ctx, const CamParams& cam, const lvk_global_match* d_sel, int n, const lvk_pt2f* d_cand_pts, const double* d_X, lvk_pt2f* d_px,
+                           lvk_pt2f* d_und, lvk_align_match* d_am, lvk_reloc_match* d_out);
+lvk_status fe_reloc_inliers(lvk_context* ctx, const uint8_t* d_mask, int n, lvk_reloc_match* d_out);
 #ifdef LVK_LK_BOUNDS
 void fe_lk_bounds_report();                             // prints what the frame path's kernels recorded in THEIR copy of g_lk_oob
 #endif

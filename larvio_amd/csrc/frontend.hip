@@ -127,7 +127,8 @@ void lvk_frontend_destroy(lvk_frontend* fe)
     void* ptrs[] = {fe->d_img, fe->w_curr, fe->wn_curr, fe->w_und, fe->wn_und, fe->new_pts, fe->w_status, fe->wn_status, fe->wn_desc, fe->eig, fe->mask,
                     fe->gf_scratch, fe->gf_cands, fe->dev, fe->user_mask, fe->d_gray,
                     fe->match.eig, fe->match.cand_pts, fe->match.n_cand, fe->match.cand_desc, fe->match.q, fe->match.q_desc, fe->match.res, fe->match.px, fe->match.und, fe->match.out,
-                    fe->align.m, fe->align.pairs, fe->align.mask, fe->align.out, fe->map.X, fe->map.cov, fe->map.desc, fe->map.sel, fe->map.info};
+                    fe->align.m, fe->align.pairs, fe->align.mask, fe->align.out, fe->map.X, fe->map.cov, fe->map.desc, fe->map.sel, fe->map.info,
+                    fe->reloc.best, fe->reloc.sel, fe->reloc.px, fe->reloc.und, fe->reloc.blob};
     for (void* p : ptrs) if (p) hipFree(p);
     for (int i = 0; i < 3; ++i) { if (fe->h_stage[i]) hipHostFree(fe->h_stage[i]); if (fe->d_ring[i]) hipFree(fe->d_ring[i]); if (fe->ev_img[i]) hipEventDestroy(fe->ev_img[i]); }
     for (int i = 0; i < LVK_MSG_SLOTS; ++i) if (fe->ev_msg[i]) hipEventDestroy(fe->ev_msg[i]);
@@ -706,7 +707,7 @@ int lvk_frontend_input_format(const lvk_frontend* fe) { return fe ? fe->pix_form
 #define FE_MATCH_MAX_CAND 4096
 #define FE_MATCH_MAX_Q    1024
 // the options with their defaults filled in and their ranges checked, as lvk_frontend_match_landmarks states them
-static lvk_status fe_match_options(lvk_frontend* fe, const lvk_match_options* opt, lvk_match_options* out)
+static lvk_status fe_match_options(lvk_frontend* fe, const char* who, const lvk_match_options* opt, lvk_match_options* out)
 {
     lvk_context* ctx = fe->ctx;
     lvk_match_options o = {0, 0., 0., 0, 0};
@@ -716,15 +717,15 @@ static lvk_status fe_match_options(lvk_frontend* fe, const lvk_match_options* op
     if (o.min_distance == 0.) o.min_distance = (double)fe->cfg.min_distance;
     if (o.max_dist == 0) o.max_dist = 58;
     if (o.ratio_pct == 0) o.ratio_pct = 100;
-    if (o.max_candidates < 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: max_candidates %d", o.max_candidates);
-    if (o.max_candidates > FE_MATCH_MAX_CAND) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_frontend_match_landmarks: max_candidates %d, at most %d", o.max_candidates, FE_MATCH_MAX_CAND);
-    if (!(o.quality > 0. && o.quality <= 1.)) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: quality must be in (0, 1]");
-    if (!std::isfinite(o.min_distance) || o.min_distance < 0.) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: min_distance is negative or not finite");
-    if (o.max_dist < 0 || o.max_dist > 256) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: max_dist %d outside 1..256", o.max_dist);
-    if (o.ratio_pct < 1 || o.ratio_pct > 100) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: ratio_pct %d outside 1..100", o.ratio_pct);
-    if (fe->n_img == 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: no frame has been processed yet");
+    if (o.max_candidates < 0) return lvk_set_error(ctx, LVK_ERR_ARG, "%s: max_candidates %d", who, o.max_candidates);
+    if (o.max_candidates > FE_MATCH_MAX_CAND) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "%s: max_candidates %d, at most %d", who, o.max_candidates, FE_MATCH_MAX_CAND);
+    if (!(o.quality > 0. && o.quality <= 1.)) return lvk_set_error(ctx, LVK_ERR_ARG, "%s: quality must be in (0, 1]", who);
+    if (!std::isfinite(o.min_distance) || o.min_distance < 0.) return lvk_set_error(ctx, LVK_ERR_ARG, "%s: min_distance is negative or not finite", who);
+    if (o.max_dist < 0 || o.max_dist > 256) return lvk_set_error(ctx, LVK_ERR_ARG, "%s: max_dist %d outside 1..256", who, o.max_dist);
+    if (o.ratio_pct < 1 || o.ratio_pct > 100) return lvk_set_error(ctx, LVK_ERR_ARG, "%s: ratio_pct %d outside 1..100", who, o.ratio_pct);
+    if (fe->n_img == 0) return lvk_set_error(ctx, LVK_ERR_ARG, "%s: no frame has been processed yet", who);
     if (fe->image_done)
-        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: the image stage of t = %.6f is still waiting for its lvk_frontend_process", fe->image_done_ts);
+        return lvk_set_error(ctx, LVK_ERR_ARG, "%s: the image stage of t = %.6f is still waiting for its lvk_frontend_process", who, fe->image_done_ts);
     *out = o;
     return LVK_OK;
 }
@@ -749,7 +750,9 @@ static lvk_status fe_match_buffers(lvk_frontend* fe)
 // The device chain of lvk_frontend_match_landmarks on n_q queries that are already in fe->match.q / q_desc (their upload, or the kernels
 // that wrote them, queued on the main stream): corners of the last processed frame, their descriptors, the matcher, the records in
 // fe->match.out.  Waits once, for the corner count; the records are not waited for.
-static lvk_status fe_match_chain(lvk_frontend* fe, const lvk_match_options& o, int n_q, int* n_cand_out)
+// The first half of that chain, shared with lvk_frontend_relocalise_map: the corners of the last processed frame into fe->match.cand_pts
+// (no mask), a wait for their count, and - when describe - their descriptors into fe->match.cand_desc, queued and not waited for.
+static lvk_status fe_match_corners(lvk_frontend* fe, const char* who, const lvk_match_options& o, bool describe, int* n_cand_out)
 {
     lvk_context* ctx = fe->ctx;
     const int w = fe->cfg.width, h = fe->cfg.height;
@@ -760,11 +763,21 @@ static lvk_status fe_match_chain(lvk_frontend* fe, const lvk_match_options& o, i
     int n_cand = 0;
     LVK_HIP(ctx, hipMemcpyAsync(&n_cand, m.n_cand, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (n_cand < 0 || n_cand > FE_MATCH_MAX_CAND) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_frontend_match_landmarks: the selection reported %d corners", n_cand);
+    if (n_cand < 0 || n_cand > FE_MATCH_MAX_CAND) return lvk_set_error(ctx, LVK_ERR_DEVICE, "%s: the selection reported %d corners", who, n_cand);
+    *n_cand_out = n_cand;
+    if (!describe) return LVK_OK;
+    return lvk_orb_describe(ctx, fe->ext[0], fe->blur[0], w, h, m.cand_pts, n_cand, m.cand_desc, nullptr);
+}
+static lvk_status fe_match_chain(lvk_frontend* fe, const char* who, const lvk_match_options& o, int n_q, int* n_cand_out)
+{
+    lvk_context* ctx = fe->ctx;
+    lvk_frontend::Match& m = fe->match;
+    int n_cand = 0;
+    lvk_status st = fe_match_corners(fe, who, o, n_q > 0, &n_cand);
+    if (st != LVK_OK) return st;
     if (n_cand_out) *n_cand_out = n_cand;
     if (n_q == 0) return LVK_OK;
-    st = lvk_orb_describe(ctx, fe->ext[0], fe->blur[0], w, h, m.cand_pts, n_cand, m.cand_desc, nullptr);
-    if (st == LVK_OK) st = lvk_orb_match_guided(ctx, m.cand_pts, m.cand_desc, n_cand, m.q, m.q_desc, n_q, o.max_dist, o.ratio_pct, m.res);
+    st = lvk_orb_match_guided(ctx, m.cand_pts, m.cand_desc, n_cand, m.q, m.q_desc, n_q, o.max_dist, o.ratio_pct, m.res);
     if (st == LVK_OK) st = fe_match_finish(ctx, fe->cam, m.res, m.cand_pts, n_q, m.px, m.und, m.out);
     return st;
 }
@@ -778,7 +791,7 @@ lvk_status lvk_frontend_match_landmarks(lvk_frontend* fe, const lvk_match_query*
     if (n_q < 0 || (n_q > 0 && (!h_q || !h_desc || !h_out))) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_landmarks: bad argument");
     if (n_q > FE_MATCH_MAX_Q) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_frontend_match_landmarks: %d queries, at most %d", n_q, FE_MATCH_MAX_Q);
     lvk_match_options o;
-    lvk_status st = fe_match_options(fe, opt, &o);
+    lvk_status st = fe_match_options(fe, "lvk_frontend_match_landmarks", opt, &o);
     if (st == LVK_OK) st = fe_match_buffers(fe);
     if (st != LVK_OK) return st;
     lvk_frontend::Match& m = fe->match;
@@ -787,7 +800,7 @@ lvk_status lvk_frontend_match_landmarks(lvk_frontend* fe, const lvk_match_query*
         LVK_HIP(ctx, hipMemcpyAsync(m.q, h_q, sizeof(lvk_match_query) * (size_t)n_q, hipMemcpyHostToDevice, ctx->stream));
         LVK_HIP(ctx, hipMemcpyAsync(m.q_desc, h_desc, (size_t)32 * n_q, hipMemcpyHostToDevice, ctx->stream));
     }
-    st = fe_match_chain(fe, o, n_q, n_cand_out);
+    st = fe_match_chain(fe, "lvk_frontend_match_landmarks", o, n_q, n_cand_out);
     if (st != LVK_OK) { (void)hipStreamSynchronize(ctx->stream); return st; }      // (the uploads read the caller's arrays)
     if (n_q == 0) return LVK_OK;
     LVK_HIP(ctx, hipMemcpyAsync(h_out, m.out, sizeof(lvk_landmark_match) * (size_t)n_q, hipMemcpyDeviceToHost, ctx->stream));
@@ -845,7 +858,7 @@ lvk_status lvk_frontend_match_map(lvk_frontend* fe, const lvk_align_result* alig
     const int most = fe_map_max_selected(select_opt);
     if (most >= 0 && cap < most) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_frontend_match_map: room for %d records, the options can select %d", cap, most);
     lvk_match_options o;
-    lvk_status st = fe_match_options(fe, match_opt, &o);
+    lvk_status st = fe_match_options(fe, "lvk_frontend_match_map", match_opt, &o);
     if (st == LVK_OK) st = fe_match_buffers(fe);
     if (st != LVK_OK) return st;
     lvk_frontend::Match& m = fe->match;
@@ -862,7 +875,7 @@ lvk_status lvk_frontend_match_map(lvk_frontend* fe, const lvk_align_result* alig
     LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const int n_q = info.n_selected;
     if (n_q < 0 || n_q > most) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_frontend_match_map: the selection reported %d points", n_q);
-    st = fe_match_chain(fe, o, n_q, &info.n_candidates);
+    st = fe_match_chain(fe, "lvk_frontend_match_map", o, n_q, &info.n_candidates);
     if (st != LVK_OK) return st;
     *n_out = n_q;
     if (h_info) *h_info = info;
@@ -887,6 +900,20 @@ lvk_status lvk_frontend_match_map(lvk_frontend* fe, const lvk_align_result* alig
 // mask come back.  Nothing a frame reads or writes is touched.
 #define FE_ALIGN_MAX_N     1024
 #define FE_ALIGN_MAX_PAIRS 4096
+// the alignment's buffers, allocated by the first call that needs them
+static lvk_status fe_align_buffers(lvk_frontend* fe)
+{
+    if (fe->align.m) return LVK_OK;
+    lvk_frontend::Align b = {};
+    if (!(dalloc(&b.m, FE_ALIGN_MAX_N) && dalloc(&b.pairs, FE_ALIGN_MAX_PAIRS) && dalloc(&b.mask, FE_ALIGN_MAX_N) && dalloc(&b.out, 1))) {
+        (void)hipGetLastError();
+        void* ptrs[] = {b.m, b.pairs, b.mask, b.out};
+        for (void* p : ptrs) if (p) hipFree(p);
+        return lvk_set_error(fe->ctx, LVK_ERR_DEVICE, "lvk_frontend_align_landmarks: allocation failed");
+    }
+    fe->align = b;
+    return LVK_OK;
+}
 lvk_status lvk_frontend_align_landmarks(lvk_frontend* fe, const lvk_align_match* h_m, int n, const double* R_wc, const double* p_wc, const lvk_align_options* opt,
                                         int max_hypotheses, uint32_t seed, lvk_align_result* h_out, uint8_t* h_mask)
 {
@@ -899,17 +926,8 @@ lvk_status lvk_frontend_align_landmarks(lvk_frontend* fe, const lvk_align_match*
     if (fe->n_img == 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_align_landmarks: no frame has been processed yet");
     if (fe->image_done)
         return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_align_landmarks: the image stage of t = %.6f is still waiting for its lvk_frontend_process", fe->image_done_ts);
+    { lvk_status as = fe_align_buffers(fe); if (as != LVK_OK) return as; }
     lvk_frontend::Align& a = fe->align;
-    if (!a.m) {
-        lvk_frontend::Align b = {};
-        if (!(dalloc(&b.m, FE_ALIGN_MAX_N) && dalloc(&b.pairs, FE_ALIGN_MAX_PAIRS) && dalloc(&b.mask, FE_ALIGN_MAX_N) && dalloc(&b.out, 1))) {
-            (void)hipGetLastError();
-            void* ptrs[] = {b.m, b.pairs, b.mask, b.out};
-            for (void* p : ptrs) if (p) hipFree(p);
-            return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_frontend_align_landmarks: allocation failed");
-        }
-        a = b;
-    }
     std::vector<lvk_align_pair> pairs(FE_ALIGN_MAX_PAIRS);
     const int n_pairs = lvk_align_draw_pairs(n, max_hypotheses, seed, pairs.data());
     if (n_pairs < 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_align_landmarks: the pairs could not be drawn");
@@ -921,6 +939,75 @@ lvk_status lvk_frontend_align_landmarks(lvk_frontend* fe, const lvk_align_match*
     LVK_HIP(ctx, hipMemcpyAsync(h_out, a.out, sizeof(lvk_align_result), hipMemcpyDeviceToHost, ctx->stream));
     if (h_mask && n > 0) LVK_HIP(ctx, hipMemcpyAsync(h_mask, a.mask, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LVK_OK;
+}
+
+// The map's yaw and translation from the last processed frame in one call (no reference counterpart): the frame's corners and descriptors
+// as the matcher detects them, lvk_orb_match_global of the resident map against them, the pairs drawn on the host for n_selected, the
+// alignment's records gathered on the device, lvk_align_ransac_2pt, one copy back.  Buffers: the matcher's corner buffers, the alignment's,
+// and fe->reloc; nothing a frame reads or writes is touched.
+lvk_status lvk_frontend_relocalise_map(lvk_frontend* fe, const double* R_wc, const double* p_wc, const lvk_match_options* match_opt, const lvk_align_options* align_opt,
+                                       int max_matches, int max_hypotheses, uint32_t seed, lvk_align_result* h_out, lvk_reloc_match* h_matches, int cap, int* n_out,
+                                       lvk_global_info* h_info)
+{
+    if (!fe) return LVK_ERR_ARG;
+    lvk_context* ctx = fe->ctx;
+    { lvk_status fs = fe_check_failed(fe); if (fs != LVK_OK) return fs; }
+    if (!R_wc || !p_wc || !h_out || !h_matches || !n_out || cap < 0 || max_matches < 0 || max_hypotheses < 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_relocalise_map: bad argument");
+    if (fe->map.n == 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_relocalise_map: no map is set (lvk_frontend_set_map)");
+    if (max_matches == 0) max_matches = FE_ALIGN_MAX_N;
+    if (max_matches > FE_ALIGN_MAX_N) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_relocalise_map: max_matches %d outside 0..%d", max_matches, FE_ALIGN_MAX_N);   // (as the stage entry refuses it)
+    if (cap < max_matches) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_frontend_relocalise_map: room for %d records, max_matches is %d", cap, max_matches);
+    if (max_hypotheses > FE_ALIGN_MAX_PAIRS) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_frontend_relocalise_map: max_hypotheses %d, at most %d", max_hypotheses, FE_ALIGN_MAX_PAIRS);
+    lvk_match_options o;
+    lvk_status st = fe_match_options(fe, "lvk_frontend_relocalise_map", match_opt, &o);
+    if (st == LVK_OK) st = fe_match_buffers(fe);
+    if (st == LVK_OK) st = fe_align_buffers(fe);
+    if (st != LVK_OK) return st;
+    lvk_frontend::Reloc& r = fe->reloc;
+    if (!r.best) {
+        lvk_frontend::Reloc b = {};
+        if (!(dalloc(&b.best, FE_MATCH_MAX_CAND) && dalloc(&b.sel, FE_ALIGN_MAX_N) && dalloc(&b.px, FE_ALIGN_MAX_N) && dalloc(&b.und, FE_ALIGN_MAX_N) && dalloc(&b.blob, 1))) {
+            (void)hipGetLastError();
+            void* ptrs[] = {b.best, b.sel, b.px, b.und, b.blob};
+            for (void* p : ptrs) if (p) hipFree(p);
+            return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_frontend_relocalise_map: allocation failed");
+        }
+        r = b;
+    }
+    lvk_frontend::Match& m = fe->match;
+    lvk_frontend::Align& a = fe->align;
+    { lvk_status qs = fe_quiesce(fe); if (qs != LVK_OK) return qs; }
+    int n_cand = 0;
+    st = fe_match_corners(fe, "lvk_frontend_relocalise_map", o, true, &n_cand);
+    if (st != LVK_OK) return st;
+    lvk_global_info info;
+    memset(&info, 0, sizeof info);
+    if (n_cand > 0) {
+        st = lvk_orb_match_global(ctx, fe->map.desc, fe->map.n, m.cand_desc, n_cand, o.max_dist, o.ratio_pct, max_matches, r.best, r.sel, &r.blob->info);
+        if (st != LVK_OK) return st;
+        LVK_HIP(ctx, hipMemcpyAsync(&info, &r.blob->info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
+        LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    } else
+        LVK_HIP(ctx, hipMemsetAsync(&r.blob->info, 0, sizeof info, ctx->stream));      // (a frame without a corner: the search launches nothing)
+    const int n = info.n_selected;
+    if (n < 0 || n > max_matches) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_frontend_relocalise_map: the search reported %d matches", n);
+    std::vector<lvk_align_pair> pairs(FE_ALIGN_MAX_PAIRS);
+    const int n_pairs = lvk_align_draw_pairs(n, max_hypotheses, seed, pairs.data());
+    if (n_pairs < 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_relocalise_map: the pairs could not be drawn");
+    if (n_pairs > 0) LVK_HIP(ctx, hipMemcpyAsync(a.pairs, pairs.data(), sizeof(lvk_align_pair) * (size_t)n_pairs, hipMemcpyHostToDevice, ctx->stream));
+    st = fe_reloc_gather(ctx, fe->cam, r.sel, n, m.cand_pts, fe->map.X, r.px, r.und, a.m, r.blob->m);
+    if (st == LVK_OK) st = lvk_align_ransac_2pt(ctx, a.m, n, a.pairs, n_pairs, R_wc, p_wc, align_opt, nullptr, a.mask, &r.blob->res);
+    if (st == LVK_OK) st = fe_reloc_inliers(ctx, a.mask, n, r.blob->m);
+    if (st != LVK_OK) { (void)hipStreamSynchronize(ctx->stream); return st; }      // (the upload reads this call's own vector)
+    const size_t head = offsetof(lvk_frontend::RelocBlob, m);
+    std::vector<uint8_t> back(head + sizeof(lvk_reloc_match) * (size_t)n);
+    LVK_HIP(ctx, hipMemcpyAsync(back.data(), r.blob, back.size(), hipMemcpyDeviceToHost, ctx->stream));
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(h_out, back.data() + offsetof(lvk_frontend::RelocBlob, res), sizeof *h_out);
+    if (h_info) memcpy(h_info, back.data() + offsetof(lvk_frontend::RelocBlob, info), sizeof *h_info);
+    if (n > 0) memcpy(h_matches, back.data() + head, sizeof(lvk_reloc_match) * (size_t)n);
+    *n_out = n;
     return LVK_OK;
 }
 

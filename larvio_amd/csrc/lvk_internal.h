@@ -69,6 +69,8 @@ enum lvk_scratch_slot {
     LVK_SCR_MATCH_CLAIM,                // guided ORB matching: one claim word per candidate
     LVK_SCR_ALIGN_HYP,                  // two-point alignment: the hypothesis records when the caller keeps none
     LVK_SCR_MAP_WORK,                   // prior-map selection: the chunk x cell table, the cells' offsets, the points' status and cell
+    LVK_SCR_GLOBAL_WORK,                // global ORB search: the slices x corners table of key pairs, then one claim word per map point.  Its own slot, shared with nobody:
+                                        // the four launches of a call follow one another on the context's stream, and so does the next call
     LVK_SCRATCH_SLOTS
 };
 #define LVK_LDS_OPTIN_KERNELS 24        // kernels that ask for more dynamic LDS than the default (fewer than that today)

@@ -212,6 +212,26 @@ class ImageProcessor:
                                                     len(out), C.byref(n), _p(info)))
         return out[:n.value].copy(), info[0]
 
+    def relocalise_map(self, R_wc, p_wc, *, max_matches=0, max_hypotheses=0, seed=0, max_candidates=0, quality=0.0, min_distance=0.0, max_dist=0, ratio_pct=0,
+                       thresh=0.0, min_depth=0.0, min_dz=0.0, min_inliers=0, max_refine_iters=0):
+        """lvk_frontend_relocalise_map: the yaw and translation of the resident map (set_map) from the last processed frame, in one call and
+        whatever the map's size: the frame's corners are searched in the whole map (lvk_orb_match_global), the best max_matches (0 = 1024) OK
+        matches in (distance, corner) order go to the two-point RANSAC.  R_wc, p_wc: the camera pose of that frame in the filter's world
+        frame; the options are match_landmarks' (ratio_pct=80 is recommended here; the default stays 100, no ratio test) and
+        align_landmarks'.  -> (result: one ALIGN_RESULT record, matches: a RELOC_MATCH array - cand: the corner, index: the map point, dist,
+        second, px, und, inlier -, info: one GLOBAL_INFO record).  larvio_amd.localize.apply_alignment takes the result, match_map takes it as
+        align.  self.last_match_candidates is not touched.  With a VioPipeline call it only after drain()."""
+        from ._lib import ALIGN_RESULT, RELOC_MATCH, GLOBAL_INFO, GLOBAL_MAX_MATCHES, MatchOptions, AlignOptions
+        if self._h is None:
+            raise LvkError("ImageProcessor.initialize() has not succeeded")
+        R = np.ascontiguousarray(R_wc, np.float64).reshape(9); p = np.ascontiguousarray(p_wc, np.float64).reshape(3)
+        res = np.zeros(1, ALIGN_RESULT); out = np.zeros(GLOBAL_MAX_MATCHES, RELOC_MATCH); info = np.zeros(1, GLOBAL_INFO); n = C.c_int(0)
+        mo = MatchOptions(int(max_candidates), float(quality), float(min_distance), int(max_dist), int(ratio_pct))
+        ao = AlignOptions(float(thresh), float(min_depth), float(min_dz), int(min_inliers), int(max_refine_iters))
+        self.ctx.check(lib().lvk_frontend_relocalise_map(self._h, _p(R), _p(p), C.byref(mo), C.byref(ao), int(max_matches), int(max_hypotheses), int(seed) & 0xFFFFFFFF,
+                                                         _p(res), _p(out), len(out), C.byref(n), _p(info)))
+        return res[0], out[:n.value].copy(), info[0]
+
     @property
     def state(self):
         return lib().lvk_frontend_state(self._h)

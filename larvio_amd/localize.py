@@ -1,21 +1,26 @@
-"""Localising against a prior map: the host steps around ImageProcessor.align_landmarks, ImageProcessor.match_landmarks and
-ImageProcessor.match_map (plain numpy, nothing here runs on the GPU).
+"""Localising against a prior map: the host steps around ImageProcessor.relocalise_map, ImageProcessor.align_landmarks,
+ImageProcessor.match_landmarks and ImageProcessor.match_map (plain numpy, nothing here runs on the GPU).
+
+Keep the map on the device, best points first - once:
+
+    image_processor.set_map(X_map, cov_map, desc)                       # up to 1,048,576 points
+    sel = ops.map_select_options(max_r2=view_limit(fe_config))          # the guard against a radtan model folding back
 
 A map from another session has its own origin and yaw (gravity fixes roll and pitch in both), so relocalise first - once, or whenever
-the alignment is lost:
+the alignment is lost.  One call, whatever the map's size: the frame's corners are searched in the whole map, the best matches go to the
+RANSAC over pairs:
 
-    m0 = image_processor.match_landmarks(any_px, np.inf, desc, ratio_pct=80)   # an infinite radius: a global descriptor search
-    am, idx = align_matches(m0, X_map)                                  # the OK records as (X, u, v)
-    res, mask = image_processor.align_landmarks(am, R_wc, p_wc)         # yaw and translation of the map, RANSAC over pairs
+    res, matches, info = image_processor.relocalise_map(R_wc, p_wc, ratio_pct=80)   # yaw and translation of the map
     p_w, cov_w = apply_alignment(res, X_map, cov_map)                   # the map in the filter's world frame (if res["status"] == ALIGN_OK)
     cov_psi_t = alignment_cov(res, sigma_px, fe_config)                 # sigma^2 A^-1 of (psi, t), if the caller wants it
 
-then keep the map on the device, best points first - once:
+For a map that is not resident (at most 1024 points a call), the same through the guided matcher:
 
-    image_processor.set_map(X_map, cov_map, desc)
-    sel = ops.map_select_options(max_r2=view_limit(fe_config))          # the guard against a radtan model folding back
+    m0 = image_processor.match_landmarks(any_px, np.inf, desc, ratio_pct=80)   # an infinite radius: a global descriptor search
+    am, idx = align_matches(m0, X_map)                                  # the OK records as (X, u, v)
+    res, mask = image_processor.align_landmarks(am, R_wc, p_wc)
 
-and per frame to localise on:
+Then per frame to localise on:
 
     rec, info = image_processor.match_map(R_wc, p_wc, align=res, cov_cam=cov_cam, select=sel)   # project, cull, pick <= 1024, match
     obs, idx = map_obs(rec, X_map, cov_map, res, sigma_px, fe_config)

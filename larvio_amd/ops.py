@@ -172,6 +172,41 @@ def orb_match_guided(ctx, cand_pts, cand_desc, q_px, q_radius, q_desc, max_dist=
     return out if check else (st, out)
 
 
+ORB_GLOBAL_SLICE, ORB_GLOBAL_TILE = 2048, 256      # GLB_SLICE, GLB_TILE of csrc/fe_global.hip: map points and corners per workgroup of the search
+ORB_GLOBAL_GUARD = 64                              # sentinel bytes (0x5A) orb_match_global keeps on either side of every output buffer
+
+
+def orb_match_global(ctx, map_desc, cand_desc, max_dist=58, ratio_pct=100, max_matches=1024, check=True):
+    """lvk_orb_match_global: the frame's described corners cand_desc (n_cand, 32) uint8 against a map's descriptors map_desc (n_map, 32) - a
+    host array, or a (DeviceBuffer, n_map) pair for a map that is already on the device.  -> dict(best: n_cand MATCH_RESULT records whose
+    cand is the MAP index, sel: the n_selected GLOBAL_MATCH records (cand = corner, index = map point) in (dist, corner) order, info: one
+    GLOBAL_INFO record, and best_raw, sel_raw, info_raw: the device buffers as bytes - sel sized for max_matches records - with
+    ORB_GLOBAL_GUARD sentinel bytes of 0x5A on either side, every output byte starting as 0x5A too).  check=False returns (status code,
+    that dict) instead of raising."""
+    from ._lib import MATCH_RESULT, GLOBAL_MATCH, GLOBAL_INFO, DeviceBuffer
+    cd = np.ascontiguousarray(cand_desc, np.uint8).reshape(-1, 32); nc = len(cd)
+    if isinstance(map_desc, tuple):
+        d_map, nm = map_desc
+    else:
+        md = np.ascontiguousarray(map_desc, np.uint8).reshape(-1, 32); nm = len(md)
+        d_map = ctx.to_device(md) if nm else None
+    G = ORB_GLOBAL_GUARD
+    sizes = dict(best=MATCH_RESULT.itemsize * nc, sel=GLOBAL_MATCH.itemsize * max(min(int(max_matches), 1024), 0), info=GLOBAL_INFO.itemsize)
+    bufs = {k: ctx.to_device(np.full(v + 2 * G, 0x5A, np.uint8)) for k, v in sizes.items()}
+    at = lambda k: C.c_void_p(bufs[k].ptr + G)
+    d_cd = ctx.to_device(cd) if nc else None
+    st = lib().lvk_orb_match_global(ctx.h, _p(d_map), nm, _p(d_cd), nc, int(max_dist), int(ratio_pct), int(max_matches), at("best"), at("sel"), at("info"))
+    if check:
+        ctx.check(st)
+    ctx.sync()
+    raw = {k: ctx.to_host(bufs[k], np.uint8, (sizes[k] + 2 * G,)).copy() for k in sizes}
+    body = lambda k: raw[k][G:G + sizes[k]]
+    info = body("info").view(GLOBAL_INFO)[0]
+    ns = int(info["n_selected"]) if st == 0 and nc else 0
+    out = dict(best=body("best").view(MATCH_RESULT), sel=body("sel").view(GLOBAL_MATCH)[:ns], info=info, **{k + "_raw": v for k, v in raw.items()})
+    return out if check else (st, out)
+
+
 def align_options(thresh=0.0, min_depth=0.0, min_dz=0.0, min_inliers=0, max_refine_iters=0):
     """lvk_align_options; a zero field takes the library's default (0.01, 0.1, 1e-6, 6, 10)"""
     from ._lib import AlignOptions
