@@ -329,6 +329,49 @@ lvk_status lvk_map_select_queries(lvk_context* ctx, const double* d_X, const dou
                                   const lvk_map_camera* cam, const lvk_align_result* align, const double R_wc[9], const double p_wc[3],
                                   const double cov_cam[36], const lvk_map_select_options* opt, lvk_map_sel* d_sel, lvk_match_query* d_q,
                                   uint8_t* d_q_desc, lvk_map_info* d_info, uint8_t* d_status);
+/* Stage entry: the start of that chain - a session's raw exports (lvk_ekf_take_lost_features_cov, lvk_ekf_take_msckf_points, the first-seen
+ * descriptors of lvk_frontend_tracks) into the map lvk_frontend_set_map expects: bad points culled, of near-duplicates the better copy
+ * kept, the rest sorted best first.  No reference counterpart.  d_X: n points (3 doubles each); d_cov: NULL or their covariances (9 doubles
+ * each, row-major); d_desc: their 32-byte descriptors, 8-byte aligned - required when r_dup > 0, otherwise NULL is allowed; d_score: NULL
+ * or n doubles, smaller is better.  FP64 throughout, no contraction, every expression in the order written here, so every output has one
+ * right value:
+ *   score      d_score[i] when d_score is given; otherwise (c00 + c11) + c22 of the point's covariance; 0 with neither.  Scores compare by
+ *              value: -0 equals +0 (it is canonicalised to +0 before anything orders by it).
+ *   cell       only when r_dup > 0: c_a = floor(X_a / r_dup) per axis - an IEEE division, then floor, so a negative coordinate rounds down,
+ *              not towards zero.
+ *   status     the first rule that applies: BAD - a non-finite entry of X, of the covariance (when given, whether or not it is the score) or
+ *              a non-finite score (a covariance trace that overflows included), a negative covariance diagonal, a score < 0; UNCERTAIN -
+ *              score > max_score; OUT_OF_RANGE - r_dup > 0 and some |c_a| > 2^20 - 1; DUPLICATE - below; otherwise KEPT.
+ *   duplicate  the points that are not BAD, UNCERTAIN or OUT_OF_RANGE are eligible.  An eligible i is DUPLICATE iff there is an eligible
+ *              j != i with (score_j, j) < (score_i, i) lexicographically, |c_a(i) - c_a(j)| <= 1 on all three axes, d2 = ((dx dx + dy dy) +
+ *              dz dz) <= r_dup r_dup with dx = X_i,x - X_j,x and so on, and a Hamming distance of the two descriptors <= dup_max_dist.  j
+ *              counts whether or not j is itself a DUPLICATE: the rule is not greedy, so it depends on no processing order - the price is
+ *              that a chain A-B-C (A suppresses B, B suppresses C, A and C apart) keeps only A.  The cell condition is part of the rule
+ *              (it can only bite where a division rounds at a cell's edge), so the answer is exact there too.  Nothing is fused or
+ *              averaged: the better copy stays as it is.
+ *   order      the KEPT points by ascending (score, original index): a stable sort.
+ * d_order: the original indices of the kept points, best first; d_X_out, d_cov_out, d_desc_out: the kept points gathered in that order, in
+ * lvk_frontend_set_map's layout - each with room for n records, n_kept of them are written and nothing beyond; d_cov_out / d_desc_out may
+ * be NULL when d_cov / d_desc is, and is neither read, written nor checked for alignment then, whatever it is.  No output may alias an input.  d_status: NULL or n bytes (LVK_MAPB_*); d_info: the count per status (they
+ * sum to n) and pad 0, written by the kernels of every call that launches (no host clear).  On the context's stream, not waited for, work
+ * buffers from the context's pool (37 bytes a point): classify; with r_dup > 0 a stable LSD radix sort by packed cell key (eight passes of
+ * three launches: count, scan, ordered scatter from wave ballots) and the neighbour search - every point visits its 27 neighbour cells by
+ * nine binary searches, candidates tested position, Hamming, priority; the cost is quadratic inside one crowded cell and is not capped -;
+ * the order's keys and the counts; the same sort on the scores' bits (non-negative finite doubles order as their bit patterns); the gather.
+ * opt may be NULL; a zero field takes its default: max_score +inf, r_dup 0 = no de-duplication (and no OUT_OF_RANGE), dup_max_dist 32.
+ * LVK_ERR_ARG, with nothing launched and the context still usable: a null pointer that is needed, n < 0, an option that is NaN or
+ * negative, dup_max_dist outside 0..256, a descriptor pointer that is not 8-byte aligned, r_dup > 0 without descriptors.
+ * LVK_ERR_CAPACITY: n > LVK_MAP_MAX_POINTS.  n == 0: LVK_OK, d_info zeroed, nothing launched. */
+#define LVK_MAPB_KEPT         0
+#define LVK_MAPB_BAD          1
+#define LVK_MAPB_UNCERTAIN    2
+#define LVK_MAPB_OUT_OF_RANGE 3
+#define LVK_MAPB_DUPLICATE    4
+typedef struct { double max_score, r_dup; int dup_max_dist, pad; } lvk_map_build_options;   /* zeros = defaults */
+typedef struct { int n_kept, n_bad, n_uncertain, n_out_of_range, n_duplicate, pad[3]; } lvk_map_build_info;
+lvk_status lvk_map_build(lvk_context* ctx, const double* d_X, const double* d_cov, const uint8_t* d_desc, const double* d_score, int n,
+                         const lvk_map_build_options* opt, int* d_order, double* d_X_out, double* d_cov_out, uint8_t* d_desc_out,
+                         uint8_t* d_status, lvk_map_build_info* d_info);
 /* Stage entry: global ORB search of a device-resident map - the first link of that chain at the map's full size.  The search runs the other
  * way round from lvk_orb_match_guided: the n_cand described corners of the frame are the queries (descriptor of corner c at d_cand_desc +
  * 32 c) and the n_map map points are the database; there is no window.  No reference counterpart.  Everything is integer, so every field
@@ -487,6 +530,19 @@ int        lvk_frontend_map_size(const lvk_frontend* fe);
 lvk_status lvk_frontend_match_map(lvk_frontend* fe, const lvk_align_result* align, const double R_wc[9], const double p_wc[3],
                                   const double cov_cam36[36], const lvk_map_select_options* select_opt, const lvk_match_options* match_opt,
                                   lvk_map_match* h_out, int cap, int* n_out, lvk_map_info* h_info);
+/* The start of that chain with the map resident on the device: a session's raw exports in, the map in force out.  h_X, h_cov9 (may be NULL),
+ * h_desc (required: the resident map has descriptors) as lvk_frontend_set_map takes them, h_score (may be NULL) and opt as lvk_map_build
+ * takes them.  The call uploads, runs lvk_map_build on the main stream in buffers of its own, waits, and makes the gathered arrays the map
+ * in force exactly as if lvk_frontend_set_map had been called with them: lvk_frontend_map_size = n_kept afterwards, n_kept == 0 (n == 0
+ * included) frees the map.  h_order (may be NULL; cap_order = its room in entries): the original indices of the kept points in the map's
+ * order, so that the caller keeps its own ids and attributes in step; info (may be NULL): the stage entry's counts.  The same preconditions
+ * and waits as lvk_frontend_set_map.  LVK_ERR_ARG: a null pointer that is needed, n < 0, cap_order < 0, the stage entry's refusals, a call
+ * between lvk_frontend_begin and the lvk_frontend_process of the same frame; LVK_ERR_CAPACITY: n > LVK_MAP_MAX_POINTS, or h_order given
+ * and cap_order < n_kept (cap_order >= n always suffices); LVK_ERR_DEVICE when the buffers cannot be had - in each case the map in force
+ * stays, and none is sticky.  Off the per-frame path: a run that never calls it launches what it launched before.  With a lvk_vio_pipe
+ * attached, call it only between lvk_vio_pipe_drain and the next lvk_vio_pipe_submit. */
+lvk_status lvk_frontend_build_map(lvk_frontend* fe, const double* h_X, const double* h_cov9, const uint8_t* h_desc, const double* h_score, int n,
+                                  const lvk_map_build_options* opt, int* h_order, int cap_order, lvk_map_build_info* info);
 /* The first link of that chain with the map resident on the device: from "last processed frame + map in force + camera pose" to the map's
  * yaw and translation in one call, whatever the map's size.  It detects and describes the frame's corners exactly as
  * lvk_frontend_match_landmarks does (lvk_min_eigen_map, lvk_good_features_from_map with no mask, a wait for the count, lvk_orb_describe;

@@ -137,6 +137,25 @@ public:
         }
         return true;
     }
+    // a session's raw exports into the resident map (lvk_frontend_build_map): bad points culled, of near-duplicates the better copy kept,
+    // the rest sorted best first and made the map in force as setMap would.  score: empty, or one per point (smaller is better; without
+    // it the covariance's trace is the score).  order (may be null): the original indices of the kept points in the map's order.
+    bool buildMap(const std::vector<double>& X, const std::vector<double>& cov9, const std::vector<uint8_t>& desc, const std::vector<double>& score = std::vector<double>(),
+                  const lvk_map_build_options* opt = nullptr, std::vector<int>* order = nullptr, lvk_map_build_info* info = nullptr)
+    {
+        const size_t n = X.size() / 3;
+        if (!fe_ || X.size() != 3 * n || desc.size() != 32 * n || (!cov9.empty() && cov9.size() != 9 * n) || (!score.empty() && score.size() != n)) return false;
+        std::vector<int> ord(n ? n : 1);
+        lvk_map_build_info got;
+        if (lvk_frontend_build_map(fe_, n ? X.data() : nullptr, cov9.empty() ? nullptr : cov9.data(), n ? desc.data() : nullptr, score.empty() ? nullptr : score.data(), (int)n, opt,
+                                   ord.data(), (int)n, &got) != LVK_OK) {
+            std::fprintf(stderr, "ImageProcessor::buildMap: %s\n", lvk_last_error(ctx_)); return false;
+        }
+        ord.resize((size_t)got.n_kept);
+        if (order) order->swap(ord);
+        if (info) *info = got;
+        return true;
+    }
     // the resident map's points in the last processed frame (lvk_frontend_match_map): projected from the pose prediction R_wc, p_wc (align:
     // the map's alignment or null, cov_cam36: the pose covariance [dtheta dp] or null), culled, at most 1024 picked cell by cell and
     // matched.  out[i].index is the map point, out[i].m.status == LVK_MATCH_OK marks a match.  With a VioPipeline only after drain().

@@ -183,6 +183,8 @@ int fe_map_max_selected(const lvk_map_select_options* opt);
 lvk_status fe_reloc_gather(lvk_context* ctx, const CamParams& cam, const lvk_global_match* d_sel, int n, const lvk_pt2f* d_cand_pts, const double* d_X, lvk_pt2f* d_px,
                            lvk_pt2f* d_und, lvk_align_match* d_am, lvk_reloc_match* d_out);
 lvk_status fe_reloc_inliers(lvk_context* ctx, const uint8_t* d_mask, int n, lvk_reloc_match* d_out);
+// fe_mapbuild.hip: does lvk_map_build accept these options (false: *why names the field)?  lvk_frontend_build_map asks before it allocates
+bool fe_map_build_options_ok(const lvk_map_build_options* opt, const char** why);
 #ifdef LVK_LK_BOUNDS
 void fe_lk_bounds_report();                             // prints what the frame path's kernels recorded in THEIR copy of g_lk_oob
 #endif

@@ -844,6 +844,83 @@ lvk_status lvk_frontend_set_map(lvk_frontend* fe, const double* h_X, const doubl
 }
 int lvk_frontend_map_size(const lvk_frontend* fe) { return fe ? fe->map.n : -1; }
 
+// A session's raw exports into the map in force (no reference counterpart): upload, lvk_map_build in buffers the call owns, one wait for the
+// counts, then the map's own buffers at their final size are filled from the gathered arrays before the old ones go - as in
+// lvk_frontend_set_map, a refusal leaves the map in force.
+lvk_status lvk_frontend_build_map(lvk_frontend* fe, const double* h_X, const double* h_cov9, const uint8_t* h_desc, const double* h_score, int n,
+                                  const lvk_map_build_options* opt, int* h_order, int cap_order, lvk_map_build_info* info)
+{
+    if (!fe) return LVK_ERR_ARG;
+    lvk_context* ctx = fe->ctx;
+    { lvk_status fs = fe_check_failed(fe); if (fs != LVK_OK) return fs; }
+    if (n < 0 || cap_order < 0 || (n > 0 && (!h_X || !h_desc))) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_build_map: bad argument");
+    const char* why = "";
+    if (!fe_map_build_options_ok(opt, &why)) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_build_map: %s", why);
+    if (n > LVK_MAP_MAX_POINTS) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_frontend_build_map: %d points, at most %d", n, LVK_MAP_MAX_POINTS);
+    if (fe->image_done)
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_build_map: the image stage of t = %.6f is still waiting for its lvk_frontend_process", fe->image_done_ts);
+    // the call's own buffers: the inputs, the gathered outputs (room for n each), the order and the counts
+    double *in_X = nullptr, *in_cov = nullptr, *in_score = nullptr, *out_X = nullptr, *out_cov = nullptr;
+    uint8_t *in_desc = nullptr, *out_desc = nullptr; int* order = nullptr; lvk_map_build_info* d_info = nullptr;
+    lvk_frontend::Map b = {};
+    lvk_map_build_info got;
+    memset(&got, 0, sizeof got);
+    auto release = [&]() {
+        void* ptrs[] = {in_X, in_cov, in_score, out_X, out_cov, in_desc, out_desc, order, d_info};
+        for (void* p : ptrs) if (p) hipFree(p);
+    };
+    auto fail = [&](lvk_status code, const char* what) {
+        (void)hipStreamSynchronize(ctx->stream);         // (the uploads read the caller's arrays)
+        (void)hipGetLastError();
+        release();
+        void* ptrs[] = {b.X, b.cov, b.desc, b.sel, b.info};
+        for (void* p : ptrs) if (p) hipFree(p);
+        return lvk_set_error(ctx, code, "lvk_frontend_build_map: %s", what);
+    };
+    if (n > 0) {
+        const size_t N = (size_t)n;
+        const bool ok = dalloc(&in_X, 3 * N) && (!h_cov9 || dalloc(&in_cov, 9 * N)) && dalloc(&in_desc, 32 * N) && (!h_score || dalloc(&in_score, N)) && dalloc(&out_X, 3 * N) &&
+                        (!h_cov9 || dalloc(&out_cov, 9 * N)) && dalloc(&out_desc, 32 * N) && dalloc(&order, N) && dalloc(&d_info, 1);
+        if (!ok) return fail(LVK_ERR_DEVICE, "allocation failed");
+        hipError_t e = hipMemcpyAsync(in_X, h_X, sizeof(double) * 3 * N, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess && h_cov9) e = hipMemcpyAsync(in_cov, h_cov9, sizeof(double) * 9 * N, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(in_desc, h_desc, 32 * N, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess && h_score) e = hipMemcpyAsync(in_score, h_score, sizeof(double) * N, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) return fail(LVK_ERR_DEVICE, hipGetErrorString(e));
+        const lvk_status st = lvk_map_build(ctx, in_X, in_cov, in_desc, in_score, n, opt, order, out_X, out_cov, out_desc, nullptr, d_info);
+        if (st != LVK_OK) { (void)hipStreamSynchronize(ctx->stream); release(); return st; }
+        e = hipMemcpyAsync(&got, d_info, sizeof got, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return fail(LVK_ERR_DEVICE, hipGetErrorString(e));
+        const int k = got.n_kept;
+        if (k < 0 || k > n) return fail(LVK_ERR_DEVICE, "the build reported an impossible count");
+        if (h_order && cap_order < k) {
+            char msg[96]; snprintf(msg, sizeof msg, "room for %d indices, %d points are kept", cap_order, k);
+            return fail(LVK_ERR_CAPACITY, msg);
+        }
+        if (k > 0) {
+            const size_t K = (size_t)k;
+            if (!(dalloc(&b.X, 3 * K) && (!h_cov9 || dalloc(&b.cov, 9 * K)) && dalloc(&b.desc, 32 * K) && dalloc(&b.sel, LVK_MAP_MAX_QUERIES) && dalloc(&b.info, 1)))
+                return fail(LVK_ERR_DEVICE, "allocation failed");
+            e = hipMemcpyAsync(b.X, out_X, sizeof(double) * 3 * K, hipMemcpyDeviceToDevice, ctx->stream);
+            if (e == hipSuccess && h_cov9) e = hipMemcpyAsync(b.cov, out_cov, sizeof(double) * 9 * K, hipMemcpyDeviceToDevice, ctx->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(b.desc, out_desc, 32 * K, hipMemcpyDeviceToDevice, ctx->stream);
+            if (e == hipSuccess && h_order) e = hipMemcpyAsync(h_order, order, sizeof(int) * K, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+            if (e != hipSuccess) return fail(LVK_ERR_DEVICE, hipGetErrorString(e));
+            b.n = k;
+        }
+        release();
+    }
+    { lvk_status qs = fe_quiesce(fe); if (qs != LVK_OK) { void* ptrs[] = {b.X, b.cov, b.desc, b.sel, b.info}; for (void* p : ptrs) if (p) hipFree(p); return qs; } }
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    void* old[] = {fe->map.X, fe->map.cov, fe->map.desc, fe->map.sel, fe->map.info};
+    for (void* p : old) if (p) hipFree(p);
+    fe->map = b;
+    if (info) *info = got;
+    return LVK_OK;
+}
+
 // The map's points in the last processed frame: lvk_map_select_queries writes the queries and their descriptors straight into the
 // matcher's buffers, the chain of lvk_frontend_match_landmarks runs on them, the host joins the two record arrays.
 lvk_status lvk_frontend_match_map(lvk_frontend* fe, const lvk_align_result* align, const double* R_wc, const double* p_wc, const double* cov_cam36,

@@ -71,6 +71,8 @@ enum lvk_scratch_slot {
     LVK_SCR_MAP_WORK,                   // prior-map selection: the chunk x cell table, the cells' offsets, the points' status and cell
     LVK_SCR_GLOBAL_WORK,                // global ORB search: the slices x corners table of key pairs, then one claim word per map point.  Its own slot, shared with nobody:
                                         // the four launches of a call follow one another on the context's stream, and so does the next call
+    LVK_SCR_MAPBUILD_WORK,              // map build: the sort's two key and index arrays, the scores' bits, the digit x chunk and status x chunk tables, the status bytes.
+                                        // Its own slot: a call's launches follow one another on the context's stream, and so does the next call
     LVK_SCRATCH_SLOTS
 };
 #define LVK_LDS_OPTIN_KERNELS 24        // kernels that ask for more dynamic LDS than the default (fewer than that today)

@@ -192,6 +192,30 @@ class ImageProcessor:
         """points of the map in force (lvk_frontend_map_size); 0: none"""
         return lib().lvk_frontend_map_size(self._h)
 
+    def build_map(self, X, cov, desc, score=None, **options):
+        """lvk_frontend_build_map: a session's raw exports into the resident map.  X (n, 3), cov (n, 3, 3) or None, desc (n, 32) uint8 -
+        larvio_amd.localize.MapCollector.arrays() gives them -, score (n,) or None (smaller is better; without it the covariance's trace
+        is the score); options: max_score, r_dup, dup_max_dist of larvio_amd.ops.map_build_options.  Bad points are culled, of
+        near-duplicates the better copy is kept, the rest is sorted best first and becomes the map in force exactly as set_map would
+        make it (map_size = n_kept).  -> (order: the original indices of the kept points in the map's order - X[order], cov[order],
+        desc[order] is the resident map -, info: one MAP_BUILD_INFO record).  A refusal (LvkError) leaves the previous map in place.  With
+        a VioPipeline call it only after drain()."""
+        from ._lib import MAP_BUILD_INFO
+        from .ops import map_build_options
+        if self._h is None:
+            raise LvkError("ImageProcessor.initialize() has not succeeded")
+        Xa = np.zeros((0, 3)) if X is None else np.ascontiguousarray(X, np.float64).reshape(-1, 3)
+        n = len(Xa)
+        cv = None if cov is None or n == 0 else np.ascontiguousarray(cov, np.float64).reshape(-1, 9)
+        d = None if n == 0 else np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        sc = None if score is None or n == 0 else np.ascontiguousarray(score, np.float64).reshape(-1)
+        if n and (len(d) != n or (cv is not None and len(cv) != n) or (sc is not None and len(sc) != n)):
+            raise ValueError(f"{n} map points but {len(d)} descriptors" + ("" if cv is None else f", {len(cv)} covariances") + ("" if sc is None else f", {len(sc)} scores"))
+        o = map_build_options(**options)
+        order = np.zeros(max(n, 1), np.int32); info = np.zeros(1, MAP_BUILD_INFO)
+        self.ctx.check(lib().lvk_frontend_build_map(self._h, _p(Xa) if n else None, _p(cv), _p(d), _p(sc), n, C.byref(o), _p(order), n, _p(info)))
+        return order[:int(info[0]["n_kept"])].copy(), info[0]
+
     def match_map(self, R_wc, p_wc, align=None, cov_cam=None, select=None, max_candidates=0, quality=0.0, min_distance=0.0, max_dist=0, ratio_pct=0):
         """lvk_frontend_match_map: the resident map's points in the last processed frame.  R_wc, p_wc: the predicted camera pose in the
         filter's world frame; align: the map's alignment - None (the map is in the world frame), the ALIGN_RESULT record of

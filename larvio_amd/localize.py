@@ -1,8 +1,20 @@
 """Localising against a prior map: the host steps around ImageProcessor.relocalise_map, ImageProcessor.align_landmarks,
 ImageProcessor.match_landmarks and ImageProcessor.match_map (plain numpy, nothing here runs on the GPU).
 
-Keep the map on the device, best points first - once:
+Collect, build, save - in the session that maps:
 
+    col = MapCollector()
+    col.add_tracks(image_processor.tracks())                            # per frame: the first-seen descriptor of every feature id
+    col.add_points(*larvio.take_msckf_points())                         # whenever: ids, positions, covariances (, observation counts)
+    col.add_points(*larvio.take_lost_features_cov())
+    ids, X, cov, desc, n_obs = col.arrays()                             # joined by id; an id without a descriptor is left out
+    order, info = image_processor.build_map(X, cov, desc, max_score=0.05, r_dup=0.05)   # cull, dedupe and sort on the GPU; now resident
+    save_map("map.npz", ids, X, cov, desc, order)                       # the raw arrays and the order: X[order] is the map
+
+In the session that localises, keep the map on the device, best points first - once:
+
+    ids, X, cov, desc, order = load_map("map.npz")
+    X_map, cov_map, desc = X[order], cov[order], desc[order]
     image_processor.set_map(X_map, cov_map, desc)                       # up to 1,048,576 points
     sel = ops.map_select_options(max_r2=view_limit(fe_config))          # the guard against a radtan model folding back
 
@@ -40,6 +52,80 @@ import numpy as np
 
 from ._lib import MATCH_OK, ALIGN_MATCH
 from .ops import LANDMARK_OBS
+
+
+class MapCollector:
+    """Joins, by feature id and over a whole session, what ImageProcessor.build_map needs: the descriptors come from tracks()["desc"] per
+    frame (the first one seen per id stays), the positions and covariances from the batches of LarVio.take_lost_features_cov /
+    take_msckf_points.  A point exported twice keeps the copy with the smaller covariance trace (a trace that is not finite loses, a tie
+    keeps the earlier copy)."""
+
+    def __init__(self):
+        self._desc = {}                  # id -> (32,) uint8
+        self._pts = {}                   # id -> (X, cov, n_obs), in the order of the first export
+
+    def add_tracks(self, tracks):
+        """tracks: what ImageProcessor.tracks() returned for a frame (its "ids" and "desc" are read)"""
+        ids = np.asarray(tracks["ids"]).reshape(-1); desc = np.asarray(tracks["desc"], np.uint8).reshape(-1, 32)
+        if len(ids) != len(desc):
+            raise ValueError(f"{len(ids)} ids but {len(desc)} descriptors")
+        for i, d in zip(ids, desc):
+            self._desc.setdefault(int(i), d.copy())
+
+    def add_points(self, ids, X, cov, n_obs=None):
+        """one export batch: ids (n,), positions (n, 3), covariances (n, 3, 3), observation counts (n,) or None (recorded as 0)"""
+        ids = np.asarray(ids).reshape(-1); X = np.asarray(X, np.float64).reshape(-1, 3); cov = np.asarray(cov, np.float64).reshape(-1, 3, 3)
+        nob = np.zeros(len(ids), np.int32) if n_obs is None else np.asarray(n_obs, np.int32).reshape(-1)
+        if not len(ids) == len(X) == len(cov) == len(nob):
+            raise ValueError(f"{len(ids)} ids, {len(X)} positions, {len(cov)} covariances, {len(nob)} observation counts")
+
+        def trace(c):
+            t = float(c[0, 0] + c[1, 1] + c[2, 2])
+            return t if np.isfinite(t) else np.inf
+        for i, x, c, k in zip(ids, X, cov, nob):
+            old = self._pts.get(int(i))
+            if old is None or trace(c) < trace(old[1]):
+                self._pts[int(i)] = (x.copy(), c.copy(), int(k))
+
+    @property
+    def n_without_descriptor(self):
+        """exported points whose id no add_tracks call has seen: arrays() leaves them out"""
+        return sum(1 for i in self._pts if i not in self._desc)
+
+    def arrays(self):
+        """-> (ids (n,) int64, X (n, 3), cov (n, 3, 3), desc (n, 32) uint8, n_obs (n,) int32) of the ids that have both a position and a
+        descriptor, in the order of their first export"""
+        keep = [i for i in self._pts if i in self._desc]
+        n = len(keep)
+        ids = np.array(keep, np.int64).reshape(n)
+        X = np.array([self._pts[i][0] for i in keep], np.float64).reshape(n, 3)
+        cov = np.array([self._pts[i][1] for i in keep], np.float64).reshape(n, 3, 3)
+        desc = np.array([self._desc[i] for i in keep], np.uint8).reshape(n, 32)
+        n_obs = np.array([self._pts[i][2] for i in keep], np.int32).reshape(n)
+        return ids, X, cov, desc, n_obs
+
+
+def save_map(path, ids, X, cov, desc, order=None):
+    """One .npz with ids, X, cov, desc and order: the raw arrays as MapCollector.arrays() gave them and the order ImageProcessor.build_map
+    returned (None: the arrays are the map as they stand, order = 0 .. n - 1); cov None is stored as an empty array.  The file is written
+    at `path` exactly (numpy adds no suffix)."""
+    X = np.asarray(X, np.float64).reshape(-1, 3); n = len(X)
+    ids = np.asarray(ids, np.int64).reshape(-1); desc = np.asarray(desc, np.uint8).reshape(-1, 32)
+    cov = np.zeros((0, 3, 3)) if cov is None else np.asarray(cov, np.float64).reshape(-1, 3, 3)
+    order = np.arange(n, dtype=np.int32) if order is None else np.asarray(order, np.int32).reshape(-1)
+    if len(ids) != n or len(desc) != n or len(cov) not in (0, n):
+        raise ValueError(f"{n} points but {len(ids)} ids, {len(desc)} descriptors, {len(cov)} covariances")
+    if len(order) and (order.min() < 0 or order.max() >= n or len(np.unique(order)) != len(order)):
+        raise ValueError("order must hold distinct indices into the arrays")
+    with open(path, "wb") as f:
+        np.savez(f, ids=ids, X=X, cov=cov, desc=desc, order=order)
+
+
+def load_map(path):
+    """-> (ids, X, cov or None, desc, order) as save_map stored them: X[order], cov[order], desc[order] is what set_map takes"""
+    with np.load(path, allow_pickle=False) as z:
+        ids, X, cov, desc, order = (z[k] for k in ("ids", "X", "cov", "desc", "order"))
+    return ids, X, (cov if len(cov) == len(X) and len(X) else None), desc, order
 
 
 def distort(xy, model, dist):

@@ -312,6 +312,48 @@ def map_select_queries(ctx, X, cov, desc, fe_config, R_wc, p_wc, align=None, cov
     return out if check else (st, out)
 
 
+def map_build_options(max_score=0.0, r_dup=0.0, dup_max_dist=0):
+    """lvk_map_build_options; a zero field takes the library's default (inf, 0 = no de-duplication, 32)"""
+    from ._lib import MapBuildOptions
+    return MapBuildOptions(float(max_score), float(r_dup), int(dup_max_dist), 0)
+
+
+MAP_BUILD_GUARD = 64    # sentinel bytes (0xA5) map_build keeps on either side of every output buffer
+
+
+def map_build(ctx, X, cov, desc, score=None, options=None, want_status=True, check=True):
+    """lvk_map_build over host arrays: X (n, 3) raw map points, cov (n, 3, 3) or None, desc (n, 32) uint8 or None, score (n,) or None
+    (smaller is better), options: map_build_options(...) or None.  -> dict(info: one MAP_BUILD_INFO record, order: the n_kept original
+    indices best first, X, cov, desc: the kept points gathered in that order (cov / desc None when not given), status: (n,) uint8 or None,
+    and order_raw, X_raw, cov_raw, desc_raw, status_raw, info_raw: the device buffers as bytes, sized for n records, with MAP_BUILD_GUARD
+    sentinel bytes of 0xA5 on either side, every output byte starting as 0xA5 too).  check=False returns (status code, that dict) instead
+    of raising."""
+    from ._lib import MAP_BUILD_INFO
+    X = np.ascontiguousarray(X, np.float64).reshape(-1, 3); n = len(X)
+    cv = None if cov is None else np.ascontiguousarray(cov, np.float64).reshape(-1, 9)
+    ds = None if desc is None else np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+    sc = None if score is None else np.ascontiguousarray(score, np.float64).reshape(-1)
+    assert (cv is None or len(cv) == n) and (ds is None or len(ds) == n) and (sc is None or len(sc) == n)
+    G = MAP_BUILD_GUARD
+    sizes = dict(order=4 * n, X=24 * n, cov=72 * n if cv is not None else 0, desc=32 * n if ds is not None else 0, status=n, info=MAP_BUILD_INFO.itemsize)
+    bufs = {k: ctx.to_device(np.full(v + 2 * G, 0xA5, np.uint8)) for k, v in sizes.items()}
+    at = lambda k: C.c_void_p(bufs[k].ptr + G)
+    dev = [ctx.to_device(a) if a is not None and n else None for a in (X, cv, ds, sc)]
+    st = lib().lvk_map_build(ctx.h, _p(dev[0]), _p(dev[1]), _p(dev[2]), _p(dev[3]), n, C.byref(options) if options is not None else None, at("order"), at("X"),
+                             at("cov") if cv is not None else None, at("desc") if ds is not None else None, at("status") if want_status else None, at("info"))
+    if check:
+        ctx.check(st)
+    ctx.sync()
+    raw = {k: ctx.to_host(bufs[k], np.uint8, (sizes[k] + 2 * G,)).copy() for k in sizes}
+    body = lambda k: raw[k][G:G + sizes[k]]
+    info = body("info").view(MAP_BUILD_INFO)[0]
+    nk = int(info["n_kept"]) if st == 0 else 0
+    out = dict(info=info, order=body("order").view(np.int32)[:nk], X=body("X").view(np.float64).reshape(-1, 3)[:nk],
+               cov=body("cov").view(np.float64).reshape(-1, 3, 3)[:nk] if cv is not None else None, desc=body("desc").reshape(-1, 32)[:nk] if ds is not None else None,
+               status=body("status") if want_status else None, **{k + "_raw": v for k, v in raw.items()})
+    return out if check else (st, out)
+
+
 def undistort(ctx, points, intr, model, dist, new_intr):
     p = _pts(points); n = len(p)
     a = np.asarray(intr, np.float64); d = np.asarray(dist, np.float64); k = np.asarray(new_intr, np.float64)
