@@ -6,6 +6,7 @@ import functools
 import numpy as np
 from oracle import lvo
 from tests import fe_frame_ref as R
+from tests import fm_cases
 from tests.test_gpu_frontend_edge import _texture, _crops
 from tests.test_gpu_frontend_stages import _two_view
 
@@ -178,9 +179,9 @@ def _nt(cap):
 # name: dict(mode, cap, n, pattern, seed, outliers, noise, dst_n (before), expect = the branch record's fields this case was built for)
 def _commit_table():
     T = {}
-    def add(name, mode, cap, n, pattern, expect, dst_n=0, outliers=0.2, noise=0.3, seed=None, dst_n_from_kept=None):
+    def add(name, mode, cap, n, pattern, expect, dst_n=0, outliers=0.2, noise=0.3, seed=None, dst_n_from_kept=None, und_from=None):
         T[name] = dict(mode=mode, cap=cap, n=n, pattern=pattern, expect=expect, dst_n=dst_n, outliers=outliers, noise=noise,
-                       seed=len(T) + 100 if seed is None else seed, dst_n_from_kept=dst_n_from_kept)
+                       seed=len(T) + 100 if seed is None else seed, dst_n_from_kept=dst_n_from_kept, und_from=und_from)
     # compaction across chunk and wavefront edges, both widths.  With 256 threads no cap reaches 2 NT + 1 points (the width changes at cap > 512):
     # n = 2 NT = cap = 512 is the largest set, two whole chunks
     sizes = {64: (0, 1, 63, 64), 512: (65, 255, 256, 257, 512), 513: (0, 1, 64, 65, 511, 512, 513), 2048: (63, 513, 1025, 2048)}
@@ -219,6 +220,13 @@ def _commit_table():
     add("m2_m20", 2, 64, 31, ("counts", 20, 5, 3), dict(fail=(), m=20, kept=20), outliers=0, noise=0)
     add("m2_mask_leaves_fewer_than_20", 2, 64, 30, ("counts", 24, 3, 3), dict(fail=("kept",), m=24, method="ransac"), outliers=1 / 3, noise=0.1, seed=7)
     add("m2_wide", 2, 2048, 700, "third", dict(width=512, fail=(), m=234, method="ransac"))
+    # the estimator off its fast path inside the commit: the alive points are a set of tests/fm_cases.py, in its order (und_from), so the
+    # path that set was proved to reach is the path this launch takes.  Table overrun at both widths, a frozen camera, and a set whose
+    # every subset is collinear (no model: the mask drops every point)
+    add("m0_fm_overrun", 0, 64, 64, ("counts", 60, 2, 2), dict(width=256, m=60, method="ransac", fail=()), und_from="overrun_n60")
+    add("m0_fm_overrun_wide", 0, 513, 513, ("counts", 500, 6, 7), dict(width=512, m=500, method="ransac", fail=()), und_from="overrun_n500")
+    add("m0_fm_frozen", 0, 64, 64, ("counts", 60, 2, 2), dict(width=256, m=60, kept=60, method="ransac", fail=()), und_from="frozen_n60")
+    add("m0_fm_all_collinear", 0, 64, 30, ("counts", 20, 5, 5), dict(width=256, m=20, kept=0, method="ransac", fail=()), und_from="all_collinear_n20")
     return T
 
 
@@ -238,7 +246,11 @@ def commit_case(name):
     # the alive points see one two-view scene (with its share of gross outliers, in order); the others carry pairs nothing may read as inliers
     alive = np.flatnonzero(status == R.ST_ALIVE)
     src["und"][:, 0] = rng.uniform(0, 700, (n, 2)); src["und"][:, 1] = rng.uniform(0, 700, (n, 2))
-    if len(alive):
+    if c["und_from"]:
+        fm = fm_cases.case(c["und_from"])
+        assert len(alive) == fm["n"]
+        src["und"][alive, 0] = fm["p1"]; src["und"][alive, 1] = fm["p2"]
+    elif len(alive):
         x1, x2 = _two_view(len(alive), c["outliers"], c["seed"], noise=c["noise"])
         perm = rng.permutation(len(alive))                    # outliers anywhere in the order, not in front
         src["und"][alive, 0] = x1[perm]; src["und"][alive, 1] = x2[perm]
@@ -256,7 +268,7 @@ def commit_case(name):
         dst["init"][:d] = -1; dst["desc"][:d] = rng.integers(0, 256, (d, 32))
     ref_dst, ref_state, br = R.commit_ref(mode, cap, src, dst, state)
     return dict(mode=mode, cap=cap, n=n, src=src, dst=dst, state=state, ref_dst=ref_dst, ref_state=ref_state, branch=br, expect=c["expect"], expect_m=expect_m,
-                pattern=c["pattern"])
+                pattern=c["pattern"], und_from=c["und_from"])
 
 
 def check_commit_case(cc):
@@ -270,6 +282,9 @@ def check_commit_case(cc):
         assert c["n"] < 4 or len(set(c["src"]["status"].tolist())) == 4
     if "method" not in c["expect"] and not br["fail"]:
         assert br["method"] == (None if br["m"] == 0 else R.mask_method(br["m"]))
+    if c["und_from"]:                                         # the estimator sees exactly that set: its path (tests/test_fm_cases.py) and its mask
+        fm_cases.check_case(c["und_from"])
+        assert br["kept"] == int(fm_cases.oracle(c["und_from"])["find"][0].sum())
     s0, s1 = c["state"], c["ref_state"]
     if c["mode"] == 1:
         if br["fail"]:
