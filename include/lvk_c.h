@@ -276,8 +276,8 @@ int        lvk_align_draw_pairs(int n, int max_hypotheses, uint32_t seed, lvk_al
  * lvk_undistort_points; width, height in pixels); align: the map's alignment - only c, s, t of the record are read, NULL = identity
  * (c = 1, s = 0, t = 0 through the same expressions); R_wc (row-major, camera to world) and p_wc as lvk_align_ransac_2pt takes them;
  * cov_cam: NULL or the 6 x 6 covariance (row-major) of the camera pose in the order [dtheta dp]: the rotation error is on the camera side,
- * R_true = R_wc (I + [dtheta]x), dp is in the world frame.  Turning the filter's IMU-pose block (lvk_ekf_get_window_cov) into that with the
- * extrinsics is the caller's job.  FP64 throughout, no contraction, every expression in the order written here (a product chain a b c is
+ * R_true = R_wc (I + [dtheta]x), dp is in the world frame.  lvk_ekf_camera_pose_cov forms all three from a clone of the filter's window, the
+ * extrinsics and the covariance where it lies.  FP64 throughout, no contraction, every expression in the order written here (a product chain a b c is
  * (a b) c, a sum of products runs over its index upwards from the first product), so every field has one right value:
  *   pose       q = (c X_x - s X_y, s X_x + c X_y);  g = ((q_x + t_x) - p_wc,x, (q_y + t_y) - p_wc,y, (X_z + t_z) - p_wc,z);
  *              p_c,i = (R_wc[0][i] g_0 + R_wc[1][i] g_1) + R_wc[2][i] g_2 (= R_wc^T (Rz X + t - p_wc));  x = p_c,x / p_c,z, y = p_c,y / p_c,z,
@@ -927,6 +927,73 @@ lvk_status lvk_ekf_update_landmarks(lvk_context* ctx, double* d_P, int ldp, int 
                                     const lvk_landmark_obs* h_obs, int n_obs, double* h_dx /* n */, double* h_info8,
                                     int* h_status /* n_obs */, double* h_gamma /* n_obs */);
 
+/* Stage entry: the camera pose of one clone of the window and its covariance in the form lvk_map_select_queries takes as cov_cam, read off
+ * a device-resident covariance (n x n, row-major, leading dimension ldp) without moving it - the link between the filter and the prior-map
+ * chain.  No reference counterpart.  The job is lvk_landmark_fix_job without the gate fields; the conventions are those of
+ * lvk_ekf_update_landmarks: R(q) maps body to world, the injection is R_b <- (I + [d_theta_b]x) R_b, p_b <- p_b + d_p_b,
+ * R_b2c <- R_b2c R(d_theta_e)^T, t_c_b <- t_c_b + d_t; twelve columns of P matter, in ascending order: 15..20 (d_theta_e, d_t), then the
+ * clone's six (d_theta_b, d_p_b).  The pose is
+ *   R_wc = R_b R_b2c^T,   p_wc = p_b + R_b t_c_b,
+ * its error is defined as lvk_map_select_queries reads it - R_wc,true = R_wc (I + [dtheta]x), the rotation error on the camera side, and
+ * p_wc,true = p_wc + dp in the world frame - and to first order, under the injection above,
+ *   dtheta = R_b2c d_theta_e + R_wc^T d_theta_b,   dp = R_b d_t - [R_b t_c_b]x d_theta_b + d_p_b,
+ * so cov_cam = J P_s J^T (order [dtheta dp]) with P_s the 12 x 12 sub-block and
+ *   J = [ R_b2c  0    R_wc^T          0
+ *         0      R_b  -[R_b t_c_b]x   I ].
+ * (The signs were confirmed against the injection by central differences of (R_wc^T R_wc', p_wc' - p_wc): tests/camera_pose_ref.py; they
+ * agree with the form above.)  FP64 throughout, no contraction, every expression in the order written here, so every output has one right
+ * value:
+ *   R_b      Eigen's Quaternion::toRotationMatrix of q_b = [x y z w] (as lvk_ekf_landmark_rel_cov takes it): tx = 2 x, ty = 2 y, tz = 2 z,
+ *            twx = tx w, twy = ty w, twz = tz w, txx = tx x, txy = ty x, txz = tz x, tyy = ty y, tyz = tz y, tzz = tz z;
+ *            R_b = [1 - (tyy + tzz), txy - twz, txz + twy; txy + twz, 1 - (txx + tzz), tyz - twx; txz - twy, tyz + twx, 1 - (txx + tyy)].
+ *   pose     R_wc[i][j] = (R_b[i][0] R_b2c[j][0] + R_b[i][1] R_b2c[j][1]) + R_b[i][2] R_b2c[j][2];
+ *            u_i = (R_b[i][0] t_c_b,0 + R_b[i][1] t_c_b,1) + R_b[i][2] t_c_b,2;   p_wc,i = p_b,i + u_i.
+ *   J        6 x 12, all zeros but: J[i][c] = R_b2c[i][c], J[i][6 + c] = R_wc[c][i], J[3 + i][3 + c] = R_b[i][c],
+ *            J[3 + i][6 + c] = (-[u]x)[i][c] (rows (0, u_2, -u_1), (-u_2, 0, u_0), (u_1, -u_0, 0)), J[3 + i][9 + c] = 1 when i == c.
+ *   T        T[i][j] = sum over l = 0..11, upwards from 0.0, of J[i][l] P_s[l][j] - the zero entries of J are terms like any other.
+ *   cov_cam  for i <= j: cov[i][j] = sum over l = 0..11, upwards from 0.0, of T[i][l] J[j][l]; cov[j][i] is a copy of it, so the
+ *            result is symmetric bit for bit.
+ * One launch of one workgroup (one wavefront; 2304 bytes of LDS: P_s, J, T) and one wait.  Nothing outside those twelve rows and columns
+ * of P is read.  When the extrinsics are not estimated their block of P is zero and cov_cam is the clone block's own J_b P_bb J_b^T.
+ * h_R_wc: 9 doubles, row-major; h_p_wc: 3; h_cov36: 36, row-major.  larvio_amd.localize.camera_pose_cov_ref is the numpy restatement.
+ * LVK_ERR_ARG, with nothing launched and the context still usable: a null pointer, ldp < n, clone_col < 21 or clone_col + 6 > n, a value
+ * of the job that is not finite, |q_b| off 1 by more than 1e-6. */
+typedef struct { int clone_col, pad0;            /* first of the clone's six columns */
+                 double q_b[4], p_b[3];          /* the clone's pose */
+                 double R_b2c[9], t_c_b[3]; }    /* the extrinsics, as lvk_ekf_get_state hands them out */
+        lvk_camera_pose_job;
+lvk_status lvk_ekf_camera_pose_cov(lvk_context* ctx, const double* d_P, int ldp, int n, const lvk_camera_pose_job* h_job,
+                                   double* h_R_wc /* 9 */, double* h_p_wc /* 3 */, double* h_cov36 /* 36 */);
+
+/* Stage entry: the last link of the prior-map chain on the device - the records of lvk_frontend_match_map into the observation rows
+ * lvk_ekf_add_landmark_obs takes, gathered from the resident map so that the host needs no copy of it.  No reference counterpart.
+ * d_rec: n_rec lvk_map_match records (at most 1024); d_X: the map's n_map points (3 doubles each, the map's own frame); d_cov: NULL or
+ * their covariances (9 doubles each, row-major; the upper triangle is read); align: the map's alignment - only c, s, t are read, NULL =
+ * identity (c = 1, s = 0, t = 0 through the same expressions, so NULL and an explicit identity record give the same bytes); sigma: the
+ * standard deviation of a matched corner in normalised units.  FP64 throughout, no contraction, every expression in the order written
+ * here, so every output has one right value:
+ *   kept      record k is kept iff m.status == LVK_MATCH_OK and 0 <= index < n_map.  An OK record whose index is outside the map is
+ *             counted in n_bad, is not emitted, and nothing is read at its index: an index is compared before it is followed.  Records
+ *             of any other status are skipped whatever their index.
+ *   p_w       with X = d_X[index]: q = (c X_x - s X_y, s X_x + c X_y), p_w = (q_x + t_x, q_y + t_y, X_z + t_z) - the expressions of
+ *             lvk_map_select_queries, so the point that is fused is bit for bit the point that was projected.
+ *   cov_w     Rz Sigma Rz^T as (Rz Sigma) Rz^T on the upper triangle a = S00, b = S01, d = S11, e = S02, f = S12, g = S22 of the point's
+ *             covariance: m00 = c a - s b, m01 = c b - s d, m10 = s a + c b, m11 = s b + c d;  w00 = m00 c - m01 s, w01 = m00 s + m01 c,
+ *             w11 = m10 s + m11 c, w02 = c e - s f, w12 = s e + c f, w22 = g;  cov_w = [w00 w01 w02; w01 w11 w12; w02 w12 w22] - entry
+ *             (i, j) and entry (j, i) are one value, so the result is symmetric bit for bit.  All zeros when d_cov is NULL.
+ *   uv        (double) m.und, both coordinates;  sigma is copied.
+ *   order     the kept records in the records' own order: d_obs[j] is the j-th kept record, d_idx[j] its row in d_rec.
+ * d_obs, d_idx: room for n_rec entries each, n_ok of them are written and nothing beyond; d_info: n_ok (the count), n_bad and pad 0,
+ * written by the kernel of every call that launches.  One launch of one workgroup on the context's stream (one lane per record; the
+ * positions come from wave ballots and a scan of the wavefronts' counts in 128 bytes of LDS - no atomics, nothing depends on the order
+ * in which anything ran: two runs on the same input give the same bytes), not waited for.
+ * LVK_ERR_ARG, with nothing launched and the context still usable: a null pointer that is needed (d_info always; d_rec, d_obs, d_idx with
+ * n_rec > 0; d_X with n_rec > 0 and n_map > 0), a negative count, a non-finite c, s or t of the alignment, a sigma that is not a finite
+ * number > 0.  LVK_ERR_CAPACITY: n_rec > 1024.  n_rec == 0: LVK_OK, d_info zeroed, nothing launched. */
+typedef struct { int n_ok, n_bad, pad[2]; } lvk_map_obs_info;
+lvk_status lvk_map_gather_obs(lvk_context* ctx, const lvk_map_match* d_rec, int n_rec, const double* d_X, const double* d_cov, int n_map,
+                              const lvk_align_result* align, double sigma, lvk_landmark_obs* d_obs, int* d_idx, lvk_map_obs_info* d_info);
+
 typedef struct {
     /* names and meaning as LarVio::loadParameters reads them (larvio.cpp:58-311, config/euroc.yaml) */
     int if_fej, estimate_extrin, estimate_td, if_zupt_valid;
@@ -1399,6 +1466,40 @@ lvk_status lvk_vio_process(lvk_frontend* fe, lvk_ekf* ekf, const lvk_image* img,
  * (adapter/: larvio::ImageProcessor / larvio::LarVio) give an unchanged blocking driver. */
 lvk_status lvk_vio_process_deferred(lvk_frontend* fe, lvk_ekf* ekf, const lvk_image* img, double ts,
                                     const lvk_imu* h_imu, int n_imu, int* n_consumed, int* has_msg, int* will_update);
+
+/* Localise in the loop: from the filter's pose of the last processed frame to queued observations of the resident prior map, in one call -
+ * the per-frame link of the prior-map chain (lvk_frontend_set_map / lvk_frontend_build_map, lvk_frontend_relocalise_map for align).  No
+ * reference counterpart.  The target clone: clone_id >= 0 names it; clone_id == -1 goes by time, equal (==) to a clone's time - the rule of
+ * lvk_ekf_add_landmark_obs without its "newer than the newest stays queued" case.  A frame the filter has no clone for (not initialised,
+ * an id that is not in the window, a time no clone has) gives h_info->status = LVK_LOCALISE_NO_CLONE and LVK_OK: nothing is launched,
+ * nothing is queued, the rest of h_info is zero and clone_id -1.  Otherwise, in order:
+ *   1  the filter's pending update is waited for, as every getter does;
+ *   2  lvk_ekf_camera_pose_cov on the filter's covariance with that clone and the current extrinsics: R_wc, p_wc, cov_cam;
+ *   3  the device chain of lvk_frontend_match_map with those three, align, select_opt and match_opt - the very code lvk_frontend_match_map
+ *      runs, records left on the device;
+ *   4  lvk_map_gather_obs' launch on those records where they lie, sigma = sigma_px / ((fx + fy) / 2) of the front-end's camera;
+ *   5  one copy back of the count, the source rows and the observations;
+ *   6  the observations are queued as ONE batch on that clone (by its id) with `tag`, through lvk_ekf_add_landmark_obs itself: its limits,
+ *      refusals and reports are unchanged.  Zero observations (nothing selected, nothing matched) are queued as the legal empty batch, so
+ *      there is one lvk_landmark_report per call that found its clone.
+ * h_info: status, n_ok = the observations queued, n_bad (lvk_map_gather_obs), the clone's id, map = lvk_frontend_match_map's counts, and
+ * the R_wc, p_wc, cov_cam of step 2 that steps 3 and 4 used.
+ * Off the per-frame path, as its parts are: it waits for the GPU (once in step 2; the selection's count, the corner count and the copy in
+ * 3 to 5), works in the matcher's buffers and one buffer of its own (allocated on first use), and changes nothing a later frame reads
+ * except the queue it is meant to fill; a run that never calls it allocates and launches what it did before.  fe and ekf may share a
+ * context or not.  With a lvk_vio_pipe attached to ekf it is legal only between lvk_vio_pipe_drain and the next lvk_vio_pipe_submit:
+ * LVK_ERR_ARG while a submitted frame's update is queued or running.  LVK_ERR_UNSUPPORTED while a shard transport is set, as
+ * lvk_ekf_add_landmark_obs.  LVK_ERR_ARG: a null fe, ekf or h_info, clone_id < -1, a time that is not finite with clone_id == -1, a sigma_px
+ * that is not a finite number > 0.  (An update queued by lvk_ekf_process_async is no refusal: step 1 waits for it.)
+ * Every refusal of the parts (no map is set, a call before the first processed frame or between lvk_frontend_begin and the
+ * lvk_frontend_process of the same frame, the options' ranges, 16 batches waiting) passes through unchanged; none is sticky, and a call
+ * refused after step 2 has queued nothing. */
+#define LVK_LOCALISE_QUEUED   0
+#define LVK_LOCALISE_NO_CLONE 1
+typedef struct { int status, n_ok, n_bad, pad; int64_t clone_id; lvk_map_info map; double R_wc[9], p_wc[3], cov_cam[36]; } lvk_localise_info;
+lvk_status lvk_vio_localise_map(lvk_frontend* fe, lvk_ekf* ekf, const lvk_align_result* align, int64_t clone_id, double time, double sigma_px,
+                                const lvk_map_select_options* select_opt, const lvk_match_options* match_opt, int64_t tag,
+                                lvk_localise_info* h_info);
 
 /* The same loop, pipelined across two HIP streams: the filter update of frame k (worker thread, ekf's context) overlaps the
  * front-end of frame k+1 (caller's thread, fe's context).  fe and ekf must have been created on DIFFERENT lvk_contexts.

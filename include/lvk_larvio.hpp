@@ -368,6 +368,20 @@ public:
         out.resize((size_t)n);
     }
     void landmarkStats(long out12[12]) const { for (int i = 0; i < 12; ++i) out12[i] = 0; if (ekf_) lvk_ekf_landmark_stats(ekf_, out12); }
+    // Localise in the loop (lvk_vio_localise_map; steps, target clone and refusals in lvk_c.h): from this filter's pose of the frame `fe`
+    // processed last to ONE queued batch of observations of fe's resident map (ImageProcessor::setMap / buildMap) - the clone's camera
+    // pose and covariance, matchMap's device chain, the gather of the matched points, addLandmarkObs, without a host copy of the map.
+    // The clone goes by id, or (clone_id -1) by time.  info.status == LVK_LOCALISE_NO_CLONE: the filter has no clone for that frame,
+    // nothing was queued.  With a VioPipeline call it only between drain() and the next processImage.
+    bool localiseMap(ImageProcessor& fe, lvk_localise_info& info, const lvk_align_result* align = nullptr, long long clone_id = -1, double time = 0.0,
+                     double sigma_px = 1.0, const lvk_map_select_options* select_opt = nullptr, const lvk_match_options* match_opt = nullptr, long long tag = 0)
+    {
+        if (!ekf_ || !fe.handle()) return false;
+        if (lvk_vio_localise_map(fe.handle(), ekf_, align, clone_id, time, sigma_px, select_opt, match_opt, tag, &info) != LVK_OK) {
+            std::fprintf(stderr, "LarVio::localiseMap: %s\n", lvk_last_error(ctx_)); return false;
+        }
+        return true;
+    }
     lvk_ekf* handle() const { return ekf_; }
 private:
     friend class VioPipeline;

@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "lvk_frontend_set_map", "lvk_frontend_map_size", "lvk_frontend_build_map", "lvk_frontend_match_map", "lvk_frontend_relocalise_map",
     "lvk_frontend_state", "lvk_frontend_lk_stats", "lvk_frontend_msg_stats", "lvk_frontend_profile_enable", "lvk_frontend_profile_read",
     "lvk_frontend_stage_name", "lvk_fe_track_stage", "lvk_fe_commit_stage", "lvk_fe_msg_stage",
-    "lvk_ekf_compress_qr", "lvk_ekf_compress_qr_groups", "lvk_ekf_qr_plan", "lvk_ekf_update", "lvk_ekf_update_ldlt", "lvk_ekf_update_ldlt_perm", "lvk_dgemm", "lvk_dgemm_ex", "lvk_chol_solve", "lvk_ekf_cov_propagate_augment", "lvk_ekf_cov_gather", "lvk_ekf_cov_reanchor", "lvk_ekf_cov_append_features", "lvk_ekf_landmark_cov", "lvk_ekf_pose_rel_cov", "lvk_ekf_landmark_rel_cov", "lvk_ekf_msckf_point_cov", "lvk_ekf_update_sparse", "lvk_ekf_update_landmarks", "lvk_ekf_create", "lvk_ekf_destroy", "lvk_ekf_process", "lvk_ekf_process_async", "lvk_ekf_wait", "lvk_ekf_set_state",
+    "lvk_ekf_compress_qr", "lvk_ekf_compress_qr_groups", "lvk_ekf_qr_plan", "lvk_ekf_update", "lvk_ekf_update_ldlt", "lvk_ekf_update_ldlt_perm", "lvk_dgemm", "lvk_dgemm_ex", "lvk_chol_solve", "lvk_ekf_cov_propagate_augment", "lvk_ekf_cov_gather", "lvk_ekf_cov_reanchor", "lvk_ekf_cov_append_features", "lvk_ekf_landmark_cov", "lvk_ekf_pose_rel_cov", "lvk_ekf_landmark_rel_cov", "lvk_ekf_msckf_point_cov", "lvk_ekf_update_sparse", "lvk_ekf_update_landmarks", "lvk_ekf_camera_pose_cov", "lvk_map_gather_obs", "lvk_vio_localise_map", "lvk_ekf_create", "lvk_ekf_destroy", "lvk_ekf_process", "lvk_ekf_process_async", "lvk_ekf_wait", "lvk_ekf_set_state",
     "lvk_ekf_dim", "lvk_ekf_is_initialized", "lvk_ekf_take_off_stamp", "lvk_ekf_get_state", "lvk_ekf_get_imu_intrinsics", "lvk_ekf_set_imu_intrinsics", "lvk_ekf_get_cov", "lvk_ekf_set_cov", "lvk_ekf_set_indefinite_policy", "lvk_ekf_indefinite_fallbacks", "lvk_ekf_last_update", "lvk_ekf_get_cov_imu", "lvk_ekf_get_clones", "lvk_ekf_get_features", "lvk_ekf_take_lost_features", "lvk_ekf_get_feature_cov", "lvk_ekf_set_lost_feature_cov", "lvk_ekf_take_lost_features_cov", "lvk_ekf_get_feature_rel", "lvk_ekf_set_msckf_points", "lvk_ekf_take_msckf_points", "lvk_ekf_set_keyframe_export", "lvk_ekf_take_keyframes", "lvk_ekf_get_window_cov", "lvk_ekf_add_fix", "lvk_ekf_set_fix_options", "lvk_ekf_take_fix_reports", "lvk_ekf_fix_stats", "lvk_ekf_add_landmark_obs", "lvk_ekf_set_landmark_options", "lvk_ekf_take_landmark_reports", "lvk_ekf_landmark_stats",
     "lvk_ekf_counters", "lvk_ekf_init_report", "lvk_ekf_profile", "lvk_ekf_profile_qr", "lvk_ekf_set_shard", "lvk_ekf_shard_stats", "lvk_shard_unique_id", "lvk_shard_comm_create", "lvk_shard_comm_destroy", "lvk_shard_comm_error", "lvk_shard_rccl_path", "lvk_shard_allgather_rccl", "lvk_shard_pack_stage", "lvk_shard_unpack_stage", "lvk_triangulate", "lvk_ekf_gate_and_stack", "lvk_ekf_feature_rows", "lvk_vio_process", "lvk_vio_process_deferred", "lvk_vio_pipe_create", "lvk_vio_pipe_destroy", "lvk_vio_pipe_push_imu", "lvk_vio_pipe_submit", "lvk_vio_pipe_drain", "lvk_vio_pipe_on_update", "lvk_vio_pipe_stats", "lvk_vio_pipe_latency", "lvk_vio_pipe_early_counts",
 ]
@@ -131,6 +131,11 @@ MAP_MATCH = np.dtype([("index", np.int32), ("cell", np.int32), ("q", MATCH_QUERY
 MAP_VISIBLE, MAP_BEHIND, MAP_FAR, MAP_OUTSIDE = 0, 1, 2, 3
 MAP_SELECTED = 0x80
 MAP_MAX_POINTS, MAP_MAX_QUERIES = 1 << 20, 1024
+# lvk_map_obs_info (lvk_map_gather_obs) and lvk_localise_info (lvk_vio_localise_map) of include/lvk_c.h, and the LVK_LOCALISE_* status codes
+MAP_OBS_INFO = np.dtype([("n_ok", np.int32), ("n_bad", np.int32), ("pad", np.int32, 2)])
+LOCALISE_INFO = np.dtype([("status", np.int32), ("n_ok", np.int32), ("n_bad", np.int32), ("pad", np.int32), ("clone_id", np.int64), ("map", MAP_INFO),
+                          ("R_wc", np.float64, (3, 3)), ("p_wc", np.float64, 3), ("cov_cam", np.float64, (6, 6))])
+LOCALISE_QUEUED, LOCALISE_NO_CLONE = 0, 1
 
 
 # lvk_global_match / lvk_global_info / lvk_reloc_match of include/lvk_c.h and the caps of lvk_orb_match_global
@@ -217,6 +222,9 @@ def lib():
             "lvk_frontend_msg_stats": ([vp, vp, vp], i),
             "lvk_frontend_profile_enable": ([vp, C.c_uint], i), "lvk_frontend_profile_read": ([vp, vp, vp, i], i),
             "lvk_frontend_stage_name": ([i], C.c_char_p),
+            "lvk_ekf_camera_pose_cov": ([vp, vp, i, i, vp, vp, vp, vp], i),
+            "lvk_map_gather_obs": ([vp, vp, i, vp, vp, i, vp, d, vp, vp, vp], i),
+            "lvk_vio_localise_map": ([vp, vp, vp, C.c_int64, d, d, C.POINTER(MapSelectOptions), C.POINTER(MatchOptions), C.c_int64, vp], i),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)

@@ -357,4 +357,54 @@ lvk_status lvk_vio_process_deferred(lvk_frontend* fe, lvk_ekf* ekf, const lvk_im
     return vio_step(fe, ekf, img, ts, h_imu, n_imu, n_consumed, has_msg, will_update, lvk_ekf_process_async);
 }
 
+// Localise in the loop (include/lvk_c.h states the steps): the clone's camera pose and covariance from the filter (be_camera_pose.hip),
+// the front-end's part (lvk_frontend_localise_obs: match_map's device chain, the gather, one copy back), the batch through
+// lvk_ekf_add_landmark_obs.  Host code only; the two handles may live on one context or on two.
+lvk_status lvk_vio_localise_map(lvk_frontend* fe, lvk_ekf* ekf, const lvk_align_result* align, int64_t clone_id, double time, double sigma_px,
+                                const lvk_map_select_options* select_opt, const lvk_match_options* match_opt, int64_t tag, lvk_localise_info* h_info)
+{
+    if (!ekf) return LVK_ERR_ARG;
+    lvk_ekf* e = ekf;
+    if (!fe || !h_info) return lvk_set_error(e->ctx, LVK_ERR_ARG, "lvk_vio_localise_map: bad argument");
+    if (clone_id < -1) return lvk_set_error(e->ctx, LVK_ERR_ARG, "lvk_vio_localise_map: clone_id %lld", (long long)clone_id);
+    if (clone_id == -1 && !std::isfinite(time)) return lvk_set_error(e->ctx, LVK_ERR_ARG, "lvk_vio_localise_map: time is not finite");
+    if (!std::isfinite(sigma_px) || !(sigma_px > 0.)) return lvk_set_error(e->ctx, LVK_ERR_ARG, "lvk_vio_localise_map: sigma_px is not a finite number > 0");
+    if (e->on_consumed == pipe_on_consumed) {           // a pipe is attached: only between its drain and the next submit
+        lvk_vio_pipe* p = (lvk_vio_pipe*)e->on_consumed_user;
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (p->in_flight > 0) return lvk_set_error(e->ctx, LVK_ERR_ARG, "lvk_vio_localise_map: the pipe has %d updates in flight (lvk_vio_pipe_drain first)", p->in_flight);
+    }
+    ekf_quiesce(e);
+    if (e->shard.fn) return lvk_set_error(e->ctx, LVK_ERR_UNSUPPORTED, "lvk_vio_localise_map: the sharded update does not apply landmark observations (lvk_ekf_set_shard is set)");
+    memset(h_info, 0, sizeof *h_info);
+    h_info->status = LVK_LOCALISE_NO_CLONE; h_info->clone_id = -1;
+    int i = -1;
+    if (e->is_gravity_set) {
+        if (clone_id >= 0) i = clone_rank(e, clone_id);
+        else for (int k = 0; k < (int)e->clones.size() && i < 0; ++k) if (e->clones[(size_t)k].time == time) i = k;
+    }
+    if (i < 0) return LVK_OK;
+    const Clone& c = e->clones[(size_t)i];
+    lvk_camera_pose_job job; memset(&job, 0, sizeof job);
+    job.clone_col = e->leg + 6 * i;
+    memcpy(job.q_b, c.q, 32); memcpy(job.p_b, c.p, 24); memcpy(job.R_b2c, e->R_b2c, 72); memcpy(job.t_c_b, e->t_c_b, 24);
+    lvk_localise_info info; memset(&info, 0, sizeof info);
+    info.status = LVK_LOCALISE_QUEUED; info.clone_id = c.id;
+    LVK_TRY(lvk_ekf_camera_pose_cov(e->ctx, e->dP[e->cur], e->ld, e->N, &job, info.R_wc, info.p_wc, info.cov_cam));
+    e->n_sync++;
+    static thread_local std::vector<lvk_landmark_obs> obs;
+    static thread_local std::vector<int> idx;
+    if (obs.size() < LVK_MAP_MAX_QUERIES) { obs.resize(LVK_MAP_MAX_QUERIES); idx.resize(LVK_MAP_MAX_QUERIES); }
+    lvk_map_obs_info oinfo;
+    const lvk_status st = lvk_frontend_localise_obs(fe, align, info.R_wc, info.p_wc, info.cov_cam, select_opt, match_opt, sigma_px, obs.data(), idx.data(), &info.map, &oinfo);
+    if (st != LVK_OK) {                                 // the front-end's message, on the handle the caller asks for it
+        lvk_context* fc = lvk_frontend_context(fe);
+        return fc == e->ctx ? st : lvk_set_error(e->ctx, st, "%s", lvk_last_error(fc));
+    }
+    info.n_ok = oinfo.n_ok; info.n_bad = oinfo.n_bad;
+    LVK_TRY(lvk_ekf_add_landmark_obs(e, tag, c.id, c.time, obs.data(), oinfo.n_ok));
+    *h_info = info;
+    return LVK_OK;
+}
+
 }  // extern "C"

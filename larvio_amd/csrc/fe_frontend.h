@@ -125,6 +125,9 @@ struct lvk_frontend {
     // corners' pixels and normalised coordinates, and the blob that goes back in one copy (RelocBlob: result, counts, match records)
     struct RelocBlob { lvk_align_result res; lvk_global_info info; lvk_reloc_match m[1024]; };
     struct Reloc { lvk_match_result* best; lvk_global_match* sel; lvk_pt2f *px, *und; RelocBlob* blob; } reloc = {};
+    // lvk_vio_localise_map's own buffer, allocated by its first call: the blob that goes back in one copy - the counts, then room for 1024
+    // source rows and 1024 observations (lvk_frontend_localise_obs lays it out for the frame's n_selected)
+    struct Loc { char* blob; } loc = {};
     // sticky: a frame that failed AFTER its image stage was queued (device error, ring overrun) leaves the buffer-set rotation and the
     // end-of-frame events out of step with the frame count; the handle then refuses further frames instead of racing on its buffers
     lvk_status failed = LVK_OK; char failed_msg[200] = {0};
@@ -178,6 +181,10 @@ lvk_status fe_match_finish(lvk_context* ctx, const CamParams& cam, const lvk_mat
                            lvk_landmark_match* d_out);
 // fe_map.hip: rows * cols * quota of the options as lvk_map_select_queries reads them, -1 when it refuses them
 int fe_map_max_selected(const lvk_map_select_options* opt);
+// fe_mapobs.hip: the launch behind lvk_map_gather_obs on the context's stream, for records whose map index and whose lvk_landmark_match lie
+// at idx_base + k idx_stride and m_base + k m_stride (bytes): one array of lvk_map_match, or the selection's and the matcher's own arrays
+lvk_status fe_map_gather_launch(lvk_context* ctx, const void* idx_base, int idx_stride, const void* m_base, int m_stride, int n_rec, const double* d_X, const double* d_cov,
+                                int n_map, const lvk_align_result* align, double sigma, lvk_landmark_obs* d_obs, int* d_idx, lvk_map_obs_info* d_info);
 // fe_global.hip: behind lvk_orb_match_global on the context's stream - the n selected corners' pixels, their normalised coordinates, the
 // alignment's match records and the host's records (inlier 0); then, behind lvk_align_ransac_2pt, inlier = the mask byte
 lvk_status fe_reloc_gather(lvk_context* ctx, const CamParams& cam, const lvk_global_match* d_sel, int n, const lvk_pt2f* d_cand_pts, const double* d_X, lvk_pt2f* d_px,

@@ -128,7 +128,7 @@ void lvk_frontend_destroy(lvk_frontend* fe)
                     fe->gf_scratch, fe->gf_cands, fe->dev, fe->user_mask, fe->d_gray,
                     fe->match.eig, fe->match.cand_pts, fe->match.n_cand, fe->match.cand_desc, fe->match.q, fe->match.q_desc, fe->match.res, fe->match.px, fe->match.und, fe->match.out,
                     fe->align.m, fe->align.pairs, fe->align.mask, fe->align.out, fe->map.X, fe->map.cov, fe->map.desc, fe->map.sel, fe->map.info,
-                    fe->reloc.best, fe->reloc.sel, fe->reloc.px, fe->reloc.und, fe->reloc.blob};
+                    fe->reloc.best, fe->reloc.sel, fe->reloc.px, fe->reloc.und, fe->reloc.blob, fe->loc.blob};
     for (void* p : ptrs) if (p) hipFree(p);
     for (int i = 0; i < 3; ++i) { if (fe->h_stage[i]) hipHostFree(fe->h_stage[i]); if (fe->d_ring[i]) hipFree(fe->d_ring[i]); if (fe->ev_img[i]) hipEventDestroy(fe->ev_img[i]); }
     for (int i = 0; i < LVK_MSG_SLOTS; ++i) if (fe->ev_msg[i]) hipEventDestroy(fe->ev_msg[i]);
@@ -921,21 +921,19 @@ lvk_status lvk_frontend_build_map(lvk_frontend* fe, const double* h_X, const dou
     return LVK_OK;
 }
 
-// The map's points in the last processed frame: lvk_map_select_queries writes the queries and their descriptors straight into the
-// matcher's buffers, the chain of lvk_frontend_match_landmarks runs on them, the host joins the two record arrays.
-lvk_status lvk_frontend_match_map(lvk_frontend* fe, const lvk_align_result* align, const double* R_wc, const double* p_wc, const double* cov_cam36,
-                                  const lvk_map_select_options* select_opt, const lvk_match_options* match_opt, lvk_map_match* h_out, int cap, int* n_out,
-                                  lvk_map_info* h_info)
+// The device side of lvk_frontend_match_map, shared with lvk_frontend_localise_obs: the checks that need no argument of the caller's own,
+// the matcher's buffers, a wait for the front-end's streams, lvk_map_select_queries straight into the matcher's buffers, a wait for the
+// selection's count, and the chain of lvk_frontend_match_landmarks on the selected queries.  On LVK_OK the n_q selected points' records
+// are in fe->map.sel and their matches in fe->match.out, queued and not waited for; *info holds the counts.  cap: the caller's room.
+static lvk_status fe_match_map_device(lvk_frontend* fe, const char* who, const lvk_align_result* align, const double* R_wc, const double* p_wc, const double* cov_cam36,
+                                      const lvk_map_select_options* select_opt, const lvk_match_options* match_opt, int cap, int* n_q_out, lvk_map_info* info_out)
 {
-    if (!fe) return LVK_ERR_ARG;
     lvk_context* ctx = fe->ctx;
-    { lvk_status fs = fe_check_failed(fe); if (fs != LVK_OK) return fs; }
-    if (!R_wc || !p_wc || !h_out || !n_out || cap < 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_map: bad argument");
-    if (fe->map.n == 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_map: no map is set (lvk_frontend_set_map)");
+    if (fe->map.n == 0) return lvk_set_error(ctx, LVK_ERR_ARG, "%s: no map is set (lvk_frontend_set_map)", who);
     const int most = fe_map_max_selected(select_opt);
-    if (most >= 0 && cap < most) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_frontend_match_map: room for %d records, the options can select %d", cap, most);
+    if (most >= 0 && cap < most) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "%s: room for %d records, the options can select %d", who, cap, most);
     lvk_match_options o;
-    lvk_status st = fe_match_options(fe, "lvk_frontend_match_map", match_opt, &o);
+    lvk_status st = fe_match_options(fe, who, match_opt, &o);
     if (st == LVK_OK) st = fe_match_buffers(fe);
     if (st != LVK_OK) return st;
     lvk_frontend::Match& m = fe->match;
@@ -951,8 +949,28 @@ lvk_status lvk_frontend_match_map(lvk_frontend* fe, const lvk_align_result* alig
     LVK_HIP(ctx, hipMemcpyAsync(&info, mp.info, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
     LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const int n_q = info.n_selected;
-    if (n_q < 0 || n_q > most) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_frontend_match_map: the selection reported %d points", n_q);
-    st = fe_match_chain(fe, "lvk_frontend_match_map", o, n_q, &info.n_candidates);
+    if (n_q < 0 || n_q > most) return lvk_set_error(ctx, LVK_ERR_DEVICE, "%s: the selection reported %d points", who, n_q);
+    st = fe_match_chain(fe, who, o, n_q, &info.n_candidates);
+    if (st != LVK_OK) return st;
+    *n_q_out = n_q; *info_out = info;
+    return LVK_OK;
+}
+
+// The map's points in the last processed frame: lvk_map_select_queries writes the queries and their descriptors straight into the
+// matcher's buffers, the chain of lvk_frontend_match_landmarks runs on them, the host joins the two record arrays.
+lvk_status lvk_frontend_match_map(lvk_frontend* fe, const lvk_align_result* align, const double* R_wc, const double* p_wc, const double* cov_cam36,
+                                  const lvk_map_select_options* select_opt, const lvk_match_options* match_opt, lvk_map_match* h_out, int cap, int* n_out,
+                                  lvk_map_info* h_info)
+{
+    if (!fe) return LVK_ERR_ARG;
+    lvk_context* ctx = fe->ctx;
+    { lvk_status fs = fe_check_failed(fe); if (fs != LVK_OK) return fs; }
+    if (!R_wc || !p_wc || !h_out || !n_out || cap < 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_match_map: bad argument");
+    lvk_frontend::Match& m = fe->match;
+    lvk_frontend::Map& mp = fe->map;
+    int n_q = 0;
+    lvk_map_info info;
+    const lvk_status st = fe_match_map_device(fe, "lvk_frontend_match_map", align, R_wc, p_wc, cov_cam36, select_opt, match_opt, cap, &n_q, &info);
     if (st != LVK_OK) return st;
     *n_out = n_q;
     if (h_info) *h_info = info;
@@ -969,6 +987,45 @@ lvk_status lvk_frontend_match_map(lvk_frontend* fe, const lvk_align_result* alig
         r.depth = sel[k].depth; r.pad = 0.f;
         r.m = res[k];
     }
+    return LVK_OK;
+}
+
+// The front-end's part of lvk_vio_localise_map: the device chain of lvk_frontend_match_map, then lvk_map_gather_obs' launch on the
+// selection's and the matcher's records where they lie (no joined copy is made), then ONE copy back of the counts, the source rows and
+// the observations, laid out for this frame's n_selected: [lvk_map_obs_info | int idx[n_q], padded to 8 bytes | lvk_landmark_obs obs[n_q]].
+// sigma = sigma_px / ((fx + fy) / 2), as larvio_amd.localize.map_obs defines it.
+#define FE_LOC_BLOB (sizeof(lvk_map_obs_info) + sizeof(int) * LVK_MAP_MAX_QUERIES + sizeof(lvk_landmark_obs) * LVK_MAP_MAX_QUERIES)
+lvk_status lvk_frontend_localise_obs(lvk_frontend* fe, const lvk_align_result* align, const double* R_wc, const double* p_wc, const double* cov_cam36,
+                                     const lvk_map_select_options* select_opt, const lvk_match_options* match_opt, double sigma_px,
+                                     lvk_landmark_obs* h_obs, int* h_idx, lvk_map_info* h_info, lvk_map_obs_info* h_oinfo)
+{
+    if (!fe) return LVK_ERR_ARG;
+    lvk_context* ctx = fe->ctx;
+    { lvk_status fs = fe_check_failed(fe); if (fs != LVK_OK) return fs; }
+    if (!R_wc || !p_wc || !h_obs || !h_idx || !h_info || !h_oinfo) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_vio_localise_map: bad argument");
+    if (!std::isfinite(sigma_px) || !(sigma_px > 0.)) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_vio_localise_map: sigma_px is not a finite number > 0");
+    if (!fe->loc.blob && fe->map.n > 0) {
+        if (hipMalloc((void**)&fe->loc.blob, FE_LOC_BLOB) != hipSuccess) { (void)hipGetLastError(); fe->loc.blob = nullptr; return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_vio_localise_map: allocation failed"); }
+    }
+    int n_q = 0;
+    lvk_status st = fe_match_map_device(fe, "lvk_vio_localise_map", align, R_wc, p_wc, cov_cam36, select_opt, match_opt, LVK_MAP_MAX_QUERIES, &n_q, h_info);
+    if (st != LVK_OK) return st;
+    memset(h_oinfo, 0, sizeof *h_oinfo);
+    if (n_q == 0) return LVK_OK;
+    const size_t o_idx = sizeof(lvk_map_obs_info), o_obs = o_idx + ((sizeof(int) * (size_t)n_q + 7) & ~(size_t)7), bytes = o_obs + sizeof(lvk_landmark_obs) * (size_t)n_q;
+    char* blob = fe->loc.blob;
+    const double sigma = sigma_px / ((fe->cam.intr[0] + fe->cam.intr[1]) / 2);
+    st = fe_map_gather_launch(ctx, &fe->map.sel->index, (int)sizeof(lvk_map_sel), fe->match.out, (int)sizeof(lvk_landmark_match), n_q, fe->map.X, fe->map.cov, fe->map.n, align,
+                              sigma, (lvk_landmark_obs*)(blob + o_obs), (int*)(blob + o_idx), (lvk_map_obs_info*)blob);
+    if (st != LVK_OK) return st;
+    std::vector<char> got(bytes);
+    LVK_HIP(ctx, hipMemcpyAsync(got.data(), blob, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(h_oinfo, got.data(), sizeof *h_oinfo);
+    const int n_ok = h_oinfo->n_ok;
+    if (n_ok < 0 || n_ok > n_q) return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_vio_localise_map: the gather reported %d observations of %d records", n_ok, n_q);
+    memcpy(h_idx, got.data() + o_idx, sizeof(int) * (size_t)n_ok);
+    memcpy(h_obs, got.data() + o_obs, sizeof(lvk_landmark_obs) * (size_t)n_ok);
     return LVK_OK;
 }
 

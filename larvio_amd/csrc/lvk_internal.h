@@ -129,6 +129,11 @@ lvk_context* lvk_frontend_context(lvk_frontend* fe);      // frontend.hip
 extern "C" lvk_status lvk_frontend_begin(lvk_frontend* fe, const lvk_image* img, double ts);   // image stage only (internal)
 // the pipelined driver's non-blocking processImage: *slot = ring entry of the feature message (when *has_msg), collected later
 extern "C" lvk_status lvk_frontend_process_async(lvk_frontend* fe, const lvk_image* img, double ts, const lvk_imu* h_imu, int n_imu, int* has_msg, int* slot);
+// the front-end's part of lvk_vio_localise_map (be_pipe.hip): lvk_frontend_match_map's device chain, lvk_map_gather_obs on its records
+// where they lie, one copy back.  h_obs / h_idx: room for LVK_MAP_MAX_QUERIES entries each
+extern "C" lvk_status lvk_frontend_localise_obs(lvk_frontend* fe, const lvk_align_result* align, const double* R_wc, const double* p_wc, const double* cov_cam36,
+                                                const lvk_map_select_options* select_opt, const lvk_match_options* match_opt, double sigma_px,
+                                                lvk_landmark_obs* h_obs, int* h_idx, lvk_map_info* h_info, lvk_map_obs_info* h_oinfo);
 extern "C" lvk_status lvk_frontend_fetch_msg(lvk_frontend* fe, int slot, lvk_feature_obs* h_out, int cap, int* n_out);
 
 struct lvk_pyramid {

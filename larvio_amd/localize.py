@@ -32,16 +32,22 @@ For a map that is not resident (at most 1024 points a call), the same through th
     am, idx = align_matches(m0, X_map)                                  # the OK records as (X, u, v)
     res, mask = image_processor.align_landmarks(am, R_wc, p_wc)
 
-Then per frame to localise on:
+Then per frame to localise on, one call on the driver (VioDriver, VioDeferred; VioPipeline between drain() and the next step()):
 
+    info = driver.localise_map(align=res, time=ts, sigma_px=sigma_px, select=sel)   # lvk_vio_localise_map: the filter's pose to a queued batch
+
+It takes the camera pose of the frame's clone and its covariance from the filter on the device (lvk_ekf_camera_pose_cov: cov_cam in the
+order [dtheta dp], rotation error on the camera side, dp in the world frame), projects the whole map, takes each search radius from the
+point's and the pose's covariance, spreads its at most 1024 queries over a grid of image cells, matches them, gathers the matched points
+and their covariances from the resident map into observation rows (lvk_map_gather_obs) and queues them on that clone; the host keeps no
+copy of the map.  info holds the counts and the pose that was used.  The same link by hand, for a check:
+
+    R_wc, p_wc, cov_cam = camera_pose_cov_ref(larvio.cov(), clone_col, clone, (R_b2c, t_c_b))   # or ops.camera_pose_cov on a device P
     rec, info = image_processor.match_map(R_wc, p_wc, align=res, cov_cam=cov_cam, select=sel)   # project, cull, pick <= 1024, match
-    obs, idx = map_obs(rec, X_map, cov_map, res, sigma_px, fe_config)
+    obs, idx = map_obs(rec, X_map, cov_map, res, sigma_px, fe_config)                          # the host-side check of lvk_map_gather_obs
     larvio.add_landmark_obs(obs["p_w"], obs["uv"], obs["sigma"], obs["cov_w"], time=ts)
 
-match_map projects the whole map on the GPU, takes each search radius from the point's and the pose's covariance (cov_cam: order
-[dtheta dp], rotation error on the camera side, dp in the world frame - converting the filter's IMU-pose block of LarVio.window_cov with
-the extrinsics is the caller's job) and spreads its at most 1024 queries over a grid of image cells.  The same on the host, for a small
-map or a check:
+And without a resident map, for a small map:
 
     px, ok = predict_pixels(p_w, R_wc, p_wc, fe_config)                # where the map's points should appear, from a pose prediction
     m = image_processor.match_landmarks(px[ok], radius, desc[ok])      # which corner of the frame each of them is
@@ -215,6 +221,56 @@ def map_obs(records, X_map, cov_map, result, sigma_px, fe_config):
     return obs, idx
 
 
+def _quat_to_rot(q):
+    """R(q), q = [x y z w], in the order lvk_ekf_camera_pose_cov states (Eigen's Quaternion::toRotationMatrix)"""
+    x, y, z, w = (np.float64(v) for v in np.asarray(q, np.float64).reshape(4))
+    tx, ty, tz = 2 * x, 2 * y, 2 * z
+    twx, twy, twz, txx, txy, txz, tyy, tyz, tzz = tx * w, ty * w, tz * w, tx * x, ty * x, tz * x, ty * y, tz * y, tz * z
+    return np.array([[1 - (tyy + tzz), txy - twz, txz + twy], [txy + twz, 1 - (txx + tzz), tyz - twx], [txz - twy, tyz + twx, 1 - (txx + tyy)]], np.float64)
+
+
+def camera_pose(clone, extrinsics):
+    """The camera pose of a clone of the filter's window, bit for bit as lvk_ekf_camera_pose_cov forms it.  clone: a record with q ([x y z w],
+    body to world) and p (one entry of LarVio.clones()); extrinsics: (R_b2c (3, 3), t_c_b (3,)) as the filter's state hands them out.
+    -> (R_wc = R_b R_b2c^T (3, 3), p_wc = p_b + R_b t_c_b (3,))"""
+    Rb = _quat_to_rot(clone["q"]); pb = np.asarray(clone["p"], np.float64).reshape(3)
+    Re = np.asarray(extrinsics[0], np.float64).reshape(3, 3); t = np.asarray(extrinsics[1], np.float64).reshape(3)
+    R_wc = np.empty((3, 3)); p_wc = np.empty(3)
+    for i in range(3):
+        for j in range(3):
+            R_wc[i, j] = (Rb[i, 0] * Re[j, 0] + Rb[i, 1] * Re[j, 1]) + Rb[i, 2] * Re[j, 2]
+        p_wc[i] = pb[i] + ((Rb[i, 0] * t[0] + Rb[i, 1] * t[1]) + Rb[i, 2] * t[2])
+    return R_wc, p_wc
+
+
+def camera_pose_cov_ref(P, clone_col, clone, extrinsics):
+    """The numpy restatement of lvk_ekf_camera_pose_cov (include/lvk_c.h), expression by expression in the order stated there - for a
+    check, or where the covariance is on the host anyway (LarVio.cov()).  P: the filter's covariance (n, n); clone_col: the first of the
+    clone's six columns (leg_dim + 6 * its rank in the window); clone, extrinsics as camera_pose takes them.
+    -> (R_wc (3, 3), p_wc (3,), cov_cam (6, 6) in the order [dtheta dp], rotation error on the camera side, dp in the world frame)"""
+    P = np.asarray(P, np.float64)
+    R_wc, p_wc = camera_pose(clone, extrinsics)
+    Rb = _quat_to_rot(clone["q"]); Re = np.asarray(extrinsics[0], np.float64).reshape(3, 3)
+    u = p_wc * 0.0
+    t = np.asarray(extrinsics[1], np.float64).reshape(3)
+    for i in range(3):
+        u[i] = (Rb[i, 0] * t[0] + Rb[i, 1] * t[1]) + Rb[i, 2] * t[2]
+    J = np.zeros((6, 12))
+    J[0:3, 0:3] = Re; J[0:3, 6:9] = R_wc.T; J[3:6, 3:6] = Rb
+    J[3:6, 6:9] = np.array([[0.0, u[2], -u[1]], [-u[2], 0.0, u[0]], [u[1], -u[0], 0.0]])
+    J[3:6, 9:12] = np.eye(3)
+    cols = np.r_[15:21, int(clone_col):int(clone_col) + 6]
+    Ps = P[np.ix_(cols, cols)]
+    T = np.zeros((6, 12))
+    for l in range(12):
+        T = T + J[:, l:l + 1] * Ps[l:l + 1, :]
+    cov = np.zeros((6, 6))
+    for l in range(12):
+        cov = cov + T[:, l:l + 1] * J[:, l:l + 1].T
+    cov = np.triu(cov) + np.triu(cov, 1).T
+    return R_wc, p_wc, cov
+
+
 def view_limit(fe_config, r_max=20.0, step=0.01):
     """The value to pass as max_r2 to match_map / ops.map_select_queries: the largest r2 = x^2 + y^2 of a normalised point, along the rays
     from the principal point towards the four image corners and the four edge midpoints, up to which the forward model is still
@@ -265,11 +321,15 @@ def align_matches(matches, X_map):
 
 def apply_alignment(result, X_map, cov_map=None):
     """p_w = Rz X + t for the map points X_map (n, 3) with the refined (c, s, t) of an ALIGN_RESULT record, and their covariances
-    (None, one 3 x 3 or n of them) rotated by Rz: what predict_pixels and landmark_obs take.  -> (p_w (n, 3), cov_w (n, 3, 3) or None)"""
-    c, s = float(result["c"]), float(result["s"])
+    (None, one 3 x 3 or n of them) rotated by Rz: what predict_pixels and landmark_obs take.  -> (p_w (n, 3), cov_w (n, 3, 3) or None).
+    p_w is formed by the expressions lvk_map_select_queries and lvk_map_gather_obs state - q = (c X_x - s X_y, s X_x + c X_y),
+    p_w = (q_x + t_x, q_y + t_y, X_z + t_z) -, so it is bit for bit the point the library projects and fuses; the covariance goes through
+    numpy's matrix product and has no fixed order."""
+    c, s = np.float64(result["c"]), np.float64(result["s"])
     Rz = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
     X_map = np.asarray(X_map, np.float64).reshape(-1, 3)
-    p_w = X_map @ Rz.T + np.asarray(result["t"], np.float64).reshape(1, 3)
+    t = np.asarray(result["t"], np.float64).reshape(3)
+    p_w = np.stack([(c * X_map[:, 0] - s * X_map[:, 1]) + t[0], (s * X_map[:, 0] + c * X_map[:, 1]) + t[1], X_map[:, 2] + t[2]], -1)
     if cov_map is None:
         return p_w, None
     cov = np.asarray(cov_map, np.float64).reshape(-1, 3, 3)

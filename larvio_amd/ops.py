@@ -634,3 +634,65 @@ def update_landmarks(ctx, P, job, obs, n=None):
     dP = ctx.to_device(P)
     ctx.check(L.lvk_ekf_update_landmarks(ctx.h, _p(dP), P.shape[1], n, _p(job), _p(obs) if len(obs) else None, len(obs), _p(dx), _p(info), _p(st), _p(g)))
     return dx, ctx.to_host(dP, np.float64, P.shape), info, st[:len(obs)], g[:len(obs)]
+
+
+# lvk_camera_pose_job (include/lvk_c.h): LANDMARK_FIX_JOB without the gate fields
+CAMERA_POSE_JOB = np.dtype([("clone_col", np.int32), ("pad0", np.int32), ("q_b", np.float64, 4), ("p_b", np.float64, 3), ("R_b2c", np.float64, 9), ("t_c_b", np.float64, 3)])
+
+
+def camera_pose_job(clone_col, q_b, p_b, R_b2c, t_c_b):
+    """one CAMERA_POSE_JOB record"""
+    j = np.zeros(1, CAMERA_POSE_JOB)
+    j["clone_col"] = int(clone_col); j["q_b"] = np.asarray(q_b, np.float64).reshape(4); j["p_b"] = np.asarray(p_b, np.float64).reshape(3)
+    j["R_b2c"] = np.asarray(R_b2c, np.float64).reshape(9); j["t_c_b"] = np.asarray(t_c_b, np.float64).reshape(3)
+    return j
+
+
+def camera_pose_cov(ctx, P, job, n=None, check=True):
+    """lvk_ekf_camera_pose_cov: the camera pose of the CAMERA_POSE_JOB record's clone and its 6 x 6 covariance [dtheta dp], read off the
+    covariance P.  P: a whole row-major buffer (its row length is the leading dimension, contents go to the device as they are) whose
+    leading n x n block (default: all rows) is the covariance.  -> (R_wc (3, 3), p_wc (3,), cov_cam (6, 6)); check=False returns
+    (status code, that triple) instead of raising - the outputs keep their NaN fill when the call is refused."""
+    P = np.ascontiguousarray(P, np.float64); job = np.ascontiguousarray(job, CAMERA_POSE_JOB).reshape(1)
+    n = P.shape[0] if n is None else int(n)
+    R = np.full((3, 3), np.nan); p = np.full(3, np.nan); cov = np.full((6, 6), np.nan)
+    dP = ctx.to_device(P)
+    st = lib().lvk_ekf_camera_pose_cov(ctx.h, _p(dP), P.shape[1], n, _p(job), _p(R), _p(p), _p(cov))
+    if check:
+        ctx.check(st)
+        return R, p, cov
+    return st, (R, p, cov)
+
+
+MAP_OBS_GUARD = 64      # sentinel bytes (0xA5) map_gather_obs keeps on either side of every output buffer
+
+
+def map_gather_obs(ctx, records, X, cov, sigma, align=None, n_rec=None, check=True):
+    """lvk_map_gather_obs over host arrays: records (a MAP_MATCH array, as match_map returns it), the map X (n_map, 3) with cov
+    (n_map, 3, 3) or None, sigma in normalised units, align: None, an ALIGN_RESULT record or (c, s, t).  -> dict(info: one MAP_OBS_INFO
+    record, obs: the n_ok LANDMARK_OBS rows, idx: the rows of `records` they came from, and obs_raw, idx_raw, info_raw: the device buffers
+    as bytes, sized for n_rec entries, with MAP_OBS_GUARD sentinel bytes of 0xA5 on either side, every output byte starting as 0xA5 too).
+    n_rec: the count handed to the library when it is not len(records).  check=False returns (status code, that dict) instead of raising."""
+    from ._lib import MAP_MATCH, MAP_OBS_INFO
+    rec = np.ascontiguousarray(records, MAP_MATCH).reshape(-1)
+    nr = len(rec) if n_rec is None else int(n_rec)
+    X = np.ascontiguousarray(X, np.float64).reshape(-1, 3); n_map = len(X)
+    cv = None if cov is None else np.ascontiguousarray(cov, np.float64).reshape(-1, 9)
+    assert cv is None or len(cv) == n_map
+    al = align_record(align)
+    G = MAP_OBS_GUARD; room = max(len(rec), 1)
+    sizes = dict(obs=LANDMARK_OBS.itemsize * room, idx=4 * room, info=MAP_OBS_INFO.itemsize)
+    bufs = {k: ctx.to_device(np.full(v + 2 * G, 0xA5, np.uint8)) for k, v in sizes.items()}
+    at = lambda k: C.c_void_p(bufs[k].ptr + G)
+    d_rec = ctx.to_device(rec) if len(rec) else None
+    d_X = ctx.to_device(X) if n_map else None; d_cov = ctx.to_device(cv) if cv is not None and n_map else None
+    st = lib().lvk_map_gather_obs(ctx.h, _p(d_rec), nr, _p(d_X), _p(d_cov), n_map, _p(al), float(sigma), at("obs"), at("idx"), at("info"))
+    if check:
+        ctx.check(st)
+    ctx.sync()
+    raw = {k: ctx.to_host(bufs[k], np.uint8, (sizes[k] + 2 * G,)).copy() for k in sizes}
+    body = lambda k: raw[k][G:G + sizes[k]]
+    info = body("info").view(MAP_OBS_INFO)[0]
+    n_ok = int(info["n_ok"]) if st == 0 else 0
+    out = dict(info=info, obs=body("obs").view(LANDMARK_OBS)[:n_ok], idx=body("idx").view(np.int32)[:n_ok], **{k + "_raw": v for k, v in raw.items()})
+    return out if check else (st, out)

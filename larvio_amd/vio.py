@@ -30,9 +30,31 @@ def _L():
     return L
 
 
+def _localise_map(fe, be, align, time, clone_id, sigma_px, select, match, tag):
+    """lvk_vio_localise_map on an ImageProcessor and a LarVio -> one LOCALISE_INFO record"""
+    from ._lib import LOCALISE_INFO, LvkError
+    from .ops import align_record
+    al = align_record(align)
+    info = np.zeros(1, LOCALISE_INFO)
+    st = lib().lvk_vio_localise_map(fe._h, be._h, _p(al), int(clone_id), float(time), float(sigma_px), C.byref(select) if select is not None else None,
+                                    C.byref(match) if match is not None else None, int(tag), _p(info))
+    if st != 0:
+        raise LvkError(f"lvk status {st}: {lib().lvk_last_error(be.ctx.h).decode()}")
+    return info[0]
+
+
 class VioDriver:
     """Keeps the driver's IMU buffer: samples with t < t_img + 0.05 are visible (larvioMain.cpp:98-102), the back-end erases
     what it consumed (larvio.cpp:511-512)."""
+
+    def localise_map(self, align=None, time=0.0, clone_id=-1, sigma_px=1.0, select=None, match=None, tag=0):
+        """lvk_vio_localise_map: from the filter's pose of the last processed frame to one queued batch of observations of the
+        front-end's resident map (ImageProcessor.set_map / build_map).  align: None, an ALIGN_RESULT record or (c, s, t); the clone goes
+        by clone_id, or by time (the frame's stamp) when clone_id is -1; select: ops.map_select_options(...) or None; match: a
+        _lib.MatchOptions or None.  -> one LOCALISE_INFO record (status LOCALISE_QUEUED or LOCALISE_NO_CLONE, n_ok, n_bad, clone_id, the
+        map's counts, and the R_wc, p_wc, cov_cam that were used).  The batch's report comes with the next update
+        (LarVio.take_landmark_reports)."""
+        return _localise_map(self.fe, self.be, align, time, clone_id, sigma_px, select, match, tag)
 
     def __init__(self, image_processor, larvio, imu_all):
         self.fe, self.be = image_processor, larvio
@@ -93,6 +115,13 @@ class VioPipeline:
         self.be.ctx.check(_L().lvk_vio_pipe_create(self.fe._h, self.be._h, C.byref(h)))
         self._h = h
         self.be.ctx.adopt(self); self.fe.ctx.adopt(self)
+        self._drained = True        # no frame submitted since the last drain()
+
+    def localise_map(self, align=None, time=0.0, clone_id=-1, sigma_px=1.0, select=None, match=None, tag=0):
+        """VioDriver.localise_map on the pipe's two handles; legal only between drain() and the next step(): raises ValueError otherwise"""
+        if not self._drained:
+            raise ValueError("VioPipeline.localise_map: frames have been submitted since the last drain(); call drain() first")
+        return _localise_map(self.fe, self.be, align, time, clone_id, sigma_px, select, match, tag)
 
     def visible_end(self, ts):
         return int(np.searchsorted(self.t, ts + 0.05, side="left"))
@@ -104,6 +133,7 @@ class VioPipeline:
             L.lvk_vio_pipe_push_imu(self._h, C.c_void_p(self._base + self.pushed * self._isz), hi - self.pushed)
             self.pushed = hi
         im, keep = make_image(img, device_ptr, stride, shape if shape is not None else self._shape, fmt=self.fe._pixfmt)
+        self._drained = False
         st = L.lvk_vio_pipe_submit(self._h, C.byref(im), float(ts), C.byref(self._has))
         if st != 0:
             self.fe.ctx.check(st); self.be.ctx.check(st)
@@ -114,6 +144,7 @@ class VioPipeline:
         st = _L().lvk_vio_pipe_drain(self._h, C.byref(nu), C.byref(nm))
         if st != 0:
             self.be.ctx.check(st); self.fe.ctx.check(st)
+        self._drained = True
         return nu.value, nm.value
 
     def stats(self, reset=False):
