@@ -403,6 +403,79 @@ typedef struct { int n_ok, n_no_candidate, n_too_far, n_ambiguous, n_conflict, n
 lvk_status lvk_orb_match_global(lvk_context* ctx, const uint8_t* d_map_desc, int n_map, const uint8_t* d_cand_desc, int n_cand,
                                 int max_dist, int ratio_pct, int max_matches, lvk_match_result* d_best, lvk_global_match* d_sel,
                                 lvk_global_info* d_info);
+/* Stage entry: a second session into the map of the first (3D-3D) - the yaw and translation that take session B's frame into the resident
+ * map's frame A, from n putative point-to-point matches, many of them wrong, by two-point RANSAC over n_pairs given pairs.  No reference
+ * counterpart.  Both frames have z along gravity, so the model is that of lvk_align_ransac_2pt: Y = Rz(psi) X + t, carried as c = cos psi,
+ * s = sin psi and t, Rz X = (c X_x - s X_y, s X_x + c X_y, X_z).  Match k carries X_k (frame B) and Y_k (frame A).  The pairs, the result
+ * record and the statuses are lvk_align_ransac_2pt's (lvk_align_pair, lvk_align_draw_pairs, lvk_align_result, LVK_ALIGN_*).  FP64
+ * throughout, no contraction, no atan2 / sin / cos, every expression in the order written here (a sum of products runs from the first
+ * product upwards):
+ *   solver     pair (i, j): a = X_i - X_j, b = Y_i - Y_j (per component), ra2 = a_x a_x + a_y a_y, rb2 = b_x b_x + b_y b_y.  No model when
+ *              i == j; when an index is outside 0..n-1 (nothing is read); when ra2 or rb2 is not > min_rho min_rho (a NaN lands here);
+ *              when |a_z - b_z| > 2 thresh; when |sqrt(ra2) - sqrt(rb2)| > 2 thresh.  Otherwise dot = a_x b_x + a_y b_y,
+ *              crs = a_x b_y - a_y b_x, nrm = sqrt(dot dot + crs crs) - no model either unless nrm > 0, which only an underflow of a
+ *              min_rho below 1e-150 can bring about -, c = dot / nrm, s = crs / nrm.  With q_k = (c X_k,x - s X_k,y, s X_k,x + c X_k,y)
+ *              (the expressions of lvk_map_select_queries): t_x = ((Y_i,x - q_i,x) + (Y_j,x - q_j,x)) / 2, t_y likewise,
+ *              t_z = ((Y_i,z - X_i,z) + (Y_j,z - X_j,z)) / 2.  One model per pair.
+ *   score      match k is an inlier iff d2 = (d_x d_x + d_y d_y) + d_z d_z <= thresh thresh with d = ((q_k,x + t_x) - Y_k,x,
+ *              (q_k,y + t_y) - Y_k,y, (X_k,z + t_z) - Y_k,z); a NaN is not an inlier.  count = the inliers.
+ *   winner     the model with the largest count; ties to the lowest hypothesis index.  d_mask[k] = 1 for its inliers, 0 otherwise; the mask
+ *              is NOT scored again after the refinement.
+ *   refinement closed form over the winner's m inliers, no iteration: mX = (sum X_k) / m, mY = (sum Y_k) / m; x' = X_k - mX, y' = Y_k - mY;
+ *              D = sum (x'_x y'_x + x'_y y'_y), C = sum (x'_x y'_y - x'_y y'_x), W = sum ((x'_x x'_x + x'_y x'_y) + (y'_x y'_x + y'_y y'_y));
+ *              nrm = sqrt(D D + C C), c = D / nrm, s = C / nrm, t = (mY_x - (c mX_x - s mX_y), mY_y - (s mX_x + c mX_y), mY_z - mX_z).
+ *              At the model that is returned, with q_k as above and r_k = the d of the score: A = sum J^T J (4 x 4, order psi, t_x, t_y,
+ *              t_z), J_k = [(-q_k,y, q_k,x, 0)^T | I3], that is A00 = sum (q_k,y q_k,y + q_k,x q_k,x), A01 = A10 = sum -q_k,y,
+ *              A02 = A20 = sum q_k,x, A11 = A22 = A33 = m, every other entry 0; rms = sqrt((sum ((r_x r_x + r_y r_y) + r_z r_z)) / m).
+ *              The sums over the inliers may be taken in any order (they are, across the lanes, in one fixed shape: two calls give the
+ *              same bytes).  The caller inverts A and scales by the points' variance - the library invents no covariance.
+ *   status     the first rule that applies: NO_MODEL no pair gave a model (fields as lvk_align_ransac_2pt sets them: hyp = root = pair_i =
+ *              pair_j = -1, c = c0 = 1, all else 0, mask zeroed); FEW_INLIERS the best count is below min_inliers (c0, s0, t0 = c, s, t =
+ *              the winner, the mask is the winner's, A = rms = 0); SINGULAR the refinement's nrm is not > 1e-12 (W / 2) - all inliers on
+ *              one vertical line in either frame - (c, s, t = the winner again, A and rms at the winner); OK.  root is 0 whenever there is
+ *              a winner, iters is always 0.
+ * d_m: n matches; d_pairs: n_pairs pairs; d_hyp: NULL or n_pairs records - n_models (0 or 1), count, c, s, t, everything zero when there is
+ * no model, the pads zero; d_mask: n bytes; d_out: one record.  Matches beyond n and records beyond n_pairs are not read or written.
+ * Two launches on the context's stream, not waited for: the hypotheses (four wavefronts a workgroup, one pair each; the workgroup stages
+ * the n matches in LDS once - 48 bytes each, 48 KB at the cap, inside the 64 KB that need no opt-in -, a wavefront scores its model across
+ * its lanes, 64 matches a step, and counts with an integer ballot); then one workgroup for the arg-max (an integer key), the mask and the
+ * refinement.  No atomics anywhere.
+ * opt may be NULL; a zero field takes its default: thresh 0.10 (metres), min_rho 0.5 (metres), min_inliers 6 (2..1024).  The defaults
+ * are design choices, not measurements: 10 cm is a few sigma of a good exported point, 0.5 m keeps a pair's yaw from being decided by
+ * that noise.  LVK_ERR_ARG, with nothing launched and the context still usable: a null pointer that is needed, a negative count, an option
+ * that is not finite, not positive or outside its range.  LVK_ERR_CAPACITY: n > 1024 (the matches are staged in LDS) or n_pairs > 4096.
+ * n < 2 or n_pairs == 0: NO_MODEL, the mask zeroed, the hypotheses kernel not launched. */
+typedef struct { double X[3], Y[3]; } lvk_align3d_match;
+typedef struct { int n_models, count, pad[2]; double c, s, t[3]; } lvk_align3d_hyp;
+typedef struct { double thresh, min_rho; int min_inliers, pad; } lvk_align3d_options;   /* zeros = defaults */
+lvk_status lvk_align_ransac_3d(lvk_context* ctx, const lvk_align3d_match* d_m, int n, const lvk_align_pair* d_pairs, int n_pairs,
+                               const lvk_align3d_options* opt, lvk_align3d_hyp* d_hyp, uint8_t* d_mask, lvk_align_result* d_out);
+/* The alignment the other way round (host only): in holds A -> B as Y = Rz X + t (its refined c, s, t are read), out takes B -> A:
+ * c' = c, s' = -s, t' = (-(c t_x + s t_y), -(c t_y - s t_x), -t_z), every other field 0.  A session that was localised online holds the
+ * map's alignment into its own world frame; lvk_frontend_merge_map wants the session's into the map.  in == out is allowed.
+ * LVK_ERR_ARG: a null pointer. */
+lvk_status lvk_align_invert(const lvk_align_result* in, lvk_align_result* out);
+/* Stage entry: an alignment applied to a point set where it lies on the device.  No reference counterpart.  d_X: n points (3 doubles each);
+ * d_cov: NULL or their covariances (9 doubles each, row-major; the upper triangle is read); d_desc: NULL or their 32-byte descriptors;
+ * align: only c, s, t of the record are read, NULL = identity (c = 1, s = 0, t = 0 through the same expressions, so NULL and an explicit
+ * identity record give the same bytes); cov_align16: NULL or the 4 x 4 covariance P (row-major; the upper triangle is read) of the
+ * alignment's (psi, t_x, t_y, t_z).  FP64 throughout, no contraction, every expression in the order written here:
+ *   p          q = (c X_x - s X_y, s X_x + c X_y), p = (q_x + t_x, q_y + t_y, X_z + t_z) - the expressions of lvk_map_select_queries.
+ *   cov        w = Rz Sigma Rz^T by the expressions of lvk_map_gather_obs (w00, w01, w11, w02, w12, w22 from a, b, d, e, f, g).  With
+ *              cov_align16: j = (-q_y, q_x, 0) and, for a <= b, k_ab = (((j_a j_b) P[0][0] + j_a P[0][1 + b]) + j_b P[0][1 + a]) +
+ *              P[1 + a][1 + b] (= J P J^T, J = [j^T | I3]); the output is w_ab + k_ab, k_ab alone without d_cov.  The full matrix is
+ *              written, entry (b, a) is a copy of entry (a, b).  This treats the alignment's error, which all points of the set share,
+ *              as independent from point to point: right for any one point, too optimistic for what depends on several of them.
+ *   desc       copied.
+ * Non-finite points and covariances pass through (lvk_map_build classifies them).  d_X_out: n x 3; d_cov_out: n x 9, written when d_cov
+ * or cov_align16 is given and required then, otherwise untouched; d_desc_out: n x 32, written and required when d_desc is given, otherwise
+ * untouched.  Each may be the tail of a larger buffer.  No output may alias an input.  One launch on the context's stream, one lane per
+ * point, chunks of 256, not waited for.
+ * LVK_ERR_ARG, with nothing launched and the context still usable: a null pointer that is needed, n < 0, a non-finite c, s or t of the
+ * alignment, a non-finite entry of cov_align16, a descriptor pointer that is not 8-byte aligned.  LVK_ERR_CAPACITY: n >
+ * LVK_MAP_MAX_POINTS.  n == 0: LVK_OK, nothing launched. */
+lvk_status lvk_map_transform(lvk_context* ctx, const double* d_X, const double* d_cov, const uint8_t* d_desc, int n, const lvk_align_result* align,
+                             const double cov_align16[16], double* d_X_out, double* d_cov_out, uint8_t* d_desc_out);
 /* replaces integrateImuData + predictFeatureTracking's matrix (image_processor.cpp:222-293): host math */
 lvk_status lvk_predict_homography(const lvk_imu* h_imu, int n_imu, double t_prev, double t_curr,
                                   const double R_cam_imu[9], const double intr[4], float H[9]);
@@ -566,6 +639,42 @@ typedef struct { int cand, index, dist, second; lvk_pt2f px, und; int inlier, pa
 lvk_status lvk_frontend_relocalise_map(lvk_frontend* fe, const double R_wc[9], const double p_wc[3], const lvk_match_options* match_opt,
                                        const lvk_align_options* align_opt, int max_matches, int max_hypotheses, uint32_t seed,
                                        lvk_align_result* h_out, lvk_reloc_match* h_matches, int cap, int* n_out, lvk_global_info* h_info);
+/* The way back into that chain: a second session's exports merged into the map in force (multi-session mapping).  h_X, h_cov9, h_desc: the
+ * n points of session B in B's own world frame, as lvk_frontend_build_map takes them (covariances and descriptors are required here).
+ * align: B -> A (Y = Rz X + t; lvk_align_invert turns the A -> B alignment of a session that was localised online), or NULL = find it;
+ * cov_align16: NULL or the alignment's covariance as lvk_map_transform takes it.  On the main stream, in buffers of the call's own - the
+ * small ones of the search and the alignment allocated by the first call and kept, the ones sized by the two maps for the call's duration:
+ *   1  upload B; lvk_map_build on B alone with build_opt (cull, B's own duplicates, best first): order_B, n_kept_B.  One wait.
+ *   2  only when align == NULL: the first min(n_kept_B, 4096) points of the sorted B are the queries of lvk_orb_match_global against the
+ *      resident map's descriptors (match_opt's max_dist and ratio_pct, zero = 58 and 100 as elsewhere, the other fields are not read;
+ *      max_matches 1024); a wait for n_selected; lvk_align_draw_pairs(n_selected, max_hypotheses, seed); a gather kernel writes the
+ *      lvk_align3d_match records, X = sorted B's point `cand`, Y = the resident point `index`; lvk_align_ransac_3d (align_opt); a wait for
+ *      the result.  A status other than LVK_ALIGN_OK ends the call with LVK_OK, *h_align_out carrying the status, the map in force
+ *      untouched, *info zeroed and h_order not written: not finding an alignment is an answer, not an error.
+ *   3  the resident arrays are copied device to device into [A | .], lvk_map_transform (the alignment, cov_align16) writes the sorted B
+ *      behind them.
+ *   4  lvk_map_build with build_opt on the concatenation, the covariance's trace the score on both sides.  On equal scores the resident
+ *      copy wins - as a duplicate's better copy and in the order -, because its index is the lower.  One wait.
+ *   5  the result becomes the map in force exactly as lvk_frontend_build_map installs it (n_kept == 0 frees the map).
+ *   6  h_order (may be NULL; cap_order = its room in entries) in the caller's view: a value i < n_A is resident point i, any other is
+ *      n_A + B's ORIGINAL index (composed through order_B), n_A the size of the map before the call - so the caller keeps its ids in step.
+ * *h_align_out (required): the alignment that was used - the stage entry's record, or a copy of *align; *info (may be NULL): the counts of
+ * step 4; *h_match_info (may be NULL): the search's counts, zero when align was given.
+ * LVK_ERR_ARG: no map is set, the resident map has no covariances, h_X, h_cov9 or h_desc is NULL with n > 0, h_align_out is NULL, n < 0,
+ * cap_order < 0, max_hypotheses < 0, with align == NULL a max_dist outside 0..256 or a ratio_pct outside 0..100 (with an alignment given
+ * the search does not run and its options are not read), a non-finite c, s or t of align, a non-finite entry of cov_align16, the stage
+ * entries' refusals of the options, a call between lvk_frontend_begin and the lvk_frontend_process of the same frame - each of these is
+ * found before anything is uploaded or launched.  LVK_ERR_CAPACITY: n_A + n > LVK_MAP_MAX_POINTS, max_hypotheses >
+ * 4096, h_order given and cap_order < n_kept (cap_order >= n_A + n always suffices).  LVK_ERR_DEVICE when the buffers cannot be had.  In
+ * each case the map in force stays, and none is sticky.  Off the per-frame path: it waits for the front-end's own streams first, changes
+ * nothing a later frame reads - a run with merges between frames publishes the bits of a run without them -, and a run that never calls it
+ * launches and allocates what it did before.  With a lvk_vio_pipe attached, call it only between lvk_vio_pipe_drain and the next
+ * lvk_vio_pipe_submit. */
+lvk_status lvk_frontend_merge_map(lvk_frontend* fe, const double* h_X, const double* h_cov9, const uint8_t* h_desc, int n,
+                                  const lvk_align_result* align, const double cov_align16[16], const lvk_match_options* match_opt,
+                                  const lvk_align3d_options* align_opt, int max_hypotheses, uint32_t seed,
+                                  const lvk_map_build_options* build_opt, lvk_align_result* h_align_out, int* h_order, int cap_order,
+                                  lvk_map_build_info* info, lvk_global_info* h_match_info);
 /* cumulative LK work: point-levels processed and iterations executed (SURVEY §8d byte model) */
 lvk_status lvk_frontend_lk_stats(lvk_frontend* fe, uint64_t* point_levels, uint64_t* iterations);
 /* feature messages published so far (getFeatureMsg, image_processor.cpp:1076-1128) and the features they carried in total:

@@ -193,6 +193,31 @@ public:
         if (matches) matches->swap(m);
         return true;
     }
+    // a second session's exports merged into the resident map (lvk_frontend_merge_map): X, cov9, desc = session B in its own world frame;
+    // align = B -> the map's frame (lvk_align_invert turns the alignment of a session that was localised online) or null = find it from
+    // the two maps; cov_align16 = the alignment's 4 x 4 covariance or null.  used.status == LVK_ALIGN_OK marks a merge - any other status
+    // with a true return means no alignment was found and the map in force stands.  order (may be null): the merged map's points in the
+    // caller's view, a value below the old mapSize that resident point, any other the old mapSize + B's original index.  With a
+    // VioPipeline only after drain().  false = refused.
+    bool mergeMap(const std::vector<double>& X, const std::vector<double>& cov9, const std::vector<uint8_t>& desc, lvk_align_result& used,
+                  const lvk_align_result* align = nullptr, const double* cov_align16 = nullptr, const lvk_map_build_options* build_opt = nullptr,
+                  const lvk_match_options* match_opt = nullptr, const lvk_align3d_options* align_opt = nullptr, int max_hypotheses = 0, uint32_t seed = 0,
+                  std::vector<int>* order = nullptr, lvk_map_build_info* info = nullptr, lvk_global_info* match_info = nullptr)
+    {
+        const size_t n = X.size() / 3;
+        if (!fe_ || X.size() != 3 * n || desc.size() != 32 * n || cov9.size() != 9 * n) return false;
+        const int n_a = lvk_frontend_map_size(fe_);
+        std::vector<int> ord((size_t)(n_a > 0 ? n_a : 0) + n + 1);
+        lvk_map_build_info got;
+        if (lvk_frontend_merge_map(fe_, n ? X.data() : nullptr, n ? cov9.data() : nullptr, n ? desc.data() : nullptr, (int)n, align, cov_align16, match_opt, align_opt,
+                                   max_hypotheses, seed, build_opt, &used, ord.data(), (int)ord.size(), &got, match_info) != LVK_OK) {
+            std::fprintf(stderr, "ImageProcessor::mergeMap: %s\n", lvk_last_error(ctx_)); return false;
+        }
+        ord.resize((size_t)got.n_kept);
+        if (order) order->swap(ord);
+        if (info) *info = got;
+        return true;
+    }
     lvk_frontend* handle() const { return fe_; }
 private:
     ImageProcessor(const ImageProcessor&); ImageProcessor& operator=(const ImageProcessor&);

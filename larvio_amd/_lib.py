@@ -21,10 +21,10 @@ ABI_SYMBOLS = [
     "lvk_clahe_u8", "lvk_pyramid_create", "lvk_pyramid_destroy", "lvk_pyramid_build", "lvk_pyramid_build_clahe",
     "lvk_pyramid_levels", "lvk_pyramid_level", "lvk_orb_prepare", "lvk_image_to_gray", "lvk_min_eigen_map", "lvk_good_features", "lvk_good_features_from_map",
     "lvk_lk_track", "lvk_orb_describe", "lvk_hamming256_rows", "lvk_undistort_points", "lvk_find_fundamental_mask", "lvk_find_fundamental",
-    "lvk_ransac_fundamental", "lvk_orb_match_guided", "lvk_align_ransac_2pt", "lvk_align_draw_pairs", "lvk_map_select_queries", "lvk_map_build", "lvk_orb_match_global", "lvk_predict_homography",
+    "lvk_ransac_fundamental", "lvk_orb_match_guided", "lvk_align_ransac_2pt", "lvk_align_draw_pairs", "lvk_map_select_queries", "lvk_map_build", "lvk_orb_match_global", "lvk_align_ransac_3d", "lvk_align_invert", "lvk_map_transform", "lvk_predict_homography",
     "lvk_frontend_create", "lvk_frontend_destroy", "lvk_frontend_process", "lvk_frontend_tracks", "lvk_frontend_new_pts",
     "lvk_frontend_set_mask", "lvk_frontend_has_mask", "lvk_frontend_set_input_format", "lvk_frontend_input_format", "lvk_frontend_match_landmarks", "lvk_frontend_align_landmarks",
-    "lvk_frontend_set_map", "lvk_frontend_map_size", "lvk_frontend_build_map", "lvk_frontend_match_map", "lvk_frontend_relocalise_map",
+    "lvk_frontend_set_map", "lvk_frontend_map_size", "lvk_frontend_build_map", "lvk_frontend_match_map", "lvk_frontend_relocalise_map", "lvk_frontend_merge_map",
     "lvk_frontend_state", "lvk_frontend_lk_stats", "lvk_frontend_msg_stats", "lvk_frontend_profile_enable", "lvk_frontend_profile_read",
     "lvk_frontend_stage_name", "lvk_fe_track_stage", "lvk_fe_commit_stage", "lvk_fe_msg_stage",
     "lvk_ekf_compress_qr", "lvk_ekf_compress_qr_groups", "lvk_ekf_qr_plan", "lvk_ekf_update", "lvk_ekf_update_ldlt", "lvk_ekf_update_ldlt_perm", "lvk_dgemm", "lvk_dgemm_ex", "lvk_chol_solve", "lvk_ekf_cov_propagate_augment", "lvk_ekf_cov_gather", "lvk_ekf_cov_reanchor", "lvk_ekf_cov_append_features", "lvk_ekf_landmark_cov", "lvk_ekf_pose_rel_cov", "lvk_ekf_landmark_rel_cov", "lvk_ekf_msckf_point_cov", "lvk_ekf_update_sparse", "lvk_ekf_update_landmarks", "lvk_ekf_camera_pose_cov", "lvk_map_gather_obs", "lvk_vio_localise_map", "lvk_ekf_create", "lvk_ekf_destroy", "lvk_ekf_process", "lvk_ekf_process_async", "lvk_ekf_wait", "lvk_ekf_set_state",
@@ -153,6 +153,15 @@ MAP_BUILD_INFO = np.dtype([("n_kept", np.int32), ("n_bad", np.int32), ("n_uncert
 MAPB_KEPT, MAPB_BAD, MAPB_UNCERTAIN, MAPB_OUT_OF_RANGE, MAPB_DUPLICATE = 0, 1, 2, 3, 4
 
 
+# lvk_align3d_match / lvk_align3d_hyp / lvk_align3d_options of include/lvk_c.h (lvk_align_ransac_3d; pairs, result and statuses are ALIGN_*)
+ALIGN3D_MATCH = np.dtype([("X", np.float64, 3), ("Y", np.float64, 3)])
+ALIGN3D_HYP = np.dtype([("n_models", np.int32), ("count", np.int32), ("pad", np.int32, 2), ("c", np.float64), ("s", np.float64), ("t", np.float64, 3)])
+
+
+class Align3dOptions(C.Structure):
+    _fields_ = [("thresh", C.c_double), ("min_rho", C.c_double), ("min_inliers", C.c_int), ("pad", C.c_int)]
+
+
 class MapBuildOptions(C.Structure):
     _fields_ = [("max_score", C.c_double), ("r_dup", C.c_double), ("dup_max_dist", C.c_int), ("pad", C.c_int)]
 
@@ -204,6 +213,9 @@ def lib():
             "lvk_map_select_queries": ([vp, vp, vp, vp, i, C.POINTER(MapCamera), vp, vp, vp, vp, C.POINTER(MapSelectOptions), vp, vp, vp, vp, vp], i),
             "lvk_map_build": ([vp, vp, vp, vp, vp, i, C.POINTER(MapBuildOptions), vp, vp, vp, vp, vp, vp], i),
             "lvk_orb_match_global": ([vp, vp, i, vp, i, i, i, i, vp, vp, vp], i),
+            "lvk_align_ransac_3d": ([vp, vp, i, vp, i, C.POINTER(Align3dOptions), vp, vp, vp], i),
+            "lvk_align_invert": ([vp, vp], i),
+            "lvk_map_transform": ([vp, vp, vp, vp, i, vp, vp, vp, vp, vp], i),
             "lvk_predict_homography": ([vp, i, d, d, vp, vp, vp], i),
             "lvk_frontend_create": ([vp, C.POINTER(FeConfig), C.POINTER(vp)], i), "lvk_frontend_destroy": ([vp], None),
             "lvk_frontend_process": ([vp, C.POINTER(Image), d, vp, i, vp, i, pi, pi], i),
@@ -218,6 +230,7 @@ def lib():
             "lvk_frontend_build_map": ([vp, vp, vp, vp, vp, i, C.POINTER(MapBuildOptions), vp, i, vp], i),
             "lvk_frontend_match_map": ([vp, vp, vp, vp, vp, C.POINTER(MapSelectOptions), C.POINTER(MatchOptions), vp, i, pi, vp], i),
             "lvk_frontend_relocalise_map": ([vp, vp, vp, C.POINTER(MatchOptions), C.POINTER(AlignOptions), i, i, C.c_uint32, vp, vp, i, pi, vp], i),
+            "lvk_frontend_merge_map": ([vp, vp, vp, vp, i, vp, vp, C.POINTER(MatchOptions), C.POINTER(Align3dOptions), i, C.c_uint32, C.POINTER(MapBuildOptions), vp, vp, i, vp, vp], i),
             "lvk_frontend_lk_stats": ([vp, vp, vp], i),
             "lvk_frontend_msg_stats": ([vp, vp, vp], i),
             "lvk_frontend_profile_enable": ([vp, C.c_uint], i), "lvk_frontend_profile_read": ([vp, vp, vp, i], i),

@@ -128,6 +128,9 @@ struct lvk_frontend {
     // lvk_vio_localise_map's own buffer, allocated by its first call: the blob that goes back in one copy - the counts, then room for 1024
     // source rows and 1024 observations (lvk_frontend_localise_obs lays it out for the frame's n_selected)
     struct Loc { char* blob; } loc = {};
+    // lvk_frontend_merge_map's own small buffers, allocated by its first call: the search's records per query and its selection, its counts,
+    // the 3D alignment's matches, pairs, mask and result
+    struct Merge { lvk_match_result* best; lvk_global_match* sel; lvk_global_info* ginfo; lvk_align3d_match* m; lvk_align_pair* pairs; uint8_t* mask; lvk_align_result* res; } merge = {};
     // sticky: a frame that failed AFTER its image stage was queued (device error, ring overrun) leaves the buffer-set rotation and the
     // end-of-frame events out of step with the frame count; the handle then refuses further frames instead of racing on its buffers
     lvk_status failed = LVK_OK; char failed_msg[200] = {0};
@@ -192,6 +195,10 @@ lvk_status fe_reloc_gather(lvk_context* ctx, const CamParams& cam, const lvk_glo
 lvk_status fe_reloc_inliers(lvk_context* ctx, const uint8_t* d_mask, int n, lvk_reloc_match* d_out);
 // fe_mapbuild.hip: does lvk_map_build accept these options (false: *why names the field)?  lvk_frontend_build_map asks before it allocates
 bool fe_map_build_options_ok(const lvk_map_build_options* opt, const char** why);
+// fe_align3d.hip: does lvk_align_ransac_3d accept these options?  And, behind lvk_orb_match_global on the context's stream, the 3D alignment's
+// match records of lvk_frontend_merge_map: X = point `cand` of the n_b sorted points of B, Y = point `index` of the n_a resident points
+bool fe_align3d_options_ok(const lvk_align3d_options* opt, const char** why);
+lvk_status fe_merge_gather(lvk_context* ctx, const lvk_global_match* d_sel, int n, const double* d_XB, int n_b, const double* d_XA, int n_a, lvk_align3d_match* d_out);
 #ifdef LVK_LK_BOUNDS
 void fe_lk_bounds_report();                             // prints what the frame path's kernels recorded in THEIR copy of g_lk_oob
 #endif

@@ -128,7 +128,8 @@ void lvk_frontend_destroy(lvk_frontend* fe)
                     fe->gf_scratch, fe->gf_cands, fe->dev, fe->user_mask, fe->d_gray,
                     fe->match.eig, fe->match.cand_pts, fe->match.n_cand, fe->match.cand_desc, fe->match.q, fe->match.q_desc, fe->match.res, fe->match.px, fe->match.und, fe->match.out,
                     fe->align.m, fe->align.pairs, fe->align.mask, fe->align.out, fe->map.X, fe->map.cov, fe->map.desc, fe->map.sel, fe->map.info,
-                    fe->reloc.best, fe->reloc.sel, fe->reloc.px, fe->reloc.und, fe->reloc.blob, fe->loc.blob};
+                    fe->reloc.best, fe->reloc.sel, fe->reloc.px, fe->reloc.und, fe->reloc.blob, fe->loc.blob,
+                    fe->merge.best, fe->merge.sel, fe->merge.ginfo, fe->merge.m, fe->merge.pairs, fe->merge.mask, fe->merge.res};
     for (void* p : ptrs) if (p) hipFree(p);
     for (int i = 0; i < 3; ++i) { if (fe->h_stage[i]) hipHostFree(fe->h_stage[i]); if (fe->d_ring[i]) hipFree(fe->d_ring[i]); if (fe->ev_img[i]) hipEventDestroy(fe->ev_img[i]); }
     for (int i = 0; i < LVK_MSG_SLOTS; ++i) if (fe->ev_msg[i]) hipEventDestroy(fe->ev_msg[i]);
@@ -1142,6 +1143,193 @@ lvk_status lvk_frontend_relocalise_map(lvk_frontend* fe, const double* R_wc, con
     if (h_info) memcpy(h_info, back.data() + offsetof(lvk_frontend::RelocBlob, info), sizeof *h_info);
     if (n > 0) memcpy(h_matches, back.data() + head, sizeof(lvk_reloc_match) * (size_t)n);
     *n_out = n;
+    return LVK_OK;
+}
+
+// A second session into the map in force (no reference counterpart): B is uploaded and built on its own, aligned to the resident map (a given
+// alignment, or lvk_orb_match_global of the sorted B against the resident descriptors and lvk_align_ransac_3d), transformed behind a copy of
+// the resident arrays, and the concatenation is built and installed as lvk_frontend_build_map installs its result.  The buffers sized by
+// the maps live for the call; fe->merge keeps the small ones.  A refusal, and an alignment that is not found, leave the map in force.
+lvk_status lvk_frontend_merge_map(lvk_frontend* fe, const double* h_X, const double* h_cov9, const uint8_t* h_desc, int n, const lvk_align_result* align,
+                                  const double* cov_align16, const lvk_match_options* match_opt, const lvk_align3d_options* align_opt, int max_hypotheses, uint32_t seed,
+                                  const lvk_map_build_options* build_opt, lvk_align_result* h_align_out, int* h_order, int cap_order, lvk_map_build_info* info,
+                                  lvk_global_info* h_match_info)
+{
+    if (!fe) return LVK_ERR_ARG;
+    lvk_context* ctx = fe->ctx;
+    { lvk_status fs = fe_check_failed(fe); if (fs != LVK_OK) return fs; }
+    if (n < 0 || cap_order < 0 || max_hypotheses < 0 || !h_align_out || (n > 0 && (!h_X || !h_cov9 || !h_desc))) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_merge_map: bad argument");
+    if (fe->map.n == 0) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_merge_map: no map is set (lvk_frontend_set_map)");
+    if (!fe->map.cov) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_merge_map: the resident map has no covariances (they are the score of the merge)");
+    // what the stage entries would refuse is refused here, before anything is uploaded or launched; the search's options are read only
+    // when the search runs
+    int max_dist = match_opt ? match_opt->max_dist : 0, ratio_pct = match_opt ? match_opt->ratio_pct : 0;
+    if (max_dist == 0) max_dist = 58;
+    if (ratio_pct == 0) ratio_pct = 100;
+    if (!align && (max_dist < 0 || max_dist > 256)) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_merge_map: max_dist %d outside 0..256", max_dist);
+    if (!align && (ratio_pct < 1 || ratio_pct > 100)) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_merge_map: ratio_pct %d outside 0..100", ratio_pct);
+    if (align && !(std::isfinite(align->c) && std::isfinite(align->s) && std::isfinite(align->t[0]) && std::isfinite(align->t[1]) && std::isfinite(align->t[2])))
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_merge_map: the alignment is not finite");
+    if (cov_align16)
+        for (int k = 0; k < 16; ++k)
+            if (!std::isfinite(cov_align16[k])) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_merge_map: cov_align16 is not finite");
+    const char* why = "";
+    if (!fe_map_build_options_ok(build_opt, &why)) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_merge_map: %s", why);
+    if (!fe_align3d_options_ok(align_opt, &why)) return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_merge_map: %s", why);
+    if (max_hypotheses > FE_ALIGN_MAX_PAIRS) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_frontend_merge_map: max_hypotheses %d, at most %d", max_hypotheses, FE_ALIGN_MAX_PAIRS);
+    const int n_a = fe->map.n;
+    if ((long long)n_a + n > LVK_MAP_MAX_POINTS) return lvk_set_error(ctx, LVK_ERR_CAPACITY, "lvk_frontend_merge_map: %d resident and %d new points, at most %d together", n_a, n, LVK_MAP_MAX_POINTS);
+    if (fe->image_done)
+        return lvk_set_error(ctx, LVK_ERR_ARG, "lvk_frontend_merge_map: the image stage of t = %.6f is still waiting for its lvk_frontend_process", fe->image_done_ts);
+    lvk_frontend::Merge& mg = fe->merge;
+    if (!mg.best) {
+        lvk_frontend::Merge b = {};
+        if (!(dalloc(&b.best, 4096) && dalloc(&b.sel, FE_ALIGN_MAX_N) && dalloc(&b.ginfo, 1) && dalloc(&b.m, FE_ALIGN_MAX_N) && dalloc(&b.pairs, FE_ALIGN_MAX_PAIRS) &&
+              dalloc(&b.mask, FE_ALIGN_MAX_N) && dalloc(&b.res, 1))) {
+            (void)hipGetLastError();
+            void* ptrs[] = {b.best, b.sel, b.ginfo, b.m, b.pairs, b.mask, b.res};
+            for (void* p : ptrs) if (p) hipFree(p);
+            return lvk_set_error(ctx, LVK_ERR_DEVICE, "lvk_frontend_merge_map: allocation failed");
+        }
+        mg = b;
+    }
+    { lvk_status qs = fe_quiesce(fe); if (qs != LVK_OK) return qs; }
+    // the call's own buffers: B as uploaded, B sorted, its order; then the concatenation, its build and that build's order
+    double *in_X = nullptr, *in_cov = nullptr, *sb_X = nullptr, *sb_cov = nullptr, *cat_X = nullptr, *cat_cov = nullptr, *out_X = nullptr, *out_cov = nullptr;
+    uint8_t *in_desc = nullptr, *sb_desc = nullptr, *cat_desc = nullptr, *out_desc = nullptr;
+    int *order_b = nullptr, *order_m = nullptr; lvk_map_build_info* d_info = nullptr;
+    lvk_frontend::Map b = {};
+    auto release = [&]() {
+        void* ptrs[] = {in_X, in_cov, sb_X, sb_cov, cat_X, cat_cov, out_X, out_cov, in_desc, sb_desc, cat_desc, out_desc, order_b, order_m, d_info};
+        for (void* p : ptrs) if (p) hipFree(p);
+    };
+    auto fail = [&](lvk_status code, const char* what) {
+        (void)hipStreamSynchronize(ctx->stream);         // (the uploads read the caller's arrays)
+        (void)hipGetLastError();
+        release();
+        void* ptrs[] = {b.X, b.cov, b.desc, b.sel, b.info};
+        for (void* p : ptrs) if (p) hipFree(p);
+        return lvk_set_error(ctx, code, "lvk_frontend_merge_map: %s", what);
+    };
+    auto pass = [&](lvk_status st) {                     // a stage entry's refusal: its own message stands
+        (void)hipStreamSynchronize(ctx->stream);
+        release();
+        void* ptrs[] = {b.X, b.cov, b.desc, b.sel, b.info};
+        for (void* p : ptrs) if (p) hipFree(p);
+        return st;
+    };
+    lvk_map_build_info got_b, got;
+    memset(&got_b, 0, sizeof got_b); memset(&got, 0, sizeof got);
+    lvk_global_info ginfo;
+    memset(&ginfo, 0, sizeof ginfo);
+    hipError_t e = hipSuccess;
+    if (!dalloc(&d_info, 1)) return fail(LVK_ERR_DEVICE, "allocation failed");
+    // ---- 1: B alone
+    if (n > 0) {
+        const size_t N = (size_t)n;
+        if (!(dalloc(&in_X, 3 * N) && dalloc(&in_cov, 9 * N) && dalloc(&in_desc, 32 * N) && dalloc(&sb_X, 3 * N) && dalloc(&sb_cov, 9 * N) && dalloc(&sb_desc, 32 * N) && dalloc(&order_b, N)))
+            return fail(LVK_ERR_DEVICE, "allocation failed");
+        e = hipMemcpyAsync(in_X, h_X, sizeof(double) * 3 * N, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(in_cov, h_cov9, sizeof(double) * 9 * N, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(in_desc, h_desc, 32 * N, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) return fail(LVK_ERR_DEVICE, hipGetErrorString(e));
+        const lvk_status st = lvk_map_build(ctx, in_X, in_cov, in_desc, nullptr, n, build_opt, order_b, sb_X, sb_cov, sb_desc, nullptr, d_info);
+        if (st != LVK_OK) return pass(st);
+        e = hipMemcpyAsync(&got_b, d_info, sizeof got_b, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return fail(LVK_ERR_DEVICE, hipGetErrorString(e));
+        if (got_b.n_kept < 0 || got_b.n_kept > n) return fail(LVK_ERR_DEVICE, "the build of the new session reported an impossible count");
+    }
+    const int k_b = got_b.n_kept;
+    // ---- 2: the alignment
+    lvk_align_result al;
+    if (align) al = *align;
+    else {
+        const int n_q = k_b < 4096 ? k_b : 4096;
+        if (n_q > 0) {
+            const lvk_status st = lvk_orb_match_global(ctx, fe->map.desc, n_a, sb_desc, n_q, max_dist, ratio_pct, FE_ALIGN_MAX_N, mg.best, mg.sel, mg.ginfo);
+            if (st != LVK_OK) return pass(st);
+            e = hipMemcpyAsync(&ginfo, mg.ginfo, sizeof ginfo, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+            if (e != hipSuccess) return fail(LVK_ERR_DEVICE, hipGetErrorString(e));
+        }
+        const int n_sel = ginfo.n_selected;
+        if (n_sel < 0 || n_sel > FE_ALIGN_MAX_N) return fail(LVK_ERR_DEVICE, "the search reported an impossible count");
+        std::vector<lvk_align_pair> pairs(FE_ALIGN_MAX_PAIRS);
+        const int n_pairs = lvk_align_draw_pairs(n_sel, max_hypotheses, seed, pairs.data());
+        if (n_pairs < 0) return fail(LVK_ERR_ARG, "the pairs could not be drawn");
+        if (n_pairs > 0) e = hipMemcpyAsync(mg.pairs, pairs.data(), sizeof(lvk_align_pair) * (size_t)n_pairs, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) return fail(LVK_ERR_DEVICE, hipGetErrorString(e));
+        lvk_status st = fe_merge_gather(ctx, mg.sel, n_sel, sb_X, n_q, fe->map.X, n_a, mg.m);
+        if (st == LVK_OK) st = lvk_align_ransac_3d(ctx, mg.m, n_sel, mg.pairs, n_pairs, align_opt, nullptr, mg.mask, mg.res);
+        if (st != LVK_OK) return pass(st);
+        e = hipMemcpyAsync(&al, mg.res, sizeof al, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // (the upload read this call's own vector)
+        if (e != hipSuccess) return fail(LVK_ERR_DEVICE, hipGetErrorString(e));
+        if (al.status != LVK_ALIGN_OK) {                 // an answer, not an error: the map in force stays
+            release();
+            *h_align_out = al;
+            if (info) memset(info, 0, sizeof *info);
+            if (h_match_info) *h_match_info = ginfo;
+            return LVK_OK;
+        }
+    }
+    // ---- 3: [A | the sorted B in A's frame]
+    const int n_cat = n_a + k_b;
+    const size_t NA = (size_t)n_a, NC = (size_t)n_cat;
+    if (!(dalloc(&cat_X, 3 * NC) && dalloc(&cat_cov, 9 * NC) && dalloc(&cat_desc, 32 * NC) && dalloc(&out_X, 3 * NC) && dalloc(&out_cov, 9 * NC) && dalloc(&out_desc, 32 * NC) &&
+          dalloc(&order_m, NC)))
+        return fail(LVK_ERR_DEVICE, "allocation failed");
+    e = hipMemcpyAsync(cat_X, fe->map.X, sizeof(double) * 3 * NA, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(cat_cov, fe->map.cov, sizeof(double) * 9 * NA, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(cat_desc, fe->map.desc, 32 * NA, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e != hipSuccess) return fail(LVK_ERR_DEVICE, hipGetErrorString(e));
+    {
+        lvk_status st = lvk_map_transform(ctx, sb_X, sb_cov, sb_desc, k_b, &al, cov_align16, cat_X + 3 * NA, cat_cov + 9 * NA, cat_desc + 32 * NA);
+        // ---- 4: the merged map
+        if (st == LVK_OK) st = lvk_map_build(ctx, cat_X, cat_cov, cat_desc, nullptr, n_cat, build_opt, order_m, out_X, out_cov, out_desc, nullptr, d_info);
+        if (st != LVK_OK) return pass(st);
+    }
+    e = hipMemcpyAsync(&got, d_info, sizeof got, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(LVK_ERR_DEVICE, hipGetErrorString(e));
+    const int k = got.n_kept;
+    if (k < 0 || k > n_cat) return fail(LVK_ERR_DEVICE, "the build reported an impossible count");
+    if (h_order && cap_order < k) {
+        char msg[96]; snprintf(msg, sizeof msg, "room for %d indices, %d points are kept", cap_order, k);
+        return fail(LVK_ERR_CAPACITY, msg);
+    }
+    // ---- 5, 6: the map's own buffers at their final size, and the order in the caller's view
+    std::vector<int> ord_m, ord_b;
+    if (k > 0) {
+        const size_t K = (size_t)k;
+        if (!(dalloc(&b.X, 3 * K) && dalloc(&b.cov, 9 * K) && dalloc(&b.desc, 32 * K) && dalloc(&b.sel, LVK_MAP_MAX_QUERIES) && dalloc(&b.info, 1))) return fail(LVK_ERR_DEVICE, "allocation failed");
+        e = hipMemcpyAsync(b.X, out_X, sizeof(double) * 3 * K, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(b.cov, out_cov, sizeof(double) * 9 * K, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(b.desc, out_desc, 32 * K, hipMemcpyDeviceToDevice, ctx->stream);
+        if (h_order) {
+            ord_m.resize(K); ord_b.resize(k_b > 0 ? (size_t)k_b : 1);
+            if (e == hipSuccess) e = hipMemcpyAsync(ord_m.data(), order_m, sizeof(int) * K, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess && k_b > 0) e = hipMemcpyAsync(ord_b.data(), order_b, sizeof(int) * (size_t)k_b, hipMemcpyDeviceToHost, ctx->stream);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return fail(LVK_ERR_DEVICE, hipGetErrorString(e));
+        if (h_order)
+            for (int p = 0; p < k; ++p) {
+                const int o = ord_m[(size_t)p];
+                if (o < 0 || o >= n_cat) return fail(LVK_ERR_DEVICE, "the build reported an impossible index");
+                h_order[p] = o < n_a ? o : n_a + ord_b[(size_t)(o - n_a)];
+            }
+        b.n = k;
+    }
+    release();
+    LVK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    void* old[] = {fe->map.X, fe->map.cov, fe->map.desc, fe->map.sel, fe->map.info};
+    for (void* p : old) if (p) hipFree(p);
+    fe->map = b;
+    *h_align_out = al;
+    if (info) *info = got;
+    if (h_match_info) *h_match_info = ginfo;
     return LVK_OK;
 }
 

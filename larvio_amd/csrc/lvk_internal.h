@@ -73,6 +73,7 @@ enum lvk_scratch_slot {
                                         // the four launches of a call follow one another on the context's stream, and so does the next call
     LVK_SCR_MAPBUILD_WORK,              // map build: the sort's two key and index arrays, the scores' bits, the digit x chunk and status x chunk tables, the status bytes.
                                         // Its own slot: a call's launches follow one another on the context's stream, and so does the next call
+    LVK_SCR_ALIGN3D_HYP,                // 3D-3D alignment: the hypothesis records when the caller keeps none
     LVK_SCRATCH_SLOTS
 };
 #define LVK_LDS_OPTIN_KERNELS 24        // kernels that ask for more dynamic LDS than the default (fewer than that today)

@@ -256,6 +256,37 @@ class ImageProcessor:
                                                          _p(res), _p(out), len(out), C.byref(n), _p(info)))
         return res[0], out[:n.value].copy(), info[0]
 
+    def merge_map(self, X, cov, desc, align=None, cov_align=None, *, max_hypotheses=0, seed=0, max_dist=0, ratio_pct=0, thresh=0.0, min_rho=0.0, min_inliers=0,
+                  **build_options):
+        """lvk_frontend_merge_map: a second session's exports merged into the resident map (multi-session mapping).  X (n, 3), cov
+        (n, 3, 3), desc (n, 32) uint8: session B in its own world frame; align: B -> the map's frame - None (find it: the sorted B is
+        searched in the resident map and lvk_align_ransac_3d aligns the matched points), an ALIGN_RESULT record or (c, s, t);
+        larvio_amd.localize.invert_alignment turns the alignment of a session that was localised online; cov_align: None or the 4 x 4
+        covariance of the alignment's (psi, t).  max_dist, ratio_pct: the search's; thresh, min_rho, min_inliers: the 3D alignment's (zero =
+        0.10 m, 0.5 m, 6); build_options: max_score, r_dup, dup_max_dist of larvio_amd.ops.map_build_options, applied to B alone and to the
+        merged map.  -> (align: the ALIGN_RESULT record that was used - with a status other than ALIGN_OK nothing was merged and the map
+        in force stands -, order: the merged map's points in the caller's view - a value below the old map_size is that resident point,
+        any other is the old map_size + B's original index -, info: one MAP_BUILD_INFO record, match_info: one GLOBAL_INFO record).  A
+        refusal (LvkError) leaves the previous map in place.  With a VioPipeline call it only after drain()."""
+        from ._lib import ALIGN_RESULT, MAP_BUILD_INFO, GLOBAL_INFO, MatchOptions
+        from .ops import map_build_options, align3d_options, align_record
+        if self._h is None:
+            raise LvkError("ImageProcessor.initialize() has not succeeded")
+        Xa = np.zeros((0, 3)) if X is None else np.ascontiguousarray(X, np.float64).reshape(-1, 3)
+        n = len(Xa)
+        cv = None if cov is None or n == 0 else np.ascontiguousarray(cov, np.float64).reshape(-1, 9)
+        d = None if desc is None or n == 0 else np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        if n and ((d is not None and len(d) != n) or (cv is not None and len(cv) != n)):
+            raise ValueError(f"{n} points but {0 if d is None else len(d)} descriptors and {0 if cv is None else len(cv)} covariances")
+        al = align_record(align)
+        P = None if cov_align is None else np.ascontiguousarray(cov_align, np.float64).reshape(16)
+        mo = MatchOptions(0, 0.0, 0.0, int(max_dist), int(ratio_pct)); ao = align3d_options(thresh, min_rho, min_inliers); bo = map_build_options(**build_options)
+        cap = max(self.map_size, 0) + n
+        used = np.zeros(1, ALIGN_RESULT); order = np.zeros(max(cap, 1), np.int32); info = np.zeros(1, MAP_BUILD_INFO); ginfo = np.zeros(1, GLOBAL_INFO)
+        self.ctx.check(lib().lvk_frontend_merge_map(self._h, _p(Xa) if n else None, _p(cv), _p(d), n, _p(al), _p(P), C.byref(mo), C.byref(ao), int(max_hypotheses),
+                                                    int(seed) & 0xFFFFFFFF, C.byref(bo), _p(used), _p(order), cap, _p(info), _p(ginfo)))
+        return used[0], order[:int(info[0]["n_kept"])].copy(), info[0], ginfo[0]      # (info is zero when nothing was merged)
+
     @property
     def state(self):
         return lib().lvk_frontend_state(self._h)

@@ -53,6 +53,15 @@ And without a resident map, for a small map:
     m = image_processor.match_landmarks(px[ok], radius, desc[ok])      # which corner of the frame each of them is
     obs, idx = landmark_obs(m, p_w[ok], cov_w[ok], sigma_px, fe_config)
 
+A second session over the same site goes into the map of the first - its exports are in their own world frame, so it is aligned first
+(found from the two maps' descriptors and points, or given: a session that was localised online holds the map's alignment into its
+world, invert_alignment turns it round):
+
+    used, order, info, minfo = image_processor.merge_map(X_b, cov_b, desc_b, r_dup=0.05)            # or align=invert_alignment(res)
+    # used["status"] == ALIGN_OK: merged; order < old map_size: that resident point, else old map_size + B's index
+
+align_points and merge_maps restate lvk_align_ransac_3d and the whole call in numpy - the judges of the tests, nothing to run per frame.
+
 distort / project / predict_pixels are the forward camera model in numpy; the library's own is in lvk_map_select_queries."""
 import numpy as np
 
@@ -342,3 +351,154 @@ def alignment_cov(result, sigma_px, fe_config):
     fx, fy = fe_config["intrinsics"][:2]
     sigma = float(sigma_px) / (0.5 * (fx + fy))
     return sigma * sigma * np.linalg.inv(np.asarray(result["A"], np.float64).reshape(4, 4))
+
+
+def invert_alignment(result):
+    """lvk_align_invert in numpy: (c, s, t) of Y = Rz X + t the other way round, by the header's expressions -> (c', s', t')"""
+    c, s = np.float64(result["c"]), np.float64(result["s"])
+    t = np.asarray(result["t"], np.float64).reshape(3)
+    return c, -s, np.array([-(c * t[0] + s * t[1]), -(c * t[1] - s * t[0]), -t[2]])
+
+
+def transform_points(X, cov=None, align=None, cov_align=None):
+    """lvk_map_transform in numpy, every expression in the header's order, so the result is the library's bit for bit.  X (n, 3), cov
+    (n, 3, 3) or None, align: None or a record / dict with c, s, t, cov_align: None or 4 x 4.  -> (p (n, 3), cov' (n, 3, 3) or None)"""
+    X = np.asarray(X, np.float64).reshape(-1, 3)
+    c, s, t = (np.float64(1.0), np.float64(0.0), np.zeros(3)) if align is None else (np.float64(align["c"]), np.float64(align["s"]), np.asarray(align["t"], np.float64).reshape(3))
+    with np.errstate(all="ignore"):
+        q0 = c * X[:, 0] - s * X[:, 1]; q1 = s * X[:, 0] + c * X[:, 1]
+        p = np.stack([q0 + t[0], q1 + t[1], X[:, 2] + t[2]], -1)
+        if cov is None and cov_align is None:
+            return p, None
+        w = {}
+        if cov is not None:
+            S = np.asarray(cov, np.float64).reshape(-1, 3, 3)
+            a, b, d, e, f, g = S[:, 0, 0], S[:, 0, 1], S[:, 1, 1], S[:, 0, 2], S[:, 1, 2], S[:, 2, 2]
+            m00 = c * a - s * b; m01 = c * b - s * d; m10 = s * a + c * b; m11 = s * b + c * d
+            w = {(0, 0): m00 * c - m01 * s, (0, 1): m00 * s + m01 * c, (1, 1): m10 * s + m11 * c, (0, 2): c * e - s * f, (1, 2): s * e + c * f, (2, 2): g.copy()}
+        if cov_align is not None:
+            P = np.asarray(cov_align, np.float64).reshape(4, 4)
+            j = [-q1, q0, np.zeros(len(X))]
+            for r in range(3):
+                for u in range(r, 3):
+                    k = (((j[r] * j[u]) * P[0, 0] + j[r] * P[0, 1 + u]) + j[u] * P[0, 1 + r]) + P[1 + r, 1 + u]
+                    w[r, u] = w[r, u] + k if cov is not None else k
+        out = np.zeros((len(X), 3, 3))
+        for (r, u), v in w.items():
+            out[:, r, u] = v; out[:, u, r] = v
+    return p, out
+
+
+ALIGN3D_DEFAULTS = dict(thresh=0.10, min_rho=0.5, min_inliers=6)
+
+
+def align_points(X, Y, pairs, thresh=0.0, min_rho=0.0, min_inliers=0):
+    """lvk_align_ransac_3d in numpy float64, every expression in the header's order: the hypotheses, their counts, the winner and its mask
+    are the library's bit for bit; the refinement's sums run in numpy's order, so c, s, t, A and rms agree to rounding.  X, Y (n, 3):
+    the matched points in B's and in the map's frame; pairs (P, 2).  -> dict(status, hyp, n_inliers, mask, c, s, t, c0, s0, t0, A, rms,
+    n_models (P,), count (P,), hc, hs (P,), ht (P, 3))"""
+    thresh = np.float64(thresh or ALIGN3D_DEFAULTS["thresh"]); min_rho = np.float64(min_rho or ALIGN3D_DEFAULTS["min_rho"]); min_inliers = int(min_inliers or ALIGN3D_DEFAULTS["min_inliers"])
+    X = np.asarray(X, np.float64).reshape(-1, 3); Y = np.asarray(Y, np.float64).reshape(-1, 3)
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    n, P = len(X), len(pairs)
+    out = dict(status=1, hyp=-1, n_inliers=0, mask=np.zeros(n, np.uint8), c=np.float64(1), s=np.float64(0), t=np.zeros(3), c0=np.float64(1), s0=np.float64(0), t0=np.zeros(3),
+               A=np.zeros((4, 4)), rms=np.float64(0), n_models=np.zeros(P, np.int32), count=np.zeros(P, np.int32), hc=np.zeros(P), hs=np.zeros(P), ht=np.zeros((P, 3)))
+    if n < 2 or P == 0:
+        return out
+    thresh2 = thresh * thresh; two = 2.0 * thresh; rho2 = min_rho * min_rho
+    i, j = pairs[:, 0], pairs[:, 1]
+    ok = (i != j) & (i >= 0) & (j >= 0) & (i < n) & (j < n)
+    ii, jj = np.where(ok, i, 0), np.where(ok, j, 0)
+    with np.errstate(all="ignore"):
+        a = X[ii] - X[jj]; b = Y[ii] - Y[jj]
+        ra2 = a[:, 0] * a[:, 0] + a[:, 1] * a[:, 1]; rb2 = b[:, 0] * b[:, 0] + b[:, 1] * b[:, 1]
+        ok &= (ra2 > rho2) & (rb2 > rho2)
+        ok &= ~(np.abs(a[:, 2] - b[:, 2]) > two)
+        ok &= ~(np.abs(np.sqrt(ra2) - np.sqrt(rb2)) > two)
+        dot = a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]; crs = a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]
+        nrm = np.sqrt(dot * dot + crs * crs)
+        ok &= nrm > 0
+        c = dot / nrm; s = crs / nrm
+        qi0 = c * X[ii, 0] - s * X[ii, 1]; qi1 = s * X[ii, 0] + c * X[ii, 1]
+        qj0 = c * X[jj, 0] - s * X[jj, 1]; qj1 = s * X[jj, 0] + c * X[jj, 1]
+        t = np.stack([((Y[ii, 0] - qi0) + (Y[jj, 0] - qj0)) / 2.0, ((Y[ii, 1] - qi1) + (Y[jj, 1] - qj1)) / 2.0, ((Y[ii, 2] - X[ii, 2]) + (Y[jj, 2] - X[jj, 2])) / 2.0], -1)
+
+        def inliers(c, s, t):
+            q0 = c[:, None] * X[None, :, 0] - s[:, None] * X[None, :, 1]; q1 = s[:, None] * X[None, :, 0] + c[:, None] * X[None, :, 1]
+            dx = (q0 + t[:, 0, None]) - Y[None, :, 0]; dy = (q1 + t[:, 1, None]) - Y[None, :, 1]; dz = (X[None, :, 2] + t[:, 2, None]) - Y[None, :, 2]
+            return ((dx * dx + dy * dy) + dz * dz) <= thresh2
+        hs_ = np.nonzero(ok)[0]
+        count = np.zeros(P, np.int64)
+        for lo in range(0, len(hs_), 256):
+            sl = hs_[lo:lo + 256]
+            count[sl] = inliers(c[sl], s[sl], t[sl]).sum(1)
+    out["n_models"] = ok.astype(np.int32); out["count"] = count.astype(np.int32)
+    out["hc"] = np.where(ok, c, 0.0); out["hs"] = np.where(ok, s, 0.0); out["ht"] = np.where(ok[:, None], t, 0.0)
+    if not ok.any():
+        return out
+    w = int(hs_[np.argmax(count[hs_])])                  # the first of the largest: ties to the lowest hypothesis
+    with np.errstate(all="ignore"):
+        mask = inliers(c[w:w + 1], s[w:w + 1], t[w:w + 1])[0]
+    m = int(count[w])
+    out.update(hyp=w, n_inliers=m, mask=mask.astype(np.uint8), c=c[w], s=s[w], t=t[w].copy(), c0=c[w], s0=s[w], t0=t[w].copy(), status=2)
+    if m < min_inliers:
+        return out
+    Xi, Yi = X[mask], Y[mask]
+    cnt = np.float64(m)
+    mX = Xi.sum(0) / cnt; mY = Yi.sum(0) / cnt
+    x = Xi[:, :2] - mX[:2]; y = Yi[:, :2] - mY[:2]
+    D = (x[:, 0] * y[:, 0] + x[:, 1] * y[:, 1]).sum(); C = (x[:, 0] * y[:, 1] - x[:, 1] * y[:, 0]).sum()
+    W = ((x[:, 0] * x[:, 0] + x[:, 1] * x[:, 1]) + (y[:, 0] * y[:, 0] + y[:, 1] * y[:, 1])).sum()
+    nr = np.sqrt(D * D + C * C)
+    cr, sr, tr, status = c[w], s[w], t[w].copy(), 3
+    if nr > 1e-12 * (W / 2.0):
+        status = 0
+        cr = D / nr; sr = C / nr
+        tr = np.array([mY[0] - (cr * mX[0] - sr * mX[1]), mY[1] - (sr * mX[0] + cr * mX[1]), mY[2] - mX[2]])
+    q0 = cr * Xi[:, 0] - sr * Xi[:, 1]; q1 = sr * Xi[:, 0] + cr * Xi[:, 1]
+    rx = (q0 + tr[0]) - Yi[:, 0]; ry = (q1 + tr[1]) - Yi[:, 1]; rz = (Xi[:, 2] + tr[2]) - Yi[:, 2]
+    A = np.zeros((4, 4))
+    A[0, 0] = (q1 * q1 + q0 * q0).sum(); A[0, 1] = A[1, 0] = (-q1).sum(); A[0, 2] = A[2, 0] = q0.sum(); A[1, 1] = A[2, 2] = A[3, 3] = cnt
+    out.update(status=status, c=cr, s=sr, t=tr, A=A, rms=np.sqrt(((rx * rx + ry * ry) + rz * rz).sum() / cnt))
+    return out
+
+
+def merge_maps(A, B, align=None, cov_align=None, max_dist=58, ratio_pct=100, thresh=0.0, min_rho=0.0, min_inliers=0, max_hypotheses=0, seed=0, build=None, match=None,
+               **build_options):
+    """lvk_frontend_merge_map in numpy: the judge of ImageProcessor.merge_map.  A, B: (X, cov, desc) of the resident map and of the new
+    session; align: None (find it) or a record / dict with c, s, t (B -> A).  build, match: the restatements of lvk_map_build and
+    lvk_orb_match_global - by default tests/map_build_ref.build and tests/orb_global_ref.match of the source tree.
+    -> dict(align: align_points' dict (or status 0 and the given c, s, t), merged: bool, order: the merged map in the caller's view, X,
+    cov, desc: the merged map, info, match_info (None when align was given), order_B, matches: (B sorted index, A index) pairs, matches_X, matches_Y, pairs: what the 3D alignment was given)"""
+    from .ops import align_draw_pairs
+    if build is None or match is None:
+        try:
+            from tests.map_build_ref import build as ref_build
+            from tests.orb_global_ref import match as ref_match
+        except ImportError as e:
+            raise ImportError("larvio_amd.localize.merge_maps takes its restatements of lvk_map_build and lvk_orb_match_global from tests/map_build_ref.py and "
+                              "tests/orb_global_ref.py of the source tree, which is not on sys.path here: run from the repository's root, or pass build= and match=") from e
+        build = build or ref_build; match = match or ref_match
+    XA, covA, descA = (np.asarray(A[0], np.float64).reshape(-1, 3), np.asarray(A[1], np.float64).reshape(-1, 3, 3), np.asarray(A[2], np.uint8).reshape(-1, 32))
+    nA = len(XA)
+    rb = build(B[0], B[1], B[2], None, **build_options)
+    out = dict(merged=False, order_B=rb["order"], match_info=None, matches=np.zeros((0, 2), np.int64), order=None, X=None, cov=None, desc=None, info=None)
+    if align is None:
+        nq = min(len(rb["order"]), 4096)
+        g = match(descA, rb["desc"][:nq], max_dist, ratio_pct, 1024)
+        sel = g["sel"]
+        pr = align_draw_pairs(len(sel), max_hypotheses, seed)
+        al = align_points(rb["X"][sel["cand"]], XA[sel["index"]], np.stack([pr["i"], pr["j"]], 1).reshape(-1, 2), thresh, min_rho, min_inliers)
+        out.update(align=al, match_info=g["info"], matches=np.stack([sel["cand"], sel["index"]], 1).astype(np.int64).reshape(-1, 2), matches_X=rb["X"][sel["cand"]],
+                   matches_Y=XA[sel["index"]], pairs=np.stack([pr["i"], pr["j"]], 1).reshape(-1, 2))
+        if al["status"] != 0:
+            return out
+    else:
+        al = dict(status=0, c=np.float64(align["c"]), s=np.float64(align["s"]), t=np.asarray(align["t"], np.float64).reshape(3).copy())
+        out["align"] = al
+    pB, covB = transform_points(rb["X"], rb["cov"], al, cov_align)
+    rm = build(np.concatenate([XA, pB]), np.concatenate([covA, covB]), np.concatenate([descA, rb["desc"]]), None, **build_options)
+    o = rm["order"].astype(np.int64)
+    order = np.where(o < nA, o, nA + rb["order"].astype(np.int64)[np.maximum(o - nA, 0)]).astype(np.int32) if len(rb["order"]) else o.astype(np.int32)
+    out.update(merged=True, order=order, X=rm["X"], cov=rm["cov"], desc=rm["desc"], info=rm["info"])
+    return out

@@ -354,6 +354,79 @@ def map_build(ctx, X, cov, desc, score=None, options=None, want_status=True, che
     return out if check else (st, out)
 
 
+def align3d_options(thresh=0.0, min_rho=0.0, min_inliers=0):
+    """lvk_align3d_options; a zero field takes the library's default (0.10 m, 0.5 m, 6)"""
+    from ._lib import Align3dOptions
+    return Align3dOptions(float(thresh), float(min_rho), int(min_inliers), 0)
+
+
+def align_invert(align):
+    """lvk_align_invert (host code): the alignment the other way round.  align: an ALIGN_RESULT record or (c, s, t) -> one ALIGN_RESULT record"""
+    from ._lib import ALIGN_RESULT
+    a = align_record(align)
+    if a is None:
+        raise ValueError("align_invert needs an alignment")
+    out = np.zeros(1, ALIGN_RESULT)
+    if lib().lvk_align_invert(_p(a), _p(out)) != 0:
+        raise ValueError("lvk_align_invert refused its arguments")
+    return out[0]
+
+
+def align_ransac_3d(ctx, matches, pairs, options=None, n=None, n_pairs=None, want_hyp=True, check=True):
+    """lvk_align_ransac_3d: matches (an ALIGN3D_MATCH array: X in session B's frame, Y in the map's) and pairs (ALIGN_PAIR); options:
+    align3d_options(...) or None.  n / n_pairs default to the arrays' lengths (smaller values leave the tails unread).
+    -> dict(hyp: the n_pairs ALIGN3D_HYP records (None unless want_hyp), mask: n bytes, result: one ALIGN_RESULT record, and hyp_raw,
+    mask_raw, result_raw: the device buffers as bytes with ALIGN_GUARD sentinel bytes of 0xA5 on either side, every output byte starting
+    as 0xA5 too).  check=False returns (status code, that dict) instead of raising."""
+    from ._lib import ALIGN3D_MATCH, ALIGN_PAIR, ALIGN3D_HYP, ALIGN_RESULT
+    m = np.ascontiguousarray(matches, ALIGN3D_MATCH); pr = np.ascontiguousarray(pairs, ALIGN_PAIR)
+    n = len(m) if n is None else int(n); npr = len(pr) if n_pairs is None else int(n_pairs)
+    G = ALIGN_GUARD
+    sizes = dict(hyp=ALIGN3D_HYP.itemsize * max(npr, 0), mask=max(n, 0), result=ALIGN_RESULT.itemsize)
+    bufs = {k: ctx.to_device(np.full(v + 2 * G, 0xA5, np.uint8)) for k, v in sizes.items()}
+    d_m = ctx.to_device(m.view(np.uint8) if len(m) else np.zeros(8, np.uint8)); d_pr = ctx.to_device(pr.view(np.uint8) if len(pr) else np.zeros(8, np.uint8))
+    st = lib().lvk_align_ransac_3d(ctx.h, _p(d_m), n, _p(d_pr), npr, C.byref(options) if options is not None else None,
+                                   C.c_void_p(bufs["hyp"].ptr + G) if want_hyp else None, C.c_void_p(bufs["mask"].ptr + G), C.c_void_p(bufs["result"].ptr + G))
+    if check:
+        ctx.check(st)
+    ctx.sync()
+    raw = {k: ctx.to_host(bufs[k], np.uint8, (sizes[k] + 2 * G,)).copy() for k in sizes}
+    out = dict(hyp=raw["hyp"][G:G + sizes["hyp"]].view(ALIGN3D_HYP) if want_hyp else None, mask=raw["mask"][G:G + sizes["mask"]],
+               result=raw["result"][G:G + sizes["result"]].view(ALIGN_RESULT)[0], hyp_raw=raw["hyp"], mask_raw=raw["mask"], result_raw=raw["result"])
+    return out if check else (st, out)
+
+
+MAP_TRANSFORM_GUARD = 64    # sentinel bytes (0xA5) map_transform keeps behind every output buffer
+
+
+def map_transform(ctx, X, cov=None, desc=None, align=None, cov_align=None, head=0, check=True):
+    """lvk_map_transform over host arrays: X (n, 3), cov (n, 3, 3) or None, desc (n, 32) uint8 or None, align: None, an ALIGN_RESULT record
+    or (c, s, t), cov_align: None or the 4 x 4 covariance of (psi, t).  The outputs are written as the tails of larger buffers: `head`
+    records of 0xA5 in front, MAP_TRANSFORM_GUARD bytes of 0xA5 behind.  -> dict(X (n, 3), cov (n, 3, 3) or None, desc (n, 32) or None, and
+    X_raw, cov_raw, desc_raw: the whole buffers as bytes).  check=False returns (status code, that dict) instead of raising."""
+    X = np.ascontiguousarray(X, np.float64).reshape(-1, 3); n = len(X)
+    cv = None if cov is None else np.ascontiguousarray(cov, np.float64).reshape(-1, 9)
+    ds = None if desc is None else np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+    assert (cv is None or len(cv) == n) and (ds is None or len(ds) == n)
+    P = None if cov_align is None else np.ascontiguousarray(cov_align, np.float64).reshape(16)
+    al = align_record(align)
+    G, h = MAP_TRANSFORM_GUARD, int(head)
+    rec = dict(X=24, cov=72, desc=32)
+    have = dict(X=True, cov=cv is not None or P is not None, desc=ds is not None)
+    bufs = {k: ctx.to_device(np.full(rec[k] * (h + n) + G, 0xA5, np.uint8)) for k in rec}
+    at = lambda k: C.c_void_p(bufs[k].ptr + rec[k] * h) if have[k] else None
+    dev = [ctx.to_device(a) if a is not None and n else None for a in (X, cv, ds)]
+    st = lib().lvk_map_transform(ctx.h, _p(dev[0]), _p(dev[1]), _p(dev[2]), n, _p(al), _p(P), at("X"), at("cov"), at("desc"))
+    if check:
+        ctx.check(st)
+    ctx.sync()
+    raw = {k: ctx.to_host(bufs[k], np.uint8, (rec[k] * (h + n) + G,)).copy() for k in rec}
+    body = lambda k: raw[k][rec[k] * h:rec[k] * (h + n)]
+    out = dict(X=body("X").view(np.float64).reshape(-1, 3), cov=body("cov").view(np.float64).reshape(-1, 3, 3) if have["cov"] else None,
+               desc=body("desc").reshape(-1, 32) if have["desc"] else None, **{k + "_raw": v for k, v in raw.items()})
+    return out if check else (st, out)
+
+
 def undistort(ctx, points, intr, model, dist, new_intr):
     p = _pts(points); n = len(p)
     a = np.asarray(intr, np.float64); d = np.asarray(dist, np.float64); k = np.asarray(new_intr, np.float64)
